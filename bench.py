@@ -3,7 +3,7 @@
 semantics) on batches of independent key frames, inputs resident in HBM (BASELINE.json
 configs[3]: 512 x 3840x2160 per GPU; configs[4]: the same per GPU over 8 GPUs).
 
-Contract (driver): `python bench.py --gpus N --steps K --warmup W`.  For N > 1 the driver launches
+Contract (driver): `python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]`.  For N > 1 the driver launches
 it under torch.distributed.run (one rank per GPU, RANK / LOCAL_RANK / WORLD_SIZE from the env);
 started by hand with --gpus N > 1 and no WORLD_SIZE, bench.py starts torch.distributed.run itself
 as a child before touching the GPU and exits with its code.  WORLD_SIZE != --gpus is an error.
@@ -12,7 +12,21 @@ A "step" = one launch of the fused kernel over the rank's whole batch.  Timed re
 sync, K steps, sync + barrier; the max over ranks is taken; value = all frames of all ranks x MP per
 frame x K / that time.  Rank 0 prints one JSON line.
 
-Workloads (--workload; the headline is uhd4, the other two are reported beside it at N = 1):
+A plain run does only that: build the batch, warm up, time the K steps, write the outputs when
+--dump-outputs is given, print the line (metric, value, ms_per_step, the kernel time from the HIP events
+of the same steps and the roofline arithmetic on it).  Everything else below -- the digest parity check
+against the reference, the other workloads, the CPU baseline, the encode stage, the end-to-end legs --
+runs only with --full.  The options that shape it (--extra, --no-cpu-baseline, --cpu-*, --e2e-*,
+--encode) act only there, so giving any of them selects --full: none is ignored silently.
+
+--dump-outputs DIR: after the timed steps, what the last step left in the batch's output buffer (the
+cropped I420 of every slot, what a caller of vp8g_decode_batch_device receives) is sampled and written
+as DIR/i420_sample.npy (float32 [frames, S]; with N > 1 ranks, i420_sample_rank<r>.npy per rank): S
+distinct byte positions per frame, one per stratum of I420 size / S bytes, drawn per global frame index
+from a generator seeded with DUMP_SEED (dump_positions), 12 Mi values (48 MiB) over all ranks.  Inputs
+and positions depend only on the arguments, so two builds can be compared value for value.
+
+Workloads (--workload; the headline is uhd4, the others are reported beside it at N = 1 with --full):
   uhd4   512 x 3840x2160 per GPU: the 4 libwebp-encoded 4K fixtures (tests/fixtures/big/uhd_*),
          entropy-decoded once on the host; global slot i <- fixture i % 4, each slot its own HBM copy
          (512 x 26.6 MB >> the 256 MB Infinity Cache: no cache inflation).
@@ -20,7 +34,7 @@ Workloads (--workload; the headline is uhd4, the other two are reported beside i
   synth  512 x 3840x2160 per GPU, all distinct: vp8_synth.c profile 0 ("measured-like"), seed
          0x5EED ^ global frame index (SURVEY.md §8(d) second mode).
   uhd4_yuv  the uhd4 batch with -yuv semantics (m06 reconstruction only, no loop filter).
-Parity: after timing, vp8g_frame_digests digests every slot's output on the device; every rank's
+Parity (--full): after timing, vp8g_frame_digests digests every slot's output on the device; every rank's
 digests are gathered and compared with tests/golden/digests.json (the digest of the reference
 decoder's own I420 for that input) -- every frame of every rank, no pixel copies.
 
@@ -29,7 +43,7 @@ roofline: HBM-bound (8-bit integer stencils, no MFMA).  Algorithmic bytes per la
 kernel duration from HIP events recorded on the launch stream.  `traffic` = the PMC HBM bytes per
 launch measured by rocprofv3 (profiles/traffic_4k_batch.json).
 
-cpu_baseline (rank 0, N = 1 only): the reference's own m06+m07 (oracle/_ref/libref.so, compiled from
+cpu_baseline (--full; rank 0, N = 1 only): the reference's own m06+m07 (oracle/_ref/libref.so, compiled from
 the reference sources) when present, else our C restatement (oracle/liboracle.so), on a bounded
 sample of the same frames, one frame per thread, at all host cores (the affinity mask, SURVEY.md
 §8(d)) and at the per-GPU CPU share (OMP_NUM_THREADS, 16 on the GPU box); the faster is `value`,
@@ -68,6 +82,11 @@ WORKLOADS = {
 }
 FIXTURES = UHD  # (back-compat name used by tools/)
 PEAK_HBM_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md, chip-level parameters)
+DUMP_SEED = 0xD0C5  # --dump-outputs: seed of the sampled byte positions
+DUMP_VALUES = 12 << 20  # --dump-outputs: values written by all ranks together (float32: 48 MiB)
+# options that shape the --full run only, with their defaults (parse(): giving one selects --full)
+FULL_DEFAULTS = {"extra": "auto", "cpu_threads": 0, "cpu_seconds": 12.0, "e2e_frames": 256, "e2e_device_frames": 1024,
+                 "encode": "png"}
 E2E_REPS = 3  # end-to-end legs: median of this many calls (host page-cache and allocator state vary call to call)
 # measured HBM traffic per launch (rocprofv3 PMC passes, tools/profile_round.sh + traffic_summary.py)
 TRAFFIC_FILES = {"uhd4": ROOT / "profiles" / "traffic_4k_batch.json", "synth": ROOT / "profiles" / "traffic_synth_batch.json"}
@@ -108,20 +127,35 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="uhd4", choices=sorted(WORKLOADS))
     ap.add_argument("--frames", type=int, default=0, help="frames per GPU (0 = the workload's: 512 / 2048 / 512)")
-    ap.add_argument("--extra", default="auto", choices=["auto", "none"],
-                    help="auto: at N = 1 also measure the other workloads (reported under 'workloads')")
+    ap.add_argument("--full", action="store_true",
+                    help="also check every frame's digest against the reference and measure the other workloads, the "
+                         "CPU baseline, the encode stage and the end-to-end legs (selected too by any of --extra, "
+                         "--no-cpu-baseline, --cpu-*, --e2e-*, --encode, which shape these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed step's I420 outputs as DIR/i420_sample.npy (float32)")
     ap.add_argument("--unfiltered", action="store_true", help="-yuv semantics (m06 only)")
     ap.add_argument("--waves", type=int, default=0, help="waves per frame workgroup (0 = default)")
+    # the options of the full run: none of them acts on a plain run, so giving one selects --full
+    ap.add_argument("--extra", default=None, choices=["auto", "none"],
+                    help="auto (default): at N = 1 also measure the other workloads (reported under 'workloads')")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="0 = all host cores for the CPU baseline (and the per-GPU share beside it)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample length (all repeats)")
-    ap.add_argument("--e2e-frames", type=int, default=256,
-                    help="frames of the end-to-end object (.webp bytes -> I420, vp8g_decode_webp_batch); 0 = off")
-    ap.add_argument("--e2e-device-frames", type=int, default=1024,
-                    help="frames of its device-m05 leg (VP8G_BATCH_DEVICE_M05); 0 = off")
-    ap.add_argument("--encode", default="png", choices=["none", "rgb", "ppm", "png"],
-                    help="also time the m08/m09 stage on the uhd4 batch's output (secondary object 'encode')")
-    return ap.parse_args(argv)
+    ap.add_argument("--cpu-threads", type=int, default=None,
+                    help="0 (default) = all host cores for the CPU baseline (and the per-GPU share beside it)")
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="target CPU-baseline sample length (all repeats; default 12)")
+    ap.add_argument("--e2e-frames", type=int, default=None,
+                    help="frames of the end-to-end object (.webp bytes -> I420, vp8g_decode_webp_batch; default 256); 0 = off")
+    ap.add_argument("--e2e-device-frames", type=int, default=None,
+                    help="frames of its device-m05 leg (VP8G_BATCH_DEVICE_M05; default 1024); 0 = off")
+    ap.add_argument("--encode", default=None, choices=["none", "rgb", "ppm", "png"],
+                    help="also time the m08/m09 stage on the uhd4 batch's output (secondary object 'encode'; default png)")
+    args = ap.parse_args(argv)
+    for k, v in FULL_DEFAULTS.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v)
+        else:
+            args.full = True
+    args.full = args.full or args.no_cpu_baseline
+    return args
 
 
 def relaunch_if_needed(args) -> None:
@@ -365,20 +399,27 @@ def run_workload(name, args, rank, world, dist, dev, golden, rank_factory=Rank):
         lib.vp8g_debug_stamps((C.c_ulonglong * 16)(), 1)
     elapsed, kern = timed(lambda: r.batch.launch(stream, args.waves), args.steps, 0 if stamps else args.warmup, dist, dev)
     status = r.batch.status_word()
-    dig = r.batch.digests(stream)
-    # every rank's digests reach rank 0 (64 bits per frame, never pixels); rank 0 checks each one
-    # against the reference's digest for that global frame (shards are contiguous and equal)
-    allg = vp8g_dist.gather_frame_digests(torch.from_numpy(dig.view(np.int64).copy()).to(dev), dist)
-    flat = allg.cpu().numpy().reshape(-1).view(np.uint64)
-    exp = [r.expected_for(i) for i in range(flat.size)]
-    match = sum(1 for d, e in zip(flat, exp) if e is not None and int(d) == int(e, 16))
-    pinned = sum(1 for e in exp if e is not None)
     ok = status == 0 and r.params_agree
     kern_ms = statistics.median(kern)
-    elapsed, kern_ms, ok = vp8g_dist.reduce_timing(elapsed, kern_ms, ok, dist, dev)
-    ok = ok and match == pinned and pinned > 0
-    total_frames = int(flat.size)
-    counts = (match, pinned)
+    total_frames = r.n * world  # (shards are contiguous and equal)
+    if args.full:
+        dig = r.batch.digests(stream)
+        # every rank's digests reach rank 0 (64 bits per frame, never pixels); rank 0 checks each one
+        # against the reference's digest for that global frame
+        allg = vp8g_dist.gather_frame_digests(torch.from_numpy(dig.view(np.int64).copy()).to(dev), dist)
+        flat = allg.cpu().numpy().reshape(-1).view(np.uint64)
+        exp = [r.expected_for(i) for i in range(flat.size)]
+        match = sum(1 for d, e in zip(flat, exp) if e is not None and int(d) == int(e, 16))
+        pinned = sum(1 for e in exp if e is not None)
+        elapsed, kern_ms, ok = vp8g_dist.reduce_timing(elapsed, kern_ms, ok, dist, dev)
+        ok = ok and match == pinned and pinned > 0
+        total_frames = int(flat.size)
+        parity = (f"bit-exact vs reference ({match}/{pinned} frames, on-device digests)" if ok
+                  else f"MISMATCH ({match}/{pinned} frames match; status {status})")
+    else:
+        elapsed, kern_ms, ok = vp8g_dist.reduce_timing(elapsed, kern_ms, ok, dist, dev)
+        parity = ("not checked (--full compares every frame's digest with the reference)" if ok
+                  else f"LAUNCH ERROR (status {status}, frame parameters agree: {r.params_agree})")
     wl = r.wl
     W, H = wl["width"], wl["height"]
     mb_per = r.batch.mb_per
@@ -392,8 +433,7 @@ def run_workload(name, args, rank, world, dist, dev, golden, rank_factory=Rank):
         "kernel_ms_per_step": round(kern_ms, 3),
         "kernel_ms_steps": [round(x, 3) for x in kern],
         "frames_per_gpu": r.n, "frames_total": total_frames, "width": W, "height": H,
-        "parity": (f"bit-exact vs reference ({counts[0]}/{counts[1]} frames, on-device digests)" if ok
-                   else f"MISMATCH ({counts[0]}/{counts[1]} frames match; status {status})"),
+        "parity": parity,
         "parity_ok": bool(ok),
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
                      "frac": round(achieved / PEAK_HBM_GBS, 4), "traffic": None,
@@ -417,7 +457,7 @@ def run_workload(name, args, rank, world, dist, dev, golden, rank_factory=Rank):
         if tj.get("frames") == r.n and tj.get("filtered") == r.filtered and tj.get("workload", "uhd4") == name:
             obj["roofline"]["traffic"] = tj.get("hbm_bytes_per_launch")
             obj["roofline"]["traffic_source"] = f"{tf.relative_to(ROOT)} ({tj.get('tag', tj.get('source', ''))})"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and r.cpu_frames:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and r.cpu_frames:
         secs = args.cpu_seconds if name == args.workload else args.cpu_seconds / 2
         obj["cpu_baseline"] = cpu_baseline(r.cpu_frames, r.filtered, args.cpu_threads or all_cores(), secs,
                                            share=None if args.cpu_threads else cpu_share())
@@ -573,6 +613,30 @@ def reference_cli(dec, files, filtered, threads, per_thread):
                       f"{threads} at a time), {rdt:.1f} s"}
 
 
+def dump_positions(n_bytes: int, s: int, frame: int):
+    """The s sampled byte positions of global frame `frame`'s n_bytes of I420: the frame is cut into s
+    equal strata (the last takes the remainder) and one position is drawn in each from
+    default_rng([DUMP_SEED, frame]) -- increasing, distinct, spread over every plane and MB row."""
+    import numpy as np
+    stride = n_bytes // s
+    return np.arange(s, dtype=np.int64) * stride + np.random.default_rng([DUMP_SEED, frame]).integers(0, stride, size=s)
+
+
+def dump_outputs(r: Rank, out_dir: pathlib.Path, rank: int, world: int) -> None:
+    """--dump-outputs: a seeded sample of the batch's output buffer as the last timed step left it.
+    Frame i of the rank (global index lo + i) contributes the bytes at dump_positions(i420, S, lo + i) of
+    its cropped I420, S = DUMP_VALUES / (frames of all ranks); the result is float32 [frames, S]."""
+    import numpy as np
+    import torch
+    b = r.batch
+    s = max(1, min(b.i420, DUMP_VALUES // (b.n * world)))
+    idx = np.stack([dump_positions(b.i420, s, r.lo + i) for i in range(b.n)])
+    got = torch.gather(b.out.view(b.n, b.frame_bytes), 1, torch.from_numpy(idx).to(b.dev))
+    out_dir.mkdir(parents=True, exist_ok=True)
+    name = "i420_sample.npy" if world == 1 else f"i420_sample_rank{rank}.npy"
+    np.save(out_dir / name, got.cpu().numpy().astype(np.float32))
+
+
 def public(obj: dict) -> dict:
     return {k: v for k, v in obj.items() if not k.startswith("_")}
 
@@ -598,7 +662,9 @@ def main(argv=None):
     r = head["_rank"]
     extra = {}
     enc_obj = e2e = None
-    if world == 1:
+    if args.dump_outputs:
+        dump_outputs(r, pathlib.Path(args.dump_outputs), rank, world)
+    if world == 1 and args.full:
         if args.encode != "none" and r.filtered and r.wl["kind"] == "fixtures":
             enc_obj = encode_object(r, args, manifest, dev)
         threads = args.cpu_threads or cpu_share()
@@ -612,7 +678,7 @@ def main(argv=None):
                     e2e["device_m05_large"] = end_to_end_device(manifest, args.e2e_device_frames, r.filtered, threads)
     del head["_rank"], r
     torch.cuda.empty_cache()
-    if world == 1 and args.extra == "auto":
+    if world == 1 and args.full and args.extra == "auto":
         for name in WORKLOADS:
             if name != args.workload and not WORKLOADS[name].get("diagnostic"):
                 o = run_workload(name, args, rank, world, dist, dev, golden)

@@ -75,7 +75,7 @@ def _worker(rank, world, port, bad, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), STUB_BAD="1" if bad else "0")
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        args = bench.parse(["--gpus", "2", "--steps", "3", "--warmup", "1", "--frames", "8", "--no-cpu-baseline"])
+        args = bench.parse(["--gpus", "2", "--steps", "3", "--warmup", "1", "--frames", "8", "--no-cpu-baseline", "--full"])
         obj = bench.run_workload("uhd4", args, rank, world, dist, torch.device("cpu"), {}, rank_factory=StubRank)
         r = obj.pop("_rank")
         q.put((rank, r.lo, r.hi, r.batch.launches, r.params_agree,
@@ -118,6 +118,40 @@ def test_ranks_detect_bad_digest_and_disagreeing_params():
     assert agree0 and not agree1  # rank 1's own parameter blocks differed from rank 0's ...
     assert p1 == [(100 + i % 3, 50 + i % 3) for i in range(8, 16)]  # ... and were replaced by them
     assert "15/16" in o0["parity"] and o0["parity_ok"] is False
+
+
+def test_plain_run_times_only(monkeypatch):
+    """Without --full the workload is set up, warmed up and timed, the launch status is read, and
+    nothing else runs: no digest pass, no CPU baseline."""
+    def no_digests(self, stream):
+        raise AssertionError("a plain run must not digest the outputs")
+    monkeypatch.setattr(StubBatch, "digests", no_digests)
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: pytest.fail("a plain run must not time the CPU"))
+    args = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2", "--frames", "8"])
+    assert not args.full and args.dump_outputs is None
+    obj = bench.run_workload("uhd4", args, 0, 1, None, torch.device("cpu"), {}, rank_factory=StubRank)
+    r = obj.pop("_rank")
+    assert r.batch.launches == 7  # --warmup 2 + --steps 5
+    assert len(obj["kernel_ms_steps"]) == 5
+    assert obj["frames_total"] == obj["frames_per_gpu"] == 8
+    assert obj["parity"].startswith("not checked") and obj["parity_ok"] and obj["cpu_baseline"] is None
+    assert obj["ms_per_step"] >= 0 and obj["unit"] == "MP/s"
+
+
+def test_full_run_options_select_full():
+    """The driver's plain call stays plain; an option that acts only on the full run selects it (never
+    ignored silently), and every such option keeps its default otherwise."""
+    plain = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", "d", "--workload", "fhd4",
+                         "--frames", "8", "--waves", "8", "--unfiltered"])
+    assert not plain.full
+    assert {k: getattr(plain, k) for k in bench.FULL_DEFAULTS} == bench.FULL_DEFAULTS and not plain.no_cpu_baseline
+    for opt in (["--encode", "ppm"], ["--encode", "png"], ["--e2e-frames", "0"], ["--e2e-device-frames", "64"],
+                ["--extra", "none"], ["--extra", "auto"], ["--no-cpu-baseline"], ["--cpu-threads", "4"],
+                ["--cpu-seconds", "2"], ["--full"]):
+        a = bench.parse(["--gpus", "1"] + opt)
+        assert a.full, opt
+    a = bench.parse(["--encode", "ppm", "--e2e-frames", "0"])
+    assert (a.encode, a.e2e_frames, a.e2e_device_frames, a.extra, a.cpu_seconds) == ("ppm", 0, 1024, "auto", 12.0)
 
 
 def test_world_size_must_match_gpus(monkeypatch):
