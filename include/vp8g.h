@@ -349,6 +349,86 @@ uint64_t vp8g_encode_workspace_size(uint32_t total_spans);
 int vp8g_encode_batch_device(const Vp8gEncDesc* h_descs, const Vp8gEncDesc* d_descs, uint32_t n, const uint8_t* d_src,
                              uint8_t* d_out, uint8_t* d_work, void* hip_stream);
 
+/* ---- Decode to a target size: crop + downscale of I420 on the device --------------------- */
+
+/* libwebp's `use_cropping` / `use_scaling` decoder options (dwebp -crop x y w h -scale w h), bit-exact
+ * to libwebp 1.2.2's rescaler.  All-zero = identity.
+ *   crop    (crop_left, crop_top, crop_w, crop_h), all 0 = the full picture; else w, h >= 1,
+ *           left + w <= width, top + h <= height; left and top are rounded down to even.
+ *   scale   scaled_w x scaled_h; one of them 0 = derived from the other with a ceiling
+ *           (h = (src_h * w + src_w - 1) / src_w over the cropped size); both 0 = crop only.
+ * DOWNSCALE ONLY: scaled_w <= the (cropped) width and scaled_h <= the (cropped) height, else EINVAL
+ * (libwebp's bilinear expand path is not implemented).
+ * The output is I420: luma scaled to the target, each chroma plane independently from
+ * ceil(window / 2) to ceil(target / 2).  RGB of a scaled picture is DEFINED as the encoder
+ * (vp8g_encode_batch_device, fancy upsampling) run on that scaled I420 -- deliberately not
+ * `dwebp -ppm -scale`, which rescales chroma straight to luma resolution and skips the fancy
+ * upsampler. */
+typedef struct {
+	uint32_t crop_left, crop_top, crop_w, crop_h;
+	uint32_t scaled_w, scaled_h;
+	uint32_t flags; /* VP8G_SCALE_* */
+} Vp8gScaleOpt;
+
+/* A `filtered` request follows libwebp's rule per frame: when scaling, the loop filter is skipped
+ * if scaled_w < width * 3 / 4 and scaled_h < height * 3 / 4 (integer products, the full picture
+ * size), so the output equals `dwebp -yuv -scale`.  Without the flag, filtered means filtered. */
+#define VP8G_SCALE_DWEBP_FILTER 1u
+
+/* One plane of a scale descriptor: W x H source window -> w x h, and how the launch tiles it (a
+ * workgroup task = tile_w output columns x run_h output rows). 80 bytes. */
+typedef struct {
+	uint64_t src;                    /* byte offset of the window's first sample in the source buffer */
+	uint64_t dst;                    /* byte offset of the plane in the output buffer */
+	uint32_t src_stride, dst_stride;
+	uint32_t src_w, src_h, dst_w, dst_h;
+	uint32_t fx, fy, fxy;            /* 2^32 / w, 2^32 / h, h * 2^32 / (W * H) (0 if >= 2^32) */
+	uint32_t group;                  /* lanes sharing one output column (power of two, <= 64) */
+	uint32_t tile_w, run_h;          /* output columns (256 / group) and output rows per task */
+	uint32_t tiles_x, ntasks;        /* tasks per row of tiles; tasks of the plane */
+	uint32_t pitch, block_rows;      /* LDS staging: bytes per source row segment, rows per block */
+} Vp8gScalePlane;
+
+/* Per-image descriptor of the scale kernel (built by vp8g_make_scale_desc).  272 bytes. */
+typedef struct {
+	uint32_t width, height;          /* output size */
+	uint32_t task0, ntasks;          /* this image's workgroup tasks in the launch */
+	uint32_t src_width, src_height;  /* the picture the options were resolved against */
+	uint32_t crop_left, crop_top;    /* resolved (even) window origin */
+	Vp8gScalePlane p[3];             /* Y, U, V */
+} Vp8gScaleDesc;
+
+/* The output size `opt` gives for a width x height picture.  0, or -1 + EINVAL (NULL argument,
+ * bad crop, upscale in either dimension, picture beyond 16383 x 16383). */
+int vp8g_scaled_size(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, uint32_t* out_w, uint32_t* out_h);
+
+/* Fill the descriptor of one width x height image whose planes sit at src_* (strides stride_*) in
+ * the source buffer; the scaled I420 (Y, U, V back to back, strides = row widths) goes to
+ * dst_offset of the output buffer, its tasks start at task0.  0, or -1 + EINVAL. */
+int vp8g_make_scale_desc(uint32_t width, uint32_t height, uint64_t src_y, uint64_t src_u, uint64_t src_v,
+                         uint32_t stride_y, uint32_t stride_uv, const Vp8gScaleOpt* opt, uint64_t dst_offset,
+                         uint32_t task0, Vp8gScaleDesc* out);
+
+/* Scale n images of mixed sizes (device-resident source planes -> scaled I420 in d_dst) in one
+ * launch on `hip_stream`.  h_descs / d_descs: host and device copies of the descriptors (tasks
+ * numbered image by image).  Writes only the images' own bytes.  Asynchronous; 0 or -1 + errno
+ * (EINVAL for inconsistent descriptors, EIO on a launch failure).  d_dst may feed
+ * vp8g_encode_batch_device on the same stream with no host copy in between. */
+int vp8g_scale_batch_device(const Vp8gScaleDesc* h_descs, const Vp8gScaleDesc* d_descs, uint32_t n, const uint8_t* d_src,
+                            uint8_t* d_dst, void* hip_stream);
+
+/* Single image: upload src, scale on the device, download into *out (yuv420_alloc layout; the
+ * caller frees it with yuv420_free).  0, or -1 + errno (EINVAL, ENOMEM, EIO). */
+int yuv420_rescale(const Yuv420Image* src, const Vp8gScaleOpt* opt, Yuv420Image* out);
+
+/* vp8g_decode_webp_batch_ex to a target size: each chunk is reconstructed as there, scaled on the
+ * device into a second, small buffer, and only that is downloaded; outs[i] has the scaled size.
+ * opts: n_opts = 1 (one option for every frame) or n (opts[i] for frame i).  `filtered` is applied
+ * per frame (VP8G_SCALE_DWEBP_FILTER).  A frame whose options are invalid for its size gets
+ * status[i] = EINVAL; the others still decode. */
+int vp8g_decode_webp_batch_scaled(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                  const Vp8gScaleOpt* opts, uint32_t n_opts, Yuv420Image* outs, int* status);
+
 /* Name of the last HIP error seen by this library in the calling thread ("" if none). */
 const char* vp8g_last_error(void);
 
@@ -363,7 +443,8 @@ const char* vp8g_last_error(void);
 #define VP8G_MODE_SPLIT_PARTS 16u /* each frame over several workgroups */
 uint32_t vp8g_last_launch_mode(void);
 
-/* ABI version of this header (bumped on any layout change). */
+/* ABI version of this header (bumped on any layout change; the scale API above is purely
+ * additive -- new symbols and structures, no existing layout touched -- and keeps 5). */
 #define VP8G_ABI_VERSION 5
 uint32_t vp8g_abi_version(void);
 

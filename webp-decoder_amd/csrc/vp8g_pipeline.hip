@@ -229,6 +229,7 @@ struct Slot {
 	bool busy = false;
 	std::vector<uint32_t> frames;  // frame indices of the chunk (packed data freed when the slot is reused)
 	std::vector<Vp8gFrameDesc> descs;
+	std::vector<Vp8gScaleDesc> sdescs;  // scaled decode: one per frame of the chunk
 	std::vector<Vp8gTokFrame> jobs;  // device m05
 	uint32_t status = 0;
 	std::vector<D2H> d2h;          // the chunk's downloads (issued by a Copier)
@@ -307,7 +308,7 @@ struct Copier {
 
 struct ChunkLayout {
 	uint64_t ym, uvm, seg, hasc, bm, masks, mboff, vals, cy, cu, cv, cy2, bits, jobs, desc, status, gctx, mbox, gprog, out,
-	    total;
+	    sdesc, sout, total;
 };
 
 hipError_t grow(Slot& s, size_t need) {
@@ -393,12 +394,16 @@ VP8G_API int vp8g_plan_batch(const ByteSpan* files, uint32_t n, uint32_t threads
 	return 0;
 }
 
-VP8G_API int vp8g_decode_webp_batch_ex(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
-                                       Yuv420Image* outs, int* status) {
+// vp8g_decode_webp_batch_ex, and with `opts` (n_opts = 1 or n) vp8g_decode_webp_batch_scaled: each
+// chunk's frames are then cropped / downscaled on the device (vp8g_scale.hip) from the chunk's
+// reconstruction buffer into a second, small one, and only that is downloaded.
+static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                        const Vp8gScaleOpt* opts, uint32_t n_opts, Yuv420Image* outs, int* status) {
 	if (!files || !outs || n == 0 || (flags & ~(VP8G_BATCH_DEVICE_M05 | VP8G_BATCH_MULTI_PARTITION))) {
 		errno = EINVAL;
 		return -1;
 	}
+	auto opt_of = [&](uint32_t i) -> const Vp8gScaleOpt* { return opts ? &opts[n_opts == 1 ? 0 : i] : nullptr; };
 	const bool tok = (flags & VP8G_BATCH_DEVICE_M05) != 0;
 	uint32_t chunk_frames_pk = kChunkFrames, chunk_frames_tok = kTokChunkFrames;
 	if (const char* e = getenv("VP8G_CHUNK_FRAMES")) {  // test knob: smaller chunks
@@ -486,6 +491,14 @@ VP8G_API int vp8g_decode_webp_batch_ex(const ByteSpan* files, uint32_t n, int fi
 	};
 	auto kf_of = [&](uint32_t i) -> const Vp8KeyFrameHeader& { return feed.dev[i] ? feed.tj[i].kf : feed.pk[i].kf; };
 	auto f_of = [&](uint32_t i) -> const Vp8DecodedFrame& { return feed.dev[i] ? feed.tj[i].hdr : feed.pk[i].f; };
+	// scaled decode: the loop filter per frame (VP8G_SCALE_DWEBP_FILTER), the output image at the scaled size
+	auto filtered_of = [&](uint32_t i) -> int {
+		return opts ? vp8f_scale_filtered(kf_of(i).width, kf_of(i).height, opt_of(i), filtered) : filtered;
+	};
+	auto alloc_out = [&](uint32_t i, uint32_t w, uint32_t h) -> int {
+		if (opts && vp8g_scaled_size(w, h, opt_of(i), &w, &h) != 0) return -1;
+		return vp8g::alloc_planes(&outs[i], w, h, false);
+	};
 	auto finish_slot = [&](Slot& s) -> bool {  // wait for a slot's chunk; false on a device failure
 		if (!s.busy) return true;
 		s.busy = false;
@@ -545,7 +558,7 @@ VP8G_API int vp8g_decode_webp_batch_ex(const ByteSpan* files, uint32_t n, int fi
 			// -- gather the next chunk: consecutive positions of one kind (device m05 or host m05),
 			// in order, as they finish
 			std::vector<uint32_t> idx;
-			uint64_t mbs = 0, vals = 0, bitsb = 0, outb = 0;
+			uint64_t mbs = 0, vals = 0, bitsb = 0, outb = 0, soutb = 0;
 			uint32_t b = a, max_cols = 0, max_rows = 0;
 			const bool ctok = feed.dev[feed.order[a]] != 0;  // this chunk's kind
 			const uint32_t cframes = ctok ? chunk_frames_tok : chunk_frames_pk;
@@ -553,9 +566,13 @@ VP8G_API int vp8g_decode_webp_batch_ex(const ByteSpan* files, uint32_t n, int fi
 			while (b < n && b - a < cframes && (feed.dev[feed.order[b]] != 0) == ctok) {
 				const uint32_t fi = feed.order[b];
 				feed.wait_ready(fi);
+				uint32_t sw = 0, sh = 0;
+				if (feed.err[fi] == 0 && opts && vp8g_scaled_size(kf_of(fi).width, kf_of(fi).height, opt_of(fi), &sw, &sh) != 0)
+					feed.err[fi] = EINVAL;  // options that do not fit this frame: the others still decode
 				if (feed.err[fi] == 0) {
 					const Vp8DecodedFrame& f = f_of(fi);
 					if (!idx.empty() && mbs + f.mb_total > cmbs) break;
+					if (opts) soutb = al256(soutb + vp8g_i420_size(sw, sh));
 					idx.push_back(fi);
 					mbs += f.mb_total;
 					if (ctok) bitsb += bits_slot(feed.tj[fi].psize);
@@ -608,6 +625,8 @@ VP8G_API int vp8g_decode_webp_batch_ex(const ByteSpan* files, uint32_t n, int fi
 			L.mbox = o, o = al256(o + (k_plan > 1 ? (uint64_t)nf * k_plan * max_cols * vp8g::kCtxBytesPerCol : 0));
 			L.gprog = o, o = al256(o + (k_plan > 1 ? (uint64_t)nf * k_plan * 4 : 0));
 			L.out = o, o = al256(o + outb);
+			L.sdesc = o, o = al256(o + (opts ? nf * sizeof(Vp8gScaleDesc) : 0));
+			L.sout = o, o = al256(o + soutb);
 			L.total = o;
 			const double tg = trace ? ms_now() : 0.0;
 			PTRY(grow(s, L.total), "hipMalloc(chunk)");
@@ -620,8 +639,8 @@ VP8G_API int vp8g_decode_webp_batch_ex(const ByteSpan* files, uint32_t n, int fi
 				uint64_t mo = 0, bo = 0, oo = 0;
 				for (uint32_t j = 0; j < nf; j++) {
 					TokJob& t = feed.tj[idx[j]];
-					if (vp8g::make_desc(&t.kf, &t.hdr, filtered, mo, oo, &s.descs[j], false) != 0 ||
-					    vp8g::alloc_planes(&outs[idx[j]], t.kf.width, t.kf.height, false) != 0) {
+					if (vp8g::make_desc(&t.kf, &t.hdr, filtered_of(idx[j]), mo, oo, &s.descs[j], false) != 0 ||
+					    alloc_out(idx[j], t.kf.width, t.kf.height) != 0) {
 						feed.err[idx[j]] = errno ? errno : EINVAL;  // (cannot happen for a frame the header parse accepted)
 						s.descs[j].flags = 0;
 					}
@@ -639,8 +658,8 @@ VP8G_API int vp8g_decode_webp_batch_ex(const ByteSpan* files, uint32_t n, int fi
 				uint64_t mo = 0, vo = 0, oo = 0;
 				for (uint32_t j = 0; j < nf; j++) {
 					Vp8gPackedFrame& p = feed.pk[idx[j]];
-					if (vp8g::make_desc(&p.kf, &p.f, filtered, mo, oo, &s.descs[j], false) != 0 ||
-					    vp8g::alloc_planes(&outs[idx[j]], p.kf.width, p.kf.height, false) != 0) {
+					if (vp8g::make_desc(&p.kf, &p.f, filtered_of(idx[j]), mo, oo, &s.descs[j], false) != 0 ||
+					    alloc_out(idx[j], p.kf.width, p.kf.height) != 0) {
 						feed.err[idx[j]] = errno ? errno : EINVAL;  // (cannot happen for a frame m05 accepted)
 						s.descs[j].flags = 0;
 					}
@@ -718,10 +737,53 @@ VP8G_API int vp8g_decode_webp_batch_ex(const ByteSpan* files, uint32_t n, int fi
 					     "recon launch");
 				PTRY(gate.done(k > 1), "hipEventRecord(gate)");
 			}
+			// -- scaled decode: crop / downscale the chunk's frames into the small buffer (same stream)
+			s.sdescs.clear();
+			if (opts) {
+				uint64_t so = 0;
+				uint32_t task0 = 0;
+				std::vector<uint32_t> sj;  // chunk position of each scale descriptor
+				for (uint32_t j = 0; j < nf; j++) {
+					const Vp8gFrameDesc& fd = s.descs[j];
+					if (!outs[idx[j]].y) continue;  // (a frame that failed above)
+					Vp8gScaleDesc sd;
+					if (vp8g_make_scale_desc(fd.width, fd.height, L.out + fd.out_y, L.out + fd.out_u, L.out + fd.out_v, fd.stride_y,
+					                         fd.stride_uv, opt_of(idx[j]), L.sout + so, task0, &sd) != 0) {
+						feed.err[idx[j]] = EINVAL;  // (cannot happen: the options were resolved when the chunk was gathered)
+						continue;
+					}
+					s.sdescs.push_back(sd);
+					sj.push_back(j);
+					task0 += sd.ntasks;
+					so = al256(so + vp8g_i420_size(sd.width, sd.height));
+				}
+				if (!s.sdescs.empty()) {
+					PTRY(hipMemcpyAsync(d + L.sdesc, s.sdescs.data(), s.sdescs.size() * sizeof(Vp8gScaleDesc), hipMemcpyHostToDevice,
+					                    stream),
+					     "H2D");
+					if (vp8g_scale_batch_device(s.sdescs.data(), (const Vp8gScaleDesc*)(d + L.sdesc), (uint32_t)s.sdescs.size(), d, d,
+					                            stream) != 0) {
+						he = hipGetLastError();
+						if (he == hipSuccess) he = hipErrorInvalidValue;
+						where = "scale launch";
+						goto fail;
+					}
+				}
+				PTRY(hipEventRecord(s.kdone, stream), "event");
+				s.d2h.clear();
+				for (size_t q = 0; q < s.sdescs.size(); q++) {
+					const Vp8gScaleDesc& sd = s.sdescs[q];
+					Yuv420Image& img = outs[idx[sj[q]]];
+					const size_t ysz = (size_t)sd.width * sd.height, uvsz = (size_t)sd.p[1].dst_w * sd.p[1].dst_h;
+					s.d2h.push_back({img.y, d + sd.p[0].dst, ysz});
+					s.d2h.push_back({img.u, d + sd.p[1].dst, uvsz});
+					s.d2h.push_back({img.v, d + sd.p[2].dst, uvsz});
+				}
+			}
 			// -- D2H into the callers' images, by this kind's Copier once the kernels are done
-			PTRY(hipEventRecord(s.kdone, stream), "event");
-			s.d2h.clear();
-			for (uint32_t j = 0; j < nf; j++) {
+			if (!opts) PTRY(hipEventRecord(s.kdone, stream), "event");
+			if (!opts) s.d2h.clear();
+			for (uint32_t j = 0; j < nf && !opts; j++) {
 				const Vp8gFrameDesc& fd = s.descs[j];
 				Yuv420Image& img = outs[idx[j]];
 				if (!img.y) continue;
@@ -800,6 +862,20 @@ fail:
 	errno = EIO;
 	return -1;
 #undef PTRY
+}
+
+VP8G_API int vp8g_decode_webp_batch_ex(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                       Yuv420Image* outs, int* status) {
+	return decode_batch(files, n, filtered, threads, flags, nullptr, 0, outs, status);
+}
+
+VP8G_API int vp8g_decode_webp_batch_scaled(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                           const Vp8gScaleOpt* opts, uint32_t n_opts, Yuv420Image* outs, int* status) {
+	if (!opts || (n_opts != 1 && n_opts != n)) {
+		errno = EINVAL;
+		return -1;
+	}
+	return decode_batch(files, n, filtered, threads, flags, opts, n_opts, outs, status);
 }
 
 VP8G_API int vp8g_decode_webp_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, Yuv420Image* outs,

@@ -1,0 +1,326 @@
+// vp8g_scale.hip -- crop + downscale of I420 on the device, bit-exact to libwebp 1.2.2's rescaler
+// (include/vp8g.h: vp8g_scale_batch_device, yuv420_rescale; host restatement host/vp8_scale.c;
+// DESIGN.md §14).
+//
+// libwebp's rescaler is a sequential import/export loop, but its result has a closed form: with
+// E(k) = ceil(k W / w) and F(j) = ceil(j H / h) (all values wrapping u32),
+//
+//   frow(y, k) = (carry + sum of s[y][x], x in [E(k), E(k+1))) * w - s[y][E(k+1)-1] * (E(k+1) w - (k+1) W)
+//                carry = k > 0 ? MULT(s[y][E(k)-1] * (E(k) w - k W), fx) : 0
+//   out(j, k)  = MULT(irow - FLOOR(frow(F(j+1)-1, k), ys), fxy)        ys = fy * (F(j+1) h - (j+1) H)
+//                irow = FLOOR(frow(F(j)-1, k), ys0) + sum of frow(y, k), y in [F(j), F(j+1))
+//
+// so every output sample depends only on its own source footprint plus one boundary row and column.
+//
+// One launch scales a batch of images of mixed sizes.  A workgroup task is one plane's tile of
+// tile_w output columns x run_h output rows.  It walks the source rows of its run top to bottom
+// (one extra row above when the run does not start the plane: the boundary row F(j0) - 1), staged
+// through LDS in blocks of block_rows row segments loaded with 16-byte loads (the next block is in
+// flight in registers while the current one is summed).  `group` lanes share an output column
+// (each sums every group-th sample of the footprint, combined by a butterfly of lane exchanges), so
+// a 17:1 and a 16383:1 reduction keep the lanes as busy as a 1:1 one; each lane keeps its column's
+// irow in a register and lane 0 of the group emits a sample at every F(j+1) boundary.
+#include <errno.h>
+#include <string.h>
+
+#include <mutex>
+
+#include "../host/vp8_front.h"
+#include "vp8g_device.h"
+
+#define VP8G_API extern "C" __attribute__((visibility("default")))
+
+namespace {
+
+constexpr uint32_t kThreads = 256;
+constexpr uint32_t kBufBytes = 16448;  // LDS staging: one 16383-sample row segment at any alignment
+constexpr uint32_t kBufChunks = kBufBytes / 16u;
+constexpr uint32_t kMaxChunks = (kBufChunks + kThreads - 1u) / kThreads;  // 16-B loads per thread and block
+constexpr uint32_t kRunSrcRows = 64;   // source rows per task (about): 1 / 64 of the rows is read twice
+constexpr uint32_t kLanePerCol = 12;   // footprint samples per lane before another lane joins the column
+constexpr uint32_t kMaxDim = 16383;
+static_assert(kBufBytes % 16 == 0 && kBufBytes >= kMaxDim + 30, "staging buffer");
+
+__device__ __forceinline__ uint32_t mult_fix(uint32_t x, uint32_t y) { return __umulhi(x, y) + ((x * y) >> 31); }
+__device__ __forceinline__ uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1u) / b; }
+
+__global__ __launch_bounds__(kThreads) void scale_kernel(const Vp8gScaleDesc* __restrict__ descs, uint32_t n,
+                                                         const uint8_t* __restrict__ src, uint8_t* __restrict__ dst) {
+	__shared__ __attribute__((aligned(16))) uint8_t lds[kBufBytes];
+	const uint32_t task = blockIdx.x, tid = threadIdx.x;
+	// the image that owns this task (tasks are numbered image by image), then its plane
+	uint32_t lo = 0, hi = n - 1u;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi + 1u) >> 1;
+		if (descs[mid].task0 <= task) lo = mid;
+		else hi = mid - 1u;
+	}
+	const Vp8gScaleDesc& D = descs[lo];
+	uint32_t t = task - D.task0;
+	if (task < D.task0 || t >= D.ntasks) return;
+	uint32_t pi = 0;
+	while (pi < 2u && t >= D.p[pi].ntasks) t -= D.p[pi].ntasks, pi++;
+	const Vp8gScalePlane& P = D.p[pi];
+	const uint32_t W = P.src_w, H = P.src_h, w = P.dst_w, h = P.dst_h;
+	const uint32_t fx = P.fx, fy = P.fy, fxy = P.fxy;
+	const uint32_t G = P.group, pitch = P.pitch, R = P.block_rows, sstride = P.src_stride;
+	if (t >= P.ntasks || G == 0 || (G & (G - 1u)) || G > 64u || P.tile_w * G != kThreads || P.tiles_x == 0) return;
+	const uint32_t tx = t % P.tiles_x, ry = t / P.tiles_x;
+
+	// -- columns: the tile's source segment [xs, xe) and this lane's footprint [e0, e1)
+	const uint32_t k0 = tx * P.tile_w, kend = min(k0 + P.tile_w, w);
+	const uint32_t j0 = ry * P.run_h, j1 = min(j0 + P.run_h, h);
+	if (k0 >= w || j0 >= h) return;
+	const uint32_t xs = k0 ? ceil_div(k0 * W, w) - 1u : 0u;  // E(k0) - 1: the first column's carry sample
+	const uint32_t xe = ceil_div(kend * W, w);                // E(kend) <= W
+	const uint32_t span = xe - xs;
+	if (span + 15u > pitch || (pitch & 15u) || R == 0 || (uint64_t)pitch * R > kBufBytes) return;  // (never: see make_plane)
+	const uint32_t gi = tid & (G - 1u), k = k0 + tid / G;
+	const bool active = k < kend;
+	uint32_t e0 = xs, e1 = xs, a0 = 0, a1 = 0;
+	if (active) {
+		e0 = ceil_div(k * W, w), e1 = ceil_div((k + 1u) * W, w);
+		a0 = e0 * w - k * W, a1 = e1 * w - (k + 1u) * W;
+	}
+	const bool carry_in = active && k > 0;
+
+	// -- rows: source rows [y_first, y_last); with j0 > 0 the first one is the boundary row F(j0) - 1
+	const bool boundary = j0 > 0;
+	const uint32_t Fj0 = ceil_div(j0 * H, h);
+	const uint32_t y_first = boundary ? Fj0 - 1u : 0u, y_last = ceil_div(j1 * H, h);
+	const uint32_t ys0 = fy * (Fj0 * h - j0 * H);
+
+	// -- staging: row r of a block sits at r * pitch, its segment starting at byte (address & 15)
+	const uintptr_t base = (uintptr_t)src + P.src;  // the window's first sample
+	const uintptr_t ok_lo = base, ok_hi = base + (uintptr_t)(H - 1u) * sstride + W;  // the window's own bytes
+	const uint32_t cpr = pitch >> 4;
+	uint32_t ch_r[kMaxChunks], ch_c[kMaxChunks];
+#pragma unroll
+	for (uint32_t m = 0; m < kMaxChunks; m++) {
+		const uint32_t q = tid + m * kThreads;
+		ch_r[m] = q / cpr, ch_c[m] = q % cpr;
+	}
+	uint4 pre[kMaxChunks];
+	auto load_block = [&](uint32_t yb, uint32_t nr) {
+#pragma unroll
+		for (uint32_t m = 0; m < kMaxChunks; m++) {
+			pre[m] = make_uint4(0, 0, 0, 0);
+			if (ch_r[m] >= nr) continue;
+			const uintptr_t row = base + (uintptr_t)(yb + ch_r[m]) * sstride + xs;  // first wanted byte
+			const uintptr_t a = (row & ~(uintptr_t)15) + 16u * ch_c[m];
+			if (a >= row + span) continue;  // past the segment
+			if (a >= ok_lo && a + 16u <= ok_hi) {
+				pre[m] = *(const uint4*)a;
+			} else {  // a chunk that straddles the window's first or last byte: only the bytes inside
+				uint32_t v[4] = {0, 0, 0, 0};
+				for (uint32_t b = 0; b < 16u; b++)
+					if (a + b >= ok_lo && a + b < ok_hi) v[b >> 2] |= (uint32_t)(*(const uint8_t*)(a + b)) << (8u * (b & 3u));
+				pre[m] = make_uint4(v[0], v[1], v[2], v[3]);
+			}
+		}
+	};
+	auto store_block = [&](uint32_t nr) {
+#pragma unroll
+		for (uint32_t m = 0; m < kMaxChunks; m++)
+			if (ch_r[m] < nr) *(uint4*)(lds + ch_r[m] * pitch + 16u * ch_c[m]) = pre[m];
+	};
+
+	// F(j+1) and ya = F(j+1) h - (j+1) H step without a divide: H = qH h + rH, and from one output row to
+	// the next F grows by qH (+ 1 when rH exceeds what the last row left over)
+	const uint32_t qH = H / h, rH = H - qH * h;
+	uint32_t irow = 0, j = j0, nextF = ceil_div((j0 + 1u) * H, h);
+	uint32_t ya = nextF * h - (j0 + 1u) * H;
+	uint8_t* out = dst + P.dst + k;
+	load_block(y_first, min(R, y_last - y_first));
+	for (uint32_t yb = y_first; yb < y_last; yb += R) {
+		const uint32_t nr = min(R, y_last - yb);
+		__syncthreads();  // the previous block has been summed
+		store_block(nr);
+		__syncthreads();
+		if (yb + R < y_last) load_block(yb + R, min(R, y_last - (yb + R)));  // in flight while this block is summed
+		for (uint32_t r = 0; r < nr; r++) {
+			const uint32_t y = yb + r;
+			const uint32_t mis = (uint32_t)((base + (uintptr_t)y * sstride + xs) & 15u);
+			const uint8_t* row = lds + r * pitch + mis - xs;  // row[x] = s[y][x] for x in [xs, xe)
+			uint32_t part = 0;
+			for (uint32_t x = e0 + gi; x < e1; x += G) part += row[x];
+			for (uint32_t o = G >> 1; o; o >>= 1) part += __shfl_xor(part, (int)o);
+			uint32_t frow = 0;
+			if (active) {
+				// (24-bit multiplies: samples < 2^8, a0 / a1 / w < 2^14, a row sum < 2^22)
+				const uint32_t carry = carry_in ? mult_fix(__umul24(row[e0 - 1u], a0), fx) : 0u;
+				frow = __umul24(carry + part, w) - __umul24(row[e1 - 1u], a1);
+			}
+			if (boundary && y == y_first) {  // the row shared with the run above: only its lower part
+				irow = ys0 ? __umulhi(frow, ys0) : 0u;
+				continue;
+			}
+			irow += frow;
+			if (y + 1u != nextF) continue;
+			const uint32_t ys = fy * ya;
+			const uint32_t frac = ys ? __umulhi(frow, ys) : 0u;
+			uint32_t v;
+			if (fxy) {
+				const int32_t sv = (int32_t)mult_fix(irow - frac, fxy);
+				v = sv > 255 ? 255u : (uint32_t)sv & 255u;
+			} else {
+				v = irow & 255u;  // (W == 1 and h == H: the sums are the samples)
+			}
+			if (active && gi == 0) out[(size_t)j * P.dst_stride] = (uint8_t)v;
+			irow = frac;
+			j++;
+			if (rH > ya) nextF += qH + 1u, ya = h - (rH - ya);
+			else nextF += qH, ya -= rH;
+		}
+	}
+}
+
+// One plane's descriptor: factors and tiling.
+void make_plane(Vp8gScalePlane* p, uint64_t src, uint32_t sstride, uint32_t W, uint32_t H, uint64_t dst, uint32_t w,
+                uint32_t h) {
+	memset(p, 0, sizeof(*p));
+	p->src = src, p->dst = dst, p->src_stride = sstride, p->dst_stride = w;
+	p->src_w = W, p->src_h = H, p->dst_w = w, p->dst_h = h;
+	vp8f_scale_factors(W, H, w, h, &p->fx, &p->fy, &p->fxy);
+	uint32_t g = 1;
+	while (g < 64u && (uint64_t)W > (uint64_t)kLanePerCol * g * w) g *= 2u;
+	p->group = g;
+	p->tile_w = kThreads / g;
+	p->tiles_x = (w + p->tile_w - 1u) / p->tile_w;
+	const uint32_t rh = (uint32_t)((uint64_t)kRunSrcRows * h / H);
+	p->run_h = rh ? rh : 1u;
+	p->ntasks = p->tiles_x * ((h + p->run_h - 1u) / p->run_h);
+	// a tile's source segment: E(k0 + tile_w) - E(k0) + 1 <= ceil(tile_w W / w) + 1 samples, at most W
+	const uint64_t sp = ((uint64_t)p->tile_w * W + w - 1u) / w + 2u;
+	const uint32_t span = sp < W ? (uint32_t)sp : W;
+	p->pitch = (span + 30u) & ~15u;  // + up to 15 bytes of misalignment, in whole 16-B chunks
+	p->block_rows = kBufBytes / p->pitch;
+}
+
+bool plane_ok(const Vp8gScalePlane& p) {
+	return p.src_w && p.src_h && p.dst_w && p.dst_h && p.dst_w <= p.src_w && p.dst_h <= p.src_h && p.src_w <= kMaxDim &&
+	       p.src_h <= kMaxDim && p.src_stride >= p.src_w && p.dst_stride >= p.dst_w && p.group && !(p.group & (p.group - 1u)) &&
+	       p.group <= 64u && p.tile_w * p.group == kThreads && p.run_h && p.tiles_x == (p.dst_w + p.tile_w - 1u) / p.tile_w &&
+	       p.ntasks == p.tiles_x * ((p.dst_h + p.run_h - 1u) / p.run_h) && !(p.pitch & 15u) && p.block_rows &&
+	       (uint64_t)p.pitch * p.block_rows <= kBufBytes &&
+	       (((uint64_t)p.tile_w * p.src_w + p.dst_w - 1u) / p.dst_w + 2u + 15u <= p.pitch || p.src_w + 15u <= p.pitch);
+}
+
+}  // namespace
+
+VP8G_API int vp8g_scaled_size(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, uint32_t* out_w, uint32_t* out_h) {
+	Vp8fScaleGeom g;
+	if (!out_w || !out_h) {
+		errno = EINVAL;
+		return -1;
+	}
+	if (vp8f_scale_resolve(width, height, opt, &g) != 0) return -1;
+	*out_w = g.out_w, *out_h = g.out_h;
+	return 0;
+}
+
+VP8G_API int vp8g_make_scale_desc(uint32_t width, uint32_t height, uint64_t src_y, uint64_t src_u, uint64_t src_v,
+                                  uint32_t stride_y, uint32_t stride_uv, const Vp8gScaleOpt* opt, uint64_t dst_offset,
+                                  uint32_t task0, Vp8gScaleDesc* d) {
+	Vp8fScaleGeom g;
+	if (!d || vp8f_scale_resolve(width, height, opt, &g) != 0 || stride_y < width || stride_uv < (width + 1u) / 2u) {
+		errno = EINVAL;
+		return -1;
+	}
+	memset(d, 0, sizeof(*d));
+	d->width = g.out_w, d->height = g.out_h;
+	d->src_width = width, d->src_height = height, d->crop_left = g.left, d->crop_top = g.top;
+	const uint32_t cw = (g.win_w + 1u) / 2u, ch = (g.win_h + 1u) / 2u, ocw = (g.out_w + 1u) / 2u, och = (g.out_h + 1u) / 2u;
+	const uint64_t co = (uint64_t)(g.top / 2u) * stride_uv + g.left / 2u;
+	const uint64_t ysz = (uint64_t)g.out_w * g.out_h, csz = (uint64_t)ocw * och;
+	make_plane(&d->p[0], src_y + (uint64_t)g.top * stride_y + g.left, stride_y, g.win_w, g.win_h, dst_offset, g.out_w, g.out_h);
+	make_plane(&d->p[1], src_u + co, stride_uv, cw, ch, dst_offset + ysz, ocw, och);
+	make_plane(&d->p[2], src_v + co, stride_uv, cw, ch, dst_offset + ysz + csz, ocw, och);
+	d->task0 = task0;
+	d->ntasks = d->p[0].ntasks + d->p[1].ntasks + d->p[2].ntasks;
+	return 0;
+}
+
+VP8G_API int vp8g_scale_batch_device(const Vp8gScaleDesc* h, const Vp8gScaleDesc* d_descs, uint32_t n, const uint8_t* d_src,
+                                     uint8_t* d_dst, void* stream) {
+	if (!h || !d_descs || !d_src || !d_dst || n == 0) {
+		errno = EINVAL;
+		return -1;
+	}
+	uint64_t total = 0;
+	for (uint32_t i = 0; i < n; i++) {
+		const Vp8gScaleDesc& d = h[i];
+		if (d.task0 != total || d.ntasks == 0 || d.ntasks != (uint64_t)d.p[0].ntasks + d.p[1].ntasks + d.p[2].ntasks ||
+		    !plane_ok(d.p[0]) || !plane_ok(d.p[1]) || !plane_ok(d.p[2])) {  // tasks must be numbered image by image
+			errno = EINVAL;
+			return -1;
+		}
+		total += d.ntasks;
+		if (total > 0x7FFFFFFFu) {
+			errno = EINVAL;
+			return -1;
+		}
+	}
+	vp8g::GateScope gate((hipStream_t)stream);  // (vp8g_device.h: no cross-workgroup launch beside it)
+	hipError_t e = gate.status();
+	if (e == hipSuccess) {
+		hipLaunchKernelGGL(scale_kernel, dim3((uint32_t)total), dim3(kThreads), 0, (hipStream_t)stream, d_descs, n, d_src, d_dst);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = gate.done(false);
+	if (e != hipSuccess) {
+		vp8g::set_error_text("scale launch", e);
+		errno = EIO;
+		return -1;
+	}
+	return 0;
+}
+
+VP8G_API int yuv420_rescale(const Yuv420Image* img, const Vp8gScaleOpt* opt, Yuv420Image* out) {
+	if (!img || !opt || !out || !img->y || !img->u || !img->v || img->width == 0 || img->height == 0 ||
+	    img->stride_y < img->width || img->stride_uv < (img->width + 1u) / 2u) {
+		errno = EINVAL;
+		return -1;
+	}
+	const uint32_t w = img->width, h = img->height, cw = (w + 1u) / 2u, ch = (h + 1u) / 2u;
+	const uint64_t ysz = (uint64_t)w * h, csz = (uint64_t)cw * ch;
+	const uint64_t o_desc = (ysz + 2 * csz + 255u) & ~255ull, o_out = o_desc + 512u;
+	Vp8gScaleDesc desc;
+	if (vp8g_make_scale_desc(w, h, 0, ysz, ysz + csz, w, cw, opt, o_out, 0, &desc) != 0) return -1;
+	memset(out, 0, sizeof(*out));
+	if (vp8g::alloc_planes(out, desc.width, desc.height, false) != 0) return -1;
+	const uint32_t ow = desc.width, oh = desc.height, ocw = (ow + 1u) / 2u, och = (oh + 1u) / 2u;
+	const uint64_t oysz = (uint64_t)ow * oh, ocsz = (uint64_t)ocw * och;
+	hipStream_t s = nullptr;
+	uint8_t* b = nullptr;
+	const char* where = "stream";
+	hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+	if (e == hipSuccess) where = "hipMalloc", e = hipMalloc((void**)&b, o_out + oysz + 2 * ocsz + 16u);
+	if (e == hipSuccess) {
+		where = "H2D";
+		if ((e = hipMemcpy2DAsync(b, w, img->y, img->stride_y, w, h, hipMemcpyHostToDevice, s)) == hipSuccess &&
+		    (e = hipMemcpy2DAsync(b + ysz, cw, img->u, img->stride_uv, cw, ch, hipMemcpyHostToDevice, s)) == hipSuccess &&
+		    (e = hipMemcpy2DAsync(b + ysz + csz, cw, img->v, img->stride_uv, cw, ch, hipMemcpyHostToDevice, s)) == hipSuccess)
+			e = hipMemcpyAsync(b + o_desc, &desc, sizeof(desc), hipMemcpyHostToDevice, s);
+	}
+	int rc = 0;
+	if (e == hipSuccess) rc = vp8g_scale_batch_device(&desc, (const Vp8gScaleDesc*)(b + o_desc), 1, b, b, s);
+	if (e == hipSuccess && rc == 0) {
+		where = "D2H";
+		if ((e = hipMemcpyAsync(out->y, b + o_out, oysz, hipMemcpyDeviceToHost, s)) == hipSuccess &&
+		    (e = hipMemcpyAsync(out->u, b + o_out + oysz, ocsz, hipMemcpyDeviceToHost, s)) == hipSuccess &&
+		    (e = hipMemcpyAsync(out->v, b + o_out + oysz + ocsz, ocsz, hipMemcpyDeviceToHost, s)) == hipSuccess)
+			where = "sync", e = hipStreamSynchronize(s);
+	}
+	if (s && e != hipSuccess) (void)hipStreamSynchronize(s);
+	if (b) (void)hipFree(b);
+	if (s) (void)hipStreamDestroy(s);
+	if (e != hipSuccess || rc != 0) {
+		const int en = e != hipSuccess ? EIO : errno;
+		if (e != hipSuccess) vp8g::set_error_text(where, e);
+		yuv420_free(out);
+		errno = en;
+		return -1;
+	}
+	return 0;
+}

@@ -5,6 +5,13 @@
  *   decoder -info <file.webp>
  *   decoder -yuv  <file.webp> <out.i420>    recon only            (m06 on the GPU)
  *   decoder -yuvf <file.webp> <out.i420>    recon + loop filter   (m06 + m07 on the GPU)
+ *   decoder -yuv|-yuvf [-crop x y w h] [-scale w h] <file.webp> <out.i420>
+ *                                           the same, cropped and / or downscaled on the GPU as
+ *                                           libwebp does (dwebp -yuv [-crop] [-scale]; a -scale
+ *                                           dimension of 0 is derived from the other; downscale only).
+ *                                           With -scale, -yuvf follows libwebp's rule and skips the loop
+ *                                           filter when both dimensions shrink below 3/4, so the file
+ *                                           equals dwebp's.  Other modes take neither option (usage).
  *   decoder -ppm  <file.webp> <out.ppm>     recon + loop filter + RGB (m08 writer, on the GPU)
  *   decoder -png  <file.webp> <out.png>     recon + loop filter + RGB (m09 writer, on the GPU)
  *   decoder -diff_mb <file.webp> <oracle.i420>   per-macroblock SAD of our -yuv vs a file
@@ -30,6 +37,7 @@ static void usage(void) {
 	fputs("  decoder -info <file.webp>\n", stderr);
 	fputs("  decoder -yuv <file.webp> <out.i420>\n", stderr);
 	fputs("  decoder -yuvf <file.webp> <out.i420>\n", stderr);
+	fputs("  decoder -yuv|-yuvf [-crop x y w h] [-scale w h] <file.webp> <out.i420>\n", stderr);
 	fputs("  decoder -ppm <file.webp> <out.ppm>\n", stderr);
 	fputs("  decoder -png <file.webp> <out.png>\n", stderr);
 	fputs("  decoder -diff_mb <file.webp> <oracle.i420>\n", stderr);
@@ -60,11 +68,20 @@ static int front(const char* path, Vp8KeyFrameHeader* kf, Vp8DecodedFrame* d) {
 	return -1;
 }
 
-static int cmd_yuv(const char* in, const char* out_path, int filtered) {
+static int cmd_yuv(const char* in, const char* out_path, int filtered, const Vp8gScaleOpt* opt) {
 	Vp8KeyFrameHeader kf;
 	Vp8DecodedFrame d;
 	if (front(in, &kf, &d) != 0) return 1;
 	Yuv420Image img;
+	if (opt) {
+		Vp8fScaleGeom g;
+		if (vp8f_scale_resolve(kf.width, kf.height, opt, &g) != 0) {
+			fputs("error: bad -crop / -scale for this picture (the crop must lie inside it; downscale only)\n", stderr);
+			vp8_decoded_frame_free(&d);
+			return 1;
+		}
+		filtered = vp8f_scale_filtered(kf.width, kf.height, opt, filtered);
+	}
 	int rc = filtered ? vp8_reconstruct_keyframe_yuv_filtered(&kf, &d, &img) : vp8_reconstruct_keyframe_yuv(&kf, &d, &img);
 	vp8_decoded_frame_free(&d);
 	if (rc != 0) {
@@ -72,6 +89,18 @@ static int cmd_yuv(const char* in, const char* out_path, int filtered) {
 		const char* he = vp8g_last_error();
 		if (he && *he) fprintf(stderr, "  (%s)\n", he);
 		return 1;
+	}
+	if (opt) {
+		Yuv420Image small;
+		rc = yuv420_rescale(&img, opt, &small);
+		yuv420_free(&img);
+		if (rc != 0) {
+			fputs("error: crop / rescale failed\n", stderr);
+			const char* he = vp8g_last_error();
+			if (he && *he) fprintf(stderr, "  (%s)\n", he);
+			return 1;
+		}
+		img = small;
 	}
 	int fd = open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
 	if (fd < 0) {
@@ -206,11 +235,34 @@ int main(int argc, char** argv) {
 		return cmd_info(argv[2]);
 	}
 	if (!strcmp(cmd, "-yuv") || !strcmp(cmd, "-yuvf")) {
-		if (argc != 4) {
+		if (argc == 4) return cmd_yuv(argv[2], argv[3], cmd[4] == 'f', NULL);
+		/* [-crop x y w h] [-scale w h] before the two file names */
+		Vp8gScaleOpt opt;
+		memset(&opt, 0, sizeof(opt));
+		opt.flags = VP8G_SCALE_DWEBP_FILTER;
+		int a = 2, seen = 0;
+		while (a < argc - 2) {
+			uint32_t v[4];
+			const int is_crop = !strcmp(argv[a], "-crop"), nv = is_crop ? 4 : 2;
+			if ((!is_crop && strcmp(argv[a], "-scale")) || (seen & (is_crop ? 1 : 2)) || a + nv >= argc - 2) break;
+			int ok = 1;
+			for (int i = 0; i < nv; i++) {
+				char* end = NULL;
+				const unsigned long x = strtoul(argv[a + 1 + i], &end, 10);
+				if (argv[a + 1 + i][0] < '0' || argv[a + 1 + i][0] > '9' || *end || x > 0xFFFFFFu) ok = 0;
+				v[i] = (uint32_t)x;
+			}
+			if (!ok) break;
+			if (is_crop) opt.crop_left = v[0], opt.crop_top = v[1], opt.crop_w = v[2], opt.crop_h = v[3];
+			else opt.scaled_w = v[0], opt.scaled_h = v[1];
+			seen |= is_crop ? 1 : 2;
+			a += 1 + nv;
+		}
+		if (!seen || a != argc - 2) {
 			usage();
 			return 2;
 		}
-		return cmd_yuv(argv[2], argv[3], cmd[4] == 'f');
+		return cmd_yuv(argv[a], argv[a + 1], cmd[4] == 'f', &opt);
 	}
 	if (!strcmp(cmd, "-ppm") || !strcmp(cmd, "-png")) {
 		if (argc != 4) {

@@ -78,6 +78,39 @@ int vp8f_token_header_memory(const uint8_t* data, size_t size, Vp8KeyFrameHeader
 int vp8f_synth_frame(uint32_t width, uint32_t height, uint64_t seed, int profile, Vp8KeyFrameHeader* kf,
                      Vp8DecodedFrame* out);
 
+/* ---- crop + downscale of I420, bit-exact to libwebp's rescaler (vp8_scale.c) ------------- */
+
+/* A Vp8gScaleOpt (include/vp8g.h) resolved against a width x height picture: the luma window
+ * (origin snapped down to even) and the output size.  The chroma window starts at
+ * (left / 2, top / 2) and is ceil(win / 2) in size; chroma is scaled to ceil(out / 2). */
+typedef struct {
+	uint32_t left, top, win_w, win_h;
+	uint32_t out_w, out_h;
+	uint32_t scaling; /* a target size was given (else crop only) */
+} Vp8fScaleGeom;
+
+/* libwebp's rules: a crop needs w, h >= 1 and left + w <= width, top + h <= height (with the
+ * caller's values); a target dimension of 0 is derived from the other with a ceiling
+ * (h = (win_h * w + win_w - 1) / win_w), both 0 = no scaling.  Downscale only: a target larger
+ * than the window in either dimension, a picture beyond 16383 x 16383, unknown flags or a NULL
+ * argument give -1 + EINVAL. */
+int vp8f_scale_resolve(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, Vp8fScaleGeom* g);
+
+/* Whether a `filtered` request runs the loop filter for this picture.  With
+ * VP8G_SCALE_DWEBP_FILTER libwebp's rule applies: when scaling, the filter is skipped if
+ * out_w < width * 3 / 4 and out_h < height * 3 / 4 (the full picture, not the crop). */
+int vp8f_scale_filtered(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, int filtered);
+
+/* The rescaler's three fixed-point factors of one plane W x H -> w x h. */
+void vp8f_scale_factors(uint32_t W, uint32_t H, uint32_t w, uint32_t h, uint32_t* fx, uint32_t* fy, uint32_t* fxy);
+
+/* Crop + downscale a width x height I420 image (plane pointers and strides) into the
+ * destination planes, which must hold the resolved output size.  Sequential; reentrant.
+ * 0, or -1 + errno (EINVAL, ENOMEM). */
+int vp8f_scale_i420(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint32_t stride_y, uint32_t stride_uv,
+                    uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, uint8_t* dy, uint8_t* du, uint8_t* dv,
+                    uint32_t dstride_y, uint32_t dstride_uv);
+
 /* FNV-1a 64 over a byte buffer (same constants as reference vp8_tokens.c:15-27). */
 uint64_t vp8f_fnv1a64(const void* data, size_t n, uint64_t h);
 

@@ -1,0 +1,160 @@
+/*
+ * vp8_scale.c -- crop + downscale of an I420 image, bit-exact to libwebp 1.2.2's rescaler
+ * (the `use_cropping` / `use_scaling` decoder options, `dwebp -crop x y w h -scale w h`, and
+ * WebPPictureRescale for 4:2:0 pictures).
+ *
+ * This is the sequential host restatement: the CPU path, and the checker of the device kernel
+ * (csrc/vp8g_scale.hip, which evaluates the same sums in closed form).  It is written from the
+ * rescaler's arithmetic as DESIGN.md §14 states it: per plane W x H -> w x h (w <= W, h <= H),
+ * every value a wrapping uint32_t,
+ *
+ *   fx = 2^32 / w, fy = 2^32 / h, fxy = (h * 2^32) / (W * H)   (0 when it does not fit 32 bits)
+ *   MULT(x, y) = (x * y + 2^31) >> 32, FLOOR(x, y) = (x * y) >> 32       (64-bit products)
+ *
+ * a source row is imported into w horizontal sums (each source sample split between the two
+ * outputs it straddles, the split carried through MULT(., fx)), imported rows accumulate, and an
+ * output row is exported whenever the vertical accumulator runs out, the straddling row split
+ * with FLOOR(., fy * remainder) and the total scaled by MULT(., fxy).
+ *
+ * Luma is scaled from the (cropped) window to the target size, each chroma plane from
+ * ceil(window / 2) to ceil(target / 2), independently.  Only shrinking (or identity) is
+ * implemented; libwebp's bilinear expand path is out of scope (EINVAL).
+ */
+#include <errno.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "vp8_front.h"
+
+#define SCALE_MAX_DIM 16383u /* VP8's 14-bit frame size; keeps every product below 2^28 */
+
+static uint32_t mult_fix(uint32_t x, uint32_t y) { return (uint32_t)(((uint64_t)x * y + (1ull << 31)) >> 32); }
+static uint32_t mult_floor(uint32_t x, uint32_t y) { return (uint32_t)(((uint64_t)x * y) >> 32); }
+
+int vp8f_scale_resolve(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, Vp8fScaleGeom* g) {
+	if (!opt || !g || width == 0 || height == 0 || width > SCALE_MAX_DIM || height > SCALE_MAX_DIM ||
+	    (opt->flags & ~VP8G_SCALE_DWEBP_FILTER))
+		goto bad;
+	{
+		uint32_t left = 0, top = 0, ww = width, wh = height;
+		if (opt->crop_left | opt->crop_top | opt->crop_w | opt->crop_h) {
+			/* libwebp's rules: the size as given, the origin snapped down to even; the bounds
+			 * are checked with the caller's own values */
+			if (opt->crop_w == 0 || opt->crop_h == 0 || (uint64_t)opt->crop_left + opt->crop_w > width ||
+			    (uint64_t)opt->crop_top + opt->crop_h > height)
+				goto bad;
+			left = opt->crop_left & ~1u, top = opt->crop_top & ~1u;
+			ww = opt->crop_w, wh = opt->crop_h;
+		}
+		uint32_t ow = opt->scaled_w, oh = opt->scaled_h;
+		if (ow == 0 && oh == 0) {
+			ow = ww, oh = wh; /* crop only */
+		} else if (ow == 0) {
+			if (oh > wh) goto bad;
+			ow = (uint32_t)(((uint64_t)ww * oh + wh - 1u) / wh);
+		} else if (oh == 0) {
+			if (ow > ww) goto bad;
+			oh = (uint32_t)(((uint64_t)wh * ow + ww - 1u) / ww);
+		}
+		if (ow == 0 || oh == 0 || ow > ww || oh > wh) goto bad; /* downscale only */
+		g->left = left, g->top = top, g->win_w = ww, g->win_h = wh, g->out_w = ow, g->out_h = oh;
+		g->scaling = (opt->scaled_w | opt->scaled_h) != 0;
+		return 0;
+	}
+bad:
+	errno = EINVAL;
+	return -1;
+}
+
+int vp8f_scale_filtered(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, int filtered) {
+	Vp8fScaleGeom g;
+	if (!filtered) return 0;
+	if (!opt || !(opt->flags & VP8G_SCALE_DWEBP_FILTER) || vp8f_scale_resolve(width, height, opt, &g) != 0 || !g.scaling)
+		return 1;
+	/* libwebp: the full picture size, integer products, strict inequalities */
+	return !(g.out_w < width * 3u / 4u && g.out_h < height * 3u / 4u);
+}
+
+void vp8f_scale_factors(uint32_t W, uint32_t H, uint32_t w, uint32_t h, uint32_t* fx, uint32_t* fy, uint32_t* fxy) {
+	const uint64_t ratio = ((uint64_t)h << 32) / ((uint64_t)W * H);
+	*fx = (uint32_t)((1ull << 32) / w);
+	*fy = (uint32_t)((1ull << 32) / h);
+	*fxy = (ratio >> 32) ? 0u : (uint32_t)ratio;
+}
+
+/* work: 2 * w words */
+static void scale_plane(const uint8_t* s, uint32_t ss, uint32_t W, uint32_t H, uint8_t* d, uint32_t ds, uint32_t w,
+                        uint32_t h, uint32_t* work) {
+	uint32_t fx, fy, fxy;
+	vp8f_scale_factors(W, H, w, h, &fx, &fy, &fxy);
+	uint32_t* irow = work;
+	uint32_t* frow = work + w;
+	memset(irow, 0, (size_t)w * sizeof(uint32_t));
+	int32_t y_accum = (int32_t)H;
+	uint32_t dy = 0;
+	for (uint32_t y = 0; y < H && dy < h; y++) {
+		/* import: horizontal sums of one source row */
+		const uint8_t* src = s + (size_t)y * ss;
+		uint32_t x_in = 0, sum = 0;
+		int32_t accum = 0;
+		for (uint32_t k = 0; k < w; k++) {
+			uint32_t base = 0;
+			accum += (int32_t)W;
+			while (accum > 0) {
+				accum -= (int32_t)w;
+				base = src[x_in++];
+				sum += base;
+			}
+			const uint32_t frac = base * (uint32_t)(-accum);
+			frow[k] = sum * w - frac;
+			sum = mult_fix(frac, fx);
+		}
+		for (uint32_t k = 0; k < w; k++) irow[k] += frow[k];
+		y_accum -= (int32_t)h;
+		if (y_accum > 0) continue;
+		/* export one output row */
+		uint8_t* dst = d + (size_t)dy * ds;
+		const uint32_t yscale = fy * (uint32_t)(-y_accum);
+		if (fxy == 0) { /* W == 1 and h == H: the sums are the samples */
+			for (uint32_t k = 0; k < w; k++) dst[k] = (uint8_t)irow[k], irow[k] = 0;
+		} else if (yscale) {
+			for (uint32_t k = 0; k < w; k++) {
+				const uint32_t frac = mult_floor(frow[k], yscale);
+				const int32_t v = (int32_t)mult_fix(irow[k] - frac, fxy);
+				dst[k] = v > 255 ? 255u : (uint8_t)v;
+				irow[k] = frac;
+			}
+		} else {
+			for (uint32_t k = 0; k < w; k++) {
+				const int32_t v = (int32_t)mult_fix(irow[k], fxy);
+				dst[k] = v > 255 ? 255u : (uint8_t)v;
+				irow[k] = 0;
+			}
+		}
+		y_accum += (int32_t)H;
+		dy++;
+	}
+}
+
+int vp8f_scale_i420(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint32_t stride_y, uint32_t stride_uv,
+                    uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, uint8_t* dy, uint8_t* du, uint8_t* dv,
+                    uint32_t dstride_y, uint32_t dstride_uv) {
+	Vp8fScaleGeom g;
+	if (!y || !u || !v || !dy || !du || !dv || vp8f_scale_resolve(width, height, opt, &g) != 0 || stride_y < width ||
+	    stride_uv < (width + 1u) / 2u || dstride_y < g.out_w || dstride_uv < (g.out_w + 1u) / 2u) {
+		errno = EINVAL;
+		return -1;
+	}
+	uint32_t* work = (uint32_t*)malloc((size_t)2 * g.out_w * sizeof(uint32_t));
+	if (!work) {
+		errno = ENOMEM;
+		return -1;
+	}
+	const uint32_t cw = (g.win_w + 1u) / 2u, ch = (g.win_h + 1u) / 2u, ocw = (g.out_w + 1u) / 2u, och = (g.out_h + 1u) / 2u;
+	const size_t co = (size_t)(g.top / 2u) * stride_uv + g.left / 2u;
+	scale_plane(y + (size_t)g.top * stride_y + g.left, stride_y, g.win_w, g.win_h, dy, dstride_y, g.out_w, g.out_h, work);
+	scale_plane(u + co, stride_uv, cw, ch, du, dstride_uv, ocw, och, work);
+	scale_plane(v + co, stride_uv, cw, ch, dv, dstride_uv, ocw, och, work);
+	free(work);
+	return 0;
+}

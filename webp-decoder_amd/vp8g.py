@@ -128,6 +128,30 @@ class Vp8gTokFrame(C.Structure):
                 ("part_off", C.c_uint32 * 8), ("part_end", C.c_uint32 * 8), ("reserved2", C.c_uint32 * 3)]
 
 
+class Vp8gScaleOpt(C.Structure):
+    """include/vp8g.h: crop window + target size (libwebp's use_cropping / use_scaling); all-zero = identity."""
+    _fields_ = [(n, C.c_uint32) for n in ("crop_left", "crop_top", "crop_w", "crop_h", "scaled_w", "scaled_h", "flags")]
+
+
+class Vp8gScalePlane(C.Structure):
+    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64)] + [(n, C.c_uint32) for n in (
+        "src_stride", "dst_stride", "src_w", "src_h", "dst_w", "dst_h", "fx", "fy", "fxy", "group", "tile_w", "run_h",
+        "tiles_x", "ntasks", "pitch", "block_rows")]
+
+
+class Vp8gScaleDesc(C.Structure):
+    """include/vp8g.h: per-image descriptor of the scale kernel (vp8g_make_scale_desc)."""
+    _fields_ = [(n, C.c_uint32) for n in ("width", "height", "task0", "ntasks", "src_width", "src_height", "crop_left",
+                                          "crop_top")] + [("p", Vp8gScalePlane * 3)]
+
+
+class Vp8fScaleGeom(C.Structure):
+    """host/vp8_front.h: a Vp8gScaleOpt resolved against a picture size."""
+    _fields_ = [(n, C.c_uint32) for n in ("left", "top", "win_w", "win_h", "out_w", "out_h", "scaling")]
+
+
+VP8G_SCALE_DWEBP_FILTER = 1
+
 PK_BLOCKS = 25  # per MB: Y 0..15, U 0..3, V 0..3, Y2
 VP8G_BATCH_DEVICE_M05 = 1
 VP8G_BATCH_MULTI_PARTITION = 2
@@ -144,6 +168,9 @@ assert C.sizeof(Vp8DecodedFrame) == 320
 assert C.sizeof(Yuv420Image) == 40
 assert C.sizeof(Vp8gFrameDesc) == 176
 assert C.sizeof(Vp8gTokFrame) == 1296
+assert C.sizeof(Vp8gScaleOpt) == 28
+assert C.sizeof(Vp8gScalePlane) == 80
+assert C.sizeof(Vp8gScaleDesc) == 272
 
 VP8G_F_LOOPFILTER = 1
 VP8G_F_SIMPLE = 2
@@ -217,6 +244,10 @@ def host_lib():
                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int),
                                                  C.c_uint]
         lib.vp8f_packed_free.restype = None
+        lib.vp8f_scale_resolve.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(Vp8gScaleOpt), C.POINTER(Vp8fScaleGeom)]
+        lib.vp8f_scale_filtered.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(Vp8gScaleOpt), C.c_int]
+        lib.vp8f_scale_i420.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                        C.POINTER(Vp8gScaleOpt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         lib._typed = True
     return lib
 
@@ -267,6 +298,14 @@ def gpu_lib():
                                                   P(Yuv420Image), P(C.c_int)]
         lib.vp8g_m05_batch_device.argtypes = [P(Vp8gTokFrame), C.c_void_p, C.c_uint32, C.c_void_p,
                                               P(Vp8gBatchArrays), C.c_void_p]
+        lib.vp8g_scaled_size.argtypes = [C.c_uint32, C.c_uint32, P(Vp8gScaleOpt), P(C.c_uint32), P(C.c_uint32)]
+        lib.vp8g_make_scale_desc.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                             C.c_uint32, P(Vp8gScaleOpt), C.c_uint64, C.c_uint32, P(Vp8gScaleDesc)]
+        lib.vp8g_scale_batch_device.argtypes = [P(Vp8gScaleDesc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]
+        lib.yuv420_rescale.argtypes = [P(Yuv420Image), P(Vp8gScaleOpt), P(Yuv420Image)]
+        lib.vp8g_decode_webp_batch_scaled.argtypes = [P(ByteSpan), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
+                                                      P(Vp8gScaleOpt), C.c_uint32, P(Yuv420Image), P(C.c_int)]
         lib._typed = True
     return lib
 
@@ -457,6 +496,81 @@ def gpu_decode_webp_batch(files: list[bytes], filtered: bool = True, threads: in
     out = []
     for i in range(n):
         out.append(_image_bytes(imgs[i]) if st[i] == 0 else None)
+        lib.yuv420_free(C.byref(imgs[i]))
+    return out, list(st)
+
+
+def scale_opt(crop=None, scale=None, dwebp_filter: bool = False) -> Vp8gScaleOpt:
+    """Vp8gScaleOpt from crop = (left, top, w, h) or None and scale = (w, h) or None (0 = derived)."""
+    c = crop or (0, 0, 0, 0)
+    s = scale or (0, 0)
+    return Vp8gScaleOpt(c[0], c[1], c[2], c[3], s[0], s[1], VP8G_SCALE_DWEBP_FILTER if dwebp_filter else 0)
+
+
+def scaled_size(w: int, h: int, opt: Vp8gScaleOpt):
+    """vp8f_scale_resolve: the output (w, h) of `opt` on a w x h picture; ValueError if invalid."""
+    g = Vp8fScaleGeom()
+    if host_lib().vp8f_scale_resolve(w, h, C.byref(opt), C.byref(g)) != 0:
+        raise ValueError(f"invalid scale options for {w}x{h}")
+    return int(g.out_w), int(g.out_h)
+
+
+def host_scale(i420: bytes, w: int, h: int, opt: Vp8gScaleOpt):
+    """vp8f_scale_i420 (the sequential CPU restatement of libwebp's rescaler) on cropped I420 bytes:
+    (scaled I420 bytes, out_w, out_h)."""
+    ow, oh = scaled_size(w, h, opt)
+    a = np.frombuffer(i420, dtype=np.uint8)
+    assert a.size == i420_size(w, h)
+    cw, ch, ocw, och = (w + 1) // 2, (h + 1) // 2, (ow + 1) // 2, (oh + 1) // 2
+    out = np.empty(i420_size(ow, oh), dtype=np.uint8)
+    sb, ob = a.ctypes.data, out.ctypes.data
+    if host_lib().vp8f_scale_i420(sb, sb + w * h, sb + w * h + cw * ch, w, cw, w, h, C.byref(opt), ob, ob + ow * oh,
+                                  ob + ow * oh + ocw * och, ow, ocw) != 0:
+        raise RuntimeError(f"vp8f_scale_i420 failed: errno={C.get_errno()}")
+    return out.tobytes(), ow, oh
+
+
+def gpu_scale(i420: bytes, w: int, h: int, opt: Vp8gScaleOpt):
+    """yuv420_rescale through libvp8g.so (upload, the HIP scale kernel, download):
+    (scaled I420 bytes, out_w, out_h)."""
+    lib = gpu_lib()
+    img, keep = image_from_i420(i420, w, h)
+    out = Yuv420Image()
+    if lib.yuv420_rescale(C.byref(img), C.byref(opt), C.byref(out)) != 0:
+        raise RuntimeError(f"yuv420_rescale failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
+    del keep
+    try:
+        return _image_bytes(out), int(out.width), int(out.height)
+    finally:
+        lib.yuv420_free(C.byref(out))
+
+
+def gpu_decode_webp_batch_scaled(files: list[bytes], scale, filtered: bool = True, threads: int = 0,
+                                 device_m05: bool = False, multi_partition: bool = False):
+    """vp8g_decode_webp_batch_scaled: .webp images decoded, cropped / downscaled on the device and only
+    the small I420 downloaded.  scale: one Vp8gScaleOpt for every frame, or a list of one per frame.
+    Returns (list of (I420 bytes, w, h) or None, list of errno)."""
+    lib = gpu_lib()
+    n = len(files)
+    bufs = [(C.c_uint8 * max(1, len(b))).from_buffer_copy(b if b else b"\0") for b in files]
+    spans = (ByteSpan * n)(*[ByteSpan(C.cast(bufs[i], C.POINTER(C.c_uint8)), len(files[i])) for i in range(n)])
+    opts = list(scale) if isinstance(scale, (list, tuple)) else [scale]
+    c_opts = (Vp8gScaleOpt * len(opts))(*opts)
+    imgs = (Yuv420Image * n)()
+    st = (C.c_int * n)()
+    import time
+    t0 = time.perf_counter()
+    rc = lib.vp8g_decode_webp_batch_scaled(spans, n, int(filtered), threads,
+                                           (VP8G_BATCH_DEVICE_M05 if device_m05 else 0)
+                                           | (VP8G_BATCH_MULTI_PARTITION if multi_partition else 0), c_opts, len(opts),
+                                           imgs, st)
+    gpu_decode_webp_batch_scaled.seconds = time.perf_counter() - t0  # the C call alone
+    en = C.get_errno()
+    if rc != 0 and (all(s == 5 for s in st) or not any(st)):  # EIO: device failure; or the call itself refused
+        raise RuntimeError(f"vp8g_decode_webp_batch_scaled failed: errno={en} {lib.vp8g_last_error()!r}")
+    out = []
+    for i in range(n):
+        out.append((_image_bytes(imgs[i]), int(imgs[i].width), int(imgs[i].height)) if st[i] == 0 else None)
         lib.yuv420_free(C.byref(imgs[i]))
     return out, list(st)
 
