@@ -15,18 +15,19 @@
 // by quarter h -- rec[c] at step c + 2h, lf[c - 1] at the same step -- and read by quarter h + 1 two
 // steps later).  Between quads (waves): quarter 3's entries go to device memory (one region of
 // ctx_cols x 160 B per frame, the snapshot buffer; write-through stores), and quarter 0's lanes
-// 0..9 load the entries of the row above (L1-bypassing loads) into ring 0: early in the step that
-// uses them, after its side info (VP8G_CTX_EARLY, round 6) or, in round 5, one step ahead.
-// Progress t means steps < t are visible.  Round 5 published it at the end of step t, after
-// `s_waitcnt vmcnt(16)` (every operation older than this step's 16 -- step t - 1's context stores
-// among them -- acknowledged); round 6 publishes the same value inside step t, right after issuing
-// the next step's prefetch, after vmcnt(5) (only that prefetch may be pending; VP8G_PUB_AT);
-// after the last step vmcnt(0) and T.
+// 0..9 load the entries of the row above (L1-bypassing loads) into ring 0 early in the step that
+// uses them, right after its side info.
+// Progress t means steps < t are visible.  Step t publishes it right after issuing the next step's
+// prefetch, behind `s_waitcnt vmcnt(5)`: only those five loads may be pending, so every older
+// operation -- step t - 1's context stores among them -- is acknowledged.  After the last step:
+// vmcnt(0) and T.
 // The quad below needs rec[t + 1] and lf[t] of this quad's quarter 3 (written at step t + 7) when it
-// issues its loads early in step t, so it waits for progress >= t + 8 (one step ahead: rec[t + 2],
-// lf[t + 1], progress >= t + 9).
+// issues its loads early in step t, so it waits for progress >= t + 8.
 // Frames: loop-filtered or unfiltered, with whole 16-B / 8-B row pieces (frame_kernel's fl_fast
 // condition; quad_supported() on the host), no loop-filter-only frames.
+// The placements and layouts that were measured against these (publish and context-load timing,
+// prefetch depth, LDS bank shift, B_PRED register hand-off, store pairing and cache policy) are in
+// DESIGN.md §3.2, "Retired experiment code".
 
 // Loop filter of one lane's luma line and chroma line (quads: role 0 is always luma, role 1 always
 // chroma, so each runs only its own edges -- frame_kernel's lanes mix both and the chroma lanes issue
@@ -113,112 +114,28 @@ DEV void lf_mb_chroma(const LfLine& L, bool en, bool mb_v, bool mb_h, bool inner
 	wave_lds_sync();
 }
 
-// Paired pixel stores (whole-piece batches; bit 1: role 0's luma rows, bit 2: both roles' chroma
-// rows): a lane keeps its piece of an even MB column for one step, and at the odd column the lanes
-// l and l ^ 1 (same piece column) trade halves, so that one store instruction writes each of the
-// two rows as two adjacent pieces -- 32 B of luma / 16 B of chroma from two lanes instead of two
-// 16-B / 8-B pieces a step apart.
-#ifndef VP8G_QPAIR
-#define VP8G_QPAIR 3
-#endif
-#ifndef VP8G_QPAIR_GENERAL  // (the general instantiation pairs its vector-stored pieces too)
-#define VP8G_QPAIR_GENERAL 1
-#endif
-constexpr int kQVmemPerStep = 13;
-#ifndef VP8G_CSPLIT  // chroma iDCT (full form) split over lane pairs (l, l + 8)
-#define VP8G_CSPLIT 1
-#endif
-#ifndef VP8G_CSPLIT_PRED  // chroma whole-block prediction split over the same lane pairs (rows 0, 1 / 2, 3)
-#define VP8G_CSPLIT_PRED 1
-#endif
-// LDS banks of the loop filter's byte gathers (verdict r05 #3): a 32-lane group holds two quarters, and
-// 16 tile rows at the 8-B-aligned 40-B pitch cover the 16 even banks whatever the quarter offset, so
-// the two quarters' rows meet 2-way.  VP8G_TSHIFT = 4 moves the filter tiles of the odd quarters 4 B
-// (one bank) along -- into the tiles' own padding -- so they take the odd banks; their 8-B row reads
-// and writes then go as dword pairs (ld2x32 / st2x32), and the tables' tile offsets get the shift added.
-// Measured (profiles/r06_ab_log.json r06g): conflict share 0.175 -> 0.072, LDS busy -11 %, but uhd4
-// +0.5 %, synth +0.4 % (the extra address VALU outweighs it: VALU binds), so the default is 0.
-#ifndef VP8G_TSHIFT
-#define VP8G_TSHIFT 0
-#endif
-DEV uint32_t tsh(int h) { return (uint32_t)(h & 1) * (uint32_t)VP8G_TSHIFT; }
-DEV u32x2 ld2x32(const uint8_t* p) {
-	if constexpr (VP8G_TSHIFT % 8 != 0) return u32x2{ld32(p), ld32(p + 4)};
-	else return ld64(p);
-}
-DEV void st2x32(uint8_t* p, u32x2 v) {
-	if constexpr (VP8G_TSHIFT % 8 != 0) st32(p, v.x), st32(p + 4, v.y);
-	else st64(p, v);
-}
-// Where a step publishes its progress: 0 = at its end, one step late (progress t after vmcnt(16): every
-// operation of step t - 1 acknowledged); 1 = right after it issues the next step's prefetch
-// (vmcnt(5)), 2 = before its loop filter (vmcnt(6): the prefetch and the context load pending) -- the
-// same promise (steps < t visible), made part of a step earlier, at the price of waiting on step t - 1's
-// stores sooner.  A/B on three boxes (profiles/r06_ab_log.json r06l, r06m, r06n): 1 = synth -1.7..-2.7 %,
-// uhd4 -0.1..-0.3 %, fhd4 -0.6..+0.6 %; 2 = synth -1.5..-2.2 %, uhd4 +-0, fhd4 -1.0 %.
-#ifndef VP8G_PUB_AT
-#define VP8G_PUB_AT 1
-#endif
-// The row above's context for step t (rec[t + 1], lf[t] of the quad above's quarter 3): 0 = loaded one
-// step ahead, after step t - 1's residual and a wait for progress >= t + 9 (round 5); 1 = loaded at the
-// top of step t itself, after a wait for progress >= t + 8, and put into ring 0 after the residual (an
-// L2 hit, hidden behind the residual): the quad below trails by one step less, and when it waits, it
-// waits before its residual instead of after it.  A/B on two boxes (profiles/r06_ab_log.json r06o, r06p):
-// uhd4 -0.5 / -0.6 %, synth -0.1 / -0.4 %, fhd4 -0.9 / -1.3 %.  2 = the progress word read at the
-// step's top and the wait (entered only if that value is short) + the load after the side info, so the
-// poll's LDS round trip overlaps the side-info permutes (r06s2, r06t2: +-0 .. -1.2 %, never worse).
-#ifndef VP8G_CTX_EARLY
-#define VP8G_CTX_EARLY 2
-#endif
-// Where the next step's prefetch is issued (and, with VP8G_PUB_AT = 1, the progress published right
-// after it): 0 = after the residual's iDCT, 1 = right after the dequantisation (the coefficients' last
-// use), the iWHT and the iDCT's time earlier.
-#ifndef VP8G_PREF_EARLY
-#define VP8G_PREF_EARLY 0
-#endif
-// Quarter 3's three context stores issued before the step's pixel stores instead of after them; the
-// publish then waits only for them (vmcnt counts in issue order): vmcnt(5 + 1 + the pixel stores)
-// instead of vmcnt(5).
-#ifndef VP8G_CTX_FIRST
-#define VP8G_CTX_FIRST 0
-#endif
-// Role 1's luma store (tile rows 16..19, final only in a frame's last MB row) skipped by a wave-uniform
-// branch when no lane has a piece (most steps): the store's 1 KB of lane data no longer passes the
-// TA -> TCP data path, which the stores keep stalled ~19 % of the kernel's cycles (r06lat).  The
-// step's vector-memory count then varies; the publish's vmcnt(5) counts only the prefetch issued after
-// the previous step's stores, so it stays exact (VP8G_CTX_FIRST, which counts the stores, excludes it).
-#ifndef VP8G_Y1_SKIP
-#define VP8G_Y1_SKIP 0
-#endif
-// The coefficient prefetch two steps ahead instead of one (a second 17-VGPR set, rotated each step):
-// the loads of step t + 1 then complete before step t's publish, which waits for step t - 1's stores
-// anyway, instead of being waited for at the top of step t + 1.
-#ifndef VP8G_PREF2
-#define VP8G_PREF2 0
-#endif
-#ifndef VP8G_WPRED_Y  // luma whole-block predictor with the mode's masks from bits of the mode
-#define VP8G_WPRED_Y 1
-#endif
-// B_PRED's wavefront with the sub-block edges handed over in registers (verdict r05 #1): a finished
-// sub-block's bottom row and right column are packed into dwords by DPP reductions over its 16 lanes
-// and broadcast back (row_newbcast), and the other group's values cross quarters with
-// v_permlane16_swap; the MB's own edges are read from LDS once, before the wavefront.  LDS keeps only
-// the tile writes and the next MB's left column.  Bit-exact, but slower (profiles/r06_ab_log.json r06h:
-// uhd4 +3.5 %, synth +5.3 %, fhd4 +3.3 %; compact path alone +1.1 / +4.7 / +1.7 %): the packing and
-// broadcasts add ~11 VALU per wavefront step (static +248 VALU, -88 LDS over both paths), and the VALU,
-// not the LDS round trip the other waves hide, is what binds.  Off by default.
-#ifndef VP8G_BP_REG  // bit 0: the compact path (<= 2 B_PRED MBs per wave), bit 1: three or four
-#define VP8G_BP_REG 0
-#endif
-template <int CTRL>
-DEV uint32_t dpp_u(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false); }
+// Paired pixel stores (role 0's luma rows and both roles' chroma rows, in both instantiations): a
+// lane keeps its piece of an even MB column for one step, and at the odd column the lanes l and
+// l ^ 1 (same piece column) trade halves, so that one store instruction writes each of the two rows
+// as two adjacent pieces -- 32 B of luma / 16 B of chroma from two lanes instead of two 16-B / 8-B
+// pieces a step apart.
+//
+// A step's vector-memory operations, in issue order (vmcnt counts in issue order, and the step loop's
+// `s_waitcnt vmcnt(N)` are written against this list): the context load (1, after the side info), the
+// next step's prefetch (5, after the residual), the pixel stores (7: role 0's luma as two paired
+// stores, role 1's luma, four paired chroma) and quarter 3's context stores (3): 16 in all.  The
+// single stores of a last column come on top, in few steps; more operations in flight only make a
+// wait stricter than it has to be.
+constexpr int kQPrefLoads = 5;
+constexpr int kQStoresPerStep = 7 + 3;
+// Cache policy of the pixel stores: write-through (sc1).  With 32-B luma / 16-B chroma pieces a
+// write-back L2 still refilled the partly written lines from HBM (1 564 B read per MB against 820);
+// sc1 writes them straight through (DESIGN.md §3.1, r05p2).
+constexpr int kQStoreCpol = kCpolSc1;
 DEV uint32_t opq_u(uint32_t v) {  // (opaque to the optimiser: keeps bit arithmetic from becoming compares)
 	asm("" : "+v"(v));
 	return v;
 }
-#ifndef VP8G_CSPLIT_FORMS  // ... and the chroma iDCT's DC-only and zero-column forms computed for those rows
-#define VP8G_CSPLIT_FORMS 1
-#endif
 // The pair exchange of a piece, as VOP2 DPP selects (quad_perm [1,0,3,2]: the partner lane l ^ 1):
 // dA = even lanes' held, odd lanes' partner's cur; dB = odd lanes' cur, even lanes' partner's held.
 // (One s_nop covers the VALU-write -> DPP-read hazard the compiler does not see inside asm.  s_not_b64
@@ -245,32 +162,8 @@ DEV void pair_swap(const u32x2& held, const u32x2& cur, u32x2& dA, u32x2& dB) {
 	    : "vcc", "scc");
 }
 #undef VP8G_SELSWAP
-template <bool kPaired>
-constexpr int qvmem_per_step() { return kQVmemPerStep + (kPaired && (VP8G_QPAIR & 1) ? 1 : 0) + (kPaired && (VP8G_QPAIR & 2) ? 2 : 0); }
-// The publish's wait (VP8G_PUB_AT = 1): only the next step's prefetch (5) pending -- or, with the context
-// stores issued first (VP8G_CTX_FIRST), also the previous step's pixel stores and this step's context load
-// (VP8G_CTX_EARLY: issued at the step's top, so it is younger than those stores).
-static_assert(!(VP8G_CTX_FIRST && VP8G_Y1_SKIP), "VP8G_CTX_FIRST counts every store of a step");
-static_assert(!(VP8G_PREF2 && VP8G_PREF_EARLY), "one prefetch placement");
-template <bool kPaired>
-constexpr int pub_vmcnt() { return VP8G_CTX_FIRST ? 5 + (VP8G_CTX_EARLY ? 1 : 0) + (qvmem_per_step<kPaired>() - 5 - 1 - 3) : 5; }
-// Cache policy of the quad kernel's pixel stores.  Unpaired (the general instantiation): plain
-// (write-back L2) -- frame_kernel's write-through (sc1) stores measured 1.3 % (uhd4) / 1.8 % (fhd4)
-// slower here (profiles/r05q6_ab.json), after the loop-top fix still +0.9 / +1.8 %; sc1 for chroma or
-// luma only +2.2 / +2.5 %; sc0 ±0; nt +150 % (profiles/r05_ab_log.json r05q8..q11).  Paired (the
-// whole-piece instantiation, VP8G_QPAIR): write-through -- with 32-B luma / 16-B chroma pieces the
-// write-back L2 still refilled the partly written lines from HBM (1 564 B read per MB against 820),
-// sc1 writes them straight through: uhd4 -2.6 %, fhd4 -0.5 % against plain paired stores (r05p2).
-#ifndef VP8G_QSTORE_AUX
-#define VP8G_QSTORE_AUX 0
-#endif
-#ifndef VP8G_QPAIR_AUX
-#define VP8G_QPAIR_AUX 16  // (kCpolSc1)
-#endif
-template <int kAux>
-DEV void qst128(Rsrc r, uint32_t off, u32x4 v) { __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)off, 0, kAux); }
-template <int kAux>
-DEV void qst64(Rsrc r, uint32_t off, u32x2 v) { __builtin_amdgcn_raw_buffer_store_b64(v, r, (int)off, 0, kAux); }
+DEV void qst128(Rsrc r, uint32_t off, u32x4 v) { __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)off, 0, kQStoreCpol); }
+DEV void qst64(Rsrc r, uint32_t off, u32x2 v) { __builtin_amdgcn_raw_buffer_store_b64(v, r, (int)off, 0, kQStoreCpol); }
 
 // kWP: every frame of the batch has whole row pieces (the bench's batches); the general instantiation
 // adds the byte path for pieces cut by the right edge or unaligned planes (+1 % when used for
@@ -281,8 +174,6 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
                                                                                  uint8_t* __restrict__ gctx, uint32_t epoch,
                                                                                  uint32_t* __restrict__ gflags, uint32_t ord_first,
                                                                                  uint32_t n_chain) {
-	constexpr bool kPair = VP8G_QPAIR != 0 && (kWP || VP8G_QPAIR_GENERAL != 0);  // paired pixel stores
-	constexpr int kAuxS = kPair ? VP8G_QPAIR_AUX : VP8G_QSTORE_AUX;               // (pixel-store cache policy)
 	static_assert(NW == 16, "the quad kernel's LDS layout is sized for 16 waves");
 	extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 	const int lane0 = (int)(threadIdx.x & 63);
@@ -538,7 +429,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 		auto lf_words = [&](int ln, uint32_t& vp, uint32_t& hp) {
 			const int h = lane0 >> 4;
 			const bool isy = ln < 16;
-			const uint32_t cp = (uint32_t)(ln >> 3) & 1u, hb = (uint32_t)(kHdrBytes + h * kQuarterBytes) + tsh(h);
+			const uint32_t cp = (uint32_t)(ln >> 3) & 1u, hb = (uint32_t)(kHdrBytes + h * kQuarterBytes);
 			const uint32_t rowp = hb + (isy ? (uint32_t)(kLfY + (4 + ln) * kTP) : (uint32_t)kLfUV + (4u + (uint32_t)(ln & 7)) * kTP + cp * kCV);
 			const uint32_t col = hb + (isy ? (uint32_t)(kLfY + ln) : (uint32_t)kLfUV + cp * kCV + (uint32_t)(ln & 7));
 			const uint32_t d = isy ? 16u : 8u;
@@ -564,7 +455,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 			const bool topY = ln < 4, topC = kc < 4;
 			const uint32_t shy = 2u * (uint32_t)h + (topY ? 0u : 1u), shc = 2u * (uint32_t)h + (topC ? 0u : 1u);
 			const uint32_t hb = (uint32_t)(kHdrBytes + h * kQuarterBytes);
-			const uint32_t sY = hb + tsh(h) + kLfY + (uint32_t)ln * kTP, sC = hb + tsh(h) + kLfUV + (uint32_t)(pc * kCV + kc * kTP);
+			const uint32_t sY = hb + kLfY + (uint32_t)ln * kTP, sC = hb + kLfUV + (uint32_t)(pc * kCV + kc * kTP);
 			sYw = (sY + (topY ? 0u : 16u)) | ((sY + (topY ? 16u : 0u)) << 16);
 			sCw = (sC + (topC ? 0u : 8u)) | ((sC + (topC ? 8u : 0u)) << 16);
 			oY = visY && !ctxY ? __umul24(prowY, sy) - shy * 16u : kNoStore;
@@ -602,17 +493,10 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 			// permutes wait for one load, the modes' for two, and the coefficients have until the
 			// dequantisation)
 			p.side = ((const __attribute__((address_space(1))) uint8_t*)sbase)[cn];
-#if VP8G_QLOAD_NT  // (experiment: non-temporal coefficient loads)
-			p.a1 = __builtin_nontemporal_load(s1);
-			p.a0 = __builtin_nontemporal_load(s0);
-			p.b0 = __builtin_nontemporal_load(s0 + 1);
-			p.b1 = __builtin_nontemporal_load(l == 9 ? s1 : s1 + 1);
-#else
 			p.a1 = *s1;  // (the B_PRED modes' permutes come next)
 			p.a0 = s0[0];
 			p.b0 = s0[1];
 			p.b1 = *(l == 9 ? s1 : s1 + 1);
-#endif
 			return p;
 		};
 		// (the loop's per-lane words are made live here, before the prefetch: reloaded from scratch at
@@ -622,14 +506,14 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 		asm volatile("" : "+v"(fY1), "+v"(fC1), "+v"(lfo1), "+v"(sY1), "+v"(sC1), "+v"(lf_vp0), "+v"(lf_hp0), "+v"(lf_vp1), "+v"(lf_hp1));
 		asm volatile("" : "+v"(cb0), "+v"(cb1), "+v"(sbase), "+v"(csh1));
 		QPref cur = qprefetch(lane0, 0);
-#if VP8G_PREF2
-		QPref nxt = qprefetch(lane0, 1);  // (two steps ahead: the step after next is loaded while this one runs)
-#endif
 		// Everything of the setup drained before the step loop (once per quad): with nothing outstanding
-		// on entry, the loop's waits are set by its back edge alone -- vmcnt(8) at the top (this step's
-		// prefetch), vmcnt(12) for the context load.  (Dummy operations to match the back edge's count
-		// were fragile: the compiler merged identical ones and placed scratch reloads after them, and
-		// the loop then waited vmcnt(0) -- every store of the previous step -- at the top of each step.)
+		// on entry, the waits the compiler places in the loop are set by its back edge alone -- vmcnt(14)
+		// and (13) for the side byte and the modes at the top (the rest of the prefetch and the previous
+		// step's ten stores are younger), vmcnt(12) and (11) for the coefficients (the context load is
+		// younger too); the context load itself is covered by the publish's wait.  (Dummy operations to
+		// match the back edge's count were fragile: the compiler merged identical ones and placed scratch
+		// reloads after them, and the loop then waited vmcnt(0) -- every store of the previous step -- at
+		// the top of each step.)
 		u32x4 mbx = u32x4{0u, 0u, 0u, 0u};
 		u32x4 hY0 = mbx;  // (paired stores: the pieces kept from the even column)
 		u32x2 hC0 = u32x2{0u, 0u}, hC1 = hC0;
@@ -662,8 +546,8 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 			const uint32_t cu = (uint32_t)c;
 			const int slot = c & 1;
 			uint8_t* const hv = wq + kHdrBytes + __umul24((uint32_t)h, (uint32_t)kQuarterBytes);  // this quarter's area (24-bit multiply: h comes from a laundered lane id)
-			uint8_t* const tY = hv + tsh(h) + kLfY;
-			uint8_t* const tC = hv + tsh(h) + kLfUV;
+			uint8_t* const tY = hv + kLfY;
+			uint8_t* const tC = hv + kLfUV;
 			uint8_t* const abY = hv + kAbY;
 			uint8_t* const left = hv + kLeft;
 			uint8_t* const rin = wq + kQRings + __umul24((uint32_t)h, (uint32_t)kRingBytes);  // ring h: the row above this quarter
@@ -673,28 +557,14 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 			m0 = m0 >= 3u ? m0 - 3u : m0;
 			const uint32_t m1 = m0 == 2u ? 0u : m0 + 1u, mm = m0 == 0u ? 2u : m0 - 1u;
 #ifdef VP8G_STAMPS
-			// (the prefetch: all but the context load and the previous step's stores)
-			// (VP8G_CTX_EARLY: the context load comes before the prefetch, so only the stores are younger)
-			if constexpr (qvmem_per_step<kPair>() == 16) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VP8G_CTX_EARLY ? 10 : 11) : "memory");
-			else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VP8G_CTX_EARLY ? 7 : 8) : "memory");
-			static_assert(qvmem_per_step<kPair>() == 16 || qvmem_per_step<kPair>() == 13, "the stamps wait counts the stores");
+			// (this step's prefetch complete: only the previous step's stores, issued after it, may be pending)
+			asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kQStoresPerStep) : "memory");
 			STAMP(13);
 #endif
-			uint32_t p_early = 0xFFFFFFFFu;  // (VP8G_CTX_EARLY = 2: the progress word read ahead of the side info)
-			if constexpr (VP8G_CTX_EARLY == 2) {
-				if (t > 0 && has_pred && !dead) p_early = __hip_atomic_load(prog + pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-			}
-			if constexpr (VP8G_CTX_EARLY == 1) {
-				// the row above's context for this step (stamps builds count this wait as side info)
-				if (t > 0) {
-					if (has_pred && !dead && !(VP8G_ABLATE & 8)) wait_prog(pw, (gprev << kProgShift) + min(t + 8u, Tprev));
-					const uint32_t lcol = lane < 2 ? t + 1u : t;
-					const bool ok = has_hbm && lane < 10 && lcol < C;
-					mbx = __builtin_amdgcn_raw_buffer_load_b128(rQ, (int)(ok ? __umul24(lcol, (uint32_t)kCtxBytesPerCol) + 16u * (uint32_t)lane : kNoStore), 0, kCpolSc1);
-				} else {
-					mbx = __builtin_amdgcn_raw_buffer_load_b128(rQ, (int)kNoStore, 0, kCpolSc1);  // (a step issues it every time)
-				}
-			}
+			// (the progress word of the quad above read ahead of the side info: the poll's LDS round trip
+			// overlaps the side-info permutes)
+			uint32_t p_early = 0xFFFFFFFFu;
+			if (t > 0 && has_pred && !dead) p_early = __hip_atomic_load(prog + pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 
 			// ---------------------------------------------- side info (quarter's lanes 9..13)
 			const u32x4 dq4a = load_dq4(l), dq4b = load_dq4(l + 16);
@@ -707,25 +577,25 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 			                        (uint32_t)__builtin_amdgcn_ds_bpermute(bml, (int)cur.a1.z), (uint32_t)__builtin_amdgcn_ds_bpermute(bml, (int)cur.a1.w)};
 			const bool bpred = ymode == 4;
 			const uint32_t y0 = r * 16, cy0 = r * 8;
-			if constexpr (VP8G_CTX_EARLY == 2) {
-				// (the same wait and load after the side info: the progress word was read before it, and the
-				// spin is entered only if that value is short)
-				if (t > 0) {
-					const uint32_t need = (gprev << kProgShift) + min(t + 8u, Tprev);
-					if (has_pred && !dead && !(VP8G_ABLATE & 8) && p_early < need) wait_prog(pw, need);
-					asm volatile("" ::: "memory");
-					const uint32_t lcol = lane < 2 ? t + 1u : t;
-					const bool ok = has_hbm && lane < 10 && lcol < C;
-					mbx = __builtin_amdgcn_raw_buffer_load_b128(rQ, (int)(ok ? __umul24(lcol, (uint32_t)kCtxBytesPerCol) + 16u * (uint32_t)lane : kNoStore), 0, kCpolSc1);
-				} else {
-					mbx = __builtin_amdgcn_raw_buffer_load_b128(rQ, (int)kNoStore, 0, kCpolSc1);
-				}
+			// The row above's context for this step (rec[t + 1], lf[t] of the quad above's quarter 3): the
+			// wait for progress >= t + 8 (the spin entered only if the value read above is short), then the
+			// load -- an L2 hit, hidden behind the residual, put into ring 0 after it.  (Stamps builds count
+			// this wait as side info.)
+			if (t > 0) {
+				const uint32_t need = (gprev << kProgShift) + min(t + 8u, Tprev);
+				if (has_pred && !dead && !(VP8G_ABLATE & 8) && p_early < need) wait_prog(pw, need);
+				asm volatile("" ::: "memory");
+				const uint32_t lcol = lane < 2 ? t + 1u : t;
+				const bool ok = has_hbm && lane < 10 && lcol < C;
+				mbx = __builtin_amdgcn_raw_buffer_load_b128(rQ, (int)(ok ? __umul24(lcol, (uint32_t)kCtxBytesPerCol) + 16u * (uint32_t)lane : kNoStore), 0, kCpolSc1);
+			} else {
+				mbx = __builtin_amdgcn_raw_buffer_load_b128(rQ, (int)kNoStore, 0, kCpolSc1);  // (a step issues it every time: the waits count it)
 			}
 			STAMP(10);
 
 			// ---------------------------------------------- residual, both roles
 			PRIO(0);
-			uint32_t rs0[8], rs1[8];
+			uint32_t rs0[8], rs1[4];  // (chroma: this lane's two rows of the block)
 			{
 				const uint32_t fd0 = pick_dq(dq4a, seg), fa0 = __builtin_amdgcn_perm(fd0, fd0, 0x03020302u);
 				const uint32_t fd1 = pick_dq(dq4b, seg), fa1 = __builtin_amdgcn_perm(fd1, fd1, 0x03020302u);
@@ -735,14 +605,6 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 				                        pk_mul(cur.b1.x, fa1), pk_mul(cur.b1.y, fa1), pk_mul(cur.b1.z, fa1), pk_mul(cur.b1.w, fa1)};
 				const bool anyac0 = ((w0[0] >> 16) | w0[1] | w0[2] | w0[3] | w0[4] | w0[5] | w0[6] | w0[7]) != 0u;
 				const bool anyac1 = ((w1[0] >> 16) | w1[1] | w1[2] | w1[3] | w1[4] | w1[5] | w1[6] | w1[7]) != 0u;
-				if constexpr (VP8G_PREF_EARLY != 0) {
-					cur = qprefetch(lane, (int)t + 1);
-					if constexpr (VP8G_PUB_AT == 1) {
-						asm volatile("s_waitcnt vmcnt(%0)" ::"n"(pub_vmcnt<kPair>()) : "memory");  // (the prefetch just issued pending)
-						if (lane == 0 && wave != VP8G_TEST_STALL_WAVE)
-							__hip_atomic_store(prog + wave, (g << kProgShift) + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-					}
-				}
 				// Y2 (non-B_PRED): inverse WHT in role-1 lanes 10..13 (frame_kernel's 26..29) through the
 				// quarter's residual park, which is written only after it
 				if (__ballot(act && !bpred) != 0ull) {
@@ -830,10 +692,11 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 				// Chroma (role 1): blocks sit in lanes l < 8 only, the lanes l + 8 hold the Y2 / mode / side
 				// roles, idle in the iDCT.  In the full form a block's work is split over the lane pair
 				// (l, l + 8) -- DPP row_ror:8 exchanges within a quarter's 16-lane row: lane l + 8 takes the
-				// block's column pair 1 in the vertical pass and rows 2..3 in the row pass (VP8G_CSPLIT)
+				// block's column pair 1 in the vertical pass and rows 2..3 in the row pass.  Every form leaves
+				// a lane its own two rows in rs1[0..3] (l: 0, 1; l + 8: 2, 3), as the chroma predictor wants them.
 				const uint64_t mac1 = __ballot(anyac1 && l < 8 && act), m23_1 = __ballot(act && l < 8 && (w1[1] | w1[3] | w1[5] | w1[7]) != 0u);
-				if (VP8G_CSPLIT && mac1 != 0ull && m23_1 != 0ull) {
-					auto ror8 = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x128, 0xF, 0xF, false); };
+				auto ror8 = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x128, 0xF, 0xF, false); };
+				if (mac1 != 0ull && m23_1 != 0ull) {
 					const bool hi = (l & 8) != 0;
 					uint32_t q[4], oh[4];
 #pragma unroll
@@ -855,17 +718,11 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 						rr2[2 * rr] = pack2((a1 + d1) >> 3, (b1 + c1) >> 3);
 						rr2[2 * rr + 1] = pack2((b1 - c1) >> 3, (a1 - d1) >> 3);
 					}
-					if constexpr (VP8G_CSPLIT_PRED != 0) {
 #pragma unroll
-						for (int k = 0; k < 4; k++) rs1[k] = rr2[k];  // (the predictor splits the rows the same way)
-					} else {
-#pragma unroll
-						for (int k = 0; k < 4; k++) rs1[k] = rr2[k], rs1[4 + k] = ror8(rr2[k]);  // (rows 2, 3 from lane l + 8)
-					}
-				} else if (VP8G_CSPLIT_PRED != 0 && VP8G_CSPLIT_FORMS != 0) {
-					// the other two forms, this lane's rows only (l: 0, 1; l + 8: 2, 3)
-					auto ror8 = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x128, 0xF, 0xF, false); };
-					const bool hi = (l & 8) != 0;
+					for (int k = 0; k < 4; k++) rs1[k] = rr2[k];
+				} else {
+					// the other two forms, this lane's rows only
+					const bool hi = (l & 8) != 0;  // (per arm on purpose: one shared definition changes the generated code)
 					if (mac1 == 0ull) {  // DC only: the block's DC from lane l
 						const uint32_t w0p = ror8(w1[0]);
 						const int d = (lo_s16(hi ? w0p : w1[0]) + 4) >> 3;
@@ -885,17 +742,6 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 							rs1[2 * rr + 1] = pack2((x0 - c1) >> 3, (x0 - d1) >> 3);
 						}
 					}
-				} else {
-					idct(w1, rs1, mac1, m23_1);
-					if constexpr (VP8G_CSPLIT_PRED != 0) {  // lane l + 8 predicts rows 2, 3: their residual from lane l
-						auto ror8 = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x128, 0xF, 0xF, false); };
-						const bool hi = (l & 8) != 0;
-#pragma unroll
-						for (int k = 0; k < 4; k++) {
-							const uint32_t v = ror8(rs1[4 + k]);
-							rs1[k] = hi ? v : rs1[k];
-						}
-					}
 				}
 				if (bpred) {  // the luma residual for the B_PRED pixel lanes
 					uint8_t* rp = hv + kResid + l * 32;
@@ -904,40 +750,29 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 				}
 			}
 			// (issued right after the dequantisation instead, the iDCT's time earlier: ±0, r05p5)
-#if VP8G_PREF2
-			cur = nxt;
-			nxt = qprefetch(lane, (int)t + 2);
-#else
-			if constexpr (VP8G_PREF_EARLY == 0) cur = qprefetch(lane, (int)t + 1);
-#endif
-			if constexpr (VP8G_PUB_AT == 1 && VP8G_PREF_EARLY == 0) {
-				asm volatile("s_waitcnt vmcnt(%0)" ::"n"(pub_vmcnt<kPair>()) : "memory");  // (the prefetch just issued pending)
-				if (lane == 0 && wave != VP8G_TEST_STALL_WAVE)
-					__hip_atomic_store(prog + wave, (g << kProgShift) + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-			}
+			cur = qprefetch(lane, (int)t + 1);
+			// Publish progress t (steps < t visible).  Only the prefetch just issued may be pending: this
+			// step's context load and every store of step t - 1 are older, so they are acknowledged.
+			asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kQPrefLoads) : "memory");
+			if (lane == 0 && wave != VP8G_TEST_STALL_WAVE)
+				__hip_atomic_store(prog + wave, (g << kProgShift) + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 			STAMP(0);
 
-			// ---------------------------------------------- row above: ring 0 fill, wait, next load
+			// ---------------------------------------------- row above: ring 0 fill
 			PRIO(1);
-			if (has_hbm && t > 0 && lane < 10) {  // rec[t + 1] (lanes 0, 1) and lf[t] (2..9), loaded last step (or at this step's top)
+			if (has_hbm && t > 0 && lane < 10) {  // rec[t + 1] (lanes 0, 1) and lf[t] (2..9), loaded after this step's side info
 				const uint32_t col = lane < 2 ? t + 1u : t;
 				// (the slot chosen first and scaled by a 24-bit multiply: selecting between two scaled scalars
 				// was folded into a select and a quarter-rate v_mul_lo_u32)
 				const uint32_t s3o = __umul24(lane < 2 ? uni((t + 1u) % 3u) : uni(t % 3u), (uint32_t)kCtxBytesPerCol);
 				if (col < C) st128(wq + kQRings + s3o + 16u * (uint32_t)lane, mbx);
 			}
-			if constexpr (VP8G_CTX_EARLY == 0) {
-				if (has_pred && !dead && !(VP8G_ABLATE & 8)) wait_prog(pw, (gprev << kProgShift) + min(t + 9u, Tprev));
-				const uint32_t lcol = lane < 2 ? t + 2u : t + 1u;
-				const bool ok = has_hbm && lane < 10 && lcol < C;
-				mbx = __builtin_amdgcn_raw_buffer_load_b128(rQ, (int)(ok ? __umul24(lcol, (uint32_t)kCtxBytesPerCol) + 16u * (uint32_t)lane : kNoStore), 0, kCpolSc1);
-			}
 			wave_lds_sync();
 			STAMP(1);
 
 			// ---------------------------------------------- borders + loop-filter top strip
 			PRIO_AFTER(2, 1);
-			const u32x2 prole0 = ld64(smem + kRoleTab + 8 * l), prole1 = ld64(smem + kRoleTab + 8 * ((VP8G_CSPLIT_PRED ? (l & 7) : l) + 16));
+			const u32x2 prole0 = ld64(smem + kRoleTab + 8 * l), prole1 = ld64(smem + kRoleTab + 8 * ((l & 7) + 16));
 			if (act) {
 				const bool top = r == 0;
 				const uint8_t* const rec0 = rin + __umul24(m0, (uint32_t)kCtxBytesPerCol);
@@ -961,9 +796,9 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 				if (lf_on && !top && l >= 4) {  // roles 20..31: the MB above's filter-state rows
 					const bool ly = (bt1 >> 22) & 1u;
 					const uint8_t* const lo = rec0 + ((bt1 >> 12) & 0xFFu);
-					uint8_t* const td = hv + tsh(h) + (bt1 & 0xFFFu) + (slot ? (ly ? 16u : 8u) : 0u);
+					uint8_t* const td = hv + (bt1 & 0xFFFu) + (slot ? (ly ? 16u : 8u) : 0u);
 					const u32x2 s0 = ld64(lo), s1 = ld64(lo + 8);
-					if (ly) st2x32(td, s0), st2x32(td + 8, s1);
+					if (ly) st64(td, s0), st64(td + 8, s1);
 					else stc64(td, s0);
 				}
 			}
@@ -972,164 +807,105 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 
 			// ---------------------------------------------- prediction + reconstruction
 			PRIO(3);
-			auto wpred = [&](int ln, const u32x2& prole, const uint32_t* rw) {
-				if (act && ln < 24 && (ln >= 16 || !bpred)) {
-					const bool yl = (prole.x >> 22) & 1u;
-					const uint8_t* ab = hv + (prole.x & 0x7FFu);
-					const uint8_t* lc = hv + (prole.y & 0x7FFu);
-					const int mode = yl ? (ymode > 4 ? 0 : ymode) : (uvmode > 3 ? 0 : uvmode);
-					const u32x2 a01 = ld64(ab), a23 = ld64(ab + 8), l01 = ld64(lc), l23 = ld64(lc + 8);
-					const uint32_t aw = ld32(hv + __builtin_amdgcn_ubfe(prole.x, 11u, 11u));
-					const uint32_t lw = ld32(lc + 4u * __builtin_amdgcn_ubfe(prole.y, 22u, 2u));
-					const int P = (int)ab[-1];
-					const uint32_t sa2 = __builtin_amdgcn_sad_u8(a01.y, 0u, __builtin_amdgcn_sad_u8(a01.x, 0u, 0u));
-					const uint32_t sl2 = __builtin_amdgcn_sad_u8(l01.y, 0u, __builtin_amdgcn_sad_u8(l01.x, 0u, 0u));
-					const uint32_t sa4 = __builtin_amdgcn_sad_u8(a23.y, 0u, __builtin_amdgcn_sad_u8(a23.x, 0u, sa2));
-					const uint32_t sl4 = __builtin_amdgcn_sad_u8(l23.y, 0u, __builtin_amdgcn_sad_u8(l23.x, 0u, sl2));
-					const bool ha = r > 0, hl = c > 0;
-					const uint32_t sum = (ha ? (yl ? sa4 : sa2) : 0u) + (hl ? (yl ? sl4 : sl2) : 0u);
-					const int shift = (yl ? 3 : 2) + (ha ? 1 : 0) + (hl ? 1 : 0);
-					int dcv;
-					asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(dcv) : "v"(128), "v"((int)((sum + (1u << (shift - 1))) >> shift)),
-					    "s"(__builtin_amdgcn_ballot_w64(ha || hl)));
-					const uint32_t mA = (mode == 1 || mode == 3) ? 0x00FF00FFu : 0u;
-					const uint32_t mL = (mode == 2 || mode == 3) ? 0x00FF00FFu : 0u;
-					const int K = (mode == 3 ? -P : 0) + (mode == 0 ? dcv : 0);
-					const uint32_t K2 = __builtin_amdgcn_perm((uint32_t)K, (uint32_t)K, 0x05040100u);
-					uint8_t* dst = hv + tsh(h) + __builtin_amdgcn_ubfe(prole.y, 11u, 11u) + (slot ? (yl ? 16u : 8u) : 0u);
-					const uint32_t A01 = pk_add(__builtin_amdgcn_perm(aw, aw, 0x0C010C00u) & mA, K2);
-					const uint32_t A23 = pk_add(__builtin_amdgcn_perm(aw, aw, 0x0C030C02u) & mA, K2);
-					uint32_t wv[4];
-					auto pack_row = [&](uint32_t q01, uint32_t q23) -> uint32_t { return sat_pk(q01) | (sat_pk(q23) << 16); };
-					if (__ballot(mode == 3) != 0ull) {
+			// luma (role 0: every lane a luma block): the mode's masks and constant from bits of the
+			// mode (0 DC, 1 V, 2 H, 3 TM) instead of compares and selects
+			if (act && !bpred) {
+				const u32x2 prole = prole0;
+				const uint8_t* ab = hv + (prole.x & 0x7FFu);
+				const uint8_t* lc = hv + (prole.y & 0x7FFu);
+				const int mode = ymode > 4 ? 0 : ymode;
+				const u32x2 a01 = ld64(ab), a23 = ld64(ab + 8), l01 = ld64(lc), l23 = ld64(lc + 8);
+				const uint32_t aw = ld32(hv + __builtin_amdgcn_ubfe(prole.x, 11u, 11u));
+				const uint32_t lw = ld32(lc + 4u * __builtin_amdgcn_ubfe(prole.y, 22u, 2u));
+				const int P = (int)ab[-1];
+				const uint32_t sa4 = __builtin_amdgcn_sad_u8(a23.y, 0u, __builtin_amdgcn_sad_u8(a23.x, 0u, __builtin_amdgcn_sad_u8(a01.y, 0u, __builtin_amdgcn_sad_u8(a01.x, 0u, 0u))));
+				const uint32_t sl4 = __builtin_amdgcn_sad_u8(l23.y, 0u, __builtin_amdgcn_sad_u8(l23.x, 0u, __builtin_amdgcn_sad_u8(l01.y, 0u, __builtin_amdgcn_sad_u8(l01.x, 0u, 0u))));
+				const bool ha = r > 0, hl = c > 0;
+				const uint32_t sum = (ha ? sa4 : 0u) + (hl ? sl4 : 0u);
+				const int shift = 3 + (ha ? 1 : 0) + (hl ? 1 : 0);
+				int dcv;
+				asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(dcv) : "v"(128), "v"((int)((sum + (1u << (shift - 1))) >> shift)),
+				    "s"(__builtin_amdgcn_ballot_w64(ha || hl)));
+				const uint32_t mb = opq_u((uint32_t)mode);
+				const uint32_t mA = (0u - ((0xAu >> mb) & 1u)) & 0x00FF00FFu;  // V, TM: the above row
+				const uint32_t mL = (0u - ((0xCu >> mb) & 1u)) & 0x00FF00FFu;  // H, TM: the left column
+				const int K = (int)((0u - (uint32_t)P) & (0u - ((0x8u >> mb) & 1u))) + (int)((uint32_t)dcv & (0u - (0x1u & ~mb & ~(mb >> 1))));
+				const uint32_t K2 = __builtin_amdgcn_perm((uint32_t)K, (uint32_t)K, 0x05040100u);
+				uint8_t* dst = hv + __builtin_amdgcn_ubfe(prole.y, 11u, 11u) + (slot ? 16u : 0u);
+				const uint32_t A01 = pk_add(__builtin_amdgcn_perm(aw, aw, 0x0C010C00u) & mA, K2);
+				const uint32_t A23 = pk_add(__builtin_amdgcn_perm(aw, aw, 0x0C030C02u) & mA, K2);
+				uint32_t wv[4];
+				auto pack_row = [&](uint32_t q01, uint32_t q23) -> uint32_t { return sat_pk(q01) | (sat_pk(q23) << 16); };
+				if (__ballot(mode == 3) != 0ull) {
 #pragma unroll
-						for (int rr = 0; rr < 4; rr++) {
-							const uint32_t L2 = __builtin_amdgcn_perm(lw, lw, 0x0C000C00u + 0x00010001u * rr) & mL;
-							wv[rr] = pack_row(pk_add(pk_clamp255(pk_add(L2, A01)), rw[2 * rr]), pk_add(pk_clamp255(pk_add(L2, A23)), rw[2 * rr + 1]));
-						}
-					} else {
-#pragma unroll
-						for (int rr = 0; rr < 4; rr++) {
-							const uint32_t L2 = __builtin_amdgcn_perm(lw, lw, 0x0C000C00u + 0x00010001u * rr) & mL;
-							wv[rr] = pack_row(pk_add(pk_add(L2, A01), rw[2 * rr]), pk_add(pk_add(L2, A23), rw[2 * rr + 1]));
-						}
+					for (int rr = 0; rr < 4; rr++) {
+						const uint32_t L2 = __builtin_amdgcn_perm(lw, lw, 0x0C000C00u + 0x00010001u * rr) & mL;
+						wv[rr] = pack_row(pk_add(pk_clamp255(pk_add(L2, A01)), rs0[2 * rr]), pk_add(pk_clamp255(pk_add(L2, A23)), rs0[2 * rr + 1]));
 					}
+				} else {
 #pragma unroll
-					for (int rr = 0; rr < 4; rr++) st32(dst + rr * kTP, wv[rr]);
-					if ((prole.x >> 24) & 1u) {  // right column -> the next MB's left column
-						const uint32_t c01 = __builtin_amdgcn_perm(wv[1], wv[0], 0x0C0C0703u);
-						const uint32_t c23 = __builtin_amdgcn_perm(wv[3], wv[2], 0x0C0C0703u);
-						st32(const_cast<uint8_t*>(lc) + 4u * __builtin_amdgcn_ubfe(prole.y, 22u, 2u), __builtin_amdgcn_perm(c23, c01, 0x05040100u));
+					for (int rr = 0; rr < 4; rr++) {
+						const uint32_t L2 = __builtin_amdgcn_perm(lw, lw, 0x0C000C00u + 0x00010001u * rr) & mL;
+						wv[rr] = pack_row(pk_add(pk_add(L2, A01), rs0[2 * rr]), pk_add(pk_add(L2, A23), rs0[2 * rr + 1]));
 					}
 				}
-			};
-			if constexpr (VP8G_WPRED_Y != 0) {
-				// luma (role 0: every lane a luma block): the mode's masks and constant from bits of the
-				// mode (0 DC, 1 V, 2 H, 3 TM) instead of compares and selects
-				if (act && !bpred) {
-					const u32x2 prole = prole0;
-					const uint8_t* ab = hv + (prole.x & 0x7FFu);
-					const uint8_t* lc = hv + (prole.y & 0x7FFu);
-					const int mode = ymode > 4 ? 0 : ymode;
-					const u32x2 a01 = ld64(ab), a23 = ld64(ab + 8), l01 = ld64(lc), l23 = ld64(lc + 8);
-					const uint32_t aw = ld32(hv + __builtin_amdgcn_ubfe(prole.x, 11u, 11u));
-					const uint32_t lw = ld32(lc + 4u * __builtin_amdgcn_ubfe(prole.y, 22u, 2u));
-					const int P = (int)ab[-1];
-					const uint32_t sa4 = __builtin_amdgcn_sad_u8(a23.y, 0u, __builtin_amdgcn_sad_u8(a23.x, 0u, __builtin_amdgcn_sad_u8(a01.y, 0u, __builtin_amdgcn_sad_u8(a01.x, 0u, 0u))));
-					const uint32_t sl4 = __builtin_amdgcn_sad_u8(l23.y, 0u, __builtin_amdgcn_sad_u8(l23.x, 0u, __builtin_amdgcn_sad_u8(l01.y, 0u, __builtin_amdgcn_sad_u8(l01.x, 0u, 0u))));
-					const bool ha = r > 0, hl = c > 0;
-					const uint32_t sum = (ha ? sa4 : 0u) + (hl ? sl4 : 0u);
-					const int shift = 3 + (ha ? 1 : 0) + (hl ? 1 : 0);
-					int dcv;
-					asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(dcv) : "v"(128), "v"((int)((sum + (1u << (shift - 1))) >> shift)),
-					    "s"(__builtin_amdgcn_ballot_w64(ha || hl)));
-					const uint32_t mb = opq_u((uint32_t)mode);
-					const uint32_t mA = (0u - ((0xAu >> mb) & 1u)) & 0x00FF00FFu;  // V, TM: the above row
-					const uint32_t mL = (0u - ((0xCu >> mb) & 1u)) & 0x00FF00FFu;  // H, TM: the left column
-					const int K = (int)((0u - (uint32_t)P) & (0u - ((0x8u >> mb) & 1u))) + (int)((uint32_t)dcv & (0u - (0x1u & ~mb & ~(mb >> 1))));
-					const uint32_t K2 = __builtin_amdgcn_perm((uint32_t)K, (uint32_t)K, 0x05040100u);
-					uint8_t* dst = hv + tsh(h) + __builtin_amdgcn_ubfe(prole.y, 11u, 11u) + (slot ? 16u : 0u);
-					const uint32_t A01 = pk_add(__builtin_amdgcn_perm(aw, aw, 0x0C010C00u) & mA, K2);
-					const uint32_t A23 = pk_add(__builtin_amdgcn_perm(aw, aw, 0x0C030C02u) & mA, K2);
-					uint32_t wv[4];
-					auto pack_row = [&](uint32_t q01, uint32_t q23) -> uint32_t { return sat_pk(q01) | (sat_pk(q23) << 16); };
-					if (__ballot(mode == 3) != 0ull) {
 #pragma unroll
-						for (int rr = 0; rr < 4; rr++) {
-							const uint32_t L2 = __builtin_amdgcn_perm(lw, lw, 0x0C000C00u + 0x00010001u * rr) & mL;
-							wv[rr] = pack_row(pk_add(pk_clamp255(pk_add(L2, A01)), rs0[2 * rr]), pk_add(pk_clamp255(pk_add(L2, A23)), rs0[2 * rr + 1]));
-						}
-					} else {
-#pragma unroll
-						for (int rr = 0; rr < 4; rr++) {
-							const uint32_t L2 = __builtin_amdgcn_perm(lw, lw, 0x0C000C00u + 0x00010001u * rr) & mL;
-							wv[rr] = pack_row(pk_add(pk_add(L2, A01), rs0[2 * rr]), pk_add(pk_add(L2, A23), rs0[2 * rr + 1]));
-						}
-					}
-#pragma unroll
-					for (int rr = 0; rr < 4; rr++) st32(dst + rr * kTP, wv[rr]);
-					if ((prole.x >> 24) & 1u) {  // right column -> the next MB's left column
-						const uint32_t c01 = __builtin_amdgcn_perm(wv[1], wv[0], 0x0C0C0703u);
-						const uint32_t c23 = __builtin_amdgcn_perm(wv[3], wv[2], 0x0C0C0703u);
-						st32(const_cast<uint8_t*>(lc) + 4u * __builtin_amdgcn_ubfe(prole.y, 22u, 2u), __builtin_amdgcn_perm(c23, c01, 0x05040100u));
-					}
+				for (int rr = 0; rr < 4; rr++) st32(dst + rr * kTP, wv[rr]);
+				if ((prole.x >> 24) & 1u) {  // right column -> the next MB's left column
+					const uint32_t c01 = __builtin_amdgcn_perm(wv[1], wv[0], 0x0C0C0703u);
+					const uint32_t c23 = __builtin_amdgcn_perm(wv[3], wv[2], 0x0C0C0703u);
+					st32(const_cast<uint8_t*>(lc) + 4u * __builtin_amdgcn_ubfe(prole.y, 22u, 2u), __builtin_amdgcn_perm(c23, c01, 0x05040100u));
 				}
-			} else {
-				wpred(l, prole0, rs0);
 			}
-			if constexpr (VP8G_CSPLIT_PRED != 0) {
-				// chroma: the block of lane l & 7, rows 0, 1 in lane l < 8 and rows 2, 3 in lane l + 8 (the
-				// residual rows are where the split iDCT leaves them)
-				if (act) {
-					const u32x2 prole = prole1;
-					const uint8_t* ab = hv + (prole.x & 0x7FFu);
-					const uint8_t* lc = hv + (prole.y & 0x7FFu);
-					const int mode = uvmode > 3 ? 0 : uvmode;
-					const u32x2 a01 = ld64(ab), l01 = ld64(lc);
-					const uint32_t aw = ld32(hv + __builtin_amdgcn_ubfe(prole.x, 11u, 11u));
-					const uint32_t lw = ld32(lc + 4u * __builtin_amdgcn_ubfe(prole.y, 22u, 2u));
-					const int P = (int)ab[-1];
-					const uint32_t sa2 = __builtin_amdgcn_sad_u8(a01.y, 0u, __builtin_amdgcn_sad_u8(a01.x, 0u, 0u));
-					const uint32_t sl2 = __builtin_amdgcn_sad_u8(l01.y, 0u, __builtin_amdgcn_sad_u8(l01.x, 0u, 0u));
-					const bool ha = r > 0, hl = c > 0;
-					const uint32_t sum = (ha ? sa2 : 0u) + (hl ? sl2 : 0u);
-					const int shift = 2 + (ha ? 1 : 0) + (hl ? 1 : 0);
-					int dcv;
-					asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(dcv) : "v"(128), "v"((int)((sum + (1u << (shift - 1))) >> shift)),
-					    "s"(__builtin_amdgcn_ballot_w64(ha || hl)));
-					const uint32_t mA = (mode == 1 || mode == 3) ? 0x00FF00FFu : 0u;
-					const uint32_t mL = (mode == 2 || mode == 3) ? 0x00FF00FFu : 0u;
-					const int K = (mode == 3 ? -P : 0) + (mode == 0 ? dcv : 0);
-					const uint32_t K2 = __builtin_amdgcn_perm((uint32_t)K, (uint32_t)K, 0x05040100u);
-					const uint32_t rb = (uint32_t)(l & 8) >> 2;  // first row of this lane: 0 or 2
-					uint8_t* dst = hv + tsh(h) + __builtin_amdgcn_ubfe(prole.y, 11u, 11u) + (slot ? 8u : 0u) + rb * kTP;
-					const uint32_t A01 = pk_add(__builtin_amdgcn_perm(aw, aw, 0x0C010C00u) & mA, K2);
-					const uint32_t A23 = pk_add(__builtin_amdgcn_perm(aw, aw, 0x0C030C02u) & mA, K2);
-					const uint32_t lsel = 0x0C000C00u + 0x00010001u * rb;
-					uint32_t wv[2];
-					auto pack_row = [&](uint32_t q01, uint32_t q23) -> uint32_t { return sat_pk(q01) | (sat_pk(q23) << 16); };
-					if (__ballot(mode == 3) != 0ull) {
+			// chroma: the block of lane l & 7, rows 0, 1 in lane l < 8 and rows 2, 3 in lane l + 8 (the
+			// residual rows are where the split iDCT leaves them)
+			if (act) {
+				const u32x2 prole = prole1;
+				const uint8_t* ab = hv + (prole.x & 0x7FFu);
+				const uint8_t* lc = hv + (prole.y & 0x7FFu);
+				const int mode = uvmode > 3 ? 0 : uvmode;
+				const u32x2 a01 = ld64(ab), l01 = ld64(lc);
+				const uint32_t aw = ld32(hv + __builtin_amdgcn_ubfe(prole.x, 11u, 11u));
+				const uint32_t lw = ld32(lc + 4u * __builtin_amdgcn_ubfe(prole.y, 22u, 2u));
+				const int P = (int)ab[-1];
+				const uint32_t sa2 = __builtin_amdgcn_sad_u8(a01.y, 0u, __builtin_amdgcn_sad_u8(a01.x, 0u, 0u));
+				const uint32_t sl2 = __builtin_amdgcn_sad_u8(l01.y, 0u, __builtin_amdgcn_sad_u8(l01.x, 0u, 0u));
+				const bool ha = r > 0, hl = c > 0;
+				const uint32_t sum = (ha ? sa2 : 0u) + (hl ? sl2 : 0u);
+				const int shift = 2 + (ha ? 1 : 0) + (hl ? 1 : 0);
+				int dcv;
+				asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(dcv) : "v"(128), "v"((int)((sum + (1u << (shift - 1))) >> shift)),
+				    "s"(__builtin_amdgcn_ballot_w64(ha || hl)));
+				const uint32_t mA = (mode == 1 || mode == 3) ? 0x00FF00FFu : 0u;
+				const uint32_t mL = (mode == 2 || mode == 3) ? 0x00FF00FFu : 0u;
+				const int K = (mode == 3 ? -P : 0) + (mode == 0 ? dcv : 0);
+				const uint32_t K2 = __builtin_amdgcn_perm((uint32_t)K, (uint32_t)K, 0x05040100u);
+				const uint32_t rb = (uint32_t)(l & 8) >> 2;  // first row of this lane: 0 or 2
+				uint8_t* dst = hv + __builtin_amdgcn_ubfe(prole.y, 11u, 11u) + (slot ? 8u : 0u) + rb * kTP;
+				const uint32_t A01 = pk_add(__builtin_amdgcn_perm(aw, aw, 0x0C010C00u) & mA, K2);
+				const uint32_t A23 = pk_add(__builtin_amdgcn_perm(aw, aw, 0x0C030C02u) & mA, K2);
+				const uint32_t lsel = 0x0C000C00u + 0x00010001u * rb;
+				uint32_t wv[2];
+				auto pack_row = [&](uint32_t q01, uint32_t q23) -> uint32_t { return sat_pk(q01) | (sat_pk(q23) << 16); };
+				if (__ballot(mode == 3) != 0ull) {
 #pragma unroll
-						for (int k = 0; k < 2; k++) {
-							const uint32_t L2 = __builtin_amdgcn_perm(lw, lw, lsel + 0x00010001u * k) & mL;
-							wv[k] = pack_row(pk_add(pk_clamp255(pk_add(L2, A01)), rs1[2 * k]), pk_add(pk_clamp255(pk_add(L2, A23)), rs1[2 * k + 1]));
-						}
-					} else {
-#pragma unroll
-						for (int k = 0; k < 2; k++) {
-							const uint32_t L2 = __builtin_amdgcn_perm(lw, lw, lsel + 0x00010001u * k) & mL;
-							wv[k] = pack_row(pk_add(pk_add(L2, A01), rs1[2 * k]), pk_add(pk_add(L2, A23), rs1[2 * k + 1]));
-						}
+					for (int k = 0; k < 2; k++) {
+						const uint32_t L2 = __builtin_amdgcn_perm(lw, lw, lsel + 0x00010001u * k) & mL;
+						wv[k] = pack_row(pk_add(pk_clamp255(pk_add(L2, A01)), rs1[2 * k]), pk_add(pk_clamp255(pk_add(L2, A23)), rs1[2 * k + 1]));
 					}
-					st32(dst, wv[0]);
-					st32(dst + kTP, wv[1]);
-					if ((prole.x >> 24) & 1u) {  // right column -> the next MB's left column (this lane's two bytes)
-						const uint32_t c01 = __builtin_amdgcn_perm(wv[1], wv[0], 0x0C0C0703u);
-						*(uint16_t*)(const_cast<uint8_t*>(lc) + 4u * __builtin_amdgcn_ubfe(prole.y, 22u, 2u) + rb) = (uint16_t)c01;
+				} else {
+#pragma unroll
+					for (int k = 0; k < 2; k++) {
+						const uint32_t L2 = __builtin_amdgcn_perm(lw, lw, lsel + 0x00010001u * k) & mL;
+						wv[k] = pack_row(pk_add(pk_add(L2, A01), rs1[2 * k]), pk_add(pk_add(L2, A23), rs1[2 * k + 1]));
 					}
 				}
-			} else {
-				wpred(l + 16, prole1, rs1);
+				st32(dst, wv[0]);
+				st32(dst + kTP, wv[1]);
+				if ((prole.x >> 24) & 1u) {  // right column -> the next MB's left column (this lane's two bytes)
+					const uint32_t c01 = __builtin_amdgcn_perm(wv[1], wv[0], 0x0C0C0703u);
+					*(uint16_t*)(const_cast<uint8_t*>(lc) + 4u * __builtin_amdgcn_ubfe(prole.y, 22u, 2u) + rb) = (uint16_t)c01;
+				}
 			}
 			wave_lds_sync();
 			STAMP(12);
@@ -1153,7 +929,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 					const bool on = h < 2 || qrest != 0u;
 					const int g = h & 1;
 					uint8_t* const hq = wq + kHdrBytes + q * kQuarterBytes;
-					uint8_t* const tYq = hq + tsh((int)q) + kLfY;
+					uint8_t* const tYq = hq + kLfY;
 					const uint8_t* const abq = hq + kAbY;
 					uint8_t* const leftq = hq + kLeft;
 					// (the target quarter's modes: every lane of a quarter holds them)
@@ -1161,100 +937,10 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 					const u32x4 bmq = u32x4{(uint32_t)__builtin_amdgcn_ds_bpermute(bsrc, (int)bmw.x), (uint32_t)__builtin_amdgcn_ds_bpermute(bsrc, (int)bmw.y),
 					                        (uint32_t)__builtin_amdgcn_ds_bpermute(bsrc, (int)bmw.z), (uint32_t)__builtin_amdgcn_ds_bpermute(bsrc, (int)bmw.w)};
 					uint8_t* const tpix = tYq + slot * 16 + 4 * kTP + kBS * g + kTP * rr + cc;
-#if !(VP8G_BP_REG & 1)
 					const uint8_t* const tA = tYq + slot * 16 + 3 * kTP + kBS * g;
 					const uint8_t* const aE = g ? tA : abq + 16;
 					uint8_t* const lB = leftq + 36 * g;
-#endif
 					const int16_t* const rsp = (const int16_t*)(hq + kResid) + l + 32 * g;
-#if VP8G_BP_REG & 1
-					{
-						// Group 0 takes sub-blocks (i0, j0), group 1 (i0 + 1, j0 - 2) at step s = 2 i + j.  Every
-						// edge a step needs is one of: the MB's above row (E[] of group-0 lanes, + the
-						// above-right word), its left column (E[] of group-1 lanes; L00 for group 0's (0, 0)),
-						// or the bottom row R[s'] / right column C[s'] of an earlier sub-block -- the group's
-						// own, or the other group's O[s'] (group 1 receives group 0's rows, group 0 group 1's
-						// columns).  The corner pixel is byte 3 of one of them.  All lanes run every step (the
-						// DPP reads need them); the stores are predicated.
-						const bool g1 = g != 0;
-						const uint8_t* const ep = g1 ? (const uint8_t*)leftq : abq + 16;
-						const uint32_t E[4] = {ld32(ep), ld32(ep + 4), ld32(ep + 8), ld32(ep + 12)};
-						const uint32_t ARc = ld32(abq + 32), L00 = ld32(leftq), PC = (uint32_t)abq[15] << 24;
-						const uint32_t shR = 8u * (uint32_t)cc, shC = 8u * (uint32_t)rr;
-						uint32_t R[8], C[9], O[8];
-#pragma unroll
-						for (int s = 0; s < 10; s++) {
-							const int i0 = s <= 3 ? 0 : (s - 2) >> 1;
-							const int j0 = s - 2 * i0;
-							const bool v1 = i0 + 1 <= 3 && j0 >= 2;
-							const bool valid = g1 ? v1 : true;
-							const int b0 = 4 * i0 + j0;
-							const int mb0_ = (int)((bmq[b0 >> 2] >> (8 * (b0 & 3))) & 0xFFu);
-							const int mb1_ = v1 ? (int)((bmq[(b0 + 2) >> 2] >> (8 * ((b0 + 2) & 3))) & 0xFFu) : 0;
-							const int mode = min(g1 ? mb1_ : mb0_, kBpModes - 1);
-							const u32x4 tb = tabp[16 * (kBpEntry / 16) * mode];
-							const int rv = rsp[16 * b0];
-							const int sm1 = s >= 1 ? s - 1 : 0, sm2 = s >= 2 ? s - 2 : 0, sm3 = s >= 3 ? s - 3 : 0;
-							// group 0's edges
-							uint32_t A, AR, L, P;
-							if (i0 == 0) {
-								A = E[j0];
-								AR = j0 < 3 ? E[j0 < 3 ? j0 + 1 : 0] : ARc;
-								L = j0 == 0 ? L00 : C[sm1];
-								P = j0 == 0 ? PC : E[j0 >= 1 ? j0 - 1 : 0];
-							} else {
-								A = R[sm2];
-								AR = j0 == 2 ? R[sm1 < 8 ? sm1 : 0] : ARc;
-								L = j0 == 2 ? O[sm1 < 8 ? sm1 : 0] : C[sm1];
-								P = j0 == 2 ? (i0 == 1 ? R[1] : O[sm3]) : R[sm3];
-							}
-							if (v1) {  // group 1's, where they differ
-								const int i = i0 + 1, j = j0 - 2;
-								const uint32_t A1 = i == 1 ? O[sm2] : R[sm2];
-								const uint32_t AR1 = (i >= 2 && j == 0) ? R[sm1] : O[sm1];
-								const uint32_t L1 = j == 0 ? E[i < 4 ? i : 0] : C[sm1];
-								const uint32_t P1 = j == 0 ? E[i - 1] : (i == 1 ? O[sm3] : R[sm3]);
-								A = g1 ? A1 : A;
-								AR = g1 ? AR1 : AR;
-								L = g1 ? L1 : L;
-								P = g1 ? P1 : P;
-							}
-							const uint32_t ey = (P & 0xFF000000u) | 0x808080u;
-							const uint32_t lo = __builtin_amdgcn_perm(ey, L, tb.x);
-							const uint32_t hi = __builtin_amdgcn_perm(AR, A, tb.x);
-							const uint32_t x3 = (hi & tb.y) | (lo & ~tb.y);
-							const int vdir = sat8(__builtin_amdgcn_sdot4((int)(x3 ^ 0x00808080u), (int)tb.z, (int)tb.w, false) >> (tb.y >> 24));
-							const int vdc = (int)((__builtin_amdgcn_sad_u8(A, 0u, __builtin_amdgcn_sad_u8(L, 0u, 4u))) >> 3);
-							const int pred = mode == 0 ? vdc : vdir;
-							const int px = sat8(pred + rv);
-							if (on && valid) {
-								tpix[kBS * i0 + 4 * s] = (uint8_t)px;
-								const bool j3 = g1 ? j0 == 5 : j0 == 3;
-								if (col3 && j3) leftq[4 * (i0 + g) + rr] = (uint8_t)px;
-							}
-							// this sub-block's bottom row and right column, packed and broadcast over its 16 lanes
-							if (s <= 8) {
-								uint32_t u = (uint32_t)px << shC;
-								u |= dpp_u<0x124>(u);  // row_ror:4
-								u |= dpp_u<0x128>(u);  // row_ror:8
-								C[s] = dpp_u<0x153>(u);  // row_newbcast:3 (a lane of column 3)
-							}
-							if (s <= 7) {
-								uint32_t t = (uint32_t)px << shR;
-								t |= dpp_u<0xB1>(t);  // quad_perm:[1,0,3,2]
-								t |= dpp_u<0x4E>(t);  // quad_perm:[2,3,0,1]
-								R[s] = dpp_u<0x15C>(t);  // row_newbcast:12 (a lane of row 3)
-								const uint32_t v = g1 ? C[s] : R[s];
-								const auto sw = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-								#ifndef VP8G_BP_SWAPX
-								O[s] = g1 ? (uint32_t)sw[0] : (uint32_t)sw[1];
-#else
-								O[s] = g1 ? (uint32_t)sw[1] : (uint32_t)sw[0];
-#endif
-							}
-						}
-					}
-#else
 					if (on) {
 #pragma unroll
 						for (int s = 0; s < 10; s++) {
@@ -1291,92 +977,10 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 							wave_lds_sync();
 						}
 					}
-#endif
 				} else if (bp_lane) {
 					// three or four: both groups in every lane of a B_PRED quarter (the loads of both groups
 					// first, as when the groups were lanes of one instruction)
 					const int16_t* const rsp = (const int16_t*)(hv + kResid) + l;
-#if VP8G_BP_REG & 2
-					// Register hand-off as above, both groups in the lane: group 1 takes group 0's rows and
-					// group 0 group 1's columns from the lane's own registers (DPP stays inside the quarter,
-					// and a quarter is wholly active or not).
-					const uint32_t EA[4] = {ld32(abY + 16), ld32(abY + 20), ld32(abY + 24), ld32(abY + 28)};
-					const uint32_t EL[4] = {ld32(left), ld32(left + 4), ld32(left + 8), ld32(left + 12)};
-					const uint32_t ARc = ld32(abY + 32), PC = (uint32_t)abY[15] << 24;
-					const uint32_t shR = 8u * (uint32_t)cc, shC = 8u * (uint32_t)rr;
-					uint32_t R0[8], C0[9], R1[8], C1[8];
-#pragma unroll
-					for (int s = 0; s < 10; s++) {
-						const int i0 = s <= 3 ? 0 : (s - 2) >> 1;
-						const int j0 = s - 2 * i0;
-						const bool vg1 = i0 + 1 <= 3 && j0 >= 2;
-						const int b0 = 4 * i0 + j0;
-						const int sm1 = s >= 1 ? s - 1 : 0, sm2 = s >= 2 ? s - 2 : 0, sm3 = s >= 3 ? s - 3 : 0;
-						uint32_t A[2], AR[2], L[2], P[2];
-						if (i0 == 0) {
-							A[0] = EA[j0];
-							AR[0] = j0 < 3 ? EA[j0 < 3 ? j0 + 1 : 0] : ARc;
-							L[0] = j0 == 0 ? EL[0] : C0[sm1];
-							P[0] = j0 == 0 ? PC : EA[j0 >= 1 ? j0 - 1 : 0];
-						} else {
-							A[0] = R0[sm2];
-							AR[0] = j0 == 2 ? R0[sm1 < 8 ? sm1 : 0] : ARc;
-							L[0] = j0 == 2 ? C1[sm1 < 8 ? sm1 : 0] : C0[sm1];
-							P[0] = j0 == 2 ? (i0 == 1 ? R0[1] : C1[sm3]) : R0[sm3];
-						}
-						if (vg1) {
-							const int i = i0 + 1, j = j0 - 2;
-							A[1] = i == 1 ? R0[sm2] : R1[sm2];
-							AR[1] = (i >= 2 && j == 0) ? R1[sm1] : R0[sm1];
-							L[1] = j == 0 ? EL[i < 4 ? i : 0] : C1[sm1];
-							P[1] = j == 0 ? EL[i - 1] : (i == 1 ? R0[sm3] : R1[sm3]);
-						}
-						int pxg[2] = {0, 0};
-#pragma unroll
-						for (int gg = 0; gg < 2; gg++) {
-							if (gg == 1 && !vg1) continue;
-							const int bm = b0 + 2 * gg;
-							const int md = min((int)((bmw[bm >> 2] >> (8 * (bm & 3))) & 0xFFu), kBpModes - 1);
-							const u32x4 tb = tabp[16 * (kBpEntry / 16) * md];
-							const int rv = rsp[16 * b0 + 32 * gg];
-							const uint32_t ey = (P[gg] & 0xFF000000u) | 0x808080u;
-							const uint32_t lo = __builtin_amdgcn_perm(ey, L[gg], tb.x);
-							const uint32_t hi = __builtin_amdgcn_perm(AR[gg], A[gg], tb.x);
-							const uint32_t x3 = (hi & tb.y) | (lo & ~tb.y);
-							const int vdir = sat8(__builtin_amdgcn_sdot4((int)(x3 ^ 0x00808080u), (int)tb.z, (int)tb.w, false) >> (tb.y >> 24));
-							const int vdc = (int)((__builtin_amdgcn_sad_u8(A[gg], 0u, __builtin_amdgcn_sad_u8(L[gg], 0u, 4u))) >> 3);
-							const int px = sat8((md == 0 ? vdc : vdir) + rv);
-							pxg[gg] = px;
-							tY[slot * 16 + 4 * kTP + kBS * gg + kTP * rr + cc + kBS * i0 + 4 * s] = (uint8_t)px;
-							const bool j3 = gg ? j0 == 5 : j0 == 3;
-							if (col3 && j3) left[4 * (i0 + gg) + rr] = (uint8_t)px;
-						}
-						if (s <= 8) {
-							uint32_t u = (uint32_t)pxg[0] << shC;
-							u |= dpp_u<0x124>(u);
-							u |= dpp_u<0x128>(u);
-							C0[s] = dpp_u<0x153>(u);
-						}
-						if (s <= 7) {
-							uint32_t t = (uint32_t)pxg[0] << shR;
-							t |= dpp_u<0xB1>(t);
-							t |= dpp_u<0x4E>(t);
-							R0[s] = dpp_u<0x15C>(t);
-						}
-						if (vg1 && s <= 7) {
-							uint32_t u = (uint32_t)pxg[1] << shC;
-							u |= dpp_u<0x124>(u);
-							u |= dpp_u<0x128>(u);
-							C1[s] = dpp_u<0x153>(u);
-							if (s <= 6) {
-								uint32_t t = (uint32_t)pxg[1] << shR;
-								t |= dpp_u<0xB1>(t);
-								t |= dpp_u<0x4E>(t);
-								R1[s] = dpp_u<0x15C>(t);
-							}
-						}
-					}
-#else
 #pragma unroll
 					for (int s = 0; s < 10; s++) {
 						const int i0 = s <= 3 ? 0 : (s - 2) >> 1;
@@ -1422,7 +1026,6 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 						}
 						wave_lds_sync();
 					}
-#endif
 				}
 			}
 			wave_lds_sync();
@@ -1432,13 +1035,8 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 			u32x2 recv;
 			{
 				const uint8_t* const src = l < 2 ? tY + 19 * kTP + slot * 16 + 8 * l : tC + (l == 3 ? kCV : 0) + 11 * kTP + slot * 8;
-				recv = l < 2 ? ld2x32(src) : ldc64(src);
+				recv = l < 2 ? ld64(src) : ldc64(src);
 				if (act && l < 4 && h < 3) st64(rout + __umul24(m0, (uint32_t)kCtxBytesPerCol) + 8 * l, recv);
-			}
-			if constexpr (VP8G_PUB_AT == 2) {
-				asm volatile("s_waitcnt vmcnt(6)" ::: "memory");  // (the prefetch and the context load pending)
-				if (lane == 0 && wave != VP8G_TEST_STALL_WAVE)
-					__hip_atomic_store(prog + wave, (g << kProgShift) + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 			}
 			STAMP(4);
 
@@ -1491,7 +1089,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 				// unfiltered: MB(r, c) is final once reconstructed; role 0 stores luma row l, role 1 chroma
 				// row l & 7 of plane l >> 3
 				const uint8_t* const srcY = tY + (4 + l) * kTP + slot * 16;
-				ya0 = ld2x32(srcY), yb0 = ld2x32(srcY + 8);
+				ya0 = ld64(srcY), yb0 = ld64(srcY + 8);
 				const int p = l >> 3, row = l & 7;
 				cv1 = ldc64(tC + p * kCV + (4 + row) * kTP + slot * 8);
 				sy0 = srcY, sc1 = tC + p * kCV + (4 + row) * kTP + slot * 8;
@@ -1504,7 +1102,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 				                u32x2& ya, u32x2& yb, u32x2& cv, const uint8_t*& srcY, const uint8_t*& srcC) {
 					const bool okc = act && (ln < 4 || c > 0);
 					srcY = wq + __builtin_amdgcn_ubfe(sYw, sl16, 16u);
-					ya = ld2x32(srcY), yb = ld2x32(srcY + 8);
+					ya = ld64(srcY), yb = ld64(srcY + 8);
 					oY = okc ? fY + t * 16u : kNoStore;
 					const int kr = ln < 12 ? ln : ln - 12;
 					const bool okcc = act && (kr < 4 || c > 0);
@@ -1550,13 +1148,8 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 				cutY(oY0, cY0, nY0, bY0), cutY(oY1, cY1, nY1, bY1);
 				cutC(oC0, cC0, nC0, bC0), cutC(oC1, cC1, nC1, bC1);
 			}
-			if constexpr (VP8G_CTX_FIRST != 0) {
-				__builtin_amdgcn_raw_buffer_store_b128(u32x4{ya1.x, ya1.y, yb1.x, yb1.y}, rQ, (int)qY, 0, kCpolSc1);
-				__builtin_amdgcn_raw_buffer_store_b64(qCv, rQ, (int)qC, 0, kCpolSc1);
-				__builtin_amdgcn_raw_buffer_store_b64(recv, rQ, (int)(h == 3 && act && l < 4 ? __umul24(cu, (uint32_t)kCtxBytesPerCol) + 8u * (uint32_t)l : kNoStore), 0,
-				                                      kCpolSc1);
-			}
-			if constexpr (kPair) {
+			{
+				// The pixel stores, paired over two MB columns (pair_swap above).
 				// piece columns and the last column a role stores itself (the last MB's rows below its top
 				// strip go out with its own stores below)
 				// (general instantiation: a last column cut by the right edge goes byte by byte, so the
@@ -1583,49 +1176,35 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 					if (near_end) sgl |= (col == lastc ? ~odd & bit : 0u) & (o < kNoStore ? bit : 0u);
 					held = cur;
 				};
-				if constexpr ((VP8G_QPAIR & 1) != 0) {
+				{  // role 0's luma row
 					const u32x4 cur = u32x4{ya0.x, ya0.y, yb0.x, yb0.y};
 					uint32_t oA, oB;
 					u32x4 dA, dB;
 					pair(oY0, cY0, lY0, 16u, cur, hY0, oA, dA, oB, dB, 1u);
-					qst128<kAuxS>(rY, oA, dA);
-					qst128<kAuxS>(rY, oB, dB);
-				} else {
-					qst128<kAuxS>(rY, oY0, u32x4{ya0.x, ya0.y, yb0.x, yb0.y});
+					qst128(rY, oA, dA);
+					qst128(rY, oB, dB);
 				}
-				if (!VP8G_Y1_SKIP || __ballot(oY1 != kNoStore) != 0ull) qst128<kAuxS>(rY, oY1, u32x4{ya1.x, ya1.y, yb1.x, yb1.y});
-				if constexpr ((VP8G_QPAIR & 2) != 0) {
+				qst128(rY, oY1, u32x4{ya1.x, ya1.y, yb1.x, yb1.y});
+				{  // both roles' chroma rows
 					uint32_t oA, oB, oA1, oB1;
 					u32x2 dA, dB, dA1, dB1;
 					pair(oC0, cC0, lC0, 8u, cv0, hC0, oA, dA, oB, dB, 2u);
 					pair(oC1, cC1, lC1, 8u, cv1, hC1, oA1, dA1, oB1, dB1, 4u);
-					qst64<kAuxS>(rC, oA, dA);
-					qst64<kAuxS>(rC, oB, dB);
-					qst64<kAuxS>(rC, oA1, dA1);
-					qst64<kAuxS>(rC, oB1, dB1);
-				} else {
-					qst64<kAuxS>(rC, oC0, cv0);
-					qst64<kAuxS>(rC, oC1, cv1);
+					qst64(rC, oA, dA);
+					qst64(rC, oB, dB);
+					qst64(rC, oA1, dA1);
+					qst64(rC, oB1, dB1);
 				}
 				if (near_end && __ballot(sgl != 0u) != 0ull) {  // (a quarter at its last column: rare)
-					if constexpr ((VP8G_QPAIR & 1) != 0) qst128<kAuxS>(rY, (sgl & 1u) ? oY0 : kNoStore, u32x4{ya0.x, ya0.y, yb0.x, yb0.y});
-					if constexpr ((VP8G_QPAIR & 2) != 0) {
-						qst64<kAuxS>(rC, (sgl & 2u) ? oC0 : kNoStore, cv0);
-						qst64<kAuxS>(rC, (sgl & 4u) ? oC1 : kNoStore, cv1);
-					}
+					qst128(rY, (sgl & 1u) ? oY0 : kNoStore, u32x4{ya0.x, ya0.y, yb0.x, yb0.y});
+					qst64(rC, (sgl & 2u) ? oC0 : kNoStore, cv0);
+					qst64(rC, (sgl & 4u) ? oC1 : kNoStore, cv1);
 				}
-			} else {
-				qst128<kAuxS>(rY, oY0, u32x4{ya0.x, ya0.y, yb0.x, yb0.y});
-				qst128<kAuxS>(rY, oY1, u32x4{ya1.x, ya1.y, yb1.x, yb1.y});
-				qst64<kAuxS>(rC, oC0, cv0);
-				qst64<kAuxS>(rC, oC1, cv1);
 			}
-			if constexpr (VP8G_CTX_FIRST == 0) {
-				__builtin_amdgcn_raw_buffer_store_b128(u32x4{ya1.x, ya1.y, yb1.x, yb1.y}, rQ, (int)qY, 0, kCpolSc1);
-				__builtin_amdgcn_raw_buffer_store_b64(qCv, rQ, (int)qC, 0, kCpolSc1);
-				__builtin_amdgcn_raw_buffer_store_b64(recv, rQ, (int)(h == 3 && act && l < 4 ? __umul24(cu, (uint32_t)kCtxBytesPerCol) + 8u * (uint32_t)l : kNoStore), 0,
-				                                      kCpolSc1);
-			}
+			// quarter 3's context -> device memory (issued every step: the waits count them)
+			__builtin_amdgcn_raw_buffer_store_b128(u32x4{ya1.x, ya1.y, yb1.x, yb1.y}, rQ, (int)qY, 0, kCpolSc1);
+			__builtin_amdgcn_raw_buffer_store_b64(qCv, rQ, (int)qC, 0, kCpolSc1);
+			__builtin_amdgcn_raw_buffer_store_b64(recv, rQ, (int)(h == 3 && act && l < 4 ? __umul24(cu, (uint32_t)kCtxBytesPerCol) + 8u * (uint32_t)l : kNoStore), 0, kCpolSc1);
 			if (!kWP && !wp && __ballot((nY0 | nY1 | nC0 | nC1) != 0u) != 0ull) {
 				for (uint32_t q = 0; q < nY0; q++) outY[bY0 + q] = sy0[q];
 				for (uint32_t q = 0; q < nY1; q++) outY[bY1 + q] = sy1[q];
@@ -1640,7 +1219,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 				{
 					const int trow = 4 + l;
 					const uint8_t* const src = tY + trow * kTP + slot * 16;
-					const u32x2 lo = ld2x32(src), hi = ld2x32(src + 8);
+					const u32x2 lo = ld64(src), hi = ld64(src + 8);
 					const bool to_ctx = own && trow >= 16 && !last_row;
 					const uint32_t eo = kCtxRecBytes + (uint32_t)(trow - 16) * 16u;
 					if (to_ctx && h < 3) st128(rout + __umul24(m0, (uint32_t)kCtxBytesPerCol) + eo, u32x4{lo.x, lo.y, hi.x, hi.y});
@@ -1649,7 +1228,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 					const uint32_t prow = y0 + (uint32_t)trow - 4u, off = __umul24(prow, sy) + cu * 16u;
 					const bool vis = own && !to_ctx && prow < H;
 					const bool full = cu * 16u + 16u <= W;
-					qst128<kAuxS>(rY, vis && (kWP || full) ? off : kNoStore, u32x4{lo.x, lo.y, hi.x, hi.y});
+					qst128(rY, vis && (kWP || full) ? off : kNoStore, u32x4{lo.x, lo.y, hi.x, hi.y});
 					if (!kWP && !wp && vis && !full)
 						for (uint32_t q = 0, n = min(W - cu * 16u, 16u); q < n; q++) outY[off + q] = src[q];
 				}
@@ -1664,7 +1243,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 					const uint32_t prow = cy0 + (uint32_t)trow - 4u, off = (p ? vofs : 0u) + __umul24(prow, suv) + cu * 8u;
 					const bool vis = own && !to_ctx && prow < CH;
 					const bool full = cu * 8u + 8u <= CW;
-					qst64<kAuxS>(rC, vis && (kWP || full) ? off : kNoStore, lo);
+					qst64(rC, vis && (kWP || full) ? off : kNoStore, lo);
 					if (!kWP && !wp && vis && !full)
 						for (uint32_t q = 0, n = min(CW - cu * 8u, 8u); q < n; q++) outU[off + q] = src[q];
 				}
@@ -1675,20 +1254,11 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 #endif
 			STAMP(6);
 
-			// ---------------------------------------------- publish progress (one step late)
+			// ---------------------------------------------- end of the step
+			// (its progress was published after the prefetch, above: the step's stores are left in flight,
+			// and the next step's publish waits for them)
 			PRIO_AFTER(7, 6);
-			// (the wait counts a step's vector-memory operations: at least this step's, so every older one)
-			if constexpr (VP8G_PUB_AT != 0) {
-			} else if constexpr (qvmem_per_step<kPair>() == 13) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
-			else if constexpr (qvmem_per_step<kPair>() == 14) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-			else if constexpr (qvmem_per_step<kPair>() == 15) asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
-			else {
-				static_assert(qvmem_per_step<kPair>() == 16, "the wait below counts a step's vector-memory operations");
-				asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-			}
 			asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-			if (VP8G_PUB_AT == 0 && lane == 0 && wave != VP8G_TEST_STALL_WAVE)
-				__hip_atomic_store(prog + wave, (g << kProgShift) + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 			STAMP(7);
 		}
 		// end of the quad: every store acknowledged, then all T steps
