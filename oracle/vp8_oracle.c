@@ -380,7 +380,24 @@ static void or_lf_params(const Vp8DecodedFrame* d, uint32_t mb, int* E, int* I, 
 	*T = (lvl >= 40) ? 2 : (lvl >= 15 ? 1 : 0);
 }
 
-int oracle_loopfilter(uint8_t* y, uint8_t* u, uint8_t* v, const Vp8DecodedFrame* d) {
+/* Census of one edge before it is filtered (the positions of an edge do not touch each other's
+ * pixels, so counting the whole edge first sees each position as or_edge will): per kind, [0] mask
+ * fail, [1] mask pass with hev, [2] mask pass without hev (the simple filter has no hev: [0], [2]). */
+static void or_edge_census(const uint8_t* q0, int along, int step, int n, int kind, int limit_or_E, int I, int T,
+                           uint64_t cn[3][3]) {
+	for (int i = 0; i < n; i++, q0 += along) {
+		if (kind == 0) cn[0][or_simple_ok(q0, step, limit_or_E) ? 2 : 0]++;
+		else if (!or_normal_ok(q0, step, limit_or_E, I)) cn[kind][0]++;
+		else cn[kind][or_hev(q0, step, T) ? 1 : 2]++;
+	}
+}
+static inline void or_walk_edge(uint64_t (*cn)[3], uint8_t* q0, int along, int step, int n, int kind, int limit_or_E, int I,
+                                int T) {
+	if (cn) or_edge_census(q0, along, step, n, kind, limit_or_E, I, T, cn);
+	or_edge(q0, along, step, n, kind, limit_or_E, I, T);
+}
+
+static int or_lf_walk(uint8_t* y, uint8_t* u, uint8_t* v, const Vp8DecodedFrame* d, uint64_t (*cn)[3]) {
 	if (!y || !u || !v || !d) {
 		errno = EINVAL;
 		return -1;
@@ -398,37 +415,60 @@ int oracle_loopfilter(uint8_t* y, uint8_t* u, uint8_t* v, const Vp8DecodedFrame*
 			uint8_t* pv = v + (size_t)r * 8 * cs + c * 8;
 			if (d->lf_use_simple) { /* luma only, reference vp8_loopfilter.c:228-244 */
 				const int mbl = (E + 2) * 2 + I, bl = E * 2 + I;
-				if (c) or_edge(py, ys, 1, 16, 0, mbl, 0, 0);
+				if (c) or_walk_edge(cn, py, ys, 1, 16, 0, mbl, 0, 0);
 				if (inner)
-					for (int k = 4; k < 16; k += 4) or_edge(py + k, ys, 1, 16, 0, bl, 0, 0);
-				if (r) or_edge(py, 1, ys, 16, 0, mbl, 0, 0);
+					for (int k = 4; k < 16; k += 4) or_walk_edge(cn, py + k, ys, 1, 16, 0, bl, 0, 0);
+				if (r) or_walk_edge(cn, py, 1, ys, 16, 0, mbl, 0, 0);
 				if (inner)
-					for (int k = 4; k < 16; k += 4) or_edge(py + k * ys, 1, ys, 16, 0, bl, 0, 0);
+					for (int k = 4; k < 16; k += 4) or_walk_edge(cn, py + k * ys, 1, ys, 16, 0, bl, 0, 0);
 			} else { /* normal, reference vp8_loopfilter.c:245-277 */
 				if (c) {
-					or_edge(py, ys, 1, 16, 1, E + 2, I, T);
-					or_edge(pu, cs, 1, 8, 1, E + 2, I, T);
-					or_edge(pv, cs, 1, 8, 1, E + 2, I, T);
+					or_walk_edge(cn, py, ys, 1, 16, 1, E + 2, I, T);
+					or_walk_edge(cn, pu, cs, 1, 8, 1, E + 2, I, T);
+					or_walk_edge(cn, pv, cs, 1, 8, 1, E + 2, I, T);
 				}
 				if (inner) {
-					for (int k = 4; k < 16; k += 4) or_edge(py + k, ys, 1, 16, 2, E, I, T);
-					or_edge(pu + 4, cs, 1, 8, 2, E, I, T);
-					or_edge(pv + 4, cs, 1, 8, 2, E, I, T);
+					for (int k = 4; k < 16; k += 4) or_walk_edge(cn, py + k, ys, 1, 16, 2, E, I, T);
+					or_walk_edge(cn, pu + 4, cs, 1, 8, 2, E, I, T);
+					or_walk_edge(cn, pv + 4, cs, 1, 8, 2, E, I, T);
 				}
 				if (r) {
-					or_edge(py, 1, ys, 16, 1, E + 2, I, T);
-					or_edge(pu, 1, cs, 8, 1, E + 2, I, T);
-					or_edge(pv, 1, cs, 8, 1, E + 2, I, T);
+					or_walk_edge(cn, py, 1, ys, 16, 1, E + 2, I, T);
+					or_walk_edge(cn, pu, 1, cs, 8, 1, E + 2, I, T);
+					or_walk_edge(cn, pv, 1, cs, 8, 1, E + 2, I, T);
 				}
 				if (inner) {
-					for (int k = 4; k < 16; k += 4) or_edge(py + k * ys, 1, ys, 16, 2, E, I, T);
-					or_edge(pu + 4 * cs, 1, cs, 8, 2, E, I, T);
-					or_edge(pv + 4 * cs, 1, cs, 8, 2, E, I, T);
+					for (int k = 4; k < 16; k += 4) or_walk_edge(cn, py + k * ys, 1, ys, 16, 2, E, I, T);
+					or_walk_edge(cn, pu + 4 * cs, 1, cs, 8, 2, E, I, T);
+					or_walk_edge(cn, pv + 4 * cs, 1, cs, 8, 2, E, I, T);
 				}
 			}
 		}
 	}
 	return 0;
+}
+
+int oracle_loopfilter(uint8_t* y, uint8_t* u, uint8_t* v, const Vp8DecodedFrame* d) { return or_lf_walk(y, u, v, d, NULL); }
+
+/* The same walk on copies of the planes, counting every edge position it visits into counts[kind]
+ * (kind 0 simple, 1 normal MB edge, 2 normal sub-block edge; cells as or_edge_census): what a set of
+ * test inputs makes the filter do.  counts is added to, not cleared. */
+int oracle_loopfilter_census(const uint8_t* y, const uint8_t* u, const uint8_t* v, const Vp8DecodedFrame* d,
+                             uint64_t counts[3][3]) {
+	if (!y || !u || !v || !d || !counts) {
+		errno = EINVAL;
+		return -1;
+	}
+	const size_t ysz = (size_t)d->mb_cols * 16 * d->mb_rows * 16, csz = ysz / 4;
+	uint8_t* b = (uint8_t*)malloc(ysz + 2 * csz);
+	if (!b) {
+		errno = ENOMEM;
+		return -1;
+	}
+	memcpy(b, y, ysz), memcpy(b + ysz, u, csz), memcpy(b + ysz + csz, v, csz);
+	const int rc = or_lf_walk(b, b + ysz, b + ysz + csz, d, counts);
+	free(b);
+	return rc;
 }
 
 int oracle_recon_padded(const Vp8DecodedFrame* d, uint8_t* y, uint8_t* u, uint8_t* v, int filtered) {

@@ -26,6 +26,12 @@ int oracle_recon_padded(const Vp8DecodedFrame* d, uint8_t* y, uint8_t* u, uint8_
 /* m07 alone, in place on a padded image (stride = width). */
 int oracle_loopfilter(uint8_t* y, uint8_t* u, uint8_t* v, const Vp8DecodedFrame* d);
 
+/* What oracle_loopfilter does on these planes (copies are filtered): edge positions visited, added
+ * into counts[kind][cell]; kind 0 simple, 1 normal MB edge, 2 normal sub-block edge; cell 0 mask
+ * fail, 1 mask pass with hev, 2 mask pass without hev (the simple filter uses cells 0 and 2). */
+int oracle_loopfilter_census(const uint8_t* y, const uint8_t* u, const uint8_t* v, const Vp8DecodedFrame* d,
+                             uint64_t counts[3][3]);
+
 /* Full m06(+m07) with crop into a malloc()ed cropped I420 image (free with oracle_image_free). */
 int oracle_reconstruct(const Vp8KeyFrameHeader* kf, const Vp8DecodedFrame* d, Yuv420Image* out, int filtered);
 void oracle_image_free(Yuv420Image* img);

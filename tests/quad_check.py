@@ -8,7 +8,10 @@ heights giving 1..19 MB rows -- last quads of one, two, three and four rows -- a
 (cropped bottom rows); ODD_SIZES adds widths that cut the right MB's pieces and rows that start
 unaligned (stride = width: the general instantiation's byte path).  All synthetic
 profiles (segments, loop-filter deltas, simple and normal filter, +-2114 coefficients), filtered and
-unfiltered, in a scrambled order with one slot in eight left empty."""
+unfiltered, in a scrambled order with one slot in eight left empty.
+
+run(frames=...) decodes a caller's frames instead (directed_frames(): every kind of tests/directed.py
+at four of the sizes, filtered at two of them); want_quad=False expects the pairs chain (VP8G_QUAD=0)."""
 import pathlib
 import sys
 
@@ -24,15 +27,28 @@ SIZES = [(16, 16), (16, 48), (32, 24), (160, 64), (48, 112), (1024, 80), (160, 9
 ODD_SIZES = SIZES[:5] + [(1, 1), (17, 16), (33, 50), (100, 70), (250, 130), (1000, 37), (8, 8), (24, 200), (52, 300), (15, 33)]
 
 
-def run(n=1800, seed=0x0A4D, launches=1, want_split=False, sizes=SIZES):
+def directed_frames(sizes, seed=11):
+    """Every directed kind at four of `sizes` (kind k: sizes k, k + 3, k + 6, k + 9 mod len); the frames
+    at even positions are decoded unfiltered by run(), those at odd positions filtered."""
+    import directed
+    return [directed.build(kind, *sizes[(k + 3 * r) % len(sizes)], seed + 4 * k + r)
+            for k, kind in enumerate(directed.KINDS) for r in range(4)]
+
+
+def run(n=1800, seed=0x0A4D, launches=1, want_split=False, sizes=SIZES, frames=None, want_quad=True):
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(seed)
-    frames = [vp8g.synth_frame(*sizes[i % len(sizes)], seed ^ (i * 0x9E37), profile=i % 3) for i in range(40)]
-    W = max(w for w, _ in sizes)
-    H = max(h for _, h in sizes)
+    sizes_only = frames is None
+    if sizes_only:
+        frames = [vp8g.synth_frame(*sizes[i % len(sizes)], seed ^ (i * 0x9E37), profile=i % 3) for i in range(40)]
+        W = max(w for w, _ in sizes)
+        H = max(h for _, h in sizes)
+    else:
+        W = max(f.width for f in frames)
+        H = max(f.height for f in frames)
     b = vp8g_batch.DeviceBatch(n, W, H, dev)
     b.out.fill_(0xA5)
-    pick = rng.integers(0, len(frames), n)
+    pick = rng.integers(0, len(frames), n) if sizes_only else rng.permutation(n) % len(frames)  # (a caller's frames: every one decoded)
     empty = set(rng.choice(n, n // 8, replace=False).tolist())
     for i in range(n):
         if i not in empty:
@@ -45,8 +61,10 @@ def run(n=1800, seed=0x0A4D, launches=1, want_split=False, sizes=SIZES):
         if b.status_word() != 0:
             return [f"status {b.status_word()}"]
         mode = b.launch_mode()
-        if not (mode & vp8g.MODE_CHAIN and mode & vp8g.MODE_QUAD) or (want_split and not mode & vp8g.MODE_MIRROR_SPLIT):
-            return [f"launch mode {mode}: not the quad chain{' with the mirror split' if want_split else ''}"]
+        if mode is None:
+            return ["launch mode unknown: the loaded library has no vp8g_last_launch_mode"]
+        if not (mode & vp8g.MODE_CHAIN and bool(mode & vp8g.MODE_QUAD) == want_quad) or (want_split and not mode & vp8g.MODE_MIRROR_SPLIT):
+            return [f"launch mode {mode}: not the {'quad' if want_quad else 'pairs'} chain{' with the mirror split' if want_split else ''}"]
     exp, bad = {}, []
     for i in range(n):
         if i in empty:
@@ -55,18 +73,33 @@ def run(n=1800, seed=0x0A4D, launches=1, want_split=False, sizes=SIZES):
         key = (j, bool(j % 2))
         if key not in exp:
             exp[key] = vp8g.oracle_reconstruct(frames[j], bool(j % 2))
-        if b.frame_output(i)[:len(exp[key])] != exp[key]:
+        got = b.frame_output(i)[:len(exp[key])]
+        if got != exp[key]:
+            if not bad:  # the first differing slot: its frame, plane and byte
+                f, k = frames[j], int(np.flatnonzero(np.frombuffer(got, np.uint8) != np.frombuffer(exp[key], np.uint8))[0])
+                ysz, csz = f.width * f.height, ((f.width + 1) // 2) * ((f.height + 1) // 2)
+                plane, o = ("Y", k) if k < ysz else (("U", k - ysz) if k < ysz + csz else ("V", k - ysz - csz))
+                first = (f"first: slot {i} frame {j} {f.width}x{f.height} filtered={key[1]} plane {plane} byte {o} "
+                         f"got {got[k]} expected {exp[key][k]}")
             bad.append(i)
     for i in sorted(empty)[:16]:
         if b.frame_output(i) != b"\xa5" * b.i420:
             bad.append(f"empty slot {i} written")
     for f in frames:
         f.free()
+    if bad and isinstance(bad[0], int):
+        bad.insert(0, first)
     return bad
 
 
 if __name__ == "__main__":
     import os
-    bad = run(launches=2, want_split=os.environ.get("VP8G_SPLITCHAIN") == "1",
-              sizes=ODD_SIZES if "--odd" in sys.argv else SIZES)
+    sizes = ODD_SIZES if "--odd" in sys.argv else SIZES
+    if "--directed" in sys.argv:
+        sys.path.insert(0, str(ROOT / "tests"))
+        bad = run(n=1200, seed=0xD1A, launches=2, want_split=os.environ.get("VP8G_SPLITCHAIN") == "1",
+                  frames=directed_frames(sizes), want_quad=os.environ.get("VP8G_QUAD") != "0")
+        print("OK" if not bad else f"BAD {len(bad)}: {bad[:8]}")
+        sys.exit(0)
+    bad = run(launches=2, want_split=os.environ.get("VP8G_SPLITCHAIN") == "1", sizes=sizes)
     print("OK" if not bad else f"BAD {len(bad)}: {bad[:8]}")

@@ -239,6 +239,7 @@ def test_device_batch_512_uhd_bench_launch(vp8g, digests):
     b, bad = run_batch(vp8g, UHD, 512, True, digests, slot0=0)
     assert not bad, f"{len(bad)} of 512 slots differ, e.g. {bad[:8]}"
     mode = b.launch_mode()  # (the quad chain, as bench.py's launch)
+    assert mode is not None, "the loaded library cannot report its launch mode"
     assert mode & vp8g.MODE_CHAIN and mode & vp8g.MODE_QUAD, mode
     # (the mirror split needs at most two frames per workgroup: 512 frames on >= 256 CUs, as on
     # MI355X; a part with fewer CUs decodes the same batch without it -- ADVICE r05)
@@ -350,6 +351,7 @@ def test_chain_two_frame_interleave(vp8g, w, h):
     torch.cuda.synchronize()
     assert b.status_word() == 0
     mode = b.launch_mode()
+    assert mode is not None, "the loaded library cannot report its launch mode"
     assert mode & vp8g.MODE_CHAIN and mode & vp8g.MODE_INTERLEAVE, mode
     bad = [i for i, f in enumerate(frames) if b.frame_output(i) != vp8g.oracle_reconstruct(f, bool(i % 5))]
     assert not bad, f"{len(bad)} of {n} slots differ, e.g. {bad[:8]}"

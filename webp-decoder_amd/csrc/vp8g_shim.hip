@@ -533,6 +533,7 @@ int vp8g::make_desc(const Vp8KeyFrameHeader* kf, const Vp8DecodedFrame* d, int f
 
 VP8G_API int vp8g_decode_batch_device(const Vp8gFrameDesc* h_descs, const Vp8gFrameDesc* d_descs, uint32_t n,
                                       const Vp8gBatchArrays* arrays, uint8_t* d_out, void* stream, uint32_t waves) {
+	g_mode = 0u;  // (include/vp8g.h: a call that fails before its launch reports mode 0, also on the EINVAL returns below)
 	if (!h_descs || !d_descs || !arrays || !d_out || !arrays->status) {
 		errno = EINVAL;
 		return -1;
@@ -554,6 +555,7 @@ VP8G_API int vp8g_decode_batch_device(const Vp8gFrameDesc* h_descs, const Vp8gFr
 
 VP8G_API int vp8g_reconstruct_batch(const Vp8KeyFrameHeader* const* kfs, const Vp8DecodedFrame* const* frames, uint32_t n,
                                     int filtered, Yuv420Image* outs) {
+	g_mode = 0u;  // (include/vp8g.h: a call that fails before its launch reports mode 0, also on the EINVAL returns below)
 	if (!kfs || !frames || !outs || n == 0) {
 		errno = EINVAL;
 		return -1;
@@ -645,6 +647,7 @@ VP8G_API int vp8g_reconstruct_batch(const Vp8KeyFrameHeader* const* kfs, const V
 }
 
 VP8G_API int vp8_reconstruct_keyframe_yuv(const Vp8KeyFrameHeader* kf, const Vp8DecodedFrame* decoded, Yuv420Image* out) {
+	g_mode = 0u;
 	if (!kf || !decoded || !out) {
 		errno = EINVAL;
 		return -1;
@@ -654,6 +657,7 @@ VP8G_API int vp8_reconstruct_keyframe_yuv(const Vp8KeyFrameHeader* kf, const Vp8
 
 VP8G_API int vp8_reconstruct_keyframe_yuv_filtered(const Vp8KeyFrameHeader* kf, const Vp8DecodedFrame* decoded,
                                                    Yuv420Image* out) {
+	g_mode = 0u;
 	if (!kf || !decoded || !out) {
 		errno = EINVAL;
 		return -1;
@@ -662,6 +666,7 @@ VP8G_API int vp8_reconstruct_keyframe_yuv_filtered(const Vp8KeyFrameHeader* kf, 
 }
 
 VP8G_API int vp8_loopfilter_apply_keyframe(Yuv420Image* img, const Vp8DecodedFrame* d) {
+	g_mode = 0u;
 	if (!img || !d) {
 		errno = EINVAL;
 		return -1;

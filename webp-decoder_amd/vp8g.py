@@ -713,6 +713,36 @@ def oracle_reconstruct(f: Frame, filtered: bool) -> bytes:
     return buf.tobytes()
 
 
+LF_KINDS = ("simple", "normal MB edge", "normal sub-block edge")
+LF_CELLS = ("mask fail", "pass, hev", "pass, no hev")
+
+
+def oracle_loopfilter_census(planes, frame: Vp8DecodedFrame) -> np.ndarray:
+    """oracle_loopfilter_census on padded planes (y, u, v as uint8 arrays; they are not modified):
+    uint64[3][3] of edge positions the oracle's loop-filter walk visits, [LF_KINDS][LF_CELLS]."""
+    lib = oracle_lib()
+    # bound here, not in oracle_lib(): a liboracle.so built before the census existed still serves every other call
+    if not hasattr(lib, "oracle_loopfilter_census"):
+        raise OSError("oracle/liboracle.so has no oracle_loopfilter_census (rebuild it: `make` at the repo root)")
+    lib.oracle_loopfilter_census.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Vp8DecodedFrame), C.c_void_p]
+    counts = np.zeros((3, 3), dtype=np.uint64)
+    y, u, v = [np.ascontiguousarray(p, dtype=np.uint8) for p in planes]
+    if lib.oracle_loopfilter_census(y.ctypes.data, u.ctypes.data, v.ctypes.data, C.byref(frame),
+                                             counts.ctypes.data) != 0:
+        raise RuntimeError("oracle census failed")
+    return counts
+
+
+def oracle_frame_census(f: Frame) -> np.ndarray:
+    """The census of the loop filter on the frame's own unfiltered reconstruction (what the filtered
+    decode of `f` makes the filter do)."""
+    w, h = int(f.frame.mb_cols) * 16, int(f.frame.mb_rows) * 16
+    y, u, v = np.empty(w * h, np.uint8), np.empty(w * h // 4, np.uint8), np.empty(w * h // 4, np.uint8)
+    if oracle_lib().oracle_recon_padded(C.byref(f.frame), y.ctypes.data, u.ctypes.data, v.ctypes.data, 0) != 0:
+        raise RuntimeError("oracle failed")
+    return oracle_loopfilter_census((y, u, v), f.frame)
+
+
 def ref_lib():
     """oracle/_ref/libref.so: the reference's own m01-m07 compiled here (may be absent)."""
     lib = _load("ref", REPO_DIR / "oracle" / "_ref" / "libref.so")

@@ -116,12 +116,14 @@ class DeviceBatch:
         torch.cuda.synchronize(self.dev)
         return self.digest_buf.cpu().numpy().view(np.uint64).copy()
 
-    def launch_mode(self) -> int:
-        """VP8G_MODE_* bits of this thread's last launch (include/vp8g.h vp8g_last_launch_mode); -1 when
-        the loaded library predates the symbol (an older build under VP8G_LIB)."""
+    def launch_mode(self) -> int | None:
+        """VP8G_MODE_* bits of this thread's last launch (include/vp8g.h vp8g_last_launch_mode); None when
+        the loaded library predates the symbol (an older build under VP8G_LIB).  None, not a number: every
+        bit of -1 is set, so `mode & MODE_QUAD` would hold for a library that cannot say; `None & bit`
+        raises instead."""
         lib = vp8g.gpu_lib()
         if not hasattr(lib, "vp8g_last_launch_mode"):
-            return -1
+            return None
         return int(lib.vp8g_last_launch_mode())
 
     def status_word(self) -> int:
