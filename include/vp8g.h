@@ -363,7 +363,8 @@ int vp8g_encode_batch_device(const Vp8gEncDesc* h_descs, const Vp8gEncDesc* d_de
  * ceil(window / 2) to ceil(target / 2).  RGB of a scaled picture is DEFINED as the encoder
  * (vp8g_encode_batch_device, fancy upsampling) run on that scaled I420 -- deliberately not
  * `dwebp -ppm -scale`, which rescales chroma straight to luma resolution and skips the fancy
- * upsampler. */
+ * upsampler.  vp8g_decode_webp_batch_tensor (below) is the on-device route to it: scaled I420 ->
+ * RGB tensor with no host copy. */
 typedef struct {
 	uint32_t crop_left, crop_top, crop_w, crop_h;
 	uint32_t scaled_w, scaled_h;
@@ -429,6 +430,74 @@ int yuv420_rescale(const Yuv420Image* src, const Vp8gScaleOpt* opt, Yuv420Image*
 int vp8g_decode_webp_batch_scaled(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
                                   const Vp8gScaleOpt* opts, uint32_t n_opts, Yuv420Image* outs, int* status);
 
+/* ---- Decode into device-resident RGB tensors ------------------------------ */
+
+/* One dense tensor for a batch of same-size pictures, left on the device in the form a model reads.
+ *   RGB     exactly the bytes of VP8G_ENC_RGB (fancy 4:2:0 upsampling, libwebp's VP8YuvToRgb);
+ *           VP8G_T_BGR swaps the channel order.
+ *   dtype   VP8G_T_U8: those bytes (scale and bias ignored).  VP8G_T_F32: (float)u8 * scale[c] + bias[c],
+ *           a round-to-nearest multiply and then a round-to-nearest add (never fused); c is the OUTPUT
+ *           channel (with VP8G_T_BGR, scale[0] applies to B).  VP8G_T_F16 / VP8G_T_BF16: that float
+ *           rounded once, to nearest-even.
+ *   layout  VP8G_T_NHWC (pixel-interleaved) or VP8G_T_NCHW (three planes per picture).
+ * Picture i of a batch starts at byte i * vp8g_tensor_slot_size() of the tensor; a slot start is in
+ * general not 16-byte aligned (3 x 3 uint8: 27-byte slots), only the base must be element-aligned. */
+#define VP8G_T_U8 0u
+#define VP8G_T_F16 1u
+#define VP8G_T_BF16 2u
+#define VP8G_T_F32 3u
+#define VP8G_T_NHWC 0u
+#define VP8G_T_NCHW 1u
+#define VP8G_T_BGR 1u /* flags */
+typedef struct {
+	uint32_t width, height;  /* of every picture of the tensor, 1 .. 16383 */
+	uint32_t dtype;          /* VP8G_T_U8 / F16 / BF16 / F32 */
+	uint32_t layout;         /* VP8G_T_NHWC / VP8G_T_NCHW */
+	uint32_t flags;          /* VP8G_T_BGR */
+	float scale[3], bias[3]; /* per output channel; finite (float dtypes) */
+} Vp8gTensorOpt;
+
+/* Per-image descriptor of the tensor kernel (built by vp8g_make_tensor_desc).  48 bytes. */
+typedef struct {
+	uint64_t src_y, src_u, src_v;  /* byte offsets of the source planes in the source buffer */
+	uint64_t dst;                  /* byte offset of the picture's slot in the output buffer */
+	uint32_t stride_y, stride_uv;  /* source plane strides */
+	uint32_t task0, ntasks;        /* this image's workgroup tasks in the launch */
+} Vp8gTensorDesc;
+
+/* Bytes of one picture of the tensor: 3 * width * height * element size.  0 + EINVAL for a NULL or
+ * invalid option (size 0 or beyond 16383, unknown dtype / layout / flag bit, non-finite scale or bias
+ * with a float dtype). */
+uint64_t vp8g_tensor_slot_size(const Vp8gTensorOpt* opt);
+
+/* Fill the descriptor of one opt->width x opt->height I420 image whose planes sit at src_* (strides
+ * stride_*) in the source buffer; its pixels go to dst_offset (a multiple of the element size; slot i
+ * of a dense tensor = i * vp8g_tensor_slot_size()) of the output buffer, its tasks start at task0.
+ * 0, or -1 + EINVAL. */
+int vp8g_make_tensor_desc(const Vp8gTensorOpt* opt, uint64_t src_y, uint64_t src_u, uint64_t src_v, uint32_t stride_y,
+                          uint32_t stride_uv, uint64_t dst_offset, uint32_t task0, Vp8gTensorDesc* out);
+
+/* Convert n device-resident I420 images to their slots of d_dst in one launch on `hip_stream`.
+ * h_descs / d_descs: host and device copies of the descriptors (tasks numbered image by image).
+ * Writes only the images' own slot bytes.  Asynchronous; 0 or -1 + errno (EINVAL: NULL pointer,
+ * invalid option, d_dst not aligned to the element size, inconsistent descriptors; EIO on a launch
+ * failure).  d_src may be the output of vp8g_scale_batch_device or of the reconstruction on the same
+ * stream, with no host copy in between. */
+int vp8g_tensor_batch_device(const Vp8gTensorDesc* h_descs, const Vp8gTensorDesc* d_descs, uint32_t n,
+                             const Vp8gTensorOpt* opt, const uint8_t* d_src, void* d_dst, void* hip_stream);
+
+/* vp8g_decode_webp_batch_ex / _scaled with the tensor as the sink: each chunk is reconstructed,
+ * scaled on the same stream when opts is given (n_opts = 1 or n; NULL / 0 = no scaling), and written
+ * to slot i of d_out (device memory, n slots) by the tensor kernel; only the chunks' status words
+ * come back to the host.  Returns after all device work is complete (the tensor is then usable from
+ * any stream).  A frame whose decoded (or scaled) size is not t->width x t->height, or whose scale
+ * options are invalid for it, gets status[i] = EINVAL; a frame that does not parse gets its errno;
+ * the slot of every failed frame is filled with zero bytes and the others still decode.  -1 + EINVAL
+ * for bad arguments (nothing is launched), -1 + EIO for a device failure. */
+int vp8g_decode_webp_batch_tensor(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                  const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, void* d_out,
+                                  int* status);
+
 /* Name of the last HIP error seen by this library in the calling thread ("" if none). */
 const char* vp8g_last_error(void);
 
@@ -443,8 +512,8 @@ const char* vp8g_last_error(void);
 #define VP8G_MODE_SPLIT_PARTS 16u /* each frame over several workgroups */
 uint32_t vp8g_last_launch_mode(void);
 
-/* ABI version of this header (bumped on any layout change; the scale API above is purely
- * additive -- new symbols and structures, no existing layout touched -- and keeps 5). */
+/* ABI version of this header (bumped on any layout change; the scale and tensor APIs above are
+ * purely additive -- new symbols and structures, no existing layout touched -- and keep 5). */
 #define VP8G_ABI_VERSION 5
 uint32_t vp8g_abi_version(void);
 

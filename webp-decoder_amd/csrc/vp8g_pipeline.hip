@@ -230,6 +230,7 @@ struct Slot {
 	std::vector<uint32_t> frames;  // frame indices of the chunk (packed data freed when the slot is reused)
 	std::vector<Vp8gFrameDesc> descs;
 	std::vector<Vp8gScaleDesc> sdescs;  // scaled decode: one per frame of the chunk
+	std::vector<Vp8gTensorDesc> tdescs;  // tensor sink: one per frame of the chunk
 	std::vector<Vp8gTokFrame> jobs;  // device m05
 	uint32_t status = 0;
 	std::vector<D2H> d2h;          // the chunk's downloads (issued by a Copier)
@@ -308,7 +309,7 @@ struct Copier {
 
 struct ChunkLayout {
 	uint64_t ym, uvm, seg, hasc, bm, masks, mboff, vals, cy, cu, cv, cy2, bits, jobs, desc, status, gctx, mbox, gprog, out,
-	    sdesc, sout, total;
+	    sdesc, sout, tdesc, total;
 };
 
 hipError_t grow(Slot& s, size_t need) {
@@ -334,8 +335,9 @@ constexpr double kDevNsPerByte = 850.0;    // device m05 latency per payload byt
 constexpr double kHostNsPerByte = 50.0;    // host m05 into the packed format, per payload byte and thread
 constexpr double kD2HNsPerByte = 0.085;    // download into fresh pageable images (~12 GB/s)
 // (rates measured on the box: tools/e2e_probe.py chunk traces, tools/hybrid_sweep.py; profiles/r02_hybrid.json)
+// download = false (the tensor sink: the pictures stay on the device) prices no download.
 void plan_frames(const ByteSpan* files, uint32_t n, bool tok, uint32_t threads, std::vector<uint8_t>& dev,
-                 std::vector<uint32_t>& order) {
+                 std::vector<uint32_t>& order, bool download = true) {
 	dev.assign(n, tok ? 1 : 0);
 	order.resize(n);
 	for (uint32_t i = 0; i < n; i++) order[i] = i;
@@ -345,6 +347,7 @@ void plan_frames(const ByteSpan* files, uint32_t n, bool tok, uint32_t threads, 
 	if (const char* e = getenv("VP8G_DEV_NS_PER_BYTE")) dev_per_b = atof(e);  // calibration knobs
 	if (const char* e = getenv("VP8G_HOST_NS_PER_BYTE")) host_per_b = atof(e);
 	if (const char* e = getenv("VP8G_D2H_NS_PER_BYTE")) d2h_per_b = atof(e);
+	if (!download) d2h_per_b = 0.0;
 	std::vector<double> outb(n, 0.0);  // I420 bytes (0 for a file whose header does not parse: it fails anyway)
 	for (uint32_t i = 0; i < n; i++) {
 		WebPContainer c;
@@ -397,9 +400,15 @@ VP8G_API int vp8g_plan_batch(const ByteSpan* files, uint32_t n, uint32_t threads
 // vp8g_decode_webp_batch_ex, and with `opts` (n_opts = 1 or n) vp8g_decode_webp_batch_scaled: each
 // chunk's frames are then cropped / downscaled on the device (vp8g_scale.hip) from the chunk's
 // reconstruction buffer into a second, small one, and only that is downloaded.
+// With `topt` (vp8g_decode_webp_batch_tensor; outs = NULL) the sink is the caller's device tensor:
+// each chunk's frames, scaled or not, are written to their slots of d_tensor by the tensor kernel
+// (vp8g_tensor.hip) on the chunk's stream, and only the chunk's status word is downloaded.
 static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
-                        const Vp8gScaleOpt* opts, uint32_t n_opts, Yuv420Image* outs, int* status) {
-	if (!files || !outs || n == 0 || (flags & ~(VP8G_BATCH_DEVICE_M05 | VP8G_BATCH_MULTI_PARTITION))) {
+                        const Vp8gScaleOpt* opts, uint32_t n_opts, Yuv420Image* outs, int* status,
+                        const Vp8gTensorOpt* topt = nullptr, uint8_t* d_tensor = nullptr) {
+	const uint64_t tslot = topt ? vp8g_tensor_slot_size(topt) : 0;
+	if (!files || (topt ? !d_tensor || !tslot || outs : !outs) || n == 0 ||
+	    (flags & ~(VP8G_BATCH_DEVICE_M05 | VP8G_BATCH_MULTI_PARTITION))) {
 		errno = EINVAL;
 		return -1;
 	}
@@ -431,7 +440,8 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 			if (cap_tok < chunk_mbs_tok) chunk_mbs_tok = cap_tok > floor_mbs ? cap_tok : floor_mbs;
 		}
 	}
-	for (uint32_t i = 0; i < n; i++) memset(&outs[i], 0, sizeof(outs[i]));
+	for (uint32_t i = 0; outs && i < n; i++) memset(&outs[i], 0, sizeof(outs[i]));
+	std::vector<uint8_t> live(n, 0);  // frame i has its output (an allocated image; a slot of the tensor)
 	if (!threads) threads = default_threads();
 	if (threads > n) threads = n;
 
@@ -443,7 +453,7 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 	if (tok) feed.tj.assign(n, TokJob{});
 	feed.err.assign(n, 0);
 	feed.ready.reset(new uint8_t[n]());
-	plan_frames(files, n, tok, threads, feed.dev, feed.order);
+	plan_frames(files, n, tok, threads, feed.dev, feed.order, topt == nullptr);
 	// VP8G_PIPE_TRACE=1: one stderr line per chunk (kind, frames, MBs, launch / retire times; diagnostics)
 	const bool trace = getenv("VP8G_PIPE_TRACE") && atoi(getenv("VP8G_PIPE_TRACE")) != 0;
 	const auto t_start = std::chrono::steady_clock::now();
@@ -497,7 +507,9 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 	};
 	auto alloc_out = [&](uint32_t i, uint32_t w, uint32_t h) -> int {
 		if (opts && vp8g_scaled_size(w, h, opt_of(i), &w, &h) != 0) return -1;
-		return vp8g::alloc_planes(&outs[i], w, h, false);
+		if (!topt && vp8g::alloc_planes(&outs[i], w, h, false) != 0) return -1;
+		live[i] = 1;
+		return 0;
 	};
 	auto finish_slot = [&](Slot& s) -> bool {  // wait for a slot's chunk; false on a device failure
 		if (!s.busy) return true;
@@ -569,6 +581,9 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 				uint32_t sw = 0, sh = 0;
 				if (feed.err[fi] == 0 && opts && vp8g_scaled_size(kf_of(fi).width, kf_of(fi).height, opt_of(fi), &sw, &sh) != 0)
 					feed.err[fi] = EINVAL;  // options that do not fit this frame: the others still decode
+				if (feed.err[fi] == 0 && topt &&
+				    ((opts ? sw : (uint32_t)kf_of(fi).width) != topt->width || (opts ? sh : (uint32_t)kf_of(fi).height) != topt->height))
+					feed.err[fi] = EINVAL;  // not the tensor's picture size
 				if (feed.err[fi] == 0) {
 					const Vp8DecodedFrame& f = f_of(fi);
 					if (!idx.empty() && mbs + f.mb_total > cmbs) break;
@@ -627,6 +642,7 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 			L.out = o, o = al256(o + outb);
 			L.sdesc = o, o = al256(o + (opts ? nf * sizeof(Vp8gScaleDesc) : 0));
 			L.sout = o, o = al256(o + soutb);
+			L.tdesc = o, o = al256(o + (topt ? nf * sizeof(Vp8gTensorDesc) : 0));
 			L.total = o;
 			const double tg = trace ? ms_now() : 0.0;
 			PTRY(grow(s, L.total), "hipMalloc(chunk)");
@@ -739,13 +755,13 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 			}
 			// -- scaled decode: crop / downscale the chunk's frames into the small buffer (same stream)
 			s.sdescs.clear();
+			std::vector<uint32_t> sj;  // chunk position of each scale descriptor
 			if (opts) {
 				uint64_t so = 0;
 				uint32_t task0 = 0;
-				std::vector<uint32_t> sj;  // chunk position of each scale descriptor
 				for (uint32_t j = 0; j < nf; j++) {
 					const Vp8gFrameDesc& fd = s.descs[j];
-					if (!outs[idx[j]].y) continue;  // (a frame that failed above)
+					if (!live[idx[j]]) continue;  // (a frame that failed above)
 					Vp8gScaleDesc sd;
 					if (vp8g_make_scale_desc(fd.width, fd.height, L.out + fd.out_y, L.out + fd.out_u, L.out + fd.out_v, fd.stride_y,
 					                         fd.stride_uv, opt_of(idx[j]), L.sout + so, task0, &sd) != 0) {
@@ -769,21 +785,56 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 						goto fail;
 					}
 				}
-				PTRY(hipEventRecord(s.kdone, stream), "event");
-				s.d2h.clear();
-				for (size_t q = 0; q < s.sdescs.size(); q++) {
-					const Vp8gScaleDesc& sd = s.sdescs[q];
-					Yuv420Image& img = outs[idx[sj[q]]];
-					const size_t ysz = (size_t)sd.width * sd.height, uvsz = (size_t)sd.p[1].dst_w * sd.p[1].dst_h;
-					s.d2h.push_back({img.y, d + sd.p[0].dst, ysz});
-					s.d2h.push_back({img.u, d + sd.p[1].dst, uvsz});
-					s.d2h.push_back({img.v, d + sd.p[2].dst, uvsz});
+			}
+			// -- tensor sink: the chunk's frames (scaled or as reconstructed) into their slots of the
+			// caller's tensor (same stream; nothing but the status word comes back)
+			s.tdescs.clear();
+			if (topt) {
+				auto add = [&](uint32_t fi, uint64_t y, uint64_t u, uint64_t v, uint32_t sy, uint32_t suv) {
+					Vp8gTensorDesc td;
+					if (vp8g_make_tensor_desc(topt, y, u, v, sy, suv, (uint64_t)fi * tslot, 0, &td) != 0) {
+						feed.err[fi] = EINVAL;  // (cannot happen: the size was checked when the chunk was gathered)
+						return;
+					}
+					td.task0 = (uint32_t)s.tdescs.size() * td.ntasks;  // (every image of a tensor has the same task count)
+					s.tdescs.push_back(td);
+				};
+				if (opts) {
+					for (size_t q = 0; q < s.sdescs.size(); q++) {
+						const Vp8gScaleDesc& sd = s.sdescs[q];
+						add(idx[sj[q]], sd.p[0].dst, sd.p[1].dst, sd.p[2].dst, sd.p[0].dst_stride, sd.p[1].dst_stride);
+					}
+				} else {
+					for (uint32_t j = 0; j < nf; j++) {
+						const Vp8gFrameDesc& fd = s.descs[j];
+						if (live[idx[j]]) add(idx[j], L.out + fd.out_y, L.out + fd.out_u, L.out + fd.out_v, fd.stride_y, fd.stride_uv);
+					}
+				}
+				if (!s.tdescs.empty()) {
+					PTRY(hipMemcpyAsync(d + L.tdesc, s.tdescs.data(), s.tdescs.size() * sizeof(Vp8gTensorDesc), hipMemcpyHostToDevice,
+					                    stream),
+					     "H2D");
+					if (vp8g_tensor_batch_device(s.tdescs.data(), (const Vp8gTensorDesc*)(d + L.tdesc), (uint32_t)s.tdescs.size(), topt,
+					                             d, d_tensor, stream) != 0) {
+						he = hipGetLastError();
+						if (he == hipSuccess) he = hipErrorInvalidValue;
+						where = "tensor launch";
+						goto fail;
+					}
 				}
 			}
+			PTRY(hipEventRecord(s.kdone, stream), "event");
 			// -- D2H into the callers' images, by this kind's Copier once the kernels are done
-			if (!opts) PTRY(hipEventRecord(s.kdone, stream), "event");
-			if (!opts) s.d2h.clear();
-			for (uint32_t j = 0; j < nf && !opts; j++) {
+			s.d2h.clear();
+			for (size_t q = 0; q < s.sdescs.size() && !topt; q++) {
+				const Vp8gScaleDesc& sd = s.sdescs[q];
+				Yuv420Image& img = outs[idx[sj[q]]];
+				const size_t ysz = (size_t)sd.width * sd.height, uvsz = (size_t)sd.p[1].dst_w * sd.p[1].dst_h;
+				s.d2h.push_back({img.y, d + sd.p[0].dst, ysz});
+				s.d2h.push_back({img.u, d + sd.p[1].dst, uvsz});
+				s.d2h.push_back({img.v, d + sd.p[2].dst, uvsz});
+			}
+			for (uint32_t j = 0; j < nf && !opts && !topt; j++) {
 				const Vp8gFrameDesc& fd = s.descs[j];
 				Yuv420Image& img = outs[idx[j]];
 				if (!img.y) continue;
@@ -803,6 +854,15 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 		for (Slot& s : slots)
 			if (!finish_slot(s)) goto fail;
 		defer_release = false;
+		if (topt) {  // tensor sink: the slot of every failed frame reads as zero bytes
+			bool any = false;
+			for (uint32_t i = 0; i < n; i++)
+				if (feed.err[i]) {
+					PTRY(hipMemsetAsync(d_tensor + (uint64_t)i * tslot, 0, tslot, streams[2]), "memset");
+					any = true;
+				}
+			if (any) PTRY(hipStreamSynchronize(streams[2]), "sync");
+		}
 	}
 	if (trace) fprintf(stderr, "[pipe] all chunks retired at %.1f ms\n", ms_now());
 
@@ -826,7 +886,7 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 			if (!feed.dev[i]) vp8f_packed_free(&feed.pk[i]);  // failed frames (the others were freed per chunk)
 			if (status) status[i] = feed.err[i];
 			if (feed.err[i] && !first) first = feed.err[i];
-			if (feed.err[i]) yuv420_free(&outs[i]);
+			if (feed.err[i] && outs) yuv420_free(&outs[i]);
 		}
 		if (first) {
 			errno = first;
@@ -856,7 +916,7 @@ fail:
 		if (c.stream) (void)hipStreamDestroy(c.stream);
 	for (uint32_t i = 0; i < n; i++) {
 		if (!feed.dev[i]) vp8f_packed_free(&feed.pk[i]);
-		yuv420_free(&outs[i]);
+		if (outs) yuv420_free(&outs[i]);
 		if (status) status[i] = EIO;
 	}
 	errno = EIO;
@@ -876,6 +936,18 @@ VP8G_API int vp8g_decode_webp_batch_scaled(const ByteSpan* files, uint32_t n, in
 		return -1;
 	}
 	return decode_batch(files, n, filtered, threads, flags, opts, n_opts, outs, status);
+}
+
+VP8G_API int vp8g_decode_webp_batch_tensor(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                           const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, void* d_out,
+                                           int* status) {
+	// (vp8g_tensor_slot_size: 0 for a NULL or invalid option)
+	if (!t || !d_out || !vp8g_tensor_slot_size(t) || (opts ? n_opts != 1 && n_opts != n : n_opts != 0) ||
+	    (uintptr_t)d_out % (vp8g_tensor_slot_size(t) / (3ull * t->width * t->height))) {
+		errno = EINVAL;
+		return -1;
+	}
+	return decode_batch(files, n, filtered, threads, flags, opts, n_opts, nullptr, status, t, (uint8_t*)d_out);
 }
 
 VP8G_API int vp8g_decode_webp_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, Yuv420Image* outs,

@@ -35,19 +35,21 @@
 #include <vector>
 
 #include "vp8g_device.h"
+#include "vp8g_rgb_device.h"
 
 #define VP8G_API extern "C" __attribute__((visibility("default")))
 #define DEV __device__ __forceinline__
 
 namespace {
 
+// the upsampler and VP8YuvToRgb (pair_rgb, chunk_rgb, pixel_rgb), shared with vp8g_tensor.hip
+using namespace vp8g_rgb;
+
 constexpr uint32_t kSpan = VP8G_ENC_SPAN;
 constexpr int kThreads = 1024;                     // task kernel
 constexpr uint32_t kPerThread = kSpan / kThreads;  // 32 contiguous file bytes per thread
 constexpr int kFinThreads = 256;                   // PNG finishing kernel
 constexpr int kFinLevels = 8;                      // log2(kFinThreads)
-constexpr uint32_t kChunk = 12;                     // pixels of a row per thread and iteration (36 bytes)
-constexpr uint32_t kUnits = kChunk / 2;            // pixel-pair units m .. m + kUnits touched by a chunk
 constexpr uint32_t kMod = 65521u;                  // Adler-32
 constexpr uint32_t kBlk = 65535u;                  // stored-deflate block payload
 constexpr uint32_t kBlkFile = kBlk + 5u;           // ... plus its header
@@ -73,36 +75,7 @@ struct CrcLds {
 	uint32_t red[2][3][kThreads / 64];  // per-wave partials, double-buffered by task parity
 };
 
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
-
 // ---- device helpers ----------------------------------------------------------------------
-// reference yuv2rgb_ppm.c:19-42: libwebp VP8YuvToRgb (14-bit fixed point, clip of v >> 6)
-// Clamp before the shift (same result as clip(v >> 6)): the shift-then-clamp form of two
-// neighbouring channels is selected as v_ashr_pk_u8_i32, whose result here kept the old upper 16
-// bits of its destination register, which then leaked into the packed colour word.
-DEV uint32_t clip6(int v) { return (uint32_t)min(max(v, 0), 16383) >> 6; }
-DEV uint32_t yuv_rgb(int y, int u, int v) {  // packed r | g << 8 | b << 16
-	const int yy = (y * 19077) >> 8;
-	const uint32_t r = clip6(yy + ((v * 26149) >> 8) - 14234);
-	const uint32_t g = clip6(yy - ((u * 6419) >> 8) - ((v * 13320) >> 8) + 8708);
-	const uint32_t b = clip6(yy + ((u * 33050) >> 8) - 17685);
-	return r | (g << 8) | (b << 16);
-}
-
-// One unit = pixels {2k-1, 2k} of a row (reference yuv2rgb_ppm.c:44-121): it blends chroma columns
-// k-1 and k of the two chroma rows around the pixel row (at the edges both columns are one, which
-// gives the 3:1 edge formula exactly).  (tl, t) = row a, (l, u) = row b; near_a = the pixel row is
-// nearer row a.  Returns the two pixels' colours.
-DEV void pair_rgb(bool near_a, int tlu, int tu, int lu, int uu, int tlv, int tv, int lv, int uv, int y_odd, int y_even,
-                  uint32_t& c_odd, uint32_t& c_even) {
-	const int au = tlu + tu + lu + uu + 8, av = tlv + tv + lv + uv + 8;
-	const int d12u = (au + 2 * (tu + lu)) >> 3, d03u = (au + 2 * (tlu + uu)) >> 3;
-	const int d12v = (av + 2 * (tv + lv)) >> 3, d03v = (av + 2 * (tlv + uv)) >> 3;
-	c_odd = yuv_rgb(y_odd, near_a ? (d12u + tlu) >> 1 : (d03u + lu) >> 1, near_a ? (d12v + tlv) >> 1 : (d03v + lv) >> 1);
-	c_even = yuv_rgb(y_even, near_a ? (d03u + tu) >> 1 : (d12u + uu) >> 1, near_a ? (d03v + tv) >> 1 : (d12v + uv) >> 1);
-}
-
 // file offset of pixel-stream byte p (PNG: stored blocks of kBlk bytes behind 5-byte headers)
 DEV uint32_t png_file_of_raw(uint32_t p) { return kPngRaw0 + p + 5u * (p / kBlk); }
 // first pixel-stream byte at or after file offset q, clamped to n
@@ -114,7 +87,6 @@ DEV uint32_t raw_of_file(const Vp8gEncDesc& d, uint32_t q) {
 }
 
 DEV uint32_t byte_of2(u32x2 v, int i) { return ((i < 4 ? v.x : v.y) >> (8 * (i & 3))) & 255u; }
-DEV uint32_t byte_of3(u32x3 v, int i) { return ((i < 4 ? v.x : (i < 8 ? v.y : v.z)) >> (8 * (i & 3))) & 255u; }
 DEV uint32_t crc_byte(const uint32_t* t0, uint32_t c, uint32_t b) { return t0[(c ^ b) & 255u] ^ (c >> 8); }
 DEV uint32_t crc_dword2(const uint32_t* t, uint32_t c, uint32_t w0, uint32_t w1) {  // slice-by-8, 8 bytes
 	c ^= w0;
@@ -138,19 +110,6 @@ DEV uint32_t op_apply(const uint32_t* col, uint32_t v) {  // GF(2) operator by c
 	return r;
 }
 
-// 8 chroma samples, columns m1 .. m1 + 7 of one row (m1 >= -1), with the edge rule of the
-// upsampler (reference yuv2rgb_ppm.c:44-121: column -1 reads column 0, columns >= cw read cw - 1):
-// one unaligned 8-byte load inside the row, then the missing edge bytes replicated.  cw >= 8.
-DEV uint64_t chroma8(const uint8_t* row, int m1, int cw) {
-	const int s = min(max(m1, 0), cw - 8);
-	uint64_t v = *(const uint64_t*)(row + s);  // unaligned: gfx950 runs in unaligned mode (tools/ubench/unaligned.hip)
-	const int dl = m1 - s;                     // -1 (left edge), 0 (inside), 1..7 (right edge)
-	if (dl < 0) v = (v << 8) | (v & 0xFFu);
-	if (dl > 0) v = (v >> (8 * dl)) | (((v >> 56) * 0x0101010101010101ull) << (64 - 8 * dl));
-	return v;
-}
-DEV uint32_t byte8(uint64_t v, int i) { return (uint32_t)(v >> (8 * i)) & 255u; }
-
 // Pixel bytes of the span [F0, F0 + kSpan) of image d's file, written straight into the file:
 // thread tid of NT takes chunks of kChunk pixels of a row (chunk index = row * chunks per row +
 // column chunk) and stores its 36 bytes with unaligned 8-byte stores (full lines form in L2 from
@@ -173,7 +132,7 @@ DEV void span_pixels(const Vp8gEncDesc& d, bool png, uint32_t F0, uint32_t tid, 
 	const uint8_t* V = src + d.src_v;
 	auto file_of = [&](uint32_t pi) { return png ? kPngRaw0 + pi + 5u * (pi / kBlk) : d.prefix_len + pi; };
 	for (uint32_t gc = g_first + tid; gc <= g_last; gc += NT) {
-		const uint32_t y = gc / CPR, x0 = (gc - y * CPR) * kChunk, m = x0 >> 1;
+		const uint32_t y = gc / CPR, x0 = (gc - y * CPR) * kChunk;
 		// chroma rows (reference yuv2rgb_ppm.c:178-202): row 0 uses row 0 twice; row y sits between
 		// a = (y-1)/2 and b = min(a+1, ch-1), nearer a when y is odd
 		const uint32_t a = y ? (y - 1u) >> 1 : 0u, b = y ? min(a + 1u, ch - 1u) : 0u;
@@ -182,22 +141,9 @@ DEV void span_pixels(const Vp8gEncDesc& d, bool png, uint32_t F0, uint32_t tid, 
 		if (png && x0 == 0) file[file_of(rowp)] = 0;  // the scanline's filter byte (0 = none)
 		const uint32_t p0 = rowp + f + 3u * x0;          // raw offset of the chunk's first pixel byte
 		if (x0 + kChunk <= W && cw >= 8u) {
-			// units m .. m+6 (unit k = pixels 2k-1, 2k) over chroma columns m-1 .. m+6 of rows a, b;
-			// pixel x0 + 2i is the even pixel of unit m+i, x0 + 2i - 1 the odd pixel of unit m+i
-			const int m1 = (int)m - 1;
-			const uint64_t ua = chroma8(U + a * d.stride_uv, m1, (int)cw), ub = chroma8(U + b * d.stride_uv, m1, (int)cw);
-			const uint64_t va = chroma8(V + a * d.stride_uv, m1, (int)cw), vb = chroma8(V + b * d.stride_uv, m1, (int)cw);
-			const u32x3 yl = *(const u32x3*)(Y + y * d.stride_y + x0);
 			uint32_t c[kChunk];
-#pragma unroll
-			for (int i = 0; i <= (int)kUnits; i++) {
-				uint32_t c_odd, c_even;
-				const int yo = i ? (int)byte_of3(yl, 2 * i - 1) : 0, ye = i < (int)kUnits ? (int)byte_of3(yl, 2 * i) : 0;
-				pair_rgb(near_a, (int)byte8(ua, i), (int)byte8(ua, i + 1), (int)byte8(ub, i), (int)byte8(ub, i + 1),
-				         (int)byte8(va, i), (int)byte8(va, i + 1), (int)byte8(vb, i), (int)byte8(vb, i + 1), yo, ye, c_odd, c_even);
-				if (i) c[2 * i - 1] = c_odd;
-				if (i < (int)kUnits) c[2 * i] = c_even;
-			}
+			chunk_rgb(Y + y * d.stride_y, U + a * d.stride_uv, U + b * d.stride_uv, V + a * d.stride_uv, V + b * d.stride_uv, x0, (int)cw,
+			          near_a, c);
 			// 12 pixels -> 36 bytes -> 9 dwords (4 pixels = 3 dwords)
 			uint32_t w[9];
 #pragma unroll
@@ -221,14 +167,8 @@ DEV void span_pixels(const Vp8gEncDesc& d, bool png, uint32_t F0, uint32_t tid, 
 		// generic chunk (a row's last, partial chunk; images narrower than 15 pixels): pixel by pixel
 		const uint32_t xe = min(x0 + kChunk, W);
 		for (uint32_t x = x0; x < xe; x++) {
-			const uint32_t k = (x + 1u) >> 1;  // unit: pixels 2k-1 (odd x) and 2k (even x)
-			const uint32_t cl = k ? k - 1u : 0u, cr = min(k, cw - 1u);
-			const uint32_t ra = a * d.stride_uv, rb = b * d.stride_uv;
-			uint32_t c_odd, c_even;
-			const int yv = Y[y * d.stride_y + x];
-			pair_rgb(near_a, U[ra + cl], U[ra + cr], U[rb + cl], U[rb + cr], V[ra + cl], V[ra + cr], V[rb + cl], V[rb + cr], yv, yv,
-			         c_odd, c_even);
-			const uint32_t col = (x & 1u) ? c_odd : c_even;
+			const uint32_t col = pixel_rgb(Y + y * d.stride_y, U + a * d.stride_uv, U + b * d.stride_uv, V + a * d.stride_uv,
+			                               V + b * d.stride_uv, x, cw, near_a);
 			const uint32_t pb = rowp + f + 3u * x;
 #pragma unroll
 			for (uint32_t i = 0; i < 3; i++) file[file_of(pb + i)] = (uint8_t)(col >> (8 * i));

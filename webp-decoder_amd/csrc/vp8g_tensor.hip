@@ -1,0 +1,287 @@
+// vp8g_tensor.hip -- device-resident I420 -> one dense RGB tensor, in the form a model reads
+// (include/vp8g.h: vp8g_tensor_batch_device).
+//
+// The pixels are those of the file encoder (vp8g_rgb.hip: "fancy" 4:2:0 upsampling, libwebp's
+// VP8YuvToRgb; both go through vp8g_rgb_device.h), but the unit of work is a run of pixels of one
+// row, not a span of a file: a thread takes one chunk of 12 pixels of a row (six pixel pairs; one
+// unaligned 8-byte load per chroma row and plane, one 12-byte luma load), converts them to the
+// element type -- out = u8 * scale[c] + bias[c], a rounded multiply and then a rounded add -- and
+// stores them:
+//   NHWC  one run of 36 elements;
+//   NCHW  three runs of 12 elements, one per plane; neighbouring lanes hold neighbouring chunks of
+//         the row, so each plane's stores are contiguous across the lanes of a wave.
+// A run whose address is dword-aligned goes out as 16- / 8- / 4-byte stores; runs of a row that
+// starts off a dword boundary (an odd slot start, an odd width) go out element by element, as do
+// the pixels of a row's last, partial chunk and of images narrower than 15 pixels (chroma rows
+// shorter than the 8-byte load).  Every store lies inside the image's own 3 * w * h elements.
+// No LDS and no barriers.  A workgroup task is 256 consecutive chunks of one image; the dtype,
+// layout and channel order are template parameters picked on the host.
+#include <errno.h>
+#include <string.h>
+
+#include <cmath>
+
+#include <hip/hip_fp16.h>
+
+#include "vp8g_device.h"
+#include "vp8g_rgb_device.h"
+
+#define VP8G_API extern "C" __attribute__((visibility("default")))
+#define DEV __device__ __forceinline__
+
+namespace {
+
+using namespace vp8g_rgb;
+
+constexpr uint32_t kThreads = 256;  // chunks per workgroup task
+constexpr uint32_t kMaxDim = 16383;
+
+// (dword-aligned, not 16- / 8-byte aligned: a run starts wherever its row does)
+typedef uint32_t u32x4a __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint32_t u32x2a __attribute__((ext_vector_type(2), aligned(4)));
+
+struct TensorParams {
+	uint32_t w, h, cw, ch;
+	uint32_t cpr;          // chunks per row
+	uint32_t chunks;       // chunks per image (cpr * h)
+	uint32_t tpi;          // workgroup tasks per image
+	uint32_t reserved;
+	uint64_t plane;        // bytes of one NCHW plane (w * h * element size)
+	float scale[3], bias[3];
+};
+
+constexpr int elem_bytes(uint32_t dt) { return dt == VP8G_T_U8 ? 1 : dt == VP8G_T_F32 ? 4 : 2; }
+
+// The element (its bits, in the low bytes) of the 8-bit value v.
+template <uint32_t DT>
+DEV uint32_t conv(uint32_t v, float s, float b) {
+	if constexpr (DT == VP8G_T_U8) {
+		return v;
+	} else {
+		// A rounded multiply, then a rounded add: hipcc contracts a * b + c into a fused multiply-add
+		// by default (and __fmul_rn / __fadd_rn are plain operators to it), so contraction is
+		// switched off for these two operations.
+#pragma clang fp contract(off)
+		const float m = (float)v * s;
+		const float f = m + b;
+		const uint32_t u = __float_as_uint(f);
+		if constexpr (DT == VP8G_T_F32) return u;
+		else if constexpr (DT == VP8G_T_F16) return (uint32_t)__half_as_ushort(__float2half_rn(f));
+		else return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;  // bfloat16, nearest-even (f is finite or infinite, never NaN)
+	}
+}
+
+// channel ch of the output order out of a packed r | g << 8 | b << 16
+template <bool BGR>
+DEV uint32_t channel(uint32_t c, int ch) {
+	return (c >> (8 * (BGR ? 2 - ch : ch))) & 255u;
+}
+
+template <uint32_t DT>
+DEV void store_elem(uint8_t* p, uint32_t e) {
+	if constexpr (DT == VP8G_T_U8) *p = (uint8_t)e;
+	else if constexpr (DT == VP8G_T_F32) *(uint32_t*)p = e;
+	else *(uint16_t*)p = (uint16_t)e;
+}
+
+// ND dwords to a dword-aligned address: 16-byte stores, then what is left
+template <int ND>
+DEV void store_dwords(uint8_t* p, const uint32_t (&dw)[ND]) {
+	int k = 0;
+#pragma unroll
+	for (; k + 4 <= ND; k += 4) *(u32x4a*)(p + 4 * k) = u32x4a{dw[k], dw[k + 1], dw[k + 2], dw[k + 3]};
+	if constexpr (ND % 4 >= 2) {
+		*(u32x2a*)(p + 4 * k) = u32x2a{dw[k], dw[k + 1]};
+		k += 2;
+	}
+	if constexpr (ND % 2 == 1) *(uint32_t*)(p + 4 * k) = dw[k];
+}
+
+// A run of R elements (R * element size a multiple of 4) to p: wide stores when p is dword-aligned,
+// else element by element.  p is element-aligned, so a float run is always dword-aligned.
+template <uint32_t DT, int R>
+DEV void store_run(uint8_t* p, const uint32_t (&e)[R]) {
+	constexpr int EB = elem_bytes(DT), PER = 4 / EB, ND = R / PER;
+	static_assert(R % PER == 0, "whole dwords");
+	uint32_t dw[ND];
+#pragma unroll
+	for (int j = 0; j < ND; j++) {
+		uint32_t v = 0;
+#pragma unroll
+		for (int q = 0; q < PER; q++) v |= e[PER * j + q] << (8 * EB * q);
+		dw[j] = v;
+	}
+	if (EB == 4 || ((uintptr_t)p & 3u) == 0) {
+		store_dwords<ND>(p, dw);
+		return;
+	}
+	if constexpr (EB < 4) {
+#pragma unroll
+		for (int i = 0; i < R; i++) store_elem<DT>(p + EB * i, e[i]);
+	}
+}
+
+template <uint32_t DT, bool PLANAR, bool BGR>
+__global__ __launch_bounds__(kThreads) void tensor_kernel(const Vp8gTensorDesc* __restrict__ D, uint32_t total, TensorParams P,
+                                                          const uint8_t* __restrict__ src, uint8_t* __restrict__ dst) {
+	constexpr uint32_t EB = (uint32_t)elem_bytes(DT);
+	const uint32_t tid = threadIdx.x, W = P.w;
+	for (uint32_t g = blockIdx.x; g < total; g += gridDim.x) {
+		const uint32_t img = g / P.tpi;  // (every image has P.tpi tasks, numbered image by image)
+		const uint32_t gc = (g - img * P.tpi) * kThreads + tid;
+		if (gc >= P.chunks) continue;
+		const Vp8gTensorDesc& d = D[img];
+		const uint32_t y = gc / P.cpr, x0 = (gc - y * P.cpr) * kChunk;
+		// chroma rows (as vp8g_rgb.hip): row 0 uses row 0 twice; row y sits between a = (y-1)/2 and
+		// b = min(a+1, ch-1), nearer a when y is odd
+		const uint32_t a = y ? (y - 1u) >> 1 : 0u, b = y ? min(a + 1u, P.ch - 1u) : 0u;
+		const bool near_a = y == 0 || (y & 1u);
+		const uint8_t* yrow = src + d.src_y + (size_t)y * d.stride_y;
+		const uint8_t* ua = src + d.src_u + (size_t)a * d.stride_uv;
+		const uint8_t* ub = src + d.src_u + (size_t)b * d.stride_uv;
+		const uint8_t* va = src + d.src_v + (size_t)a * d.stride_uv;
+		const uint8_t* vb = src + d.src_v + (size_t)b * d.stride_uv;
+		uint8_t* out = dst + d.dst;
+		const size_t pix = (size_t)y * W + x0;  // the chunk's first pixel in the image
+		if (x0 + kChunk <= W && P.cw >= 8u) {
+			uint32_t c[kChunk];
+			chunk_rgb(yrow, ua, ub, va, vb, x0, (int)P.cw, near_a, c);
+			if constexpr (PLANAR) {
+#pragma unroll
+				for (int ch = 0; ch < 3; ch++) {
+					uint32_t e[kChunk];
+#pragma unroll
+					for (int i = 0; i < (int)kChunk; i++) e[i] = conv<DT>(channel<BGR>(c[i], ch), P.scale[ch], P.bias[ch]);
+					store_run<DT, (int)kChunk>(out + (size_t)ch * P.plane + pix * EB, e);
+				}
+			} else if constexpr (DT == VP8G_T_U8) {
+				// 12 pixels -> 36 bytes -> 9 dwords (4 pixels = 3 dwords), as the file encoder packs them
+				uint8_t* p = out + pix * 3u;
+				if (BGR) {
+#pragma unroll
+					for (int i = 0; i < (int)kChunk; i++) c[i] = (c[i] & 0xFF00u) | (c[i] >> 16) | ((c[i] & 0xFFu) << 16);
+				}
+				if (((uintptr_t)p & 3u) == 0) {
+					uint32_t dw[9];
+#pragma unroll
+					for (int k = 0; k < 3; k++) {
+						dw[3 * k + 0] = c[4 * k] | (c[4 * k + 1] << 24);
+						dw[3 * k + 1] = (c[4 * k + 1] >> 8) | (c[4 * k + 2] << 16);
+						dw[3 * k + 2] = (c[4 * k + 2] >> 16) | (c[4 * k + 3] << 8);
+					}
+					store_dwords<9>(p, dw);
+				} else {
+#pragma unroll
+					for (int i = 0; i < 3 * (int)kChunk; i++) p[i] = (uint8_t)(c[i / 3] >> (8 * (i % 3)));
+				}
+			} else {
+				uint32_t e[3 * kChunk];
+#pragma unroll
+				for (int i = 0; i < (int)kChunk; i++)
+#pragma unroll
+					for (int ch = 0; ch < 3; ch++) e[3 * i + ch] = conv<DT>(channel<BGR>(c[i], ch), P.scale[ch], P.bias[ch]);
+				store_run<DT, 3 * (int)kChunk>(out + pix * 3u * EB, e);
+			}
+			continue;
+		}
+		// generic chunk (a row's last, partial chunk; images narrower than 15 pixels): pixel by pixel
+		const uint32_t xe = min(x0 + kChunk, W);
+		for (uint32_t x = x0; x < xe; x++) {
+			const uint32_t col = pixel_rgb(yrow, ua, ub, va, vb, x, P.cw, near_a);
+			const size_t px = (size_t)y * W + x;
+#pragma unroll
+			for (int ch = 0; ch < 3; ch++) {
+				uint8_t* p = PLANAR ? out + (size_t)ch * P.plane + px * EB : out + (px * 3u + (uint32_t)ch) * EB;
+				store_elem<DT>(p, conv<DT>(channel<BGR>(col, ch), P.scale[ch], P.bias[ch]));
+			}
+		}
+	}
+}
+
+using KernelFn = void (*)(const Vp8gTensorDesc*, uint32_t, TensorParams, const uint8_t*, uint8_t*);
+#define VP8G_T_ROW(DT) \
+	{ {tensor_kernel<DT, false, false>, tensor_kernel<DT, false, true>}, {tensor_kernel<DT, true, false>, tensor_kernel<DT, true, true>} }
+const KernelFn kKernels[4][2][2] = {VP8G_T_ROW(VP8G_T_U8), VP8G_T_ROW(VP8G_T_F16), VP8G_T_ROW(VP8G_T_BF16), VP8G_T_ROW(VP8G_T_F32)};
+#undef VP8G_T_ROW
+
+bool opt_ok(const Vp8gTensorOpt* t) {
+	if (!t || t->width == 0 || t->height == 0 || t->width > kMaxDim || t->height > kMaxDim || t->dtype > VP8G_T_F32 ||
+	    t->layout > VP8G_T_NCHW || (t->flags & ~VP8G_T_BGR))
+		return false;
+	if (t->dtype != VP8G_T_U8)
+		for (int c = 0; c < 3; c++)
+			if (!std::isfinite(t->scale[c]) || !std::isfinite(t->bias[c])) return false;
+	return true;
+}
+
+uint32_t tasks_per_image(const Vp8gTensorOpt& t) {
+	const uint32_t chunks = ((t.width + kChunk - 1u) / kChunk) * t.height;
+	return (chunks + kThreads - 1u) / kThreads;
+}
+
+}  // namespace
+
+VP8G_API uint64_t vp8g_tensor_slot_size(const Vp8gTensorOpt* t) {
+	if (!opt_ok(t)) {
+		errno = EINVAL;
+		return 0;
+	}
+	return 3ull * t->width * t->height * (uint64_t)elem_bytes(t->dtype);
+}
+
+VP8G_API int vp8g_make_tensor_desc(const Vp8gTensorOpt* t, uint64_t src_y, uint64_t src_u, uint64_t src_v, uint32_t stride_y,
+                                   uint32_t stride_uv, uint64_t dst_offset, uint32_t task0, Vp8gTensorDesc* d) {
+	if (!d || !opt_ok(t) || stride_y < t->width || stride_uv < (t->width + 1u) / 2u ||
+	    dst_offset % (uint64_t)elem_bytes(t->dtype)) {
+		errno = EINVAL;
+		return -1;
+	}
+	memset(d, 0, sizeof(*d));
+	d->src_y = src_y, d->src_u = src_u, d->src_v = src_v, d->dst = dst_offset;
+	d->stride_y = stride_y, d->stride_uv = stride_uv;
+	d->task0 = task0, d->ntasks = tasks_per_image(*t);
+	return 0;
+}
+
+VP8G_API int vp8g_tensor_batch_device(const Vp8gTensorDesc* h, const Vp8gTensorDesc* d_descs, uint32_t n, const Vp8gTensorOpt* t,
+                                      const uint8_t* d_src, void* d_dst, void* stream) {
+	if (!h || !d_descs || !d_src || !d_dst || n == 0 || !opt_ok(t)) {
+		errno = EINVAL;
+		return -1;
+	}
+	const uint32_t eb = (uint32_t)elem_bytes(t->dtype), tpi = tasks_per_image(*t);
+	uint64_t total = 0;
+	bool ok = (uintptr_t)d_dst % eb == 0;
+	for (uint32_t i = 0; ok && i < n; i++) {  // tasks must be numbered image by image
+		ok = h[i].task0 == total && h[i].ntasks == tpi && h[i].stride_y >= t->width && h[i].stride_uv >= (t->width + 1u) / 2u &&
+		     h[i].dst % eb == 0;
+		total += tpi;
+		if (total > 0x7FFFFFFFu) ok = false;
+	}
+	if (!ok) {
+		errno = EINVAL;
+		return -1;
+	}
+	TensorParams P;
+	memset(&P, 0, sizeof(P));
+	P.w = t->width, P.h = t->height, P.cw = (t->width + 1u) / 2u, P.ch = (t->height + 1u) / 2u;
+	P.cpr = (t->width + kChunk - 1u) / kChunk, P.chunks = P.cpr * t->height, P.tpi = tpi;
+	P.plane = (uint64_t)t->width * t->height * eb;
+	for (int c = 0; c < 3; c++) P.scale[c] = t->scale[c], P.bias[c] = t->bias[c];
+	const int cus = vp8g::device_cus();
+	const uint32_t grid = min((uint32_t)total, (uint32_t)(cus > 0 ? cus : 256) * 16u);
+	vp8g::GateScope gate((hipStream_t)stream);  // (vp8g_device.h: no cross-workgroup launch beside it)
+	hipError_t e = gate.status();
+	if (e == hipSuccess) {
+		hipLaunchKernelGGL(kKernels[t->dtype][t->layout][t->flags & VP8G_T_BGR], dim3(grid), dim3(kThreads), 0, (hipStream_t)stream,
+		                   d_descs, (uint32_t)total, P, d_src, (uint8_t*)d_dst);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = gate.done(false);
+	if (e != hipSuccess) {
+		vp8g::set_error_text("tensor launch", e);
+		errno = EIO;
+		return -1;
+	}
+	return 0;
+}

@@ -150,7 +150,24 @@ class Vp8fScaleGeom(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("left", "top", "win_w", "win_h", "out_w", "out_h", "scaling")]
 
 
+class Vp8gTensorOpt(C.Structure):
+    """include/vp8g.h: picture size, element type, layout and normalisation of a device RGB tensor."""
+    _fields_ = [(n, C.c_uint32) for n in ("width", "height", "dtype", "layout", "flags")] + [
+        ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
+class Vp8gTensorDesc(C.Structure):
+    """include/vp8g.h: per-image descriptor of the tensor kernel (vp8g_make_tensor_desc)."""
+    _fields_ = [(n, C.c_uint64) for n in ("src_y", "src_u", "src_v", "dst")] + [(n, C.c_uint32) for n in (
+        "stride_y", "stride_uv", "task0", "ntasks")]
+
+
 VP8G_SCALE_DWEBP_FILTER = 1
+
+T_DTYPES = {"uint8": 0, "float16": 1, "bfloat16": 2, "float32": 3}  # VP8G_T_U8 / F16 / BF16 / F32
+T_ELEM = {0: 1, 1: 2, 2: 2, 3: 4}
+T_LAYOUTS = {"NHWC": 0, "NCHW": 1}
+VP8G_T_BGR = 1
 
 PK_BLOCKS = 25  # per MB: Y 0..15, U 0..3, V 0..3, Y2
 VP8G_BATCH_DEVICE_M05 = 1
@@ -171,6 +188,8 @@ assert C.sizeof(Vp8gTokFrame) == 1296
 assert C.sizeof(Vp8gScaleOpt) == 28
 assert C.sizeof(Vp8gScalePlane) == 80
 assert C.sizeof(Vp8gScaleDesc) == 272
+assert C.sizeof(Vp8gTensorOpt) == 44
+assert C.sizeof(Vp8gTensorDesc) == 48
 
 VP8G_F_LOOPFILTER = 1
 VP8G_F_SIMPLE = 2
@@ -306,6 +325,17 @@ def gpu_lib():
         lib.yuv420_rescale.argtypes = [P(Yuv420Image), P(Vp8gScaleOpt), P(Yuv420Image)]
         lib.vp8g_decode_webp_batch_scaled.argtypes = [P(ByteSpan), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
                                                       P(Vp8gScaleOpt), C.c_uint32, P(Yuv420Image), P(C.c_int)]
+        if not hasattr(lib, "vp8g_tensor_batch_device"):  # (libraries built before the tensor path: A/B of old builds)
+            lib._typed = True
+            return lib
+        lib.vp8g_tensor_slot_size.argtypes = [P(Vp8gTensorOpt)]
+        lib.vp8g_tensor_slot_size.restype = C.c_uint64
+        lib.vp8g_make_tensor_desc.argtypes = [P(Vp8gTensorOpt), C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                              C.c_uint64, C.c_uint32, P(Vp8gTensorDesc)]
+        lib.vp8g_tensor_batch_device.argtypes = [P(Vp8gTensorDesc), C.c_void_p, C.c_uint32, P(Vp8gTensorOpt), C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]
+        lib.vp8g_decode_webp_batch_tensor.argtypes = [P(ByteSpan), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
+                                                      P(Vp8gScaleOpt), C.c_uint32, P(Vp8gTensorOpt), C.c_void_p, P(C.c_int)]
         lib._typed = True
     return lib
 
@@ -572,6 +602,139 @@ def gpu_decode_webp_batch_scaled(files: list[bytes], scale, filtered: bool = Tru
     for i in range(n):
         out.append((_image_bytes(imgs[i]), int(imgs[i].width), int(imgs[i].height)) if st[i] == 0 else None)
         lib.yuv420_free(C.byref(imgs[i]))
+    return out, list(st)
+
+
+def _dtype_name(dtype) -> str:
+    name = dtype if isinstance(dtype, str) else (str(dtype) if str(dtype).startswith("torch.") else np.dtype(dtype).name)
+    name = name.replace("torch.", "")
+    if name not in T_DTYPES:
+        raise ValueError(f"tensor dtype {dtype!r}: one of {sorted(T_DTYPES)}")
+    return name
+
+
+def tensor_opt(size, dtype, layout: str = "NCHW", mean=None, std=None, scale=None, bias=None,
+               bgr: bool = False) -> Vp8gTensorOpt:
+    """Vp8gTensorOpt for pictures of size = (w, h).  out = u8 * scale[c] + bias[c] per OUTPUT channel, either
+    given directly or as mean / std on the 0..1 range (scale = 1 / (255 std), bias = -mean / std, computed in
+    Python floats and stored as float32: what the structure holds is the contract).  Scalars apply to
+    every channel.  Default: scale 1, bias 0."""
+    if (mean is not None or std is not None) and (scale is not None or bias is not None):
+        raise ValueError("give mean / std or scale / bias, not both")
+
+    def three(v, default):
+        v = default if v is None else v
+        v = [v] * 3 if isinstance(v, (int, float)) else list(v)
+        if len(v) != 3:
+            raise ValueError("per-channel values come in threes")
+        return [float(x) for x in v]
+
+    if mean is not None or std is not None:
+        m, s = three(mean, 0.0), three(std, 1.0)
+        sc, bi = [1.0 / (255.0 * x) for x in s], [-a / x for a, x in zip(m, s)]
+    else:
+        sc, bi = three(scale, 1.0), three(bias, 0.0)
+    if layout not in T_LAYOUTS:
+        raise ValueError(f"tensor layout {layout!r}: NHWC or NCHW")
+    return Vp8gTensorOpt(int(size[0]), int(size[1]), T_DTYPES[_dtype_name(dtype)], T_LAYOUTS[layout], VP8G_T_BGR if bgr else 0,
+                         (C.c_float * 3)(*sc), (C.c_float * 3)(*bi))
+
+
+def _tensor_shape(n: int, opt: Vp8gTensorOpt):
+    return (n, 3, opt.height, opt.width) if opt.layout == T_LAYOUTS["NCHW"] else (n, opt.height, opt.width, 3)
+
+
+def _torch_dtype(opt: Vp8gTensorOpt):
+    import torch
+    return (torch.uint8, torch.float16, torch.bfloat16, torch.float32)[opt.dtype]
+
+
+def host_tensor(i420: bytes, w: int, h: int, opt: Vp8gTensorOpt):
+    """The numpy / torch-CPU restatement of the tensor semantics (include/vp8g.h) for one cropped
+    I420 picture: the m08 restatement's RGB (oracle_encode), the channel order, a float32 multiply and
+    then a float32 add, one rounding to the element type, the layout.  A torch CPU tensor [3, H, W] or
+    [H, W, 3].  Tests and tools use it as the expected value."""
+    import torch
+    assert (w, h) == (opt.width, opt.height)
+    ppm = oracle_encode(i420, w, h, "ppm")
+    rgb = np.frombuffer(ppm, np.uint8, w * h * 3, len(ppm) - w * h * 3).reshape(h, w, 3)
+    if opt.flags & VP8G_T_BGR:
+        rgb = rgb[:, :, ::-1]
+    if opt.dtype == T_DTYPES["uint8"]:
+        out = torch.from_numpy(np.array(rgb))  # (a writable, contiguous copy)
+    else:
+        scale, bias = np.array(list(opt.scale), np.float32), np.array(list(opt.bias), np.float32)
+        f = rgb.astype(np.float32) * scale + bias  # (two float32 operations, each rounded to nearest)
+        assert f.dtype == np.float32
+        if opt.dtype == T_DTYPES["float16"]:
+            with np.errstate(over="ignore"):
+                out = torch.from_numpy(f.astype(np.float16))
+        elif opt.dtype == T_DTYPES["bfloat16"]:
+            out = torch.from_numpy(f).to(torch.bfloat16)
+        else:
+            out = torch.from_numpy(f)
+    return out.permute(2, 0, 1).contiguous() if opt.layout == T_LAYOUTS["NCHW"] else out.contiguous()
+
+
+def gpu_tensor(i420_list, w: int, h: int, opt: Vp8gTensorOpt):
+    """vp8g_tensor_batch_device over cropped I420 pictures of one size: upload them, one launch, and the
+    torch.Tensor [N, 3, H, W] or [N, H, W, 3] it leaves on the device."""
+    import torch
+    lib = gpu_lib()
+    dev = torch.device("cuda", 0)
+    n, fsz, cw, ch = len(i420_list), i420_size(w, h), (w + 1) // 2, (h + 1) // 2
+    slot = lib.vp8g_tensor_slot_size(C.byref(opt))
+    if not slot or (w, h) != (opt.width, opt.height) or any(len(b) != fsz for b in i420_list):
+        raise ValueError("gpu_tensor: invalid options or picture sizes")
+    descs = (Vp8gTensorDesc * n)()
+    task0 = 0
+    for i in range(n):
+        o = i * fsz
+        if lib.vp8g_make_tensor_desc(C.byref(opt), o, o + w * h, o + w * h + cw * ch, w, cw, i * slot, task0,
+                                     C.byref(descs[i])) != 0:
+            raise ValueError("vp8g_make_tensor_desc failed")
+        task0 += descs[i].ntasks
+    src = torch.from_numpy(np.frombuffer(b"".join(i420_list), dtype=np.uint8).copy()).to(dev)
+    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
+    out = torch.empty(_tensor_shape(n, opt), dtype=_torch_dtype(opt), device=dev)
+    stream = torch.cuda.current_stream(dev)
+    if lib.vp8g_tensor_batch_device(descs, C.c_void_p(d_descs.data_ptr()), n, C.byref(opt), C.c_void_p(src.data_ptr()),
+                                    C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)) != 0:
+        raise RuntimeError(f"vp8g_tensor_batch_device failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
+    stream.synchronize()
+    return out
+
+
+def gpu_decode_webp_batch_tensor(files: list[bytes], opt: Vp8gTensorOpt, scale=None, filtered: bool = True, threads: int = 0,
+                                 device_m05: bool = False, multi_partition: bool = False):
+    """vp8g_decode_webp_batch_tensor: .webp images decoded, optionally cropped / downscaled (scale: None,
+    one Vp8gScaleOpt for every frame, or a list of one per frame), converted and left on the device.
+    Returns (torch.Tensor on the device, [N, 3, H, W] or [N, H, W, 3] of the requested dtype, list of
+    errno); the slot of a failed frame is zero.  torch only allocates the tensor: its data_ptr() is
+    handed to the C call."""
+    import time
+    import torch
+    lib = gpu_lib()
+    n = len(files)
+    bufs = [(C.c_uint8 * max(1, len(b))).from_buffer_copy(b if b else b"\0") for b in files]
+    spans = (ByteSpan * n)(*[ByteSpan(C.cast(bufs[i], C.POINTER(C.c_uint8)), len(files[i])) for i in range(n)])
+    opts = [] if scale is None else (list(scale) if isinstance(scale, (list, tuple)) else [scale])
+    c_opts = (Vp8gScaleOpt * len(opts))(*opts) if opts else None
+    if not lib.vp8g_tensor_slot_size(C.byref(opt)):
+        raise ValueError("gpu_decode_webp_batch_tensor: invalid tensor options")
+    dev = torch.device("cuda", 0)
+    out = torch.empty(_tensor_shape(n, opt), dtype=_torch_dtype(opt), device=dev)
+    torch.cuda.synchronize(dev)
+    st = (C.c_int * n)()
+    t0 = time.perf_counter()
+    rc = lib.vp8g_decode_webp_batch_tensor(spans, n, int(filtered), threads,
+                                           (VP8G_BATCH_DEVICE_M05 if device_m05 else 0)
+                                           | (VP8G_BATCH_MULTI_PARTITION if multi_partition else 0), c_opts, len(opts),
+                                           C.byref(opt), C.c_void_p(out.data_ptr()), st)
+    gpu_decode_webp_batch_tensor.seconds = time.perf_counter() - t0  # the C call alone
+    en = C.get_errno()
+    if rc != 0 and (all(s == 5 for s in st) or not any(st)):  # EIO: device failure; or the call itself refused
+        raise RuntimeError(f"vp8g_decode_webp_batch_tensor failed: errno={en} {lib.vp8g_last_error()!r}")
     return out, list(st)
 
 
