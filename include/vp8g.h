@@ -349,7 +349,7 @@ uint64_t vp8g_encode_workspace_size(uint32_t total_spans);
 int vp8g_encode_batch_device(const Vp8gEncDesc* h_descs, const Vp8gEncDesc* d_descs, uint32_t n, const uint8_t* d_src,
                              uint8_t* d_out, uint8_t* d_work, void* hip_stream);
 
-/* ---- Decode to a target size: crop + downscale of I420 on the device --------------------- */
+/* ---- Decode to a target size: crop + rescale of I420 on the device ----------------------- */
 
 /* libwebp's `use_cropping` / `use_scaling` decoder options (dwebp -crop x y w h -scale w h), bit-exact
  * to libwebp 1.2.2's rescaler.  All-zero = identity.
@@ -357,8 +357,11 @@ int vp8g_encode_batch_device(const Vp8gEncDesc* h_descs, const Vp8gEncDesc* d_de
  *           left + w <= width, top + h <= height; left and top are rounded down to even.
  *   scale   scaled_w x scaled_h; one of them 0 = derived from the other with a ceiling
  *           (h = (src_h * w + src_w - 1) / src_w over the cropped size); both 0 = crop only.
- * DOWNSCALE ONLY: scaled_w <= the (cropped) width and scaled_h <= the (cropped) height, else EINVAL
- * (libwebp's bilinear expand path is not implemented).
+ * Without VP8G_SCALE_EXPAND, DOWNSCALE ONLY: scaled_w <= the (cropped) width and scaled_h <= the
+ * (cropped) height, else EINVAL.  With it a target dimension may be anything up to 16383: a plane
+ * that grows in x or in y takes libwebp's bilinear expand path in that axis (per plane and per
+ * axis: 500 x 200 -> 224 x 224 shrinks x and expands y; 5 -> 6 expands luma while chroma 3 -> 3 is a
+ * copy), bit-exact as well.
  * The output is I420: luma scaled to the target, each chroma plane independently from
  * ceil(window / 2) to ceil(target / 2).  RGB of a scaled picture is DEFINED as the encoder
  * (vp8g_encode_batch_device, fancy upsampling) run on that scaled I420 -- deliberately not
@@ -375,16 +378,29 @@ typedef struct {
  * if scaled_w < width * 3 / 4 and scaled_h < height * 3 / 4 (integer products, the full picture
  * size), so the output equals `dwebp -yuv -scale`.  Without the flag, filtered means filtered. */
 #define VP8G_SCALE_DWEBP_FILTER 1u
+/* Allow a target larger than the (cropped) source in either dimension (libwebp's expand path).
+ * Bit 2 and every bit above 4 are unknown: EINVAL. */
+#define VP8G_SCALE_EXPAND 4u
 
 /* One plane of a scale descriptor: W x H source window -> w x h, and how the launch tiles it (a
- * workgroup task = tile_w output columns x run_h output rows). 80 bytes. */
+ * workgroup task = tile_w output columns x run_h output rows). 80 bytes.
+ * A plane that expands (src_w < dst_w or src_h < dst_h) belongs to the expand kernel, marked by
+ * group = 0; its fields then mean:
+ *   fx, fy, fxy   libwebp's values for the plane's mode (vp8f_scale_factors; unused ones 0)
+ *   src_h < dst_h:  tile_w = 64, 128 or 256 (the smallest that holds dst_w, else 256), pitch = 4 * tile_w
+ *                   (bytes of one row of horizontal sums in LDS), block_rows = 32768 / pitch (rows the
+ *                   LDS holds), run_h = block_rows - 1 (a run never needs more source rows than
+ *                   run_h + 1)
+ *   else:           tile_w = 256 (one output column per lane), run_h = max(1, 64 * dst_h / src_h),
+ *                   pitch = block_rows = 0 (no LDS)
+ *   tiles_x, ntasks as below. */
 typedef struct {
 	uint64_t src;                    /* byte offset of the window's first sample in the source buffer */
 	uint64_t dst;                    /* byte offset of the plane in the output buffer */
 	uint32_t src_stride, dst_stride;
 	uint32_t src_w, src_h, dst_w, dst_h;
 	uint32_t fx, fy, fxy;            /* 2^32 / w, 2^32 / h, h * 2^32 / (W * H) (0 if >= 2^32) */
-	uint32_t group;                  /* lanes sharing one output column (power of two, <= 64) */
+	uint32_t group;                  /* lanes sharing one output column (power of two, <= 64); 0 = expanding plane */
 	uint32_t tile_w, run_h;          /* output columns (256 / group) and output rows per task */
 	uint32_t tiles_x, ntasks;        /* tasks per row of tiles; tasks of the plane */
 	uint32_t pitch, block_rows;      /* LDS staging: bytes per source row segment, rows per block */
@@ -400,7 +416,8 @@ typedef struct {
 } Vp8gScaleDesc;
 
 /* The output size `opt` gives for a width x height picture.  0, or -1 + EINVAL (NULL argument,
- * bad crop, upscale in either dimension, picture beyond 16383 x 16383). */
+ * bad crop, upscale in either dimension without VP8G_SCALE_EXPAND, a target beyond 16383 with it,
+ * unknown flag bit, picture beyond 16383 x 16383). */
 int vp8g_scaled_size(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, uint32_t* out_w, uint32_t* out_h);
 
 /* Fill the descriptor of one width x height image whose planes sit at src_* (strides stride_*) in
@@ -411,7 +428,8 @@ int vp8g_make_scale_desc(uint32_t width, uint32_t height, uint64_t src_y, uint64
                          uint32_t task0, Vp8gScaleDesc* out);
 
 /* Scale n images of mixed sizes (device-resident source planes -> scaled I420 in d_dst) in one
- * launch on `hip_stream`.  h_descs / d_descs: host and device copies of the descriptors (tasks
+ * launch on `hip_stream`, plus a second launch (the expand kernel) on the same stream when some
+ * plane of the batch expands; each kernel leaves the other's tasks alone.  h_descs / d_descs: host and device copies of the descriptors (tasks
  * numbered image by image).  Writes only the images' own bytes.  Asynchronous; 0 or -1 + errno
  * (EINVAL for inconsistent descriptors, EIO on a launch failure).  d_dst may feed
  * vp8g_encode_batch_device on the same stream with no host copy in between. */

@@ -12,6 +12,14 @@ Every leg: the cold first call discarded, then the median of the warm runs.  Wri
 profiles/scale_bench.json and prints the table of DESIGN.md §14.
 
   python tools/scale_bench.py [--frames 512] [--runs 12] [--e2e-frames 256] [--e2e-runs 5]
+
+ --expand: instead, the expand kernel (VP8G_SCALE_EXPAND) alone over N device-resident random I420
+      frames: 160x120 -> 224x224, 500x200 -> 224x224 (x shrinks, y expands) and 256x256 -> 512x512, each
+      next to a yardstick in the same process: the shrink kernel writing the same number of output
+      samples at a ratio just under 1 ((w + 1) x (h + 1) -> w x h).  HIP-event ms and the achieved
+      read + write rate.  Writes profiles/scale_expand_bench.json and prints its rows of §14.
+
+  python tools/scale_bench.py --expand [--frames 512] [--runs 12]
 """
 import argparse
 import ctypes as C
@@ -79,6 +87,73 @@ class ScaleLeg:
     def frame(self, i):
         n = vp8g.i420_size(*self.size)
         return self.out[i * self.slot:i * self.slot + n].cpu().numpy().tobytes()
+
+
+class PlainLeg:
+    """One vp8g_scale_batch_device call over n tight random I420 frames of one size."""
+
+    def __init__(self, n, size, target, expand, dev):
+        import numpy as np
+        self.lib, self.n, (sw, sh), (tw, th) = vp8g.gpu_lib(), n, size, target
+        self.opt = vp8g.scale_opt(scale=target, expand=expand)
+        fsz, slot = vp8g.i420_size(sw, sh), (vp8g.i420_size(tw, th) + 255) // 256 * 256
+        cw, ch = (sw + 1) // 2, (sh + 1) // 2
+        self.frames = [np.random.default_rng(77 + i).integers(0, 256, size=fsz, dtype=np.uint8) for i in range(4)]
+        self.src = torch.from_numpy(np.concatenate([self.frames[i % 4] for i in range(n)])).to(dev)
+        self.descs = (vp8g.Vp8gScaleDesc * n)()
+        task0 = 0
+        for i in range(n):
+            o = i * fsz
+            assert self.lib.vp8g_make_scale_desc(sw, sh, o, o + sw * sh, o + sw * sh + cw * ch, sw, cw, C.byref(self.opt),
+                                                 i * slot, task0, C.byref(self.descs[i])) == 0
+            task0 += self.descs[i].ntasks
+        self.tasks, self.slot, self.size, self.target = task0, slot, size, target
+        self.bytes = n * (fsz + vp8g.i420_size(tw, th))  # read + written
+        self.d_descs = torch.frombuffer(bytearray(bytes(self.descs)), dtype=torch.uint8).to(dev)
+        self.out = torch.empty(n * slot + 16, dtype=torch.uint8, device=dev)
+
+    def launch(self, stream):
+        rc = self.lib.vp8g_scale_batch_device(self.descs, C.c_void_p(self.d_descs.data_ptr()), self.n,
+                                              C.c_void_p(self.src.data_ptr()), C.c_void_p(self.out.data_ptr()), C.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"vp8g_scale_batch_device: {self.lib.vp8g_last_error()!r}")
+
+    def parity(self):
+        n = vp8g.i420_size(*self.target)
+        return all(self.out[i * self.slot:i * self.slot + n].cpu().numpy().tobytes()
+                   == vp8g.host_scale(self.frames[i % 4].tobytes(), *self.size, self.opt)[0] for i in (0, 1, 2, 3, self.n - 1))
+
+
+def expand_legs(args, dev):
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    out = {"frames": args.frames, "legs": []}
+    for size, target in (((160, 120), (224, 224)), ((500, 200), (224, 224)), ((256, 256), (512, 512))):
+        row = {"source": list(size), "target": list(target)}
+        for key, leg in (("expand", PlainLeg(args.frames, size, target, True, dev)),
+                         ("yardstick_shrink", PlainLeg(args.frames, (target[0] + 1, target[1] + 1), target, False, dev))):
+            t = timed_ms(lambda: leg.launch(stream), args.runs, dev)
+            rate = leg.bytes / (t["ms"] * 1e-3) / 1e12
+            t.update({"source": list(leg.size), "tasks": leg.tasks, "bytes_read_and_written": leg.bytes,
+                      "TBs": round(rate, 3), "fraction_of_achievable": round(rate / HBM_ACHIEVABLE_TBS, 3),
+                      "parity": "bit-exact vs host restatement (5 frames)" if leg.parity() else "MISMATCH"})
+            row[key] = t
+            del leg
+        row["expand_over_yardstick"] = round(row["expand"]["ms"] / row["yardstick_shrink"]["ms"], 3)
+        out["legs"].append(row)
+    return out
+
+
+def expand_table(res) -> str:
+    rows = ["| leg | median | min .. max | note |", "|---|---|---|---|"]
+    for r in res["expand"]["legs"]:
+        for key in ("expand", "yardstick_shrink"):
+            x = r[key]
+            name = "expand" if key == "expand" else "yardstick, shrink kernel"
+            rows.append(f"| {name}: {res['expand']['frames']} x {x['source'][0]}x{x['source'][1]} -> {r['target'][0]}x{r['target'][1]} | "
+                        f"{x['ms']} ms | {x['min']} .. {x['max']} | {x['TBs']} TB/s read + written = {x['fraction_of_achievable']} of "
+                        f"{HBM_ACHIEVABLE_TBS} TB/s; {x['tasks']} tasks"
+                        + (f"; {r['expand_over_yardstick']} of the yardstick |" if key == "expand" else " |"))
+    return "\n".join(rows)
 
 
 def kernel_legs(args, dev):
@@ -177,11 +252,18 @@ def main() -> int:
     ap.add_argument("--runs", type=int, default=12)
     ap.add_argument("--e2e-frames", type=int, default=256)
     ap.add_argument("--e2e-runs", type=int, default=5)
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "scale_bench.json"))
+    ap.add_argument("--expand", action="store_true", help="the expand kernel's legs only (profiles/scale_expand_bench.json)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.runs < 10 or args.e2e_runs < 5:
         ap.error("--runs >= 10 and --e2e-runs >= 5")
     dev = torch.device("cuda", 0)
+    if args.expand:
+        res = {"device": torch.cuda.get_device_name(dev), "expand": expand_legs(args, dev)}
+        pathlib.Path(args.out or ROOT / "profiles" / "scale_expand_bench.json").write_text(json.dumps(res, indent=1) + "\n")
+        print(expand_table(res))
+        return 0
+    args.out = args.out or str(ROOT / "profiles" / "scale_bench.json")
     res = {"device": torch.cuda.get_device_name(dev), "kernel": kernel_legs(args, dev)}
     torch.cuda.empty_cache()
     res["end_to_end"] = e2e_legs(args)

@@ -398,8 +398,9 @@ VP8G_API int vp8g_plan_batch(const ByteSpan* files, uint32_t n, uint32_t threads
 }
 
 // vp8g_decode_webp_batch_ex, and with `opts` (n_opts = 1 or n) vp8g_decode_webp_batch_scaled: each
-// chunk's frames are then cropped / downscaled on the device (vp8g_scale.hip) from the chunk's
-// reconstruction buffer into a second, small one, and only that is downloaded.
+// chunk's frames are then cropped / rescaled on the device (vp8g_scale.hip) from the chunk's
+// reconstruction buffer into a second one (small, unless VP8G_SCALE_EXPAND grows the frames: what a
+// frame grows by counts against the chunk's memory budget), and only that is downloaded.
 // With `topt` (vp8g_decode_webp_batch_tensor; outs = NULL) the sink is the caller's device tensor:
 // each chunk's frames, scaled or not, are written to their slots of d_tensor by the tensor kernel
 // (vp8g_tensor.hip) on the chunk's stream, and only the chunk's status word is downloaded.
@@ -571,6 +572,7 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 			// in order, as they finish
 			std::vector<uint32_t> idx;
 			uint64_t mbs = 0, vals = 0, bitsb = 0, outb = 0, soutb = 0;
+			uint64_t xmbs = 0;  // expanding frames: scaled bytes beyond the frame's own size, priced in MBs of the chunk budget
 			uint32_t b = a, max_cols = 0, max_rows = 0;
 			const bool ctok = feed.dev[feed.order[a]] != 0;  // this chunk's kind
 			const uint32_t cframes = ctok ? chunk_frames_tok : chunk_frames_pk;
@@ -586,8 +588,11 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 					feed.err[fi] = EINVAL;  // not the tensor's picture size
 				if (feed.err[fi] == 0) {
 					const Vp8DecodedFrame& f = f_of(fi);
-					if (!idx.empty() && mbs + f.mb_total > cmbs) break;
-					if (opts) soutb = al256(soutb + vp8g_i420_size(sw, sh));
+					const uint64_t ownb = vp8g_i420_size(kf_of(fi).width, kf_of(fi).height), sclb = opts ? vp8g_i420_size(sw, sh) : 0;
+					const uint64_t fx = sclb > ownb ? (sclb - ownb + 1535u) / 1536u : 0u;  // (0 unless VP8G_SCALE_EXPAND grows it)
+					if (!idx.empty() && mbs + xmbs + f.mb_total + fx > cmbs) break;
+					xmbs += fx;
+					if (opts) soutb = al256(soutb + sclb);
 					idx.push_back(fi);
 					mbs += f.mb_total;
 					if (ctok) bitsb += bits_slot(feed.tj[fi].psize);

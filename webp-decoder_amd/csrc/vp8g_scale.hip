@@ -1,4 +1,4 @@
-// vp8g_scale.hip -- crop + downscale of I420 on the device, bit-exact to libwebp 1.2.2's rescaler
+// vp8g_scale.hip -- crop + rescale of I420 on the device, bit-exact to libwebp 1.2.2's rescaler
 // (include/vp8g.h: vp8g_scale_batch_device, yuv420_rescale; host restatement host/vp8_scale.c;
 // DESIGN.md §14).
 //
@@ -20,6 +20,11 @@
 // (each sums every group-th sample of the footprint, combined by a butterfly of lane exchanges), so
 // a 17:1 and a 16383:1 reduction keep the lanes as busy as a 1:1 one; each lane keeps its column's
 // irow in a register and lane 0 of the group emits a sample at every F(j+1) boundary.
+//
+// Planes that expand in x or in y (VP8G_SCALE_EXPAND; libwebp's bilinear path) belong to a second
+// kernel, expand_kernel below, launched on the same stream only when a batch has such a plane.  The
+// two kernels share the task numbering (image by image, then plane by plane); a plane's `group`
+// field says whose it is (0 = expand_kernel), and each kernel returns at once from the other's tasks.
 #include <errno.h>
 #include <string.h>
 
@@ -175,6 +180,207 @@ __global__ __launch_bounds__(kThreads) void scale_kernel(const Vp8gScaleDesc* __
 	}
 }
 
+
+// ---- expanding planes -------------------------------------------------------------------------
+//
+// libwebp's expand path has a closed form too.  With xe = W < w (x_add = w - 1, x_sub = W - 1):
+//
+//   frow(y, k) = R (w - 1) + (L - R) acc      i = max(0, ceil(k (W-1) / (w-1)) - 1), L = s[y][i], R = s[y][i+1]
+//                                             acc = (i + 1)(w - 1) - k (W - 1)           (W == 1: R = L)
+//
+// and with ye = H < h output row j is a blend of the last two imported rows, cur = m - 1 and prev = m - 2:
+//
+//   m = 1 + ceil(j (H-1) / (h-1)), r = (m - 1)(h - 1) - j (H - 1), B = r 2^32 / (h - 1), A = 2^32 - B
+//   out(j, k) = MULT((A frow(cur, k) + B frow(prev, k) + 2^31) >> 32, fy)     (r == 0: MULT(frow(cur, k), fy))
+//
+// An axis that does not expand keeps the shrink arithmetic above (footprint sums; accumulate / export).
+//
+// ye (x either way): a task is tile_w output columns x run_h output rows.  A horizontal pass, one lane
+// per column, turns the source rows the run touches, m(j0) - 2 ... m(j1 - 1) - 1 (at most run_h + 1),
+// into rows of u32 sums in LDS; a vertical pass, four adjacent columns per lane and 256 / (tile_w / 4)
+// output rows at a time, blends two LDS rows per output row and stores a dword where the address
+// allows.  B and the LDS row of every output row of the run are computed once, into LDS.  When x
+// shrinks here, a lane sums its footprint with a plain loop (a 1000:1 shrink beside an expansion is
+// not a performance target).
+// xe and not ye: one lane per output column walks the run's source rows with its irow in a register,
+// exactly as scale_kernel does with group = 1; the four lanes of an aligned dword combine their
+// samples by lane exchange and one of them stores it.
+// Source samples are read straight from global memory (two taps per sum; the rows are re-read from
+// L1 / L2 by the neighbouring columns).
+constexpr uint32_t kXLdsBytes = 32768;                        // rows of horizontal sums
+constexpr uint32_t kXMinTile = 64, kXMaxTile = 256;           // output columns per task (ye)
+constexpr uint32_t kXMaxRows = kXLdsBytes / (4u * kXMinTile);  // 128 LDS rows at the narrowest tile
+constexpr uint32_t kXRunSrcRows = 64;                         // source rows per task (about), xe and not ye
+
+__device__ __forceinline__ uint32_t clamp_u8(uint32_t v) { return (int32_t)v > 255 ? 255u : v & 255u; }
+
+__global__ __launch_bounds__(kThreads) void expand_kernel(const Vp8gScaleDesc* __restrict__ descs, uint32_t n,
+                                                          const uint8_t* __restrict__ src, uint8_t* __restrict__ dst) {
+	__shared__ __attribute__((aligned(16))) uint32_t sums[kXLdsBytes / 4u];
+	__shared__ uint32_t row_b[kXMaxRows], row_cur[kXMaxRows];
+	const uint32_t task = blockIdx.x, tid = threadIdx.x;
+	uint32_t lo = 0, hi = n - 1u;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi + 1u) >> 1;
+		if (descs[mid].task0 <= task) lo = mid;
+		else hi = mid - 1u;
+	}
+	const Vp8gScaleDesc& D = descs[lo];
+	uint32_t t = task - D.task0;
+	if (task < D.task0 || t >= D.ntasks) return;
+	uint32_t pi = 0;
+	while (pi < 2u && t >= D.p[pi].ntasks) t -= D.p[pi].ntasks, pi++;
+	const Vp8gScalePlane& P = D.p[pi];
+	const uint32_t W = P.src_w, H = P.src_h, w = P.dst_w, h = P.dst_h;
+	const bool xexp = W < w, yexp = H < h;
+	if (P.group != 0 || !(xexp || yexp) || t >= P.ntasks || P.tiles_x == 0 || P.run_h == 0) return;  // (scale_kernel's plane)
+	const uint32_t fx = P.fx, fy = P.fy, fxy = P.fxy, tw = P.tile_w, sstride = P.src_stride;
+	if (tw < kXMinTile || tw > kXMaxTile || (tw & (tw - 1u))) return;  // (never: see make_plane)
+	const uint32_t tx = t % P.tiles_x, ry = t / P.tiles_x;
+	const uint32_t k0 = tx * tw, kend = min(k0 + tw, w);
+	const uint32_t j0 = ry * P.run_h, j1 = min(j0 + P.run_h, h);
+	if (k0 >= w || j0 >= h) return;
+
+	// -- this lane's column of the horizontal pass: the two taps (xe) or the footprint [e0, e1)
+	const uint32_t c = tid & (tw - 1u), k = k0 + c;
+	const bool colok = k < kend;
+	uint32_t i0 = 0, acc = 0, e0 = 0, e1 = 0, a0 = 0, a1 = 0;
+	if (colok) {
+		if (xexp) {
+			const uint32_t up = ceil_div(k * (W - 1u), w - 1u);
+			i0 = up ? up - 1u : 0u;
+			acc = (i0 + 1u) * (w - 1u) - k * (W - 1u);
+		} else {
+			e0 = ceil_div(k * W, w), e1 = ceil_div((k + 1u) * W, w);
+			a0 = e0 * w - k * W, a1 = e1 * w - (k + 1u) * W;
+		}
+	}
+	const uint8_t* sbase = src + P.src;  // the window's first sample; every load below is row y < H, column < W
+	// four source rows at a time, so that their loads are in flight together
+	auto hsum4 = [&](const uint32_t (&y)[4], uint32_t (&f)[4]) {
+		const uint8_t* row[4];
+#pragma unroll
+		for (uint32_t q = 0; q < 4u; q++) row[q] = sbase + (size_t)y[q] * sstride;
+		if (xexp) {
+#pragma unroll
+			for (uint32_t q = 0; q < 4u; q++) {
+				const uint32_t L = row[q][i0], R = W > 1u ? row[q][i0 + 1u] : L;
+				f[q] = R * (w - 1u) + (L - R) * acc;
+			}
+			return;
+		}
+		uint32_t sum[4] = {0, 0, 0, 0}, last[4] = {0, 0, 0, 0}, cs[4] = {0, 0, 0, 0};
+		if (k > 0) {
+#pragma unroll
+			for (uint32_t q = 0; q < 4u; q++) cs[q] = row[q][e0 - 1u];
+		}
+		for (uint32_t x = e0; x < e1; x++) {  // (e1 > e0: W >= w)
+#pragma unroll
+			for (uint32_t q = 0; q < 4u; q++) last[q] = row[q][x], sum[q] += last[q];
+		}
+#pragma unroll
+		for (uint32_t q = 0; q < 4u; q++) f[q] = (mult_fix(cs[q] * a0, fx) + sum[q]) * w - last[q] * a1;
+	};
+
+	if (yexp) {
+		const uint32_t rows = P.block_rows;
+		if (P.pitch != 4u * tw || rows != kXLdsBytes / P.pitch || P.run_h + 1u > rows) return;  // (never)
+		auto m_of = [&](uint32_t j) { return H > 1u ? 1u + ceil_div(j * (H - 1u), h - 1u) : 1u; };
+		const uint32_t m0 = m_of(j0), y_first = m0 >= 2u ? m0 - 2u : 0u, y_last = m_of(j1 - 1u);
+		const uint32_t nrows = y_last - y_first, nout = j1 - j0;
+		if (nrows > rows) return;  // (never: H < h, so a run of run_h rows touches at most run_h + 1)
+		for (uint32_t jj = tid; jj < nout; jj += kThreads) {
+			const uint32_t j = j0 + jj, m = m_of(j), r = (m - 1u) * (h - 1u) - j * (H - 1u), d = h - 1u;
+			// B = floor(r 2^32 / d) in two 16-bit steps (r < d < 2^14)
+			const uint32_t q1 = (r << 16) / d, r1 = (r << 16) - q1 * d;
+			row_b[jj] = (q1 << 16) + (r1 << 16) / d;
+			row_cur[jj] = m - 1u - y_first;
+		}
+		const uint32_t rstep = kThreads / tw;
+		for (uint32_t r = tid / tw; r < nrows; r += 4u * rstep) {
+			uint32_t y[4], f[4] = {0, 0, 0, 0};
+#pragma unroll
+			for (uint32_t q = 0; q < 4u; q++) y[q] = y_first + min(r + q * rstep, nrows - 1u);  // (past the run: a row again, dropped)
+			if (colok) hsum4(y, f);
+#pragma unroll
+			for (uint32_t q = 0; q < 4u; q++)
+				if (r + q * rstep < nrows) sums[(r + q * rstep) * tw + c] = f[q];
+		}
+		__syncthreads();
+		const uint32_t lanes_x = tw >> 2, cx = (tid & (lanes_x - 1u)) << 2, kk = k0 + cx;
+		if (kk >= kend) return;
+		for (uint32_t jj = tid / lanes_x; jj < nout; jj += kThreads / lanes_x) {
+			const uint32_t B = row_b[jj], cur = row_cur[jj];
+			const uint4 cv = *(const uint4*)&sums[cur * tw + cx];
+			uint32_t f[4] = {cv.x, cv.y, cv.z, cv.w};
+			if (B) {
+				const uint4 pv = *(const uint4*)&sums[(cur - 1u) * tw + cx];  // (B != 0 only with m >= 2)
+				const uint32_t g[4] = {pv.x, pv.y, pv.z, pv.w};
+				const uint32_t A = 0u - B;
+#pragma unroll
+				for (uint32_t q = 0; q < 4u; q++)
+					f[q] = (uint32_t)(((uint64_t)A * f[q] + (uint64_t)B * g[q] + (1ull << 31)) >> 32);
+			}
+#pragma unroll
+			for (uint32_t q = 0; q < 4u; q++) f[q] = clamp_u8(mult_fix(f[q], fy));
+			uint8_t* o = dst + P.dst + (size_t)(j0 + jj) * P.dst_stride + kk;
+			if (kk + 3u < kend && !((uintptr_t)o & 3u)) {
+				*(uint32_t*)o = f[0] | (f[1] << 8) | (f[2] << 16) | (f[3] << 24);
+			} else {
+#pragma unroll
+				for (uint32_t q = 0; q < 4u; q++)
+					if (kk + q < kend) o[q] = (uint8_t)f[q];
+			}
+		}
+		return;
+	}
+
+	// -- xe and not ye: scale_kernel's row walk (tile_w = 256: c == tid), the sums from the two taps
+	if (tw != kThreads || !xexp) return;  // (never)
+	auto hsum = [&](uint32_t y) -> uint32_t {
+		const uint8_t* row = sbase + (size_t)y * sstride;
+		const uint32_t L = row[i0], R = W > 1u ? row[i0 + 1u] : L;
+		return R * (w - 1u) + (L - R) * acc;
+	};
+	const bool boundary = j0 > 0;
+	const uint32_t Fj0 = ceil_div(j0 * H, h);
+	const uint32_t y_first = boundary ? Fj0 - 1u : 0u, y_last = ceil_div(j1 * H, h);
+	const uint32_t ys0 = fy * (Fj0 * h - j0 * H);
+	const uint32_t qH = H / h, rH = H - qH * h;
+	uint32_t irow = 0, j = j0, nextF = ceil_div((j0 + 1u) * H, h);
+	uint32_t ya = nextF * h - (j0 + 1u) * H;
+	uint8_t* out = dst + P.dst + k;
+	const uint32_t lane = tid & 63u;
+	for (uint32_t y = y_first; y < y_last; y++) {
+		const uint32_t frow = colok ? hsum(y) : 0u;
+		if (boundary && y == y_first) {
+			irow = ys0 ? __umulhi(frow, ys0) : 0u;
+			continue;
+		}
+		irow += frow;
+		if (y + 1u != nextF) continue;
+		const uint32_t ys = fy * ya;
+		const uint32_t frac = ys ? __umulhi(frow, ys) : 0u;
+		const uint32_t v = fxy ? clamp_u8(mult_fix(irow - frac, fxy)) : irow & 255u;  // (fxy == 0: w == 2 and h == H)
+		// the lane whose byte starts an aligned dword stores it for the three lanes after it
+		const uint32_t pk = v | ((uint32_t)__shfl_down((int)v, 1) << 8) | ((uint32_t)__shfl_down((int)v, 2) << 16) |
+		                    ((uint32_t)__shfl_down((int)v, 3) << 24);
+		uint8_t* o = out + (size_t)j * P.dst_stride;
+		const uint32_t a = (uint32_t)((uintptr_t)o & 3u);
+		if (colok) {
+			if (lane >= a && lane - a <= 60u && k - a + 3u < kend) {
+				if (a == 0) *(uint32_t*)o = pk;
+			} else {
+				*o = (uint8_t)v;
+			}
+		}
+		irow = frac;
+		j++;
+		if (rH > ya) nextF += qH + 1u, ya = h - (rH - ya);
+		else nextF += qH, ya -= rH;
+	}
+}
+
 // One plane's descriptor: factors and tiling.
 void make_plane(Vp8gScalePlane* p, uint64_t src, uint32_t sstride, uint32_t W, uint32_t H, uint64_t dst, uint32_t w,
                 uint32_t h) {
@@ -182,6 +388,22 @@ void make_plane(Vp8gScalePlane* p, uint64_t src, uint32_t sstride, uint32_t W, u
 	p->src = src, p->dst = dst, p->src_stride = sstride, p->dst_stride = w;
 	p->src_w = W, p->src_h = H, p->dst_w = w, p->dst_h = h;
 	vp8f_scale_factors(W, H, w, h, &p->fx, &p->fy, &p->fxy);
+	if (W < w || H < h) {  // expand_kernel's plane: group = 0 (include/vp8g.h)
+		if (H < h) {
+			p->tile_w = kXMinTile;
+			while (p->tile_w < kXMaxTile && p->tile_w < w) p->tile_w *= 2u;
+			p->pitch = 4u * p->tile_w;
+			p->block_rows = kXLdsBytes / p->pitch;
+			p->run_h = p->block_rows - 1u;
+		} else {
+			p->tile_w = kThreads;
+			const uint32_t rh = (uint32_t)((uint64_t)kXRunSrcRows * h / H);
+			p->run_h = rh ? rh : 1u;
+		}
+		p->tiles_x = (w + p->tile_w - 1u) / p->tile_w;
+		p->ntasks = p->tiles_x * ((h + p->run_h - 1u) / p->run_h);
+		return;
+	}
 	uint32_t g = 1;
 	while (g < 64u && (uint64_t)W > (uint64_t)kLanePerCol * g * w) g *= 2u;
 	p->group = g;
@@ -197,7 +419,26 @@ void make_plane(Vp8gScalePlane* p, uint64_t src, uint32_t sstride, uint32_t W, u
 	p->block_rows = kBufBytes / p->pitch;
 }
 
+bool expands(const Vp8gScalePlane& p) { return p.src_w < p.dst_w || p.src_h < p.dst_h; }
+
 bool plane_ok(const Vp8gScalePlane& p) {
+	if (p.src_w && p.src_h && expands(p)) {  // expand_kernel's plane: exactly what make_plane gives
+		uint32_t fx, fy, fxy, tw = kThreads;
+		if (p.dst_w > kMaxDim || p.dst_h > kMaxDim || p.src_w > kMaxDim || p.src_h > kMaxDim || p.src_stride < p.src_w ||
+		    p.dst_stride < p.dst_w || p.group != 0)
+			return false;
+		vp8f_scale_factors(p.src_w, p.src_h, p.dst_w, p.dst_h, &fx, &fy, &fxy);
+		if (p.fx != fx || p.fy != fy || p.fxy != fxy) return false;
+		if (p.src_h < p.dst_h) {
+			for (tw = kXMinTile; tw < kXMaxTile && tw < p.dst_w;) tw *= 2u;
+			if (p.pitch != 4u * tw || p.block_rows != kXLdsBytes / p.pitch || p.run_h != p.block_rows - 1u) return false;
+		} else {
+			const uint32_t rh = (uint32_t)((uint64_t)kXRunSrcRows * p.dst_h / p.src_h);
+			if (p.pitch != 0 || p.block_rows != 0 || p.run_h != (rh ? rh : 1u)) return false;
+		}
+		return p.tile_w == tw && p.tiles_x == (p.dst_w + tw - 1u) / tw &&
+		       p.ntasks == p.tiles_x * ((p.dst_h + p.run_h - 1u) / p.run_h);
+	}
 	return p.src_w && p.src_h && p.dst_w && p.dst_h && p.dst_w <= p.src_w && p.dst_h <= p.src_h && p.src_w <= kMaxDim &&
 	       p.src_h <= kMaxDim && p.src_stride >= p.src_w && p.dst_stride >= p.dst_w && p.group && !(p.group & (p.group - 1u)) &&
 	       p.group <= 64u && p.tile_w * p.group == kThreads && p.run_h && p.tiles_x == (p.dst_w + p.tile_w - 1u) / p.tile_w &&
@@ -248,6 +489,7 @@ VP8G_API int vp8g_scale_batch_device(const Vp8gScaleDesc* h, const Vp8gScaleDesc
 		return -1;
 	}
 	uint64_t total = 0;
+	bool any_shrink = false, any_expand = false;
 	for (uint32_t i = 0; i < n; i++) {
 		const Vp8gScaleDesc& d = h[i];
 		if (d.task0 != total || d.ntasks == 0 || d.ntasks != (uint64_t)d.p[0].ntasks + d.p[1].ntasks + d.p[2].ntasks ||
@@ -255,6 +497,7 @@ VP8G_API int vp8g_scale_batch_device(const Vp8gScaleDesc* h, const Vp8gScaleDesc
 			errno = EINVAL;
 			return -1;
 		}
+		for (uint32_t pi = 0; pi < 3u; pi++) (expands(d.p[pi]) ? any_expand : any_shrink) = true;
 		total += d.ntasks;
 		if (total > 0x7FFFFFFFu) {
 			errno = EINVAL;
@@ -263,8 +506,12 @@ VP8G_API int vp8g_scale_batch_device(const Vp8gScaleDesc* h, const Vp8gScaleDesc
 	}
 	vp8g::GateScope gate((hipStream_t)stream);  // (vp8g_device.h: no cross-workgroup launch beside it)
 	hipError_t e = gate.status();
-	if (e == hipSuccess) {
+	if (e == hipSuccess && any_shrink) {
 		hipLaunchKernelGGL(scale_kernel, dim3((uint32_t)total), dim3(kThreads), 0, (hipStream_t)stream, d_descs, n, d_src, d_dst);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess && any_expand) {  // same grid, same numbering: each kernel returns from the other's tasks
+		hipLaunchKernelGGL(expand_kernel, dim3((uint32_t)total), dim3(kThreads), 0, (hipStream_t)stream, d_descs, n, d_src, d_dst);
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess) e = gate.done(false);

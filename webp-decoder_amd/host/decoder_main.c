@@ -5,10 +5,11 @@
  *   decoder -info <file.webp>
  *   decoder -yuv  <file.webp> <out.i420>    recon only            (m06 on the GPU)
  *   decoder -yuvf <file.webp> <out.i420>    recon + loop filter   (m06 + m07 on the GPU)
- *   decoder -yuv|-yuvf [-crop x y w h] [-scale w h] <file.webp> <out.i420>
- *                                           the same, cropped and / or downscaled on the GPU as
+ *   decoder -yuv|-yuvf [-crop x y w h] [-scale w h [-expand]] <file.webp> <out.i420>
+ *                                           the same, cropped and / or rescaled on the GPU as
  *                                           libwebp does (dwebp -yuv [-crop] [-scale]; a -scale
- *                                           dimension of 0 is derived from the other; downscale only).
+ *                                           dimension of 0 is derived from the other; downscale only
+ *                                           unless -expand is given, which needs -scale).
  *                                           With -scale, -yuvf follows libwebp's rule and skips the loop
  *                                           filter when both dimensions shrink below 3/4, so the file
  *                                           equals dwebp's.  Other modes take neither option (usage).
@@ -37,7 +38,7 @@ static void usage(void) {
 	fputs("  decoder -info <file.webp>\n", stderr);
 	fputs("  decoder -yuv <file.webp> <out.i420>\n", stderr);
 	fputs("  decoder -yuvf <file.webp> <out.i420>\n", stderr);
-	fputs("  decoder -yuv|-yuvf [-crop x y w h] [-scale w h] <file.webp> <out.i420>\n", stderr);
+	fputs("  decoder -yuv|-yuvf [-crop x y w h] [-scale w h [-expand]] <file.webp> <out.i420>\n", stderr);
 	fputs("  decoder -ppm <file.webp> <out.ppm>\n", stderr);
 	fputs("  decoder -png <file.webp> <out.png>\n", stderr);
 	fputs("  decoder -diff_mb <file.webp> <oracle.i420>\n", stderr);
@@ -76,7 +77,7 @@ static int cmd_yuv(const char* in, const char* out_path, int filtered, const Vp8
 	if (opt) {
 		Vp8fScaleGeom g;
 		if (vp8f_scale_resolve(kf.width, kf.height, opt, &g) != 0) {
-			fputs("error: bad -crop / -scale for this picture (the crop must lie inside it; downscale only)\n", stderr);
+			fputs("error: bad -crop / -scale for this picture (the crop must lie inside it; downscale only without -expand)\n", stderr);
 			vp8_decoded_frame_free(&d);
 			return 1;
 		}
@@ -243,6 +244,12 @@ int main(int argc, char** argv) {
 		int a = 2, seen = 0;
 		while (a < argc - 2) {
 			uint32_t v[4];
+			if (!strcmp(argv[a], "-expand") && !(seen & 4)) { /* a -scale target may exceed the (cropped) picture */
+				opt.flags |= VP8G_SCALE_EXPAND;
+				seen |= 4;
+				a++;
+				continue;
+			}
 			const int is_crop = !strcmp(argv[a], "-crop"), nv = is_crop ? 4 : 2;
 			if ((!is_crop && strcmp(argv[a], "-scale")) || (seen & (is_crop ? 1 : 2)) || a + nv >= argc - 2) break;
 			int ok = 1;
@@ -258,7 +265,7 @@ int main(int argc, char** argv) {
 			seen |= is_crop ? 1 : 2;
 			a += 1 + nv;
 		}
-		if (!seen || a != argc - 2) {
+		if (!seen || a != argc - 2 || ((seen & 4) && !(seen & 2))) { /* (-expand needs -scale) */
 			usage();
 			return 2;
 		}

@@ -78,7 +78,7 @@ int vp8f_token_header_memory(const uint8_t* data, size_t size, Vp8KeyFrameHeader
 int vp8f_synth_frame(uint32_t width, uint32_t height, uint64_t seed, int profile, Vp8KeyFrameHeader* kf,
                      Vp8DecodedFrame* out);
 
-/* ---- crop + downscale of I420, bit-exact to libwebp's rescaler (vp8_scale.c) ------------- */
+/* ---- crop + rescale of I420, bit-exact to libwebp's rescaler (vp8_scale.c) --------------- */
 
 /* A Vp8gScaleOpt (include/vp8g.h) resolved against a width x height picture: the luma window
  * (origin snapped down to even) and the output size.  The chroma window starts at
@@ -91,9 +91,10 @@ typedef struct {
 
 /* libwebp's rules: a crop needs w, h >= 1 and left + w <= width, top + h <= height (with the
  * caller's values); a target dimension of 0 is derived from the other with a ceiling
- * (h = (win_h * w + win_w - 1) / win_w), both 0 = no scaling.  Downscale only: a target larger
- * than the window in either dimension, a picture beyond 16383 x 16383, unknown flags or a NULL
- * argument give -1 + EINVAL. */
+ * (h = (win_h * w + win_w - 1) / win_w), both 0 = no scaling.  Without VP8G_SCALE_EXPAND downscale
+ * only: a target larger than the window in either dimension is -1 + EINVAL; with it a target
+ * dimension (given or derived) may be up to 16383.  A picture beyond 16383 x 16383, unknown flags
+ * or a NULL argument give -1 + EINVAL. */
 int vp8f_scale_resolve(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, Vp8fScaleGeom* g);
 
 /* Whether a `filtered` request runs the loop filter for this picture.  With
@@ -101,10 +102,12 @@ int vp8f_scale_resolve(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt,
  * out_w < width * 3 / 4 and out_h < height * 3 / 4 (the full picture, not the crop). */
 int vp8f_scale_filtered(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, int filtered);
 
-/* The rescaler's three fixed-point factors of one plane W x H -> w x h. */
+/* The rescaler's three fixed-point factors of one plane W x H -> w x h, for the plane's mode per
+ * axis (libwebp's values: fx = 0 when W < w, where it is unused; H < h: fy = 2^32 / x_add and
+ * fxy = 0, unused). */
 void vp8f_scale_factors(uint32_t W, uint32_t H, uint32_t w, uint32_t h, uint32_t* fx, uint32_t* fy, uint32_t* fxy);
 
-/* Crop + downscale a width x height I420 image (plane pointers and strides) into the
+/* Crop + rescale a width x height I420 image (plane pointers and strides) into the
  * destination planes, which must hold the resolved output size.  Sequential; reentrant.
  * 0, or -1 + errno (EINVAL, ENOMEM). */
 int vp8f_scale_i420(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint32_t stride_y, uint32_t stride_uv,

@@ -5,8 +5,8 @@
  *
  * This is the sequential host restatement: the CPU path, and the checker of the device kernel
  * (csrc/vp8g_scale.hip, which evaluates the same sums in closed form).  It is written from the
- * rescaler's arithmetic as DESIGN.md §14 states it: per plane W x H -> w x h (w <= W, h <= H),
- * every value a wrapping uint32_t,
+ * rescaler's arithmetic as DESIGN.md §14 states it: per plane W x H -> w x h, every value a wrapping
+ * uint32_t.  Shrinking (w <= W, h <= H):
  *
  *   fx = 2^32 / w, fy = 2^32 / h, fxy = (h * 2^32) / (W * H)   (0 when it does not fit 32 bits)
  *   MULT(x, y) = (x * y + 2^31) >> 32, FLOOR(x, y) = (x * y) >> 32       (64-bit products)
@@ -16,9 +16,18 @@
  * output row is exported whenever the vertical accumulator runs out, the straddling row split
  * with FLOOR(., fy * remainder) and the total scaled by MULT(., fxy).
  *
+ * Expanding (VP8G_SCALE_EXPAND; per plane and per axis, xe = W < w, ye = H < h) is libwebp's
+ * bilinear path.  With xe, x_add = w - 1 and x_sub = W - 1 and a row is imported as
+ * frow[k] = R * x_add + (L - R) * accum over the two source samples L, R that output k lies between
+ * (fx unused; a shrinking y then uses fxy = (h * 2^32) / ((w - 1) * H)).  With ye, y_add = H - 1,
+ * y_sub = h - 1, fy = 2^32 / x_add, nothing accumulates: irow and frow swap before every import so
+ * that they hold the last two imported rows, and an output row is their blend
+ * MULT((A * frow + B * irow + 2^31) >> 32, fy) with B = (-y_accum * 2^32) / y_sub, A = 2^32 - B
+ * (MULT(frow, fy) when y_accum is 0).
+ *
  * Luma is scaled from the (cropped) window to the target size, each chroma plane from
- * ceil(window / 2) to ceil(target / 2), independently.  Only shrinking (or identity) is
- * implemented; libwebp's bilinear expand path is out of scope (EINVAL).
+ * ceil(window / 2) to ceil(target / 2), independently, each with its own mode.  Without
+ * VP8G_SCALE_EXPAND a target beyond the window in either dimension is EINVAL.
  */
 #include <errno.h>
 #include <stdlib.h>
@@ -33,9 +42,10 @@ static uint32_t mult_floor(uint32_t x, uint32_t y) { return (uint32_t)(((uint64_
 
 int vp8f_scale_resolve(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, Vp8fScaleGeom* g) {
 	if (!opt || !g || width == 0 || height == 0 || width > SCALE_MAX_DIM || height > SCALE_MAX_DIM ||
-	    (opt->flags & ~VP8G_SCALE_DWEBP_FILTER))
+	    (opt->flags & ~(VP8G_SCALE_DWEBP_FILTER | VP8G_SCALE_EXPAND)))
 		goto bad;
 	{
+		const int expand = (opt->flags & VP8G_SCALE_EXPAND) != 0;
 		uint32_t left = 0, top = 0, ww = width, wh = height;
 		if (opt->crop_left | opt->crop_top | opt->crop_w | opt->crop_h) {
 			/* libwebp's rules: the size as given, the origin snapped down to even; the bounds
@@ -50,13 +60,14 @@ int vp8f_scale_resolve(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt,
 		if (ow == 0 && oh == 0) {
 			ow = ww, oh = wh; /* crop only */
 		} else if (ow == 0) {
-			if (oh > wh) goto bad;
+			if (expand ? oh > SCALE_MAX_DIM : oh > wh) goto bad;
 			ow = (uint32_t)(((uint64_t)ww * oh + wh - 1u) / wh);
 		} else if (oh == 0) {
-			if (ow > ww) goto bad;
+			if (expand ? ow > SCALE_MAX_DIM : ow > ww) goto bad;
 			oh = (uint32_t)(((uint64_t)wh * ow + ww - 1u) / ww);
 		}
-		if (ow == 0 || oh == 0 || ow > ww || oh > wh) goto bad; /* downscale only */
+		if (ow == 0 || oh == 0) goto bad;
+		if (expand ? (ow > SCALE_MAX_DIM || oh > SCALE_MAX_DIM) : (ow > ww || oh > wh)) goto bad; /* downscale only */
 		g->left = left, g->top = top, g->win_w = ww, g->win_h = wh, g->out_w = ow, g->out_h = oh;
 		g->scaling = (opt->scaled_w | opt->scaled_h) != 0;
 		return 0;
@@ -76,10 +87,53 @@ int vp8f_scale_filtered(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt
 }
 
 void vp8f_scale_factors(uint32_t W, uint32_t H, uint32_t w, uint32_t h, uint32_t* fx, uint32_t* fy, uint32_t* fxy) {
-	const uint64_t ratio = ((uint64_t)h << 32) / ((uint64_t)W * H);
-	*fx = (uint32_t)((1ull << 32) / w);
-	*fy = (uint32_t)((1ull << 32) / h);
-	*fxy = (ratio >> 32) ? 0u : (uint32_t)ratio;
+	const int xe = W < w, ye = H < h;
+	const uint32_t x_add = xe ? w - 1u : W, x_sub = xe ? W - 1u : w;
+	*fx = xe ? 0u : (uint32_t)((1ull << 32) / x_sub);
+	if (ye) {
+		*fy = (uint32_t)((1ull << 32) / x_add);
+		*fxy = 0u;
+	} else {
+		const uint64_t ratio = ((uint64_t)h << 32) / ((uint64_t)x_add * H);
+		*fy = (uint32_t)((1ull << 32) / h);
+		*fxy = (ratio >> 32) ? 0u : (uint32_t)ratio;
+	}
+}
+
+/* import: the horizontal sums of one source row (shrinking or identity) */
+static void import_shrink(const uint8_t* src, uint32_t W, uint32_t w, uint32_t fx, uint32_t* frow) {
+	uint32_t x_in = 0, sum = 0;
+	int32_t accum = 0;
+	for (uint32_t k = 0; k < w; k++) {
+		uint32_t base = 0;
+		accum += (int32_t)W;
+		while (accum > 0) {
+			accum -= (int32_t)w;
+			base = src[x_in++];
+			sum += base;
+		}
+		const uint32_t frac = base * (uint32_t)(-accum);
+		frow[k] = sum * w - frac;
+		sum = mult_fix(frac, fx);
+	}
+}
+
+/* import: bilinear interpolation of one source row (W < w) */
+static void import_expand(const uint8_t* src, uint32_t W, uint32_t w, uint32_t* frow) {
+	const uint32_t x_add = w - 1u, x_sub = W - 1u;
+	uint32_t x_in = 0, left = src[0], right = W > 1u ? src[1] : left;
+	int32_t accum = (int32_t)x_add;
+	x_in++;
+	for (uint32_t k = 0;;) {
+		frow[k] = right * x_add + (left - right) * (uint32_t)accum;
+		if (++k >= w) break;
+		accum -= (int32_t)x_sub;
+		if (accum < 0) {
+			left = right;
+			right = src[++x_in];
+			accum += (int32_t)x_add;
+		}
+	}
 }
 
 /* work: 2 * w words */
@@ -87,51 +141,65 @@ static void scale_plane(const uint8_t* s, uint32_t ss, uint32_t W, uint32_t H, u
                         uint32_t h, uint32_t* work) {
 	uint32_t fx, fy, fxy;
 	vp8f_scale_factors(W, H, w, h, &fx, &fy, &fxy);
+	const int xe = W < w, ye = H < h;
+	const uint32_t y_add = ye ? H - 1u : H, y_sub = ye ? h - 1u : h;
 	uint32_t* irow = work;
 	uint32_t* frow = work + w;
-	memset(irow, 0, (size_t)w * sizeof(uint32_t));
-	int32_t y_accum = (int32_t)H;
-	uint32_t dy = 0;
-	for (uint32_t y = 0; y < H && dy < h; y++) {
-		/* import: horizontal sums of one source row */
-		const uint8_t* src = s + (size_t)y * ss;
-		uint32_t x_in = 0, sum = 0;
-		int32_t accum = 0;
-		for (uint32_t k = 0; k < w; k++) {
-			uint32_t base = 0;
-			accum += (int32_t)W;
-			while (accum > 0) {
-				accum -= (int32_t)w;
-				base = src[x_in++];
-				sum += base;
+	memset(work, 0, (size_t)2 * w * sizeof(uint32_t));
+	int32_t y_accum = (int32_t)(ye ? y_sub : y_add);
+	uint32_t y = 0, dy = 0;
+	while (dy < h) {
+		while (y_accum > 0 && y < H) { /* import until an output row is due */
+			if (ye) {
+				uint32_t* const tmp = irow;
+				irow = frow, frow = tmp;
 			}
-			const uint32_t frac = base * (uint32_t)(-accum);
-			frow[k] = sum * w - frac;
-			sum = mult_fix(frac, fx);
+			if (xe) import_expand(s + (size_t)y * ss, W, w, frow);
+			else import_shrink(s + (size_t)y * ss, W, w, fx, frow);
+			if (!ye)
+				for (uint32_t k = 0; k < w; k++) irow[k] += frow[k];
+			y++;
+			y_accum -= (int32_t)y_sub;
 		}
-		for (uint32_t k = 0; k < w; k++) irow[k] += frow[k];
-		y_accum -= (int32_t)h;
-		if (y_accum > 0) continue;
+		if (y_accum > 0) break; /* (never: the source rows run out with the last output row) */
 		/* export one output row */
 		uint8_t* dst = d + (size_t)dy * ds;
-		const uint32_t yscale = fy * (uint32_t)(-y_accum);
-		if (fxy == 0) { /* W == 1 and h == H: the sums are the samples */
-			for (uint32_t k = 0; k < w; k++) dst[k] = (uint8_t)irow[k], irow[k] = 0;
-		} else if (yscale) {
-			for (uint32_t k = 0; k < w; k++) {
-				const uint32_t frac = mult_floor(frow[k], yscale);
-				const int32_t v = (int32_t)mult_fix(irow[k] - frac, fxy);
-				dst[k] = v > 255 ? 255u : (uint8_t)v;
-				irow[k] = frac;
+		if (ye) {
+			if (y_accum == 0) {
+				for (uint32_t k = 0; k < w; k++) {
+					const int32_t v = (int32_t)mult_fix(frow[k], fy);
+					dst[k] = v > 255 ? 255u : (uint8_t)v;
+				}
+			} else {
+				const uint32_t B = (uint32_t)(((uint64_t)(uint32_t)(-y_accum) << 32) / y_sub);
+				const uint32_t A = (uint32_t)((1ull << 32) - B);
+				for (uint32_t k = 0; k < w; k++) {
+					const uint64_t I = (uint64_t)A * frow[k] + (uint64_t)B * irow[k];
+					const uint32_t J = (uint32_t)((I + (1ull << 31)) >> 32);
+					const int32_t v = (int32_t)mult_fix(J, fy);
+					dst[k] = v > 255 ? 255u : (uint8_t)v;
+				}
 			}
 		} else {
-			for (uint32_t k = 0; k < w; k++) {
-				const int32_t v = (int32_t)mult_fix(irow[k], fxy);
-				dst[k] = v > 255 ? 255u : (uint8_t)v;
-				irow[k] = 0;
+			const uint32_t yscale = fy * (uint32_t)(-y_accum);
+			if (fxy == 0) { /* x_add == 1 and h == H: the sums are the samples */
+				for (uint32_t k = 0; k < w; k++) dst[k] = (uint8_t)irow[k], irow[k] = 0;
+			} else if (yscale) {
+				for (uint32_t k = 0; k < w; k++) {
+					const uint32_t frac = mult_floor(frow[k], yscale);
+					const int32_t v = (int32_t)mult_fix(irow[k] - frac, fxy);
+					dst[k] = v > 255 ? 255u : (uint8_t)v;
+					irow[k] = frac;
+				}
+			} else {
+				for (uint32_t k = 0; k < w; k++) {
+					const int32_t v = (int32_t)mult_fix(irow[k], fxy);
+					dst[k] = v > 255 ? 255u : (uint8_t)v;
+					irow[k] = 0;
+				}
 			}
 		}
-		y_accum += (int32_t)H;
+		y_accum += (int32_t)y_add;
 		dy++;
 	}
 }

@@ -163,6 +163,7 @@ class Vp8gTensorDesc(C.Structure):
 
 
 VP8G_SCALE_DWEBP_FILTER = 1
+VP8G_SCALE_EXPAND = 4
 
 T_DTYPES = {"uint8": 0, "float16": 1, "bfloat16": 2, "float32": 3}  # VP8G_T_U8 / F16 / BF16 / F32
 T_ELEM = {0: 1, 1: 2, 2: 2, 3: 4}
@@ -530,11 +531,13 @@ def gpu_decode_webp_batch(files: list[bytes], filtered: bool = True, threads: in
     return out, list(st)
 
 
-def scale_opt(crop=None, scale=None, dwebp_filter: bool = False) -> Vp8gScaleOpt:
-    """Vp8gScaleOpt from crop = (left, top, w, h) or None and scale = (w, h) or None (0 = derived)."""
+def scale_opt(crop=None, scale=None, dwebp_filter: bool = False, expand: bool = False) -> Vp8gScaleOpt:
+    """Vp8gScaleOpt from crop = (left, top, w, h) or None and scale = (w, h) or None (0 = derived).
+    expand: VP8G_SCALE_EXPAND, a target may exceed the (cropped) source in either dimension."""
     c = crop or (0, 0, 0, 0)
     s = scale or (0, 0)
-    return Vp8gScaleOpt(c[0], c[1], c[2], c[3], s[0], s[1], VP8G_SCALE_DWEBP_FILTER if dwebp_filter else 0)
+    flags = (VP8G_SCALE_DWEBP_FILTER if dwebp_filter else 0) | (VP8G_SCALE_EXPAND if expand else 0)
+    return Vp8gScaleOpt(c[0], c[1], c[2], c[3], s[0], s[1], flags)
 
 
 def scaled_size(w: int, h: int, opt: Vp8gScaleOpt):
