@@ -1,0 +1,459 @@
+"""Directed VP8 streams: the entropy front ends' pin (host/vp8_parse.c dense and packed, vp8f_token_header,
+csrc/vp8g_m05.hip, the expand step of vp8g_pipeline.hip).
+
+Every stream of the corpus was written by libwebp's encoder, which never sends loop-filter deltas,
+delta-mode segments, quantiser deltas other than uv_dc = -2, segmentation without a map or without
+data, the colour-space / clamping / scale bits, a non-skipped macroblock of all-EOB blocks, arbitrary
+probability tables, a magnitude above 1752 or more than 240 macroblock columns.  Here a frame made by
+vp8g.synth_frame / directed.build is written as a .webp by the test-only writer oracle/libstreamw.so
+(oracle/vp8_stream_writer.c, RFC 6386) under a parameter block that sets all of those, and the front
+ends must return exactly that frame.
+
+CASES is the one table; a case is a dict
+  name    unique key (also the key of tests/golden/stream_kat.json)
+  frame   frame recipe: p0 / p1 / p2 (vp8g.synth_frame profiles), p0c (p0 with |coefficient| <= 6, so that
+          under no quantiser a transform leaves int16 and libwebp stays a second witness), a directed kind (wrap, mixed, skip,
+          bpred_all, bpred_none, lf00..lf15), allskip (p0 with every coefficient zero), sparse
+          (directed uni_dc_dc: one DC per block)
+  header  header recipe (HEADERS below); `simple` picks the filter for every recipe but the lfNN kinds,
+          which carry their own
+  probs   default / quarter / all / fit   (PROBS)
+  skip    off / p1 / p128 / p255 / none / half   (SKIPS)
+  size, seed, log2k (token partitions = 1 << log2k), cut (per partition: trailing bytes left out)
+  twin    for a native multi-partition case: the one-partition case of the same frame
+
+build(case) -> Built(frame, data, census, params): the canonical frame (what a decoder can return:
+canonical()), the stream and the writer's census.  Everything is seeded; build() is cached.
+"""
+import ctypes as C
+import functools
+import pathlib
+import sys
+
+import numpy as np
+
+ROOT = pathlib.Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT / "webp-decoder_amd"))
+import directed  # noqa: E402
+import vp8g  # noqa: E402
+
+TOKENS = ("EOB", "ZERO", "ONE", "TWO", "THREE", "FOUR", "CAT1", "CAT2", "CAT3", "CAT4", "CAT5", "CAT6")
+SKIP_EMPTY, SKIP_NONE, SKIP_HALF = 0, 1, 2
+CUT_ALL = 0xFFFFFFFF
+MAX_MAGNITUDE = 67 + 2047  # DCT_CAT6 with all 11 extra bits (RFC 6386 13.2)
+
+
+class StreamParams(C.Structure):
+    """oracle/vp8_stream_writer.c Vp8StreamParams"""
+    _fields_ = [("color_space", C.c_uint8), ("clamp_type", C.c_uint8), ("x_scale", C.c_uint8), ("y_scale", C.c_uint8),
+                ("update_mb_segmentation_map", C.c_uint8), ("seg_tree_probs", C.c_uint8 * 3),
+                ("update_segment_feature_data", C.c_uint8), ("lf_delta_update", C.c_uint8), ("log2_nparts", C.c_uint8),
+                ("refresh_entropy_probs", C.c_uint8), ("use_skip", C.c_uint8), ("skip_prob", C.c_uint8),
+                ("skip_policy", C.c_uint8), ("reserved", C.c_uint8), ("skip_seed", C.c_uint64), ("cut", C.c_uint32 * 8),
+                ("coeff_probs", C.c_uint8 * 1056)]
+
+
+class StreamCensus(C.Structure):
+    """oracle/vp8_stream_writer.c Vp8StreamCensus"""
+    _fields_ = [("tokens", C.c_uint64 * 12), ("ymode", C.c_uint64 * 5), ("uv_mode", C.c_uint64 * 4),
+                ("bmode", C.c_uint64 * 10), ("segment", C.c_uint64 * 4), ("skip_bits", C.c_uint64 * 2),
+                ("max_magnitude", C.c_uint32), ("nparts", C.c_uint32), ("part0_size", C.c_uint32),
+                ("part_off", C.c_uint32 * 8), ("part_end", C.c_uint32 * 8), ("part_off_mod4", C.c_uint32 * 8),
+                ("prob_updates", C.c_uint32), ("payload_size", C.c_uint32)]
+
+
+_lib = None
+
+
+def writer_lib():
+    global _lib
+    if _lib is None:
+        path = ROOT / "oracle" / "libstreamw.so"
+        if not path.exists():
+            raise RuntimeError("oracle/libstreamw.so missing: run make")
+        _lib = C.CDLL(str(path), use_errno=True)
+        _lib.vp8_stream_write.argtypes = [C.POINTER(vp8g.Vp8KeyFrameHeader), C.POINTER(vp8g.Vp8DecodedFrame),
+                                          C.POINTER(StreamParams), C.c_void_p, C.c_size_t, C.POINTER(StreamCensus),
+                                          C.c_void_p, C.c_void_p]
+        _lib.vp8_stream_write.restype = C.c_long
+        _lib.vp8_stream_default_probs.restype = C.POINTER(C.c_uint8)
+        _lib.vp8_stream_params_size.restype = _lib.vp8_stream_census_size.restype = C.c_size_t
+        assert _lib.vp8_stream_params_size() == C.sizeof(StreamParams) == 1112
+        assert _lib.vp8_stream_census_size() == C.sizeof(StreamCensus) == 416
+    return _lib
+
+
+def default_probs() -> np.ndarray:
+    return np.ctypeslib.as_array(writer_lib().vp8_stream_default_probs(), shape=(1056,)).copy()
+
+
+def q_tables():
+    """RFC 6386 14.1 (dc, ac) quantiser tables of host/vp8_tables.inc."""
+    lib = writer_lib()
+    lib.vp8_stream_dc_q.restype = lib.vp8_stream_ac_q.restype = C.POINTER(C.c_int16)
+    return [np.ctypeslib.as_array(p(), shape=(128,)).astype(int) for p in (lib.vp8_stream_dc_q, lib.vp8_stream_ac_q)]
+
+
+def expected_desc_tables(h):
+    """RFC 6386 9.3, 9.6, 14.1, 15.2 restated: what a frame header `h` makes of the per-segment
+    dequantisation factors [4][Y1dc, Y1ac, UVdc, UVac, Y2dc, Y2ac] and of the loop-filter parameters
+    [4][is B_PRED][level, interior limit, hev threshold, 0] (Vp8gFrameDesc.dq / .lf, include/vp8g.h).
+    The segment level is clamped to 0..63 before the deltas are added and again after (the reference)."""
+    dc, ac = q_tables()
+    cq = lambda x: min(max(int(x), 0), 127)  # noqa: E731
+    dq, lf = np.zeros((4, 6), int), np.zeros((4, 2, 4), int)
+    for s in range(4):
+        q = int(h.q_index)
+        if h.segmentation_enabled:
+            q = h.seg_quant_idx[s] if h.segmentation_abs else q + h.seg_quant_idx[s]
+        dq[s] = [dc[cq(q + h.y1_dc_delta_q)], ac[cq(q)], min(dc[cq(q + h.uv_dc_delta_q)], 132), ac[cq(q + h.uv_ac_delta_q)],
+                 2 * dc[cq(q + h.y2_dc_delta_q)], max(ac[cq(q + h.y2_ac_delta_q)] * 155 // 100, 8)]
+        for bp in range(2):
+            lvl = int(h.lf_level)
+            if h.segmentation_enabled:
+                lvl = h.seg_lf_level[s] if h.segmentation_abs else lvl + h.seg_lf_level[s]
+            lvl = min(max(lvl, 0), 63)
+            if h.lf_delta_enabled:
+                lvl = min(max(lvl + h.lf_ref_delta[0] + (h.lf_mode_delta[0] if bp else 0), 0), 63)
+            il = lvl
+            if h.lf_sharpness:
+                il = min(il >> (2 if h.lf_sharpness > 4 else 1), 9 - h.lf_sharpness)
+            lf[s, bp] = [lvl, max(il, 1), 2 if lvl >= 40 else (1 if lvl >= 15 else 0), 0]
+    return dq, lf
+
+
+def write(f, prm, want_branches=False):
+    """vp8_stream_write: (stream bytes, census, skip_written[, branch counts]); OSError(errno) when it refuses."""
+    cap = 4096 + 64 * f.mb_total + 4 * sum(int(np.count_nonzero(f.array(n))) for n in ("coeff_y", "coeff_u", "coeff_v", "coeff_y2"))
+    out = (C.c_uint8 * cap)()
+    cs = StreamCensus()
+    skipped = np.zeros(f.mb_total, np.uint8)
+    br = np.zeros((4, 8, 3, 11, 2), np.uint32)
+    C.set_errno(0)
+    n = writer_lib().vp8_stream_write(C.byref(f.kf), C.byref(f.frame), C.byref(prm), out, cap, C.byref(cs),
+                                      skipped.ctypes.data, br.ctypes.data)
+    if n <= 0:
+        raise OSError(C.get_errno(), "vp8_stream_write refused the frame")
+    res = (bytes(out[:n]), cs, skipped)
+    return res + (br,) if want_branches else res
+
+
+# ---- header recipes --------------------------------------------------------------------------------
+# A recipe rewrites header fields of the frame and writer parameters; `s` (0 normal filter, 1 simple)
+# also flips the signs of the directed values, so that each field is sent with both signs.
+
+def _set4(arr, vals):
+    for i in range(len(arr)):
+        arr[i] = vals[i]
+
+
+def _sgn(vals, s):
+    return tuple(-v for v in vals[::-1]) if s else tuple(vals)
+
+
+def _h_plain(h, prm, rng, s):
+    pass
+
+
+def _h_bits(h, prm, rng, s):
+    """colour-space and clamping bits, scale bits 1 and 2 (swapped for the simple filter)"""
+    prm.color_space, prm.clamp_type = 1, 1
+    prm.x_scale, prm.y_scale = (2, 1) if s else (1, 2)
+    prm.refresh_entropy_probs = 1
+
+
+def _h_lfdelta(h, prm, rng, s):
+    h.lf_delta_enabled, h.lf_level, h.lf_sharpness = 1, 37, 5
+    _set4(h.lf_ref_delta, _sgn((-9, 1, 2, 3), s))
+    _set4(h.lf_mode_delta, _sgn((-63, 0, 63, -1), s))
+
+
+def _h_lfdelta_keep(h, prm, rng, s):
+    """lf_delta_enabled with no update: the deltas stay at their defaults (0)"""
+    h.lf_delta_enabled = 1
+    prm.lf_delta_update = 0
+
+
+def _h_segdelta(h, prm, rng, s):
+    h.segmentation_enabled, h.segmentation_abs = 1, 0
+    h.q_index, h.lf_level = 64, 32
+    _set4(h.seg_quant_idx, _sgn((-5, 7, 0, -63), s))
+    _set4(h.seg_lf_level, _sgn((-31, 3, 0, 31), s))
+
+
+def _h_segclamp(h, prm, rng, s):
+    """delta-mode segments whose sums leave 0..127 / 0..63 at both ends"""
+    h.segmentation_enabled, h.segmentation_abs = 1, 0
+    h.q_index, h.lf_level = 100, 40
+    _set4(h.seg_quant_idx, _sgn((-127, 127, 28, -101), s))  # 100 + .: -27, 227, 128, -1
+    _set4(h.seg_lf_level, _sgn((-63, 63, 24, -41), s))      # 40 + .: -23, 103, 64, -1
+    if s:
+        h.q_index, h.lf_level = 27, 23                      # 27 + (101, -28, -127, 127), 23 + (41, -24, -63, 63)
+
+
+def _h_seg_nomap(h, prm, rng, s):
+    h.segmentation_enabled, h.segmentation_abs = 1, s
+    _set4(h.seg_quant_idx, (20, 40, 60, 80) if s else (-20, 5, 9, 30))
+    _set4(h.seg_lf_level, (10, 20, 30, 40) if s else (-10, 4, 8, 12))
+    prm.update_mb_segmentation_map = 0
+
+
+def _h_seg_nodata(h, prm, rng, s):
+    h.segmentation_enabled = 1
+    prm.update_segment_feature_data = 0
+
+
+def _h_seg_map255(h, prm, rng, s):
+    h.segmentation_enabled = 1
+    _set4(prm.seg_tree_probs, (255, 255, 255, 0))
+
+
+def _h_seg_maprand(h, prm, rng, s):
+    h.segmentation_enabled = 1
+    for i in range(3):
+        prm.seg_tree_probs[i] = int(rng.integers(1, 255))
+
+
+def _h_q(q, d):
+    def recipe(h, prm, rng, s):
+        h.q_index = q
+        h.y1_dc_delta_q = h.y2_dc_delta_q = h.y2_ac_delta_q = h.uv_dc_delta_q = h.uv_ac_delta_q = d
+    return recipe
+
+
+def _h_mini(h, prm, rng, s):
+    """the hand-written feasibility stream's header: everything at once"""
+    _h_bits(h, prm, rng, s)
+    h.segmentation_enabled, h.segmentation_abs = 1, 0
+    _set4(h.seg_quant_idx, _sgn((-5, 7, 0, -127), s))
+    _set4(h.seg_lf_level, _sgn((-63, 3, 0, 63), s))
+    prm.update_mb_segmentation_map = 0
+    _h_lfdelta(h, prm, rng, s)
+    h.q_index = 100
+    h.y1_dc_delta_q, h.y2_dc_delta_q, h.y2_ac_delta_q, h.uv_dc_delta_q, h.uv_ac_delta_q = _sgn((-15, 15, -7, 3, -1), s)
+
+
+HEADERS = {"plain": _h_plain, "bits": _h_bits, "lfdelta": _h_lfdelta, "lfdelta_keep": _h_lfdelta_keep,
+           "segdelta": _h_segdelta, "segclamp": _h_segclamp, "seg_nomap": _h_seg_nomap, "seg_nodata": _h_seg_nodata,
+           "seg_map255": _h_seg_map255, "seg_maprand": _h_seg_maprand, "q0_m15": _h_q(0, -15), "q0_p15": _h_q(0, 15),
+           "q127_m15": _h_q(127, -15), "q127_p15": _h_q(127, 15), "mini": _h_mini}
+PROBS = ("default", "quarter", "all", "fit")
+SKIPS = {"off": (0, 0, SKIP_EMPTY), "p1": (1, 1, SKIP_EMPTY), "p128": (1, 128, SKIP_EMPTY), "p255": (1, 255, SKIP_EMPTY),
+         "none": (1, 128, SKIP_NONE), "half": (1, 77, SKIP_HALF)}
+SIZES = [(16, 16), (33, 50), (320, 64), (48, 144), (16383, 16), (16, 16383)]
+LARGE = SIZES[4:]
+COEFF_KINDS = ("p0", "p1", "p2", "wrap", "mixed", "skip", "bpred_all", "bpred_none")
+# libwebp's SIMD inverse transforms add in int16 lanes: a profile-0 block has at most 6 values, the two
+# passes scale a value by at most 1.31^2, the largest dequantisation factor is 440 (Y2 AC at index 127):
+# 6 * 6 * 440 * 1.72 < 32768
+P0C_MAX = 6
+FULL_RANGE = ("p1", "p2", "wrap", "mixed", "bpred_all", "bpred_none", "sparse")  # |c| up to 2114: beyond libwebp's int16 path
+
+
+def _case(name, frame, header="plain", simple=0, probs="default", skip="p128", size=(33, 50), seed=1, log2k=0, cut=(),
+          twin=None):
+    return dict(name=name, frame=frame, header=header, simple=simple, probs=probs, skip=skip, size=tuple(size), seed=seed,
+                log2k=log2k, cut=tuple(cut), twin=twin)
+
+
+def _table():
+    cases, small, skips = [], SIZES[:4], list(SKIPS)
+    i = 0
+    # every header recipe with the normal and with the simple filter; coefficient kind, size, table and skip cycle
+    for hname in HEADERS:
+        for s in (0, 1):
+            cases.append(_case(f"h_{hname}_{'sn'[1 - s]}", ("p0c", "p1", "p2")[i % 3], hname, s, PROBS[i % 4], skips[i % 6],
+                               small[(i // 2) % 4], 100 + i))
+            i += 1
+    # LF_CASES of tests/directed.py through the bitstream
+    for k in range(16):
+        cases.append(_case(f"lf{k:02d}", f"lf{k:02d}", "plain", k & 1, PROBS[k % 4], skips[(k + 1) % 6], small[1 + k % 3], 40 + k))
+    # coefficient kinds at two sizes
+    for k, kind in enumerate(COEFF_KINDS):
+        for j, size in enumerate(((33, 50), (320, 64))):
+            cases.append(_case(f"c_{kind}_{size[0]}x{size[1]}", kind, "plain", (k + j) & 1, PROBS[(k + j) % 4],
+                               skips[(k + 2 * j) % 6], size, 7 + j))
+    # probability tables x skip variants on one frame kind per table
+    for a, pv in enumerate(PROBS):
+        for b, sv in enumerate(SKIPS):
+            if (a + b) % 2:
+                continue
+            cases.append(_case(f"ps_{pv}_{sv}", ("skip", "p1", "p0", "sparse")[a], "plain", b & 1, pv, sv,
+                               (16, 16) if (a + b) % 3 == 0 else (33, 50), 300 + 10 * a + b))
+    # the column and the row limit (profile 0 only)
+    for size in LARGE:
+        tag = f"{size[0]}x{size[1]}"
+        cases.append(_case(f"big_{tag}_plain", "p0", "plain", 0, "default", "p128", size, 11))
+        cases.append(_case(f"big_{tag}_mini", "p0c", "mini", 1, "quarter", "half", size, 12))
+    # native 2 / 4 / 8 partitions: every size, and several streams per count (start offsets modulo 4)
+    by = {c["name"]: c for c in cases}
+    multi = []
+    for size in SIZES:
+        same = [c for c in cases if c["size"] == size]
+        for c, counts in ((same[len(same) // 3], (1, 2, 3)), (same[-1], (2,))):
+            for log2k in counts:
+                multi.append(dict(c, name=f"{c['name']}_mp{1 << log2k}", log2k=log2k, twin=c["name"]))
+    # cut variants: the (only) token partition 1, 2, 3 bytes short and empty
+    cuts = []
+    for n in ("c_p0_33x50", "h_segdelta_n"):
+        for cut, tag in ((1, "cut1"), (2, "cut2"), (3, "cut3"), (CUT_ALL, "empty")):
+            cuts.append(dict(by[n], name=f"{n}_{tag}", cut=(cut,)))
+    cuts.append(_case("allskip_empty", "allskip", "plain", 0, "default", "p128", (48, 144), 5, 0, (CUT_ALL,)))
+    cuts.append(_case("allskip_mp1", "allskip", "plain", 0, "default", "p128", (48, 144), 5))
+    cuts.append(_case("allskip_mp4_empty", "allskip", "plain", 0, "default", "p128", (48, 144), 5, 2, (CUT_ALL,) * 4,
+                      twin="allskip_mp1"))
+    return cases + multi + cuts
+
+
+CASES = _table()
+BY_NAME = {c["name"]: c for c in CASES}
+assert len(BY_NAME) == len(CASES)
+
+# Native multi-partition streams with partitions in the middle declared short or empty: a partition's
+# reader must see zeros past its own end, not the next partition's bytes.  Neither the reference (one
+# partition only) nor libwebp (refuses short partitions) decodes these, so they are not in the golden
+# file: the bar is device == host (tests/test_gpu_streams.py), as for the corpus' truncated payloads.
+MP_CUT_CASES = [dict(BY_NAME["lf06_mp4"], name="lf06_mp4_cutmid", cut=(2, CUT_ALL, 1, 3)),
+                dict(BY_NAME["h_mini_s_mp8"], name="h_mini_s_mp8_cutmid", cut=(0, 3, CUT_ALL, 0, 1, 2, CUT_ALL, 5)),
+                dict(BY_NAME["h_seg_map255_n_mp2"], name="h_seg_map255_n_mp2_cutfirst", cut=(CUT_ALL, 0))]
+BY_NAME.update({c["name"]: c for c in MP_CUT_CASES})
+
+
+def is_cut(case):
+    """The declared partitions are shorter than what was encoded (round trip to the frame not expected,
+    unless nothing is read from them: the all-skipped frame)."""
+    return bool(case["cut"]) and case["frame"] != "allskip"
+
+
+def base_profile0(case):
+    """Built on profile 0 (small coefficients): libwebp must agree with the reference."""
+    return case["frame"] not in FULL_RANGE
+
+
+# ---- frames ----------------------------------------------------------------------------------------
+
+def _raw_frame(case):
+    kind, (w, h), seed = case["frame"], case["size"], case["seed"]
+    if kind in ("p0", "p1", "p2"):
+        f = vp8g.synth_frame(w, h, seed, int(kind[1]))
+    elif kind == "p0c":
+        f = vp8g.synth_frame(w, h, seed, 0)
+        for n in ("coeff_y", "coeff_u", "coeff_v", "coeff_y2"):
+            np.clip(f.array(n), -P0C_MAX, P0C_MAX, out=f.array(n))
+    elif kind == "allskip":
+        f = vp8g.synth_frame(w, h, seed, 0)
+        for n in ("coeff_y", "coeff_u", "coeff_v", "coeff_y2"):
+            f.array(n)[:] = 0
+    elif kind == "sparse":
+        f = directed.build("uni_dc_dc", w, h, seed)
+    else:
+        f = directed.build(kind, w, h, seed)
+    # out-of-range modes (profile 2; the reconstruction treats them as DC) have no code: fold them into range
+    f.array("ymode")[:] %= 5
+    f.array("uv_mode")[:] %= 4
+    f.array("bmode")[:] %= 10
+    return f
+
+
+def canonical(f, prm, skipped):
+    """Rewrite `f` in place to what a decoder returns for the stream written from it under `prm`."""
+    h = f.frame
+    seg = bool(h.segmentation_enabled)
+    if not seg or not prm.update_segment_feature_data:
+        h.segmentation_abs = 0
+        _set4(h.seg_quant_idx, (0,) * 4)
+        _set4(h.seg_lf_level, (0,) * 4)
+    h.segmentation_enabled, h.segmentation_abs = int(seg), int(bool(h.segmentation_abs))
+    if not (seg and prm.update_mb_segmentation_map):
+        f.array("segment_id")[:] = 0
+    h.lf_use_simple, h.lf_delta_enabled = int(bool(h.lf_use_simple)), int(bool(h.lf_delta_enabled))
+    if not h.lf_delta_enabled or not prm.lf_delta_update:
+        _set4(h.lf_ref_delta, (0,) * 4)
+        _set4(h.lf_mode_delta, (0,) * 4)
+    ym = f.array("ymode")
+    bp = ym == 4
+    f.array("coeff_y").reshape(-1, 16, 16)[~bp, :, 0] = 0
+    f.array("coeff_y2").reshape(-1, 16)[bp] = 0
+    implied = np.array([0, 2, 3, 1, 0], np.uint8)[ym]  # DC->B_DC, V->B_VE, H->B_HE, TM->B_TM
+    bm = f.array("bmode").reshape(-1, 16)
+    bm[~bp] = implied[~bp, None]
+    f.array("has_coeff")[:] = directed.coded(f)
+    f.array("skip_coeff")[:] = skipped
+
+
+def _other(rng, default):
+    """A value in 1..255 different from `default`, per entry (so that each one is sent)."""
+    v = rng.integers(1, 255, default.size)
+    return (v + (v >= default)).astype(np.uint8)
+
+
+def _params(case, f, rng):
+    prm = StreamParams()
+    prm.update_mb_segmentation_map = prm.update_segment_feature_data = prm.lf_delta_update = 1
+    _set4(prm.seg_tree_probs, (255, 255, 255, 0))
+    prm.log2_nparts = case["log2k"]
+    prm.use_skip, prm.skip_prob, prm.skip_policy = SKIPS[case["skip"]]
+    prm.skip_seed = 0x9E3779B9 + case["seed"]
+    for p, c in enumerate(case["cut"]):
+        prm.cut[p] = c
+    probs = default_probs()
+    if case["probs"] == "quarter":
+        idx = rng.choice(1056, 264, replace=False)
+        probs[idx] = _other(rng, probs[idx])
+    elif case["probs"] == "all":
+        probs[:] = _other(rng, probs)
+    C.memmove(prm.coeff_probs, probs.ctypes.data, 1056)
+    return prm
+
+
+class Built:
+    def __init__(self, case, frame, data, census, params):
+        self.case, self.frame, self.data, self.census, self.params = case, frame, data, census, params
+
+
+@functools.lru_cache(maxsize=None)
+def _build(name):
+    case = BY_NAME[name]
+    rng = np.random.default_rng([0x57E4, case["seed"], len(case["name"]), *case["size"]])
+    f = _raw_frame(case)
+    if not case["frame"].startswith("lf"):
+        f.frame.lf_use_simple = case["simple"]
+    prm = _params(case, f, rng)
+    HEADERS[case["header"]](f.frame, prm, rng, case["simple"])
+    if case["probs"] == "fit":
+        # the table fitted to the frame's own tokens: P(bit 0) of every tree node from a first pass's counts
+        _, _, _, br = write(f, prm, want_branches=True)
+        n0, n = br[..., 0].astype(np.float64), br.sum(axis=-1)
+        fit = np.where(n > 0, np.clip(np.rint(256.0 * n0 / np.maximum(n, 1)), 1, 255), default_probs().reshape(4, 8, 3, 11))
+        fit = np.ascontiguousarray(fit.astype(np.uint8))
+        C.memmove(prm.coeff_probs, fit.ctypes.data, 1056)
+    data, cs, skipped = write(f, prm)
+    canonical(f, prm, skipped)
+    f.kf.first_partition_len, f.kf.x_scale, f.kf.y_scale = cs.part0_size, prm.x_scale, prm.y_scale
+    return Built(case, f, data, cs, prm)
+
+
+def build(case):
+    return _build(case["name"] if isinstance(case, dict) else case)
+
+
+def fresh(case):
+    """build(case) without the cache: a frame the caller may rewrite."""
+    return _build.__wrapped__(case["name"] if isinstance(case, dict) else case)
+
+
+def single_partition():
+    return [c for c in CASES if c["log2k"] == 0]
+
+
+def multi_partition():
+    return [c for c in CASES if c["log2k"] > 0]
+
+
+def decode(data, multi=False):
+    """vp8f_decode_memory -> vp8g.Frame, or None (the dense decoder has no multi-partition mode)."""
+    kf, df, st = vp8g.Vp8KeyFrameHeader(), vp8g.Vp8DecodedFrame(), C.c_int(0)
+    buf = (C.c_uint8 * len(data)).from_buffer_copy(data)
+    if vp8g.host_lib().vp8f_decode_memory(buf, len(data), C.byref(kf), C.byref(df), C.byref(st)) != 0:
+        return None
+    return vp8g.Frame(kf, df)
