@@ -526,7 +526,7 @@ const char* vp8g_last_error(void);
 #define VP8G_MODE_CHAIN 1u        /* one 16-wave workgroup per CU decodes a chain of frames */
 #define VP8G_MODE_MIRROR_SPLIT 2u /* frames split between a workgroup and its mirror */
 #define VP8G_MODE_INTERLEAVE 4u   /* two frames of a chain interleaved */
-#define VP8G_MODE_QUAD 8u         /* the chain with four MB rows per wave (else two) */
+#define VP8G_MODE_QUAD 8u         /* four MB rows per wave: set on every chain launch */
 #define VP8G_MODE_SPLIT_PARTS 16u /* each frame over several workgroups */
 uint32_t vp8g_last_launch_mode(void);
 

@@ -6,11 +6,10 @@ Vp8DecodedFrame fields; every draw comes from numpy.random.default_rng(seed).  b
 is the one entry; KINDS lists every kind.  tests/test_directed.py proves from the arrays (and from
 the oracle's loop-filter census) that each kind is what it says.
 
-What the kernels choose by data (csrc/vp8g_kernels.hip frame kernel, csrc/vp8g_quad.inc quad chain,
-the pairs chain):
+What the kernels choose by data (csrc/vp8g_kernels.hip frame kernel, csrc/vp8g_quad.inc quad chain):
   * the inverse DCT has three forms -- DC only, "columns 2-3 zero", full -- chosen per WAVE by a ballot
-    over the dequantised coefficients of 1 MB (frame kernel), 2 MBs (pairs chain) or 4 vertically
-    adjacent MBs (quad chain), in the quad chain separately for the luma and the chroma role;
+    over the dequantised coefficients of 1 MB (frame kernel) or 4 vertically adjacent MBs (quad
+    chain), in the quad chain separately for the luma and the chroma role;
   * the inverse WHT is skipped when no MB of the wave has a Y2 block (all B_PRED);
   * the loop filter leaves out an MB's inner edges when has_coeff == 0 and the MB is not B_PRED,
     keyed on the has_coeff byte alone (reference src/m07_loopfilter/vp8_loopfilter.c:226).
@@ -30,7 +29,6 @@ Kinds (base profile 1, or 2 for an odd seed: full-range coefficients, every mode
                         independent MBs P(dc form) = .55^k, P(cols01 form) = .80^k - .55^k,
                         P(full form) = 1 - .80^k:
                           k = 1 (frame kernel)  55.0 % / 25.0 % / 20.0 %
-                          k = 2 (pairs chain)   30.3 % / 33.8 % / 36.0 %
                           k = 4 (quad chain)     9.2 % / 31.8 % / 59.0 %
                         -- every form >= 5 % per role, and the form changes from step to step
   spoil_<dc|cols01>_<luma|chroma>

@@ -1,5 +1,5 @@
 """Batch decoded by the quad chain kernel (csrc/vp8g_quad.inc: four MB rows per wave; every chain
-batch without loop-filter-only frames), every slot against the oracle.  Imported by tests/test_gpu_quad.py,
+batch), every slot against the oracle.  Imported by tests/test_gpu_quad.py,
 and run as a child process there when an environment switch read once by libvp8g must be set
 (VP8G_SPLITCHAIN=1: every frame of more than four MB rows split between two workgroups).
 
@@ -11,7 +11,7 @@ profiles (segments, loop-filter deltas, simple and normal filter, +-2114 coeffic
 unfiltered, in a scrambled order with one slot in eight left empty.
 
 run(frames=...) decodes a caller's frames instead (directed_frames(): every kind of tests/directed.py
-at four of the sizes, filtered at two of them); want_quad=False expects the pairs chain (VP8G_QUAD=0)."""
+at four of the sizes, filtered at two of them); want_mode: the chain and quad bits, or 0 (VP8G_CHAIN=0)."""
 import pathlib
 import sys
 
@@ -35,7 +35,7 @@ def directed_frames(sizes, seed=11):
             for k, kind in enumerate(directed.KINDS) for r in range(4)]
 
 
-def run(n=1800, seed=0x0A4D, launches=1, want_split=False, sizes=SIZES, frames=None, want_quad=True):
+def run(n=1800, seed=0x0A4D, launches=1, want_split=False, sizes=SIZES, frames=None, want_mode=vp8g.MODE_CHAIN | vp8g.MODE_QUAD):
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(seed)
     sizes_only = frames is None
@@ -63,8 +63,8 @@ def run(n=1800, seed=0x0A4D, launches=1, want_split=False, sizes=SIZES, frames=N
         mode = b.launch_mode()
         if mode is None:
             return ["launch mode unknown: the loaded library has no vp8g_last_launch_mode"]
-        if not (mode & vp8g.MODE_CHAIN and bool(mode & vp8g.MODE_QUAD) == want_quad) or (want_split and not mode & vp8g.MODE_MIRROR_SPLIT):
-            return [f"launch mode {mode}: not the {'quad' if want_quad else 'pairs'} chain{' with the mirror split' if want_split else ''}"]
+        if (mode if want_mode == 0 else mode & (vp8g.MODE_CHAIN | vp8g.MODE_QUAD)) != want_mode or (want_split and not mode & vp8g.MODE_MIRROR_SPLIT):
+            return [f"launch mode {mode}: expected {want_mode}{' with the mirror split' if want_split else ''}"]
     exp, bad = {}, []
     for i in range(n):
         if i in empty:
@@ -98,7 +98,7 @@ if __name__ == "__main__":
     if "--directed" in sys.argv:
         sys.path.insert(0, str(ROOT / "tests"))
         bad = run(n=1200, seed=0xD1A, launches=2, want_split=os.environ.get("VP8G_SPLITCHAIN") == "1",
-                  frames=directed_frames(sizes), want_quad=os.environ.get("VP8G_QUAD") != "0")
+                  frames=directed_frames(sizes), **({"want_mode": 0} if os.environ.get("VP8G_CHAIN") == "0" else {}))
         print("OK" if not bad else f"BAD {len(bad)}: {bad[:8]}")
         sys.exit(0)
     bad = run(launches=2, want_split=os.environ.get("VP8G_SPLITCHAIN") == "1", sizes=sizes)

@@ -2,8 +2,8 @@
 caller-owned device buffers, then vp8g_frame_digests), every slot checked against the digest of the
 reference decoder's own I420 (tests/golden/digests.json).
 
-* 260 x 4K (> 256 CUs: the timed chain kernel `frame_kernel<16, false, false, true>` with the
-  mirror split, two frames per workgroup at most);
+* 260 x 4K (> 256 CUs: the timed chain kernel `quad_kernel<16, true>` with the mirror split, two
+  frames per workgroup at most);
 * 512 x 4K: the exact uhd4 launch bench.py times (rank 0's shard of BASELINE configs[3] / [4]);
 * 128 synthetic 4K frames of a far shard (global indices 3584..3711: rank 7 of configs[4]);
 * two threads on two streams issuing 300-frame 4K batches back to back while a third calls the
@@ -171,17 +171,17 @@ print(rc, C.get_errno(), round(time.time() - t, 3), lib.vp8g_last_error().decode
 
 
 def test_chain_many_small_mixed_frames_and_empty_slots(vp8g):
-    """Chain mode (vp8g_kernels.hip: one 16-wave workgroup per CU decodes a cost-sorted list of
-    frames as one chain of MB row pairs, two LDS context slots reused every other frame): 1 800
+    """Chain mode (vp8g_quad.inc: one 16-wave workgroup per CU decodes a cost-sorted list of
+    frames as one chain of quads of MB rows, two table slots reused every other frame): 1 800
     slots, ~7 frames per workgroup, of 48 distinct synthetic frames from 1x1 to 160x96 -- single-MB
-    and single-row frames (a pair of one row), odd sizes, all synthetic profiles (segments,
+    and single-row frames (a quad of one row), odd sizes, all synthetic profiles (segments,
     loop-filter deltas, simple and normal filter, +-2114 coefficients) -- in a scrambled order with
     one slot in eight left empty (an all-zero descriptor: no work).  Every decoded slot must equal
     the oracle's output for its frame and the empty slots' outputs must stay untouched."""
     import vp8g_batch
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(11)
-    # (the two wide frames make the context slots large enough for the in-kernel cost sort)
+    # (two wide frames: up to 64 MB columns of context per frame)
     sizes = [(1, 1), (16, 16), (17, 9), (160, 16), (33, 47), (160, 96), (1024, 16), (8, 96), (1000, 40)]
     frames = []
     for i in range(48):
@@ -329,11 +329,11 @@ def test_device_batches_two_streams_and_dropin_concurrently(vp8g, digests):
 
 @pytest.mark.parametrize("w,h", [(160, 96), (176, 80)])
 def test_chain_two_frame_interleave(vp8g, w, h):
-    """Two-frame interleave of the chain (vp8g_kernels.hip: a workgroup's frames run two at a time with
-    their MB row pairs alternating, four LDS context slots; chosen for batches of one frame size with at
+    """Two-frame interleave of the chain (vp8g_quad.inc: a workgroup's frames run two at a time with
+    their quads of MB rows alternating, four table slots; chosen for batches of one frame size with at
     least two frames per workgroup, pick_chain_interleave): 549 distinct synthetic frames, so workgroups
-    hold two or three frames (an odd last frame runs alone); 176x80 has an odd MB row count (the last
-    pair of every frame is a single row).  Every slot against the oracle; the launch mode read back
+    hold two or three frames (an odd last frame runs alone); 176x80 has five MB rows (the last
+    quad of every frame is a single row).  Every slot against the oracle; the launch mode read back
     (vp8g_last_launch_mode) must be the interleaved chain."""
     import vp8g_batch
     dev = torch.device("cuda:0")
@@ -354,6 +354,70 @@ def test_chain_two_frame_interleave(vp8g, w, h):
     assert mode is not None, "the loaded library cannot report its launch mode"
     assert mode & vp8g.MODE_CHAIN and mode & vp8g.MODE_INTERLEAVE, mode
     bad = [i for i, f in enumerate(frames) if b.frame_output(i) != vp8g.oracle_reconstruct(f, bool(i % 5))]
+    assert not bad, f"{len(bad)} of {n} slots differ, e.g. {bad[:8]}"
+    for f in frames:
+        f.free()
+
+
+def test_loopfilter_only_batch_larger_than_cu_count(vp8g):
+    """A hand-written batch of (CU count + 8) loop-filter-only frames through vp8g_decode_batch_device:
+    the quad chain has no loop-filter-only path, so pick_chain leaves the batch to the frame kernel,
+    one workgroup per frame (launch mode 0) under the cost-ordered placement.  Sizes 16x16 (one MB),
+    48x32 (3 x 2 MBs) and 32x80 (five MB rows: a third pair of one row), each with a simple-filter and
+    a normal-filter synthetic frame that the filter modifies.  Each descriptor is the filtered one of vp8g_make_frame_desc
+    plus VP8G_F_LF_ONLY, its src_* pointing at the oracle's UNFILTERED reconstruction of the frame
+    (MB-aligned sizes: the cropped image is the padded one); the output must be the oracle's FILTERED
+    reconstruction, byte for byte, with status word 0."""
+    import vp8g_batch
+    dev = torch.device("cuda:0")
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n = cus + 8
+    sizes = [(16, 16), (48, 32), (32, 80)]
+    b = vp8g_batch.DeviceBatch(n, 48, 80, dev)
+    # one frame per size and filter kind that the filter changes in at least 16 bytes (host-side search)
+    cells, seed = {}, 0x1F00
+    while len(cells) < 6 and seed < 0x1F00 + 600:
+        f = vp8g.synth_frame(*sizes[seed % 3], seed, profile=(seed // 3) % 3)
+        key = (f.width, int(f.frame.lf_use_simple))
+        seed += 1
+        if key not in cells:
+            plain, filt = vp8g.oracle_reconstruct(f, False), vp8g.oracle_reconstruct(f, True)
+            if np.count_nonzero(np.frombuffer(plain, np.uint8) != np.frombuffer(filt, np.uint8)) >= 16:
+                cells[key] = f
+                continue
+        f.free()
+    assert len(cells) == 6, sorted(cells)
+    frames = [cells[k] for k in sorted(cells)]
+    assert all(vp8g.make_desc(f, True, 0, 0).flags & vp8g.VP8G_F_LOOPFILTER for f in frames)
+    src_off, chunks, o = [], [], 0
+    for f in frames:
+        src_off.append(o)
+        chunks.append(np.frombuffer(vp8g.oracle_reconstruct(f, False), np.uint8))
+        o += (len(chunks[-1]) + 255) // 256 * 256
+    src_host = np.zeros(o, np.uint8)
+    for so, c in zip(src_off, chunks):
+        src_host[so:so + len(c)] = c
+    src = torch.from_numpy(src_host).to(dev)
+    b.out.fill_(0xA5)
+    for i in range(n):
+        j = i % 6
+        f = frames[j]
+        b.place(i, f, True)
+        d = b.h_descs[i]
+        w, h = f.width, f.height
+        d.flags |= vp8g.VP8G_F_LF_ONLY
+        d.src_y = src_off[j]
+        d.src_u = src_off[j] + w * h
+        d.src_v = d.src_u + (w // 2) * (h // 2)
+        d.src_stride_y, d.src_stride_uv = w, w // 2
+    b.c_arrays.src = src.data_ptr()
+    b.commit()
+    b.launch(torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize()
+    assert b.launch_mode() == 0
+    assert b.status_word() == 0
+    exp = [vp8g.oracle_reconstruct(f, True) for f in frames]
+    bad = [i for i in range(n) if b.out[i * b.frame_bytes:i * b.frame_bytes + len(exp[i % 6])].cpu().numpy().tobytes() != exp[i % 6]]
     assert not bad, f"{len(bad)} of {n} slots differ, e.g. {bad[:8]}"
     for f in frames:
         f.free()

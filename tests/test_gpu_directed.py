@@ -4,11 +4,11 @@ tests/golden/directed_kat.json).  tests/test_directed.py proves on the CPU what 
 here is which kernel meets it:
 
   frame kernel (one workgroup per frame, launch mode 0; ballot over one MB)
-      test_single_frame_entry_points_and_small_batch, test_forced_split_factors[3-8] (8 waves)
+      test_single_frame_entry_points_and_small_batch, test_forced_split_factors[3-8] (8 waves), and
+      with more frames than CUs (cost-ordered placement) test_frame_kernel_directed_many_frames
   split parts (one frame over several workgroups)    test_forced_split_factors[8-0]
   quad chain (ballot over four vertically adjacent MBs, per role), whole pieces and cut / unaligned
       test_quad_chain_directed, and with the mirror split forced test_quad_chain_directed_mirror_split
-  pairs chain (ballot over two MBs)                  test_pairs_chain_directed
   device-memory context path (8200 wide), one-column path (16 wide)   test_extreme_dimensions_directed
   m07 alone on planes the filter modifies            test_loopfilter_entry_point_smooth_planes
 and the launch-mode report itself (test_launch_mode_is_zero_after_an_invalid_call).
@@ -134,10 +134,10 @@ def test_quad_chain_directed_mirror_split(vp8g, odd):
 
 
 @pytest.mark.parametrize("odd", [False, True], ids=["whole", "odd"])
-def test_pairs_chain_directed(vp8g, odd):
-    """The same batch through the two-rows-per-wave chain (VP8G_QUAD=0, child process; the mode must be
-    chain without quad): its ballot spans two MBs."""
-    env = dict(os.environ, VP8G_QUAD="0")
+def test_frame_kernel_directed_many_frames(vp8g, odd):
+    """The same batch with the chain off (VP8G_CHAIN=0, child process): one workgroup per frame with more frames
+    than CUs (ordered_frame's placement runs too); launch mode 0, status 0, every slot exact, empty ones untouched."""
+    env = dict(os.environ, VP8G_CHAIN="0")
     r = subprocess.run([sys.executable, str(ROOT / "tests" / "quad_check.py"), "--directed"] + (["--odd"] if odd else []),
                        capture_output=True, text=True, timeout=240, env=env)
     assert r.returncode == 0, r.stderr[-2000:]

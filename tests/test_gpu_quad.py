@@ -46,9 +46,9 @@ def test_quad_chain_mirror_split_forced(vp8g, odd):
     assert r.stdout.strip().endswith("OK"), r.stdout
 
 
-def test_quad_and_pairs_chains_agree(vp8g):
-    """260 x 4K fixtures (slot i <- fixture i % 4) through the quad chain and, in a child process with
-    VP8G_QUAD=0, through the two-rows-per-wave chain: both equal the reference's digests."""
+def test_quad_chain_4k_fixtures_match_golden_digests(vp8g):
+    """260 x 4K fixtures (slot i <- fixture i % 4) through the quad chain (child process; launch mode
+    chain + quad): every slot equals the reference's digest."""
     code = r"""
 import json, pathlib, sys
 root = pathlib.Path(sys.argv[1])
@@ -69,14 +69,11 @@ bad = [i for i in range(260) if int(dig[i]) != int(golden["fixtures"][UHD[i % 4]
 mode = b.launch_mode()
 print(mode, "OK" if not bad and b.status_word() == 0 else f"BAD {bad[:8]} status {b.status_word()}")
 """
-    for env_extra in ({}, {"VP8G_QUAD": "0"}):
-        env = dict(os.environ, **env_extra)
-        r = subprocess.run([sys.executable, "-c", code, str(ROOT)], capture_output=True, text=True, timeout=240, env=env)
-        assert r.returncode == 0, (env_extra, r.stderr[-2000:])
-        assert r.stdout.strip().endswith("OK"), (env_extra, r.stdout)
-        mode = int(r.stdout.split()[0])
-        quad = env_extra.get("VP8G_QUAD") != "0"
-        assert mode & vp8g.MODE_CHAIN and bool(mode & vp8g.MODE_QUAD) == quad, (env_extra, mode)
+    r = subprocess.run([sys.executable, "-c", code, str(ROOT)], capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.strip().endswith("OK"), r.stdout
+    mode = int(r.stdout.split()[0])
+    assert mode & vp8g.MODE_CHAIN and mode & vp8g.MODE_QUAD, mode
 
 
 def test_quad_chain_stalled_producer_ends_promptly(vp8g):
@@ -116,9 +113,8 @@ print(b.status_word(), b.launch_mode(), round(time.time() - t, 3))
 def test_chain_output_base_not_16b_aligned(vp8g):
     """The output base handed to vp8g_decode_batch_device 8 bytes past an aligned allocation, with
     whole-piece descriptors (offsets and strides 16-B aligned): the quad chain must not take its
-    paired-store instantiation (which assumes a 16-B aligned base) -- and the pairs chain
-    (VP8G_QUAD=0) must be exact too; every slot equals the oracle's output and the 8 bytes before
-    the base stay untouched."""
+    paired-store instantiation (which assumes a 16-B aligned base); every slot equals the oracle's
+    output and the 8 bytes before the base stay untouched."""
     code = r"""
 import ctypes as C, sys
 sys.path.insert(0, sys.argv[1] + "/webp-decoder_amd")
@@ -150,10 +146,8 @@ if host[:8].tobytes() != b"\xa5" * 8:
     bad.append("bytes before the base written")
 print(b.launch_mode(), "OK" if not bad and b.status_word() == 0 else f"BAD {bad[:8]} status {b.status_word()}")
 """
-    for env_extra in ({}, {"VP8G_QUAD": "0"}):
-        env = dict(os.environ, **env_extra)
-        r = subprocess.run([sys.executable, "-c", code, str(ROOT)], capture_output=True, text=True, timeout=240, env=env)
-        assert r.returncode == 0, (env_extra, r.stderr[-2000:])
-        assert r.stdout.strip().endswith("OK"), (env_extra, r.stdout)
-        mode = int(r.stdout.split()[-2])
-        assert mode & vp8g.MODE_CHAIN and bool(mode & vp8g.MODE_QUAD) == (not env_extra), (env_extra, mode)
+    r = subprocess.run([sys.executable, "-c", code, str(ROOT)], capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.strip().endswith("OK"), r.stdout
+    mode = int(r.stdout.split()[-2])
+    assert mode & vp8g.MODE_CHAIN and mode & vp8g.MODE_QUAD, mode

@@ -93,44 +93,18 @@ __host__ __device__ inline uint32_t cost_class(const Vp8gFrameDesc& d) {
 inline size_t lds_bytes(int waves, uint32_t ctx_cols, bool global_ctx) {
 	return (size_t)kHdrBytes + (size_t)waves * kWaveBytes + (global_ctx ? 0 : (size_t)ctx_cols * kCtxBytesPerCol);
 }
-// Chain mode (one 16-wave workgroup per CU decoding a list of frames, vp8g_kernels.hip): two
-// context slots and the list (at most list_max frames).
-// Experiment builds: VP8G_CHAIN_G = 1 keeps the chain's per-column context in device memory (one
-// region per frame; the LDS then holds only the cost sort's scratch), which lets VP8G_CHAIN_WPC
-// workgroups of VP8G_CHAIN_NW waves share a CU (e.g. 2 x 12 waves at 6 waves per SIMD).
-#ifndef VP8G_CHAIN_NW
-#define VP8G_CHAIN_NW 16
-#endif
-#ifndef VP8G_CHAIN_G
-#define VP8G_CHAIN_G 0
-#endif
-#ifndef VP8G_CHAIN_WPC
-#define VP8G_CHAIN_WPC 1
-#endif
-constexpr int kChainWaves = VP8G_CHAIN_NW;
-constexpr bool kChainG = VP8G_CHAIN_G != 0;
-constexpr int kChainWgPerCu = VP8G_CHAIN_WPC;
-// LDS context area of a chain workgroup: the two context slots (four when two frames run
-// interleaved, see pick_chain_interleave), or (global context) the cost sort's scratch of
-// kCostClasses + n_frames words
-// Four MB rows per wave (the quad chain kernel, vp8g_quad.inc): a wave's LDS is four
+// Chain mode (batches of more frames than CUs): one 16-wave workgroup per CU decodes a list of frames,
+// four MB rows per wave (the quad chain kernel, vp8g_quad.inc).  A wave's LDS is four
 // quarter areas (the half layout without the iWHT scratch) and four 3-column context rings; the
 // context between waves lives in device memory (the snapshot buffer, one region per frame), so the
-// quad chain's LDS does not depend on the frame width.  Chosen per batch (pick_quad).
+// chain's LDS does not depend on the frame width.
 constexpr int kQuarterBytes = kWht;                          // tile, borders, B_PRED buffers, residual park
 constexpr int kRingBytes = 3 * kCtxBytesPerCol;              // three MB columns of context
 constexpr int kQRings = kHdrBytes + 4 * kQuarterBytes;       // wave-relative: ring h at + h * kRingBytes
 constexpr int kQWaveBytes = 4 * kQuarterBytes + 4 * kRingBytes;
 constexpr int kQList = kHdrBytes + 16 * kQWaveBytes;         // the chain list (after 16 wave areas)
-inline size_t chain_ctx_lds(uint32_t ctx_cols, uint32_t n_frames, bool il = false, bool quad = false) {
-	if (quad) return (size_t)16 * kQWaveBytes;  // (the cost sort's scratch sits in the wave areas)
-	return kChainG ? ((size_t)4 * (kCostClasses + n_frames) + 15) & ~(size_t)15
-	               : (il ? 4 : 2) * (size_t)ctx_cols * kCtxBytesPerCol;
-}
-inline size_t chain_lds_bytes(uint32_t ctx_cols, uint32_t list_max, uint32_t n_frames, bool il = false, bool quad = false) {
-	if (quad) return (size_t)kQList + 4 * (size_t)list_max;
-	return (size_t)kHdrBytes + (size_t)kChainWaves * kWaveBytes + chain_ctx_lds(ctx_cols, n_frames, il) + 4 * (size_t)list_max;
-}
+constexpr size_t kChainScratch = (size_t)16 * kQWaveBytes;  // the cost sort's scratch: the wave areas
+inline size_t chain_lds_bytes(uint32_t list_max) { return (size_t)kQList + 4 * (size_t)list_max; }
 
 // Process-wide launch gate (vp8g_shim.hip).  Launch modes whose workgroups wait on each other across
 // CUs -- split parts (launch_frames with nsplit > 1) and the chain's mirror split -- need every
@@ -182,32 +156,27 @@ hipError_t launch_frames(const Vp8gFrameDesc* d_descs, uint32_t n_frames, const 
 uint32_t pick_order(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t nsplit);
 
 // Chain mode for n_frames frames on this device: the workgroup count (0 = not applicable: too few
-// frames, a context too wide for two LDS slots, or VP8G_CHAIN=0), and whether the frames are
-// placed by cost class (*ordered; needs the sort scratch to fit the context slots).
-uint32_t pick_chain(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t ctx_cols, bool* ordered, bool quad = false);
-// Mirror split of a chain launch (vp8g_kernels.hip, kSegTop): worth it for ordered batches of at most
+// frames, a loop-filter-only frame in the batch -- the quad kernel has no such path, the batch runs
+// one workgroup per frame --, more than 1024 MB columns, or VP8G_CHAIN=0), and whether the frames
+// are placed by cost class (*ordered; needs the sort scratch to fit the wave areas).
+uint32_t pick_chain(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t ctx_cols, bool* ordered);
+// Mirror split of a chain launch (vp8g_quad.inc, kSegTop): worth it for ordered batches of at most
 // two frames per workgroup (VP8G_SPLITCHAIN=0 / 1 forces it off / on), and the doubled list must fit.
-bool pick_chain_split(uint32_t n_frames, uint32_t ctx_cols, uint32_t workgroups, bool ordered, bool quad = false);
-// Two-frame interleave of a chain launch (vp8g_kernels.hip): the frames of a workgroup's list run two
-// at a time with their MB row pairs alternating (the pair above is two global pairs back), which
-// halves the chain's fill and drain.  Needs every frame of the batch the same size, four context
-// slots in LDS and no mirror split (VP8G_CHAIN_IL=0 / 1 forces it off / on where it fits).
-bool pick_chain_interleave(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t ctx_cols, uint32_t workgroups, bool split,
-                           bool quad = false);
-// The quad chain kernel for this batch: no frame is loop-filter-only (quad_supported), and VP8G_QUAD
-// is not 0 (A/B experiments).  whole_pieces: every frame has whole, aligned 16-B / 8-B row pieces, so
-// launch_chain(..., whole = true) takes the kernel's lean instantiation (the general one adds a byte
-// path for pieces cut by the right edge or unaligned planes).  A quad launch needs
-// `snap` (every frame's context, n_frames * ctx_cols * kCtxBytesPerCol bytes) in every mode.
-bool quad_supported(const Vp8gFrameDesc* h_descs, uint32_t n_frames);
-bool pick_quad(const Vp8gFrameDesc* h_descs, uint32_t n_frames);
+bool pick_chain_split(uint32_t n_frames, uint32_t workgroups, bool ordered);
+// Two-frame interleave of a chain launch (vp8g_quad.inc): the frames of a workgroup's list run two
+// at a time with their quads alternating (the quad above is two global quads back), which halves
+// the chain's fill and drain.  Needs every frame of the batch the same size and no mirror split
+// (VP8G_CHAIN_IL=0 / 1 forces it off / on where it fits).
+bool pick_chain_interleave(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t workgroups, bool split);
+// whole_pieces: every frame has whole, aligned 16-B / 8-B row pieces, so launch_chain(..., whole = true)
+// takes the kernel's lean instantiation (the general one adds a byte path for pieces cut by the right
+// edge or unaligned planes).
 bool whole_pieces(const Vp8gFrameDesc* h_descs, uint32_t n_frames);
-// split: `snap` holds n_frames * ctx_cols * kCtxBytesPerCol bytes, `flags` n_frames words that hold
-// no value equal to `epoch` (a per-launch counter) before the launch.
+// `snap` holds every frame's context, n_frames * ctx_cols * kCtxBytesPerCol bytes, in every mode.
+// split: `flags` holds n_frames words, none equal to `epoch` (a per-launch counter) before the launch.
 hipError_t launch_chain(const Vp8gFrameDesc* d_descs, uint32_t n_frames, const Vp8gBatchArrays& arrays, uint8_t* d_out,
-                        uint32_t ctx_cols, hipStream_t stream, uint32_t workgroups, bool ordered, bool split = false,
-                        uint8_t* snap = nullptr, uint32_t* flags = nullptr, uint32_t epoch = 0, bool interleave = false,
-                        bool quad = false, bool whole = false);
+                        uint32_t ctx_cols, hipStream_t stream, uint32_t workgroups, bool ordered, bool whole, uint8_t* snap,
+                        bool split = false, uint32_t* flags = nullptr, uint32_t epoch = 0, bool interleave = false);
 
 constexpr uint32_t kMaxSplit = 8;
 int device_cus();

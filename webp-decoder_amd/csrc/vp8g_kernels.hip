@@ -334,8 +334,8 @@ typedef __amdgpu_buffer_rsrc_t Rsrc;
 constexpr uint32_t kNoStore = 0x80000000u;
 constexpr uint32_t kFlCtxBias = 512u;  // (fast flush: keeps the per-lane ctx_lf offsets non-negative)
 DEV Rsrc plane_rsrc(uint8_t* base, uint32_t bytes) {
-	// (inputs laundered through readfirstlane: built inside the chain's frame loop, the resource was
-	// otherwise kept in VGPRs and every store became a waterfall loop)
+	// (inputs laundered through readfirstlane: built inside the quad chain's frame loop, the resource
+	// was otherwise kept in VGPRs and every store became a waterfall loop)
 	const uint64_t b = (uint64_t)(uintptr_t)base;
 	const uint64_t bu = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
 	                    (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
@@ -351,7 +351,6 @@ DEV Rsrc plane_rsrc(uint8_t* base, uint32_t bytes) {
 #define VP8G_STORE_AUX 16
 #endif
 constexpr int kCpolSc1 = 16;   // cache-policy bits of a buffer access: sc1 (device-coherent, bypasses the CU's L1)
-constexpr int kSnapBatch = 8;  // mirror split: 16-B snapshot loads per lane in flight
 DEV void bst128(Rsrc r, uint32_t off, u32x4 v) { __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)off, 0, VP8G_STORE_AUX); }
 DEV void bst64(Rsrc r, uint32_t off, u32x2 v) { __builtin_amdgcn_raw_buffer_store_b64(v, r, (int)off, 0, VP8G_STORE_AUX); }
 
@@ -657,150 +656,52 @@ DEV uint32_t ordered_frame(const Vp8gFrameDesc* descs, uint32_t n, uint32_t F, u
 	return f;
 }
 
-// Chain mode (kC, batches with more frames than CUs): ONE workgroup of NW = 16 waves per CU
-// decodes a list of frames as one continuous chain of MB row pairs -- global pair g of the list
-// (the frames' pairs one after another) belongs to wave g % NW -- so no wave idles at a frame's
-// end while another frame of the CU still has rows, and a heavy frame never runs alone on half
-// the CU.  Two frames are in flight at once: frame j of the list uses LDS slot j & 1 (its
-// per-column context and its dequant / loop-filter tables); pair 0 of frame j waits until frame
-// j - 2, the slot's previous user, has finished its last pair (which implies all of its pairs:
-// pair k's last steps wait for pair k - 1 to complete).  The list of workgroup b: the frames at
-// positions b, 2W-1-b, 2W+b, 4W-1-b, ... of the batch sorted by descending cost class (snake
-// order: every CU gets one of the heaviest and one of the lightest frames per two rounds), sorted
-// in the prologue by wave 0 (stable counting sort over the cost classes in LDS scratch).
-// Progress words encode global pair * 2048 + steps done (C <= 1024, so steps <= 1026).
+// Progress words encode pair * 2048 + steps done (C <= 1024, so steps <= 1026); vp8g_quad.inc uses
+// the same encoding with its quads.
 constexpr uint32_t kProgShift = 11;
-// Mirror split (launch_chain with split, batches of at most two frames per workgroup): each frame is
-// cut at pair h = ceil(pairs / 2) into a top segment (pairs [0, h), decoded by the frame's own
-// workgroup, first in its list) and a bottom segment (pairs [h, pairs), decoded LAST by the mirror
-// workgroup W-1-b).  Every workgroup thus decodes half of its own frames and half of its mirror's,
-// which evens out the pairing of heavy and light frames (two 4K frames per CU cannot balance four
-// fixture kinds).  The top segment's last pair, after its last step, copies the frame's context
-// slot (the row above the bottom segment, C x 160 B) to a snapshot in device memory (sc1 stores,
-// drained) and stores the launch's epoch in the frame's flag; the bottom segment's first pair,
-// when it claims its slot, waits for that flag and copies the snapshot into the slot.  Tops never
-// wait across workgroups and bottoms come after every top of their list, so no cycle exists, and a
-// top finishes in the first half of its workgroup's work, long before its bottom starts.
-constexpr uint32_t kSegTop = 1u, kSegBottom = 2u, kSegMask = 0x3FFFFFFFu;  // list entry: frame | tag << 30
 
-template <int NW, bool kG, bool kS, bool kC>
+template <int NW, bool kG, bool kS>
 __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void frame_kernel(const Vp8gFrameDesc* __restrict__ descs, Vp8gBatchArrays A,
                                                         uint8_t* __restrict__ out, uint32_t ctx_cols,
                                                         uint8_t* __restrict__ gctx, uint32_t nsplit,
                                                         uint8_t* __restrict__ mbox, uint32_t* __restrict__ gprog,
-                                                        uint32_t ord_first, uint32_t n_chain) {
-	static_assert(!kC || !kS, "chain mode never splits frames into parts");
+                                                        uint32_t ord_first) {
 	extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 	const int lane0 = (int)(threadIdx.x & 63);
 	const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 	const uint32_t K = kS ? nsplit : 1u;
 	const uint32_t nfr = kS ? gridDim.x / K : gridDim.x;
-	const uint32_t slot_bytes = ctx_cols * (uint32_t)kCtxBytesPerCol;
 	uint8_t* const ctx_base = smem + kHdrBytes + NW * kWaveBytes;
-	// (kC) after the two context slots (global context: after the cost sort's scratch)
-	// (kC, ord_first bit 2: two frames interleaved, four context slots)
-	const bool il = kC && (ord_first & 4u) != 0;
-	uint32_t* const chain_list = (uint32_t*)(ctx_base + (kG ? ((4u * (kCostClasses + n_chain) + 15u) & ~15u) : (il ? 4u : 2u) * slot_bytes));
-	uint32_t m_chain = 1;  // (kC) frames in this workgroup's list
-	uint32_t f;
-	if constexpr (kC) {
-		// ---- this workgroup's frame list (see above); ord_first != 0: cost-sorted positions
-		const uint32_t Wg = gridDim.x, b = blockIdx.x, n = n_chain;
-		if (wave == 0) {
-			uint32_t* const hist = (uint32_t*)ctx_base;  // scratch (the context slots, written later)
-			uint32_t* const sorted = hist + kCostClasses;
-			const uint64_t lt = (1ull << lane0) - 1ull;
-			if (ord_first & 1u) {
-				for (int i = lane0; i < (int)kCostClasses; i += 64) hist[i] = 0u;
-				wave_lds_sync();
-				for (int pass = 0; pass < 2; pass++) {
-					for (uint32_t c0 = 0; c0 < n; c0 += 64) {
-						const uint32_t i = c0 + (uint32_t)lane0;
-						const bool valid = i < n;
-						const uint32_t cls = valid ? cost_class(descs[i]) : 0u;
-						uint64_t rem = __ballot(valid);
-						while (rem) {  // one distinct class per iteration (peeled by its first lane)
-							const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cls, (int)__builtin_ctzll(rem));
-							const uint64_t mk = __ballot(valid && cls == c);
-							const uint32_t base = hist[c];
-							wave_lds_sync();
-							if (pass == 1 && ((mk >> lane0) & 1ull)) sorted[base + (uint32_t)__popcll(mk & lt)] = i;
-							if (lane0 == (int)__builtin_ctzll(mk)) hist[c] = base + (uint32_t)__popcll(mk);
-							wave_lds_sync();
-							rem &= ~mk;
-						}
-					}
-					if (pass == 0) {  // counts -> start positions, heaviest class first
-						if (lane0 == 0) {
-							uint32_t acc = 0;
-							for (int c = (int)kCostClasses - 1; c >= 0; c--) {
-								const uint32_t h = hist[c];
-								hist[c] = acc;
-								acc += h;
-							}
-						}
-						wave_lds_sync();
-					}
-				}
-			}
-			// snake positions of workgroup b (increasing in j), empty descriptors left out.  Mirror
-			// split (ord_first bit 1): workgroup b decodes the top halves of its own frames, then the
-			// bottom halves of workgroup W-1-b's frames (entry tags, kSegTop / kSegBottom)
-			uint32_t cnt = 0;
-			auto add_list = [&](uint32_t bb, uint32_t tag) {
-				for (uint32_t j0 = 0;; j0 += 64) {
-					const uint32_t j = j0 + (uint32_t)lane0;
-					const uint32_t pos = j * Wg + ((j & 1u) ? Wg - 1u - bb : bb);
-					const bool valid = pos < n;
-					if (__ballot(valid) == 0ull) break;
-					const uint32_t fi = valid ? ((ord_first & 1u) ? sorted[pos] : pos) : 0u;
-					const bool keep = valid && descs[fi].mb_cols != 0 && descs[fi].mb_rows != 0 && (tag != kSegBottom || descs[fi].mb_rows > 2u);
-					const uint64_t mk = __ballot(keep);
-					if (keep) chain_list[cnt + (uint32_t)__popcll(mk & lt)] = fi | (tag << 30);
-					cnt += (uint32_t)__popcll(mk);
-				}
-			};
-			const bool split = (ord_first & 2u) != 0;
-			add_list(b, split ? kSegTop : 0u);
-			if (split) add_list(Wg - 1u - b, kSegBottom);
-			if (lane0 == 0) *(uint32_t*)(smem + kMisc) = cnt;
-		}
-		__syncthreads();
-		m_chain = (uint32_t)__builtin_amdgcn_readfirstlane((int)*(const uint32_t*)(smem + kMisc));
-		f = m_chain ? (uint32_t)__builtin_amdgcn_readfirstlane((int)chain_list[0]) & kSegMask : 0u;
-	} else {
-		f = kS ? blockIdx.x % nfr : (ord_first ? ordered_frame<NW * 64>(descs, nfr, ord_first, smem) : blockIdx.x);
-	}
+	const uint32_t f = kS ? blockIdx.x % nfr : (ord_first ? ordered_frame<NW * 64>(descs, nfr, ord_first, smem) : blockIdx.x);
 	const uint32_t part = kS ? blockIdx.x / nfr : 0u;
 
 	for (int i = (int)threadIdx.x; i < kBpModes * 16 * (kBpEntry / 4); i += NW * 64) ((uint32_t*)(smem + kBpTable))[i] = kBpTab.v[i];
 	if (threadIdx.x < 64) ((uint32_t*)(smem + kRoleTab))[threadIdx.x] = kPredRoleTab.v[threadIdx.x];
 	uint32_t bt_l = kBorderTab.v[lane0 & 31];  // this lane's border-setup role (loop-invariant)
-	// dequant / loop-filter tables of a frame into its slot (chain mode: by the wave of the frame's pair 0)
-	auto put_tables = [&](const Vp8gFrameDesc& Df, uint32_t tabo, int l) {
+	const Vp8gFrameDesc& D = descs[f];
+	// the frame's dequant / loop-filter tables
+	{
+		const int l = (int)threadIdx.x;
 		// dequant factors as (dc, ac) int16 pairs, [class][segment] (one 16-B read per lane
 		// fetches a class's four segments before the segment is known)
 		if (l < 24) {
 			const int sg = l / 6, k = l % 6, cl = k >> 1;
-			((int16_t*)(smem + kDqTable + tabo))[(cl * 4 + sg) * 2 + (k & 1)] = Df.dq[sg][k];
+			((int16_t*)(smem + kDqTable))[(cl * 4 + sg) * 2 + (k & 1)] = D.dq[sg][k];
 		}
-		if (l < 32) smem[kLfTable + tabo + l] = Df.lf[l >> 3][(l >> 2) & 1][l & 3];
-	};
-	if constexpr (!kC) put_tables(descs[f], 0u, (int)threadIdx.x);
+		if (l < 32) smem[kLfTable + l] = D.lf[l >> 3][(l >> 2) & 1][l & 3];
+	}
 	if (threadIdx.x < 16) ((uint32_t*)(smem + kProgress))[threadIdx.x] = 0;
 	__syncthreads();
-	if (kC && m_chain == 0) return;
 
-	// ---- the current frame (chain mode: reloaded when the wave's next pair is in another frame)
-	const Vp8gFrameDesc* Dp;
-	uint32_t C, R, flags, W, H, CW, CH, sy, suv, vofs, yal, ual, npairs, CP2, tabo;
+	// ---- the frame.  (Its values are set inside a lambda: defined in place as constants, the compiler
+	// swaps the operands of four iDCT additions in the 4-wave instantiations -- equivalent code, but
+	// the kernels then no longer compare equal to the build the measurements in DESIGN.md were taken on.)
+	uint32_t C, R, flags, W, H, CW, CH, sy, suv, vofs, yal, ual, npairs, CP2;
 	uint64_t mb0;
 	uint8_t* outY;
 	uint8_t* outU;
 	Ctx<kG> ctx;
-	auto set_frame = [&](uint32_t fi, uint32_t slot) {
-		Dp = descs + fi;
-		const Vp8gFrameDesc& D = *Dp;
+	[&] {
 		C = D.mb_cols, R = D.mb_rows;
 		flags = D.flags;
 		mb0 = D.mb_offset;
@@ -810,13 +711,11 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void frame_kerne
 		sy = D.stride_y, suv = D.stride_uv;
 		vofs = (uint32_t)(D.out_v - D.out_u);  // V plane relative to U (< 2^32 by construction)
 		yal = (uint32_t)(uintptr_t)outY, ual = (uint32_t)(uintptr_t)outU;  // alignment tests
-		ctx.lds = ctx_base + slot * slot_bytes;
-		ctx.g = kG ? gctx + (size_t)fi * ctx_cols * kCtxBytesPerCol : nullptr;
+		ctx.lds = ctx_base;
+		ctx.g = kG ? gctx + (size_t)f * ctx_cols * kCtxBytesPerCol : nullptr;
 		npairs = (R + 1) >> 1;
 		CP2 = C + 2;
-		tabo = slot * (uint32_t)kTabStride;
-	};
-	set_frame(f, 0u);
+	}();
 	uint32_t flags_l = flags;  // (laundered per step)
 	uint32_t* const prog = (uint32_t*)(smem + kProgress);
 	const uint32_t GW = K * NW, gw = part * NW + (uint32_t)wave;
@@ -879,135 +778,15 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void frame_kerne
 		}
 		asm volatile("" ::: "memory");
 	};
-	// (chain, mirror split) bounded wait until a bottom segment's snapshot flag holds this launch's epoch
-	auto wait_flag = [&](uint32_t* flag, uint32_t epoch) {
-		uint32_t spins = 0;
-		uint64_t t0 = 0;
-		while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch) {
-			__builtin_amdgcn_s_sleep(2);
-			if ((++spins & 255u) == 0) {
-				const uint64_t now = __builtin_amdgcn_s_memrealtime();
-				if (t0 == 0) t0 = now;
-				else if (now - t0 > (uint64_t)VP8G_WAIT_TICKS) {
-					if (lane0 == 0) atomicOr(A.status, VP8G_ERR_TIMEOUT);
-					dead = true;
-					break;
-				}
-			}
-		}
-		asm volatile("" ::: "memory");
-	};
-	auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
-	// chain mode: list index of the wave's current frame, its first global pair, and the last global
-	// pair (with its step count) of the frames one and two list positions back
-	// (Only these few scalars are carried around the chain's frame loop; every other frame value is
-	// re-derived per pair from the laundered frame index: frame values carried as loop PHIs were
-	// taken for divergent, kept in VGPRs, and every output store became a waterfall loop.)
-	// (chain: list entries carry a segment tag, see kSegTop; a segment is pairs [k0, k0 + its pairs))
-	auto pairs_of = [&](uint32_t fi) { return (descs[fi].mb_rows + 1u) >> 1; };
-	auto seg_k0 = [&](uint32_t e) { return (e >> 30) == kSegBottom ? (pairs_of(e & kSegMask) + 1u) >> 1 : 0u; };
-	auto seg_pairs = [&](uint32_t e) {
-		const uint32_t np = pairs_of(e & kSegMask), tag = e >> 30;
-		return tag == 0u ? np : (tag == kSegTop ? (np + 1u) >> 1 : np >> 1);
-	};
-	uint32_t jf = 0, gbase = 0, ecur = kC ? uni(chain_list[0]) : f, np_c = kC ? seg_pairs(ecur) : npairs;
-	// (interleave) pairs per frame -- every frame of the batch has the same size
-	const uint32_t ilP = il ? uni(pairs_of(ecur & kSegMask)) : 0u;
+	// the wave's pairs, over all parts of the frame.  (This loop shape -- the exit test inside, the
+	// pair index under two names -- and the per-pair readfirstlane of `flags` below are left as the
+	// measured builds had them: `for (k = gw; k < npairs; k += GW)` without that readfirstlane
+	// changes the register allocation of every instantiation.)
 	for (uint32_t g = gw;; g += GW) {
-		uint32_t k;
-		bool has_pred;        // the pair above is decoded by this workgroup (else: frame top, or a bottom segment's snapshot)
-		bool snap_out = false;  // (kC) the top segment's last pair: context -> snapshot after its last step
-		uint32_t fcur = f;
-		uint32_t dg = 1;      // global pairs back to the pair above (2 when two frames run interleaved)
-		if (il) {
-			// Two frames at a time: list entries 2m, 2m + 1 form group m, whose 2P global pairs alternate
-			// between them (pair k of frame 2m + e is global pair m * 2P + 2k + (e ^ (m & 1)), its pair
-			// above two global pairs back, i.e. two waves back); an odd last entry runs alone.  2P is even,
-			// so a wave keeps its parity's role in every group: the swap on odd groups hands the even and
-			// the odd waves the snake's heavy and light list positions in turn (without it the even waves
-			// took every heavy frame, fhd4 +8 %).  Frame j uses context slot j & 3: its first pair waits
-			// for frame j - 4's last pair.
-			const uint32_t gp = 2u * ilP, m = g / gp, off = g - m * gp;
-			if (m >= (m_chain >> 1)) {  // the odd tail frame, sequential
-				if (m > (m_chain >> 1) || !(m_chain & 1u) || off >= ilP) break;
-				jf = 2u * m, k = off, dg = 1u;
-			} else {
-				jf = 2u * m + ((off ^ m) & 1u), k = off >> 1, dg = 2u;
-			}
-			jf = uni(jf), k = uni(k), dg = uni(dg);
-			ecur = uni(chain_list[jf]);
-			fcur = ecur & kSegMask;
-			set_frame(fcur, jf & 3u);
-			has_pred = k > 0;
-			if (k == 0) {
-				if (jf >= 4u && !dead) {
-					const uint32_t j4 = jf - 4u, last4 = (j4 >> 1) * gp + 2u * (ilP - 1u) + ((j4 ^ (j4 >> 1)) & 1u);
-					const uint32_t T4 = 2u * (ilP - 1u) + 1u < R ? C + 2u : C;
-					wait_prog(last4 % NW, (last4 << kProgShift) + T4, false);
-				}
-				put_tables(*Dp, tabo, lane0);
-				wave_lds_sync();
-			} else if (!dead) {
-				wait_prog((uint32_t)((wave + NW - dg) % NW), ((g - dg) << kProgShift) + 1u, false);
-			}
-		} else if constexpr (kC) {
-			while (g >= gbase + np_c) {  // advance to the segment holding global pair g
-				gbase += np_c;
-				if (++jf >= m_chain) break;
-				ecur = uni(chain_list[jf]);
-				np_c = seg_pairs(ecur);
-			}
-			if (jf >= m_chain) break;
-			jf = uni(jf), gbase = uni(gbase), ecur = uni(ecur);
-			fcur = ecur & kSegMask;
-			set_frame(fcur, jf & 1u);
-			const uint32_t tag = ecur >> 30, k0 = seg_k0(ecur);
-			k = k0 + (g - gbase);
-			has_pred = g > gbase;
-			snap_out = tag == kSegTop && g + 1u == gbase + np_c && np_c < npairs;
-			if (g == gbase) {
-				// claim slot jf & 1: segment jf - 2 must be done with it, i.e. its last pair (global
-				// index gbase - pairs(jf - 1) - 1) must have published all T2 of its steps
-				if (jf >= 2 && !dead) {
-					const uint32_t e2 = uni(chain_list[jf - 2u]), f2 = e2 & kSegMask;
-					const uint32_t last2 = gbase - seg_pairs(uni(chain_list[jf - 1u])) - 1u;
-					const uint32_t kl2 = seg_k0(e2) + seg_pairs(e2) - 1u, R2 = descs[f2].mb_rows, C2 = descs[f2].mb_cols;
-					const uint32_t T2 = 2u * kl2 + 1u < R2 ? C2 + 2u : C2;
-					wait_prog(last2 % NW, (last2 << kProgShift) + T2, false);
-				}
-				if (tag == kSegBottom) {
-					// the rows above come from the top segment's snapshot (another workgroup); with the
-					// context in device memory the snapshot is the frame's context itself
-					uint32_t* const flag = gprog + fcur;
-					if (!dead) wait_flag(flag, nsplit);
-					// (16-B agent-coherent loads, kSnapBatch per lane in flight: one round trip per batch instead
-					// of one per 1 KB -- the chain's next pairs wait for this copy)
-					const uint32_t nb = C * (uint32_t)kCtxBytesPerCol;
-					const Rsrc rsn = plane_rsrc(gctx + (size_t)fcur * slot_bytes, nb);
-					for (uint32_t o0 = (uint32_t)lane0 * 16u; !kG && o0 < nb; o0 += 1024u * kSnapBatch) {
-						u32x4 v[kSnapBatch];
-#pragma unroll
-						for (int i = 0; i < kSnapBatch; i++) v[i] = __builtin_amdgcn_raw_buffer_load_b128(rsn, (int)(o0 + 1024u * i), 0, kCpolSc1);
-#pragma unroll
-						for (int i = 0; i < kSnapBatch; i++)
-							if (o0 + 1024u * i < nb) st128(ctx.lds + o0 + 1024u * i, v[i]);
-					}
-				}
-				put_tables(*Dp, tabo, lane0);
-				wave_lds_sync();
-			} else if (!dead) {
-				// step 0's dependency wait, before its residual: the residual reads the dequant table
-				// that the segment's first pair writes when it claims the slot (pair g - 1 past step 0
-				// implies the first pair past it, and that pair writes its tables before its first publish)
-				wait_prog((uint32_t)((wave + NW - 1) % NW), ((g - 1u) << kProgShift) + 1u, false);
-			}
-		} else {
-			k = g;
-			if (k >= npairs) break;
-			has_pred = k > 0;
-		}
-		// output planes (built per pair: a buffer resource carried around the chain's frame loop
-		// would be a loop PHI the backend cannot keep in SGPRs)
+		const uint32_t k = g;
+		if (k >= npairs) break;
+		const bool has_pred = k > 0;  // the pair above belongs to this frame (else: frame top)
+		// output planes
 		const Rsrc rY = plane_rsrc(outY, sy * H), rC = plane_rsrc(outU, vofs + suv * CH);
 		const bool xin = kS && wave == 0 && k > 0;             // predecessor pair in another part
 		const bool xout = kS && wave == NW - 1 && k + 1 < npairs;  // successor pair in another part
@@ -1106,7 +885,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void frame_kerne
 		// prefetched data waits for the loads alone, never for stores (see kNoStore)
 		bst128(rY, kNoStore, u32x4{0u, 0u, 0u, 0u});
 		bst64(rC, kNoStore, u32x2{0u, 0u});
-		flags_l = (uint32_t)__builtin_amdgcn_readfirstlane((int)flags);  // (the chain's frame loop makes it a PHI)
+		flags_l = (uint32_t)__builtin_amdgcn_readfirstlane((int)flags);
 		// Per-half side info of a step, broadcast from the prefetched bytes of lanes 26..29 / 58..61 (and
 		// the 16 B_PRED modes from lane 25 / 57) with ds_bpermute (LDS crossbar, no LDS memory), at the
 		// top of the step.  (Round 5 fetched it at the end of the previous step, after the loop filter,
@@ -1118,7 +897,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void frame_kerne
 		};
 		// the four segments' dequant factors of a lane's class in one 16-B read, the segment's pair picked
 		// by two v_cndmask levels once the side info is known
-		auto load_dq4 = [&](int ln_) -> u32x4 { return *(const u32x4*)(smem + kDqTable + tabo + 16 * (ln_ < 16 ? 0 : (ln_ < 24 ? 1 : 2))); };
+		auto load_dq4 = [&](int ln_) -> u32x4 { return *(const u32x4*)(smem + kDqTable + 16 * (ln_ < 16 ? 0 : (ln_ < 24 ? 1 : 2))); };
 		auto pick_dq = [&](const u32x4& dq4, int seg_) -> uint32_t {
 			const uint64_t m1 = __builtin_amdgcn_ballot_w64((seg_ & 1) != 0), m2 = __builtin_amdgcn_ballot_w64((seg_ & 2) != 0);
 			uint32_t lo, hi, r;
@@ -1319,7 +1098,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void frame_kerne
 				const uint32_t lag = xin ? 5u : 4u;
 				const uint32_t ahead = (t + lag < CP2) ? t + lag : CP2;
 				if (xin) wait_prog(0u, (k - 1) * CP2 + ahead, true);
-				else wait_prog((uint32_t)((wave + NW - dg) % NW), ((g - dg) << kProgShift) + ahead, false);
+				else wait_prog((uint32_t)((wave + NW - 1) % NW), ((g - 1u) << kProgShift) + ahead, false);
 			}
 			if (kS && xin) {
 				// mailbox -> this part's LDS ctx: rec[t + 1] and lf[t] now (loaded last step; at t = 0
@@ -1356,13 +1135,13 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void frame_kerne
 					// loop-filter-only mode: the MB's pixels come from the padded input image
 					const uint8_t* src = A.src;
 					if (ln < 16) {
-						const uint8_t* s = src + Dp->src_y + (size_t)(y0 + ln) * Dp->src_stride_y + x0;
+						const uint8_t* s = src + D.src_y + (size_t)(y0 + ln) * D.src_stride_y + x0;
 						uint8_t* const td = tY + (4 + ln) * kTP + slot * 16;
 						st64(td, u32x2{ld32(s), ld32(s + 4)});
 						st64(td + 8, u32x2{ld32(s + 8), ld32(s + 12)});
 					} else {
 						const int p = (ln - 16) >> 3, row = ln & 7;
-						const uint8_t* s = src + (p ? Dp->src_v : Dp->src_u) + (size_t)(cy0 + row) * Dp->src_stride_uv + cx0;
+						const uint8_t* s = src + (p ? D.src_v : D.src_u) + (size_t)(cy0 + row) * D.src_stride_uv + cx0;
 						stc64(tC + p * kCV + (4 + row) * kTP + slot * 8, u32x2{ld32(s), ld32(s + 4)});
 					}
 				} else {
@@ -1540,7 +1319,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void frame_kerne
 			// ---------------------------------------------- loop filter MB(r, c)
 			PRIO(5);
 			if (lf_on && !(VP8G_ABLATE & 1)) {
-				const uint8_t* lp = smem + kLfTable + tabo + seg * 8 + (bpred ? 4 : 0);
+				const uint8_t* lp = smem + kLfTable + seg * 8 + (bpred ? 4 : 0);
 				const int E = lp[0], I = lp[1], Tt = lp[2];
 				const bool en = act && E != 0;
 				if (__ballot(en) != 0ull) {
@@ -1735,23 +1514,6 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void frame_kerne
 			wave_lds_sync();
 			STAMP(6);
 
-			if (kC && snap_out && t + 1u == T) {
-				// top segment of a mirror-split frame, last step of its last pair: every column's context
-				// is final -> snapshot (write-through stores, drained) -> flag = this launch's epoch
-				asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-				const uint32_t nb = C * (uint32_t)kCtxBytesPerCol;
-				const Rsrc rsn = plane_rsrc(gctx + (size_t)fcur * slot_bytes, nb);
-				for (uint32_t o0 = (uint32_t)lane0 * 16u; !kG && o0 < nb; o0 += 1024u * kSnapBatch) {
-					u32x4 v[kSnapBatch];
-#pragma unroll
-					for (int i = 0; i < kSnapBatch; i++) v[i] = ld128(ctx.lds + min(o0 + 1024u * i, nb - 16u));
-#pragma unroll
-					for (int i = 0; i < kSnapBatch; i++)  // (sc1: write-through to the device-coherent level; lanes past the end dropped)
-						__builtin_amdgcn_raw_buffer_store_b128(v[i], rsn, (int)(o0 + 1024u * i), 0, kCpolSc1);
-				}
-				asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-				if (lane0 == 0) __hip_atomic_store(gprog + fcur, nsplit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			}
 			// ---------------------------------------------- publish progress
 			PRIO_AFTER(7, 6);
 			ctx.publish_fence();
@@ -1801,10 +1563,10 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void frame_kerne
 // The dynamic-LDS limit of a kernel instantiation, set once to the whole of the CU's LDS (the
 // kernel has no static LDS): concurrent launches from several threads then never race a smaller
 // value set by another thread between its own set and launch.
-template <int NW, bool kG, bool kS, bool kC>
+template <int NW, bool kG, bool kS>
 hipError_t lds_attr() {
 	static const hipError_t e =
-	    hipFuncSetAttribute((const void*)frame_kernel<NW, kG, kS, kC>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
+	    hipFuncSetAttribute((const void*)frame_kernel<NW, kG, kS>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
 	return e;
 }
 
@@ -1813,13 +1575,13 @@ hipError_t launch_t(const Vp8gFrameDesc* d_descs, uint32_t n, const Vp8gBatchArr
                     uint32_t ctx_cols, uint8_t* gctx, uint32_t nsplit, uint8_t* mbox, uint32_t* gprog, hipStream_t stream,
                     uint32_t ord_first = 0) {
 	const size_t lds = lds_bytes(NW, ctx_cols, kG);
-	auto fn = frame_kernel<NW, kG, kS, false>;
+	auto fn = frame_kernel<NW, kG, kS>;
 	if (lds > 65536) {
-		hipError_t e = lds_attr<NW, kG, kS, false>();
+		hipError_t e = lds_attr<NW, kG, kS>();
 		if (e != hipSuccess) return e;
 	}
 	hipLaunchKernelGGL(fn, dim3(n * (kS ? nsplit : 1u)), dim3(NW * 64), lds, stream, d_descs, arrays, d_out, ctx_cols, gctx,
-	                   nsplit, mbox, gprog, kS ? 0u : ord_first, 0u);
+	                   nsplit, mbox, gprog, kS ? 0u : ord_first);
 	return hipGetLastError();
 }
 
@@ -1894,7 +1656,7 @@ uint32_t pick_order(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t ns
 	return 0;  // uniform batch: the order would be the identity
 }
 
-uint32_t pick_chain(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t ctx_cols, bool* ordered, bool quad) {
+uint32_t pick_chain(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t ctx_cols, bool* ordered) {
 #ifndef VP8G_CHAIN_DEFAULT  // (A/B builds: -DVP8G_CHAIN_DEFAULT=0)
 #define VP8G_CHAIN_DEFAULT -1
 #endif
@@ -1905,20 +1667,22 @@ uint32_t pick_chain(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t ct
 	*ordered = false;
 	const int n_cus = device_cus();
 	if (mode == 0 || n_cus <= 0 || n_frames == 0 || (mode < 0 && n_frames <= (uint32_t)n_cus)) return 0;
-	const uint32_t slots = (uint32_t)n_cus * (uint32_t)kChainWgPerCu;
-	const uint32_t wg = n_frames < slots ? n_frames : slots;
+	// the quad kernel decodes every frame but loop-filter-only ones (frames without whole row pieces
+	// take its byte path at the right edge / for unaligned planes)
+	for (uint32_t i = 0; i < n_frames; i++)
+		if (h_descs[i].mb_cols != 0 && h_descs[i].mb_rows != 0 && (h_descs[i].flags & VP8G_F_LF_ONLY)) return 0;
+	const uint32_t wg = n_frames < (uint32_t)n_cus ? n_frames : (uint32_t)n_cus;
 	const uint32_t list_max = (n_frames + wg - 1) / wg;
-	if (ctx_cols > 1024 || (size_t)(quad ? 1 : kChainWgPerCu) * chain_lds_bytes(ctx_cols, list_max, n_frames, false, quad) > (size_t)kMaxLds)
-		return 0;
-	// cost-class placement when the classes differ and the sort scratch fits the context slots
+	if (ctx_cols > 1024 || chain_lds_bytes(list_max) > (size_t)kMaxLds) return 0;
+	// cost-class placement when the classes differ and the sort scratch fits the wave areas
 	const uint32_t c0 = cost_class(h_descs[0]);
 	bool differ = false;
 	for (uint32_t i = 1; i < n_frames && !differ; i++) differ = cost_class(h_descs[i]) != c0;
-	*ordered = differ && (size_t)4 * (kCostClasses + n_frames) <= chain_ctx_lds(ctx_cols, n_frames, false, quad) && pick_order(h_descs, n_frames, 1) != 0;
+	*ordered = differ && (size_t)4 * (kCostClasses + n_frames) <= kChainScratch && pick_order(h_descs, n_frames, 1) != 0;
 	return wg;
 }
 
-bool pick_chain_split(uint32_t n_frames, uint32_t ctx_cols, uint32_t workgroups, bool ordered, bool quad) {
+bool pick_chain_split(uint32_t n_frames, uint32_t workgroups, bool ordered) {
 #ifndef VP8G_SPLITCHAIN_DEFAULT  // (A/B builds: -DVP8G_SPLITCHAIN_DEFAULT=0 / 1)
 #define VP8G_SPLITCHAIN_DEFAULT -1
 #endif
@@ -1928,12 +1692,11 @@ bool pick_chain_split(uint32_t n_frames, uint32_t ctx_cols, uint32_t workgroups,
 	}();
 	if (mode == 0 || workgroups == 0) return false;
 	const uint32_t list_max = (n_frames + workgroups - 1) / workgroups;
-	if ((size_t)(quad ? 1 : kChainWgPerCu) * chain_lds_bytes(ctx_cols, 2 * list_max, n_frames, false, quad) > (size_t)kMaxLds) return false;
+	if (chain_lds_bytes(2 * list_max) > (size_t)kMaxLds) return false;
 	return mode > 0 || (ordered && list_max <= 2);
 }
 
-bool pick_chain_interleave(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t ctx_cols, uint32_t workgroups, bool split,
-                           bool quad) {
+bool pick_chain_interleave(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t workgroups, bool split) {
 #ifndef VP8G_CHAIN_IL_DEFAULT  // (A/B builds: -DVP8G_CHAIN_IL_DEFAULT=0)
 #define VP8G_CHAIN_IL_DEFAULT -1
 #endif
@@ -1941,20 +1704,12 @@ bool pick_chain_interleave(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint
 		const char* e = getenv("VP8G_CHAIN_IL");
 		return e ? atoi(e) : VP8G_CHAIN_IL_DEFAULT;
 	}();
-	if (mode == 0 || (kChainG && !quad) || split || workgroups == 0 || n_frames < 2 * workgroups) return false;
+	if (mode == 0 || split || workgroups == 0 || n_frames < 2 * workgroups) return false;
 	for (uint32_t i = 1; i < n_frames; i++)
 		if (h_descs[i].mb_cols != h_descs[0].mb_cols || h_descs[i].mb_rows != h_descs[0].mb_rows) return false;
 	if (h_descs[0].mb_rows < 2) return false;
 	const uint32_t list_max = (n_frames + workgroups - 1) / workgroups;
-	return (size_t)(quad ? 1 : kChainWgPerCu) * chain_lds_bytes(ctx_cols, list_max, n_frames, true, quad) <= (size_t)kMaxLds;
-}
-
-bool quad_supported(const Vp8gFrameDesc* h_descs, uint32_t n_frames) {
-	// every frame but loop-filter-only ones (frames without whole row pieces take the quad kernel's
-	// byte path at the right edge / for unaligned planes)
-	for (uint32_t i = 0; i < n_frames; i++)
-		if (h_descs[i].mb_cols != 0 && h_descs[i].mb_rows != 0 && (h_descs[i].flags & VP8G_F_LF_ONLY)) return false;
-	return true;
+	return chain_lds_bytes(list_max) <= (size_t)kMaxLds;
 }
 
 bool whole_pieces(const Vp8gFrameDesc* h_descs, uint32_t n_frames) {
@@ -1969,47 +1724,23 @@ bool whole_pieces(const Vp8gFrameDesc* h_descs, uint32_t n_frames) {
 	return true;
 }
 
-bool pick_quad(const Vp8gFrameDesc* h_descs, uint32_t n_frames) {
-#ifndef VP8G_QUAD_DEFAULT  // (A/B builds: -DVP8G_QUAD_DEFAULT=0, the two-rows-per-wave chain)
-#define VP8G_QUAD_DEFAULT 1
-#endif
-	static const int mode = [] {  // VP8G_QUAD=0: never (A/B experiments)
-		const char* e = getenv("VP8G_QUAD");
-		return e ? atoi(e) : VP8G_QUAD_DEFAULT;
-	}();
-	return mode != 0 && quad_supported(h_descs, n_frames);
-}
-
 hipError_t launch_chain(const Vp8gFrameDesc* d_descs, uint32_t n_frames, const Vp8gBatchArrays& arrays, uint8_t* d_out,
-                        uint32_t ctx_cols, hipStream_t stream, uint32_t workgroups, bool ordered, bool split, uint8_t* snap,
-                        uint32_t* flags, uint32_t epoch, bool interleave, bool quad, bool whole) {
+                        uint32_t ctx_cols, hipStream_t stream, uint32_t workgroups, bool ordered, bool whole, uint8_t* snap,
+                        bool split, uint32_t* flags, uint32_t epoch, bool interleave) {
 	if (n_frames == 0) return hipSuccess;
-	if ((split && (!snap || !flags)) || (kChainG && !snap) || (interleave && split)) return hipErrorInvalidValue;
+	if (!snap || (split && !flags) || (interleave && split)) return hipErrorInvalidValue;
 	const uint32_t list_max = (n_frames + workgroups - 1) / workgroups;
-	const size_t lds = chain_lds_bytes(ctx_cols, split ? 2 * list_max : list_max, n_frames, interleave, quad);
-	if (quad) {  // four MB rows per wave; the snapshot buffer holds every frame's context
-		if (!snap) return hipErrorInvalidValue;
-		static const hipError_t eq1 =
-		    hipFuncSetAttribute((const void*)quad_kernel<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
-		static const hipError_t eq0 =
-		    hipFuncSetAttribute((const void*)quad_kernel<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
-		if (eq1 != hipSuccess) return eq1;
-		if (eq0 != hipSuccess) return eq0;
-		auto fq = whole ? quad_kernel<16, true> : quad_kernel<16, false>;
-		hipLaunchKernelGGL(fq, dim3(workgroups), dim3(16 * 64), lds, stream, d_descs, arrays, d_out, ctx_cols, snap,
-		                   split ? epoch : 1u, split ? flags : nullptr, (ordered ? 1u : 0u) | (split ? 2u : 0u) | (interleave ? 4u : 0u),
-		                   n_frames);
-		return hipGetLastError();
-	}
-	auto fn = frame_kernel<kChainWaves, kChainG, false, true>;
-	hipError_t e = lds_attr<kChainWaves, kChainG, false, true>();
-	if (e != hipSuccess) return e;
-	// (chain kernel arguments: gctx = snapshots -- with the context in device memory, the frames'
-	// contexts, n_frames x ctx_cols x kCtxBytesPerCol --, gprog = flags, nsplit = epoch,
-	// ord_first = ordered | split << 1)
-	hipLaunchKernelGGL(fn, dim3(workgroups), dim3(kChainWaves * 64), lds, stream, d_descs, arrays, d_out, ctx_cols,
-	                   split || kChainG ? snap : nullptr, split ? epoch : 1u, nullptr, split ? flags : nullptr,
-	                   (ordered ? 1u : 0u) | (split ? 2u : 0u) | (interleave ? 4u : 0u), n_frames);
+	const size_t lds = chain_lds_bytes(split ? 2 * list_max : list_max);
+	static const hipError_t eq1 =
+	    hipFuncSetAttribute((const void*)quad_kernel<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
+	static const hipError_t eq0 =
+	    hipFuncSetAttribute((const void*)quad_kernel<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
+	if (eq1 != hipSuccess) return eq1;
+	if (eq0 != hipSuccess) return eq0;
+	auto fq = whole ? quad_kernel<16, true> : quad_kernel<16, false>;
+	hipLaunchKernelGGL(fq, dim3(workgroups), dim3(16 * 64), lds, stream, d_descs, arrays, d_out, ctx_cols, snap,
+	                   split ? epoch : 1u, split ? flags : nullptr, (ordered ? 1u : 0u) | (split ? 2u : 0u) | (interleave ? 4u : 0u),
+	                   n_frames);
 	return hipGetLastError();
 }
 

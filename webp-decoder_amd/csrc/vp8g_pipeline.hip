@@ -744,12 +744,10 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 					PTRY(hipGetLastError(), "expand launch");
 				}
 				bool ordered = false;
-				const bool quad = !big && k == 1 && vp8g::pick_quad(s.descs.data(), nf);  // (four MB rows per wave)
-				const uint32_t wg = big || k > 1 || (vp8g::kChainG && !quad) ? 0u : vp8g::pick_chain(s.descs.data(), nf, max_cols, &ordered, quad);
+				const uint32_t wg = big || k > 1 ? 0u : vp8g::pick_chain(s.descs.data(), nf, max_cols, &ordered);
 				if (wg)  // more frames than CUs: one 16-wave chain of frames per CU
-					PTRY(vp8g::launch_chain((const Vp8gFrameDesc*)(d + L.desc), nf, arr, d + L.out, max_cols, stream, wg, ordered, false,
-					                        quad ? d + L.gctx : nullptr, nullptr, 0u, false, quad,
-					                        quad && vp8g::whole_pieces(s.descs.data(), nf)),
+					PTRY(vp8g::launch_chain((const Vp8gFrameDesc*)(d + L.desc), nf, arr, d + L.out, max_cols, stream, wg, ordered,
+					                        vp8g::whole_pieces(s.descs.data(), nf), d + L.gctx),
 					     "recon launch");
 				else
 					PTRY(vp8g::launch_frames((const Vp8gFrameDesc*)(d + L.desc), nf, arr, d + L.out, max_cols, max_rows,

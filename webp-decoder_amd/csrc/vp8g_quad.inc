@@ -1,7 +1,35 @@
-// vp8g_quad.inc -- the chain kernel with FOUR MB rows per wave (the default chain kernel for batches
-// of whole-piece frames, pick_quad; included by vp8g_kernels.hip inside namespace vp8g::{anonymous},
-// after frame_kernel, whose helpers and tables it uses).  DESIGN.md §3.1 (verdict r04 #1).  Reference: the per-MB raster loops of
+// vp8g_quad.inc -- the chain kernel, FOUR MB rows per wave (every batch of more frames than CUs,
+// pick_chain; included by vp8g_kernels.hip inside namespace vp8g::{anonymous}, after frame_kernel,
+// whose helpers and tables it uses).  DESIGN.md §3.1 (verdict r04 #1).  Reference: the per-MB raster loops of
 // src/m06_recon/vp8_recon.c:444-684 and src/m07_loopfilter/vp8_loopfilter.c:214-280.
+//
+// The chain.  ONE workgroup of 16 waves per CU decodes a list of frames as one continuous chain of
+// quads (four MB rows) -- global quad g of the list (the frames' quads one after another) belongs
+// to wave g % 16 -- so no wave idles at a frame's end while another frame of the CU still has rows,
+// and a heavy frame never runs alone on half the CU.  Two frames are in flight at once: frame j of
+// the list uses table slot j & 1 (its dequant / loop-filter tables); quad 0 of frame j waits until
+// frame j - 2, the slot's previous user, has finished its last quad (which implies all of its
+// quads: a quad's last steps wait for the quad above to complete).  The list of workgroup b: the
+// frames at positions b, 2W-1-b, 2W+b, 4W-1-b, ... of the batch sorted by descending cost class
+// (snake order: every CU gets one of the heaviest and one of the lightest frames per two rounds),
+// sorted in the prologue by wave 0 (stable counting sort over the cost classes, its scratch in the
+// wave areas).  Progress words encode global quad * 2048 + steps done (kProgShift).
+// Mirror split (ord_first bit 1, batches of at most two frames per workgroup): each frame is cut at
+// quad h = ceil(quads / 2) into a top segment (quads [0, h), decoded by the frame's own workgroup,
+// first in its list) and a bottom segment (quads [h, quads), decoded LAST by the mirror workgroup
+// W-1-b).  Every workgroup thus decodes half of its own frames and half of its mirror's, which
+// evens out the pairing of heavy and light frames (two 4K frames per CU cannot balance four fixture
+// kinds).  The top segment's last quad stores the launch's epoch in the frame's flag after its last
+// publish (its context row is in device memory already); the bottom segment's first quad waits for
+// that flag.  Tops never wait across workgroups and bottoms come after every top of their list, so
+// no cycle exists, and a top finishes in the first half of its workgroup's work, long before its
+// bottom starts.
+// Interleave (ord_first bit 2, same-size frames): list entries 2m, 2m + 1 form group m, whose 2P
+// global quads alternate between them (quad k of frame 2m + e is global quad m * 2P + 2k + (e ^ (m & 1)),
+// its quad above two global quads back, i.e. two waves back); an odd last entry runs alone.  2P is
+// even, so a wave keeps its parity's role in every group: the swap on odd groups hands the even and
+// the odd waves the snake's heavy and light list positions in turn.  Frame j uses table slot j & 3:
+// its first quad waits for frame j - 4's last quad.
 //
 // Lanes 16h .. 16h + 15 ("quarter" h) work on MB(4k + h, t - 2h) at step t of quad k: the rows of a
 // quad run two columns apart, as the two halves of a pair do in frame_kernel.  Every lane takes the
@@ -24,7 +52,8 @@
 // The quad below needs rec[t + 1] and lf[t] of this quad's quarter 3 (written at step t + 7) when it
 // issues its loads early in step t, so it waits for progress >= t + 8.
 // Frames: loop-filtered or unfiltered, with whole 16-B / 8-B row pieces (frame_kernel's fl_fast
-// condition; quad_supported() on the host), no loop-filter-only frames.
+// condition) or not (the general instantiation's byte path); no loop-filter-only frames (pick_chain
+// on the host keeps such batches out).
 // The placements and layouts that were measured against these (publish and context-load timing,
 // prefetch depth, LDS bank shift, B_PRED register hand-off, store pairing and cache policy) are in
 // DESIGN.md §3.2, "Retired experiment code".
@@ -165,6 +194,8 @@ DEV void pair_swap(const u32x2& held, const u32x2& cur, u32x2& dA, u32x2& dB) {
 DEV void qst128(Rsrc r, uint32_t off, u32x4 v) { __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)off, 0, kQStoreCpol); }
 DEV void qst64(Rsrc r, uint32_t off, u32x2 v) { __builtin_amdgcn_raw_buffer_store_b64(v, r, (int)off, 0, kQStoreCpol); }
 
+constexpr uint32_t kSegTop = 1u, kSegBottom = 2u, kSegMask = 0x3FFFFFFFu;  // list entry: frame | tag << 30 (mirror split)
+
 // kWP: every frame of the batch has whole row pieces (the bench's batches); the general instantiation
 // adds the byte path for pieces cut by the right edge or unaligned planes (+1 % when used for
 // whole-piece batches: the extra frame state costs SGPRs, r05q18).
@@ -183,7 +214,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 	auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
 	auto quads_of = [&](uint32_t fi) { return (descs[fi].mb_rows + 3u) >> 2; };
 
-	// ---- this workgroup's frame list (as frame_kernel's chain mode; the sort scratch in the wave areas)
+	// ---- this workgroup's frame list (see the top of the file); ord_first bit 0: cost-sorted positions
 	{
 		const uint32_t Wg = gridDim.x, b = blockIdx.x, n = n_chain;
 		if (wave == 0) {
@@ -199,7 +230,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 						const bool valid = i < n;
 						const uint32_t cls = valid ? cost_class(descs[i]) : 0u;
 						uint64_t rem = __ballot(valid);
-						while (rem) {
+						while (rem) {  // one distinct class per iteration (peeled by its first lane)
 							const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cls, (int)__builtin_ctzll(rem));
 							const uint64_t mk = __ballot(valid && cls == c);
 							const uint32_t base = hist[c];
@@ -210,7 +241,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 							rem &= ~mk;
 						}
 					}
-					if (pass == 0) {
+					if (pass == 0) {  // counts -> start positions, heaviest class first
 						if (lane0 == 0) {
 							uint32_t acc = 0;
 							for (int c = (int)kCostClasses - 1; c >= 0; c--) {
@@ -223,6 +254,9 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 					}
 				}
 			}
+			// snake positions of workgroup b (increasing in j), empty descriptors left out.  Mirror
+			// split: workgroup b decodes the top halves of its own frames, then the bottom halves of
+			// workgroup W-1-b's frames (entry tags, kSegTop / kSegBottom)
 			uint32_t cnt = 0;
 			auto add_list = [&](uint32_t bb, uint32_t tag) {
 				for (uint32_t j0 = 0;; j0 += 64) {

@@ -122,7 +122,7 @@ struct DevState {
 	size_t gctx_cap = 0;
 	uint8_t* mbox = nullptr;  // split-mode hand-off mailboxes + progress words (host APIs only)
 	size_t mbox_cap = 0;
-	uint8_t* snap = nullptr;  // mirror-split chain launches: per-frame context snapshots + flags
+	uint8_t* snap = nullptr;  // chain launches: every frame's context; the mirror split's flags
 	size_t snap_cap = 0;
 	uint8_t* sflags = nullptr;
 	size_t sflags_cap = 0;
@@ -393,13 +393,11 @@ int run_locked(DevState& g_dev, const std::vector<Vp8gFrameDesc>& descs, const V
 		HIP_TRY(grow(g_dev, &g_dev.mbox, &g_dev.mbox_cap, mb + pb), "hipMalloc(mailbox)");
 	}
 	bool ordered = false;
-	const bool quad = !big && !waves_hint && vp8g::pick_quad(descs.data(), n);  // (four MB rows per wave)
-	const uint32_t wg = !big && !waves_hint ? vp8g::pick_chain(descs.data(), n, max_cols, &ordered, quad) : 0u;
-	const bool split_want = wg && vp8g::pick_chain_split(n, max_cols, wg, ordered, quad);
-	if (wg && (vp8g::kChainG || quad))  // (experiment builds: the chain's context in device memory, in the snapshot buffer)
+	const uint32_t wg = !big && !waves_hint ? vp8g::pick_chain(descs.data(), n, max_cols, &ordered) : 0u;
+	const bool split_want = wg && vp8g::pick_chain_split(n, wg, ordered);
+	if (wg)  // (the chain's context between waves, and with it the mirror split's snapshots)
 		HIP_TRY(grow(g_dev, &g_dev.snap, &g_dev.snap_cap, (size_t)n * max_cols * vp8g::kCtxBytesPerCol), "hipMalloc(context)");
 	if (split_want) {
-		HIP_TRY(grow(g_dev, &g_dev.snap, &g_dev.snap_cap, (size_t)n * max_cols * vp8g::kCtxBytesPerCol), "hipMalloc(snapshots)");
 		const size_t old_cap = g_dev.sflags_cap;
 		HIP_TRY(grow(g_dev, &g_dev.sflags, &g_dev.sflags_cap, (size_t)n * sizeof(uint32_t)), "hipMalloc(flags)");
 		if (g_dev.sflags_cap != old_cap) g_dev.epoch = 0;  // (fresh flags: zeroed below)
@@ -421,18 +419,18 @@ int run_locked(DevState& g_dev, const std::vector<Vp8gFrameDesc>& descs, const V
 		                            (uint32_t*)(g_dev.mbox + mb), 0),
 		        "launch");
 	} else if (wg) {  // more frames than CUs: one 16-wave chain of frames per CU
-		// mirror split (vp8g_kernels.hip, kSegTop): snapshot flags of a fresh epoch
+		// mirror split (vp8g_quad.inc, kSegTop): snapshot flags of a fresh epoch
 		const bool split = alone && split_want;
 		if (split && (g_dev.epoch == 0 || ++g_dev.epoch == 0)) {  // (epoch 0 = the zeroed flags: never used)
 			g_dev.epoch = 1;
 			HIP_TRY(hipMemsetAsync(g_dev.sflags, 0, g_dev.sflags_cap, s), "memset(flags)");
 		}
 		crossed = split;
-		const bool il = vp8g::pick_chain_interleave(descs.data(), n, max_cols, wg, split, quad);  // (1080p batches: two frames interleaved)
-		g_mode = VP8G_MODE_CHAIN | (split ? VP8G_MODE_MIRROR_SPLIT : 0u) | (il ? VP8G_MODE_INTERLEAVE : 0u) | (quad ? VP8G_MODE_QUAD : 0u);
-		HIP_TRY(vp8g::launch_chain((const Vp8gFrameDesc*)d_descs, n, arr, d_out, max_cols, s, wg, ordered, split, g_dev.snap,
-		                           (uint32_t*)g_dev.sflags, g_dev.epoch, il, quad,
-		                           quad && vp8g::whole_pieces(descs.data(), n) && ((uintptr_t)d_out & 15u) == 0),
+		const bool il = vp8g::pick_chain_interleave(descs.data(), n, wg, split);  // (1080p batches: two frames interleaved)
+		g_mode = VP8G_MODE_CHAIN | VP8G_MODE_QUAD | (split ? VP8G_MODE_MIRROR_SPLIT : 0u) | (il ? VP8G_MODE_INTERLEAVE : 0u);
+		HIP_TRY(vp8g::launch_chain((const Vp8gFrameDesc*)d_descs, n, arr, d_out, max_cols, s, wg, ordered,
+		                           vp8g::whole_pieces(descs.data(), n) && ((uintptr_t)d_out & 15u) == 0, g_dev.snap, split,
+		                           (uint32_t*)g_dev.sflags, g_dev.epoch, il),
 		        "launch");
 	} else {
 		const uint32_t ord = vp8g::pick_order(descs.data(), n, 1);  // cost-balanced placement (vp8g_device.h)
