@@ -516,6 +516,89 @@ int vp8g_decode_webp_batch_tensor(const ByteSpan* files, uint32_t n, int filtere
                                   const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, void* d_out,
                                   int* status);
 
+/* ---- Alpha of extended (VP8X) files --------------------------------------- */
+
+/* The ALPH chunk entropy-decodes on the host (vp8f_alpha_decode, host/vp8_front.h) into a plane of
+ * residuals; turning those into alpha is a prediction that runs on the device:
+ *   alpha(x, y) = (pred + residual(x, y)) & 255, with pred = 0 at (0, 0), the left neighbour on the top
+ *   row and the neighbour above in the left column for every filter != 0, and otherwise
+ *   filter 1 left, 2 above, 3 clip255(left + above - aboveleft); filter 0: alpha = residual.
+ * Per-plane descriptor (built by vp8g_make_alpha_desc).  48 bytes. */
+typedef struct {
+	uint64_t src;                    /* byte offset of the residual plane in the source buffer */
+	uint64_t dst;                    /* byte offset of the alpha plane in the output buffer */
+	uint32_t width, height;          /* 1 .. 16383 */
+	uint32_t src_stride, dst_stride; /* >= width */
+	uint32_t filter;                 /* 0 .. 3 */
+	uint32_t task0, ntasks;          /* this plane's workgroup tasks in the launch (one per plane) */
+	uint32_t reserved;
+} Vp8gAlphaDesc;
+
+/* 0, or -1 + EINVAL (NULL, a size of 0 or beyond 16383, filter > 3, a stride below the width). */
+int vp8g_make_alpha_desc(uint32_t width, uint32_t height, uint32_t filter, uint64_t src, uint32_t src_stride, uint64_t dst,
+                         uint32_t dst_stride, uint32_t task0, Vp8gAlphaDesc* out);
+
+/* Un-predict n planes of mixed sizes and filters in one launch on `hip_stream`.  h_descs / d_descs:
+ * host and device copies of the descriptors (tasks numbered plane by plane).  Writes only each plane's
+ * own width x height bytes.  Asynchronous; 0 or -1 + errno (EINVAL: NULL pointer, n = 0, an invalid or
+ * inconsistent descriptor; EIO on a launch failure).  No workgroup waits on another and nothing
+ * spins on memory: the kernel has no timeout path. */
+int vp8g_alpha_unfilter_batch_device(const Vp8gAlphaDesc* h_descs, const Vp8gAlphaDesc* d_descs, uint32_t n,
+                                     const uint8_t* d_src, uint8_t* d_dst, void* hip_stream);
+
+/* vp8g_make_scale_desc for ONE plane scaled as luma -- the A plane: libwebp rescales it with the luma
+ * arithmetic, the same window (origin snapped to even) and the same target.  p[0] is that plane (src:
+ * its byte offset, stride >= width; output tight at dst_offset); p[1] and p[2] carry no tasks.
+ * vp8g_scale_batch_device takes such descriptors beside three-plane ones.  0, or -1 + EINVAL. */
+int vp8g_make_scale_desc_plane(uint32_t width, uint32_t height, uint64_t src, uint32_t stride, const Vp8gScaleOpt* opt,
+                               uint64_t dst_offset, uint32_t task0, Vp8gScaleDesc* out);
+
+/* The alpha plane of one image of the 4-channel tensor kernel: src_a = byte offset of the plane in
+ * the source buffer (stride_a >= width), or VP8G_T_OPAQUE for a picture without alpha. */
+typedef struct {
+	uint64_t src_a;
+	uint32_t stride_a;
+	uint32_t reserved;
+} Vp8gTensorAlpha;
+#define VP8G_T_OPAQUE UINT64_MAX
+
+/* vp8g_tensor_slot_size for the 4-channel tensor: 4 * width * height * element size. */
+uint64_t vp8g_tensor_slot_size_a(const Vp8gTensorOpt* opt);
+
+/* vp8g_tensor_batch_device with alpha as a fourth channel: [N,H,W,4] / [N,4,H,W], channels R,G,B,A
+ * (B,G,R,A with VP8G_T_BGR); descriptors from vp8g_make_tensor_desc, whose dst offset is then the start
+ * of the picture's 4-channel slot (slot i of a dense tensor = i * vp8g_tensor_slot_size_a()).  The
+ * three colour channels are exactly those of the 3-channel kernel (scale and bias have three
+ * entries and never touch A).  A for VP8G_T_U8 is the alpha byte; for VP8G_T_F32 the float nearest to
+ * a / 255 (an IEEE division: 255 -> 1.0f exactly); for F16 / BF16 that float rounded once to
+ * nearest-even.  Not premultiplied.  h_alpha / d_alpha: host and device copies of the n alpha entries
+ * (stride_a >= width unless opaque, else EINVAL). */
+int vp8g_tensor_batch_device_a(const Vp8gTensorDesc* h_descs, const Vp8gTensorDesc* d_descs, const Vp8gTensorAlpha* h_alpha,
+                               const Vp8gTensorAlpha* d_alpha, uint32_t n, const Vp8gTensorOpt* opt, const uint8_t* d_src,
+                               void* d_dst, void* hip_stream);
+
+/* vp8g_decode_webp_batch_ex / _scaled (opts NULL, n_opts 0: no scaling) with the extended container in
+ * front: simple files as before, VP8X files too (ICC / EXIF / XMP and unknown chunks skipped); alpha is
+ * ignored, as `dwebp -yuv` ignores it.  A file the extended parser refuses gets its errno in status[i]
+ * (ENOTSUP: animation, a lossless main image). */
+int vp8g_decode_webp_batch_x(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                             const Vp8gScaleOpt* opts, uint32_t n_opts, Yuv420Image* outs, int* status);
+
+/* vp8g_decode_webp_batch_tensor with the extended container in front.  xflags (other bits EINVAL):
+ *   0              the 3-channel tensor, alpha ignored;
+ *   VP8G_X_ALPHA   the 4-channel tensor (n slots of vp8g_tensor_slot_size_a bytes, as vp8g_tensor_batch_device_a
+ *                  writes them).  A worker thread entropy-decodes a frame's ALPH chunk (vp8f_alpha_decode, in
+ *                  both m05 modes); the residual plane is uploaded into the chunk buffer, un-predicted, cropped /
+ *                  rescaled with the frame's opts as luma, and read by the tensor kernel, all on the chunk's
+ *                  stream.  A frame without alpha gets opaque A.  A frame whose ALPH does not decode gets
+ *                  status[i] = EINVAL and a zero slot, as libwebp fails the whole picture; the others still
+ *                  decode.  VP8G_SCALE_DWEBP_FILTER and the loop filter do not concern A.  Alpha planes count
+ *                  against the chunk memory budget; vp8g_plan_batch does not price ALPH bytes. */
+#define VP8G_X_ALPHA 1u
+int vp8g_decode_webp_batch_tensor_x(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                    const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, uint32_t xflags,
+                                    void* d_out, int* status);
+
 /* Name of the last HIP error seen by this library in the calling thread ("" if none). */
 const char* vp8g_last_error(void);
 

@@ -158,6 +158,9 @@ struct Feed {
 	std::vector<uint8_t> dev;       // frame i: m05 on the device (workers fill tj[i], else pk[i])
 	std::vector<uint32_t> order;    // position -> frame index
 	unsigned fflags = 0;  // front-end flags (VP8F_MULTI_PARTITION)
+	bool alpha = false;             // also entropy-decode the ALPH chunk (VP8G_X_ALPHA): ares[i] = the residual plane
+	std::vector<uint8_t*> ares;     // (malloc; NULL = no alpha; freed with the frame's host data)
+	std::vector<uint32_t> afilter;
 	std::vector<Vp8gPackedFrame> pk;
 	std::vector<TokJob> tj;
 	std::vector<int> err;
@@ -187,6 +190,20 @@ struct Feed {
 					e = errno ? errno : EINVAL;
 			} else if (vp8f_decode_packed_memory(files[i].data, files[i].size, &pk[i], &stage, fflags) != 0)
 				e = errno ? errno : EINVAL;
+			if (alpha && e == 0) {  // a picture whose ALPH does not decode fails as a whole, as in libwebp
+				WebPContainerX x;
+				const Vp8KeyFrameHeader& kf = dev[i] ? tj[i].kf : pk[i].kf;
+				if (webp_parse_extended(files[i], &x) == 0 && x.alph_chunk_offset) {
+					ares[i] = (uint8_t*)malloc((size_t)kf.width * kf.height);
+					if (!ares[i]) e = ENOMEM;
+					else if (vp8f_alpha_decode(files[i].data + x.alph_chunk_offset, x.alph_chunk_size, kf.width, kf.height, ares[i],
+					                           &afilter[i], nullptr) != 0) {
+						e = errno ? errno : EINVAL;
+						free(ares[i]);
+						ares[i] = nullptr;
+					}
+				}
+			}
 			{
 				std::lock_guard<std::mutex> lk(mu);
 				err[i] = e;
@@ -231,6 +248,9 @@ struct Slot {
 	std::vector<Vp8gFrameDesc> descs;
 	std::vector<Vp8gScaleDesc> sdescs;  // scaled decode: one per frame of the chunk
 	std::vector<Vp8gTensorDesc> tdescs;  // tensor sink: one per frame of the chunk
+	std::vector<Vp8gAlphaDesc> adescs;   // alpha sink: the chunk's frames that have an ALPH plane
+	std::vector<Vp8gScaleDesc> asdescs;  //   their alpha planes through the rescaler
+	std::vector<Vp8gTensorAlpha> talpha; //   one per tensor descriptor
 	std::vector<Vp8gTokFrame> jobs;  // device m05
 	uint32_t status = 0;
 	std::vector<D2H> d2h;          // the chunk's downloads (issued by a Copier)
@@ -309,7 +329,7 @@ struct Copier {
 
 struct ChunkLayout {
 	uint64_t ym, uvm, seg, hasc, bm, masks, mboff, vals, cy, cu, cv, cy2, bits, jobs, desc, status, gctx, mbox, gprog, out,
-	    sdesc, sout, tdesc, total;
+	    sdesc, sout, tdesc, ares, aout, asout, adesc, asdesc, talpha, total;
 };
 
 hipError_t grow(Slot& s, size_t need) {
@@ -337,7 +357,7 @@ constexpr double kD2HNsPerByte = 0.085;    // download into fresh pageable image
 // (rates measured on the box: tools/e2e_probe.py chunk traces, tools/hybrid_sweep.py; profiles/r02_hybrid.json)
 // download = false (the tensor sink: the pictures stay on the device) prices no download.
 void plan_frames(const ByteSpan* files, uint32_t n, bool tok, uint32_t threads, std::vector<uint8_t>& dev,
-                 std::vector<uint32_t>& order, bool download = true) {
+                 std::vector<uint32_t>& order, bool download = true, bool extended = false) {
 	dev.assign(n, tok ? 1 : 0);
 	order.resize(n);
 	for (uint32_t i = 0; i < n; i++) order[i] = i;
@@ -351,8 +371,11 @@ void plan_frames(const ByteSpan* files, uint32_t n, bool tok, uint32_t threads, 
 	std::vector<double> outb(n, 0.0);  // I420 bytes (0 for a file whose header does not parse: it fails anyway)
 	for (uint32_t i = 0; i < n; i++) {
 		WebPContainer c;
+		WebPContainerX x;
 		Vp8KeyFrameHeader kf;
-		if (files[i].data && webp_parse_simple_lossy(files[i], &c) == 0 &&
+		if (extended && files[i].data && webp_parse_extended(files[i], &x) == 0 && x.extended)  // (the canvas is the frame size)
+			outb[i] = (double)vp8g_i420_size(x.canvas_width, x.canvas_height);
+		else if (files[i].data && webp_parse_simple_lossy(files[i], &c) == 0 &&
 		    vp8_parse_keyframe_header(ByteSpan{files[i].data + c.vp8_chunk_offset, c.vp8_chunk_size}, &kf) == 0)
 			outb[i] = (double)vp8g_i420_size(kf.width, kf.height);
 	}
@@ -406,9 +429,10 @@ VP8G_API int vp8g_plan_batch(const ByteSpan* files, uint32_t n, uint32_t threads
 // (vp8g_tensor.hip) on the chunk's stream, and only the chunk's status word is downloaded.
 static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
                         const Vp8gScaleOpt* opts, uint32_t n_opts, Yuv420Image* outs, int* status,
-                        const Vp8gTensorOpt* topt = nullptr, uint8_t* d_tensor = nullptr) {
-	const uint64_t tslot = topt ? vp8g_tensor_slot_size(topt) : 0;
-	if (!files || (topt ? !d_tensor || !tslot || outs : !outs) || n == 0 ||
+                        const Vp8gTensorOpt* topt = nullptr, uint8_t* d_tensor = nullptr, bool extended = false,
+                        bool alpha = false) {
+	const uint64_t tslot = topt ? (alpha ? vp8g_tensor_slot_size_a(topt) : vp8g_tensor_slot_size(topt)) : 0;
+	if (!files || (topt ? !d_tensor || !tslot || outs : !outs) || n == 0 || (alpha && !(topt && extended)) ||
 	    (flags & ~(VP8G_BATCH_DEVICE_M05 | VP8G_BATCH_MULTI_PARTITION))) {
 		errno = EINVAL;
 		return -1;
@@ -449,12 +473,15 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 	Feed feed;
 	feed.files = files;
 	feed.n = n;
-	feed.fflags = (flags & VP8G_BATCH_MULTI_PARTITION) ? VP8F_MULTI_PARTITION : 0u;
+	feed.fflags = ((flags & VP8G_BATCH_MULTI_PARTITION) ? VP8F_MULTI_PARTITION : 0u) | (extended ? VP8F_EXTENDED : 0u);
 	feed.pk.assign(n, Vp8gPackedFrame{});
 	if (tok) feed.tj.assign(n, TokJob{});
 	feed.err.assign(n, 0);
+	feed.alpha = alpha;
+	feed.ares.assign(n, nullptr);
+	feed.afilter.assign(n, 0);
 	feed.ready.reset(new uint8_t[n]());
-	plan_frames(files, n, tok, threads, feed.dev, feed.order, topt == nullptr);
+	plan_frames(files, n, tok, threads, feed.dev, feed.order, topt == nullptr, extended);
 	// VP8G_PIPE_TRACE=1: one stderr line per chunk (kind, frames, MBs, launch / retire times; diagnostics)
 	const bool trace = getenv("VP8G_PIPE_TRACE") && atoi(getenv("VP8G_PIPE_TRACE")) != 0;
 	const auto t_start = std::chrono::steady_clock::now();
@@ -489,6 +516,10 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 	bool defer_release = false;
 	std::vector<Vp8gPackedFrame> late;
 	auto release = [&](Slot& s) {
+		for (uint32_t i : s.frames) {
+			free(feed.ares[i]);
+			feed.ares[i] = nullptr;
+		}
 		for (uint32_t i : s.frames)
 			if (!feed.dev[i]) {
 				if (defer_release) {
@@ -571,7 +602,7 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 			// -- gather the next chunk: consecutive positions of one kind (device m05 or host m05),
 			// in order, as they finish
 			std::vector<uint32_t> idx;
-			uint64_t mbs = 0, vals = 0, bitsb = 0, outb = 0, soutb = 0;
+			uint64_t mbs = 0, vals = 0, bitsb = 0, outb = 0, soutb = 0, ab = 0, asb = 0;
 			uint64_t xmbs = 0;  // expanding frames: scaled bytes beyond the frame's own size, priced in MBs of the chunk budget
 			uint32_t b = a, max_cols = 0, max_rows = 0;
 			const bool ctok = feed.dev[feed.order[a]] != 0;  // this chunk's kind
@@ -589,10 +620,15 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 				if (feed.err[fi] == 0) {
 					const Vp8DecodedFrame& f = f_of(fi);
 					const uint64_t ownb = vp8g_i420_size(kf_of(fi).width, kf_of(fi).height), sclb = opts ? vp8g_i420_size(sw, sh) : 0;
-					const uint64_t fx = sclb > ownb ? (sclb - ownb + 1535u) / 1536u : 0u;  // (0 unless VP8G_SCALE_EXPAND grows it)
+					uint64_t fx = sclb > ownb ? (sclb - ownb + 1535u) / 1536u : 0u;  // (0 unless VP8G_SCALE_EXPAND grows it)
+					// alpha planes count against the chunk's memory budget: residual + un-predicted (+ scaled)
+					const uint64_t apl = feed.ares[fi] ? (uint64_t)kf_of(fi).width * kf_of(fi).height : 0u;
+					const uint64_t aspl = apl && opts ? (uint64_t)sw * sh : 0u;
+					fx += (2u * apl + aspl + 1535u) / 1536u;
 					if (!idx.empty() && mbs + xmbs + f.mb_total + fx > cmbs) break;
 					xmbs += fx;
 					if (opts) soutb = al256(soutb + sclb);
+					if (apl) ab = al256(ab + apl), asb = al256(asb + aspl);
 					idx.push_back(fi);
 					mbs += f.mb_total;
 					if (ctok) bitsb += bits_slot(feed.tj[fi].psize);
@@ -648,6 +684,12 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 			L.sdesc = o, o = al256(o + (opts ? nf * sizeof(Vp8gScaleDesc) : 0));
 			L.sout = o, o = al256(o + soutb);
 			L.tdesc = o, o = al256(o + (topt ? nf * sizeof(Vp8gTensorDesc) : 0));
+			L.ares = o, o = al256(o + ab);
+			L.aout = o, o = al256(o + ab);
+			L.asout = o, o = al256(o + asb);
+			L.adesc = o, o = al256(o + (alpha ? nf * sizeof(Vp8gAlphaDesc) : 0));
+			L.asdesc = o, o = al256(o + (alpha ? nf * sizeof(Vp8gScaleDesc) : 0));
+			L.talpha = o, o = al256(o + (alpha ? nf * sizeof(Vp8gTensorAlpha) : 0));
 			L.total = o;
 			const double tg = trace ? ms_now() : 0.0;
 			PTRY(grow(s, L.total), "hipMalloc(chunk)");
@@ -789,11 +831,73 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 					}
 				}
 			}
+			// -- alpha sink: the residual planes of the chunk's frames that have one are uploaded, un-predicted
+			// (vp8g_alpha.hip) and, with opts, cropped / rescaled as luma, all on the chunk's stream;
+			// aplane[chunk position] = where the tensor kernel finds the frame's alpha (opaque if none)
+			s.adescs.clear();
+			s.asdescs.clear();
+			std::vector<Vp8gTensorAlpha> aplane(nf, Vp8gTensorAlpha{VP8G_T_OPAQUE, 0, 0});
+			if (alpha) {
+				uint64_t ao = 0, aso = 0;
+				uint32_t atask = 0;
+				std::vector<uint32_t> aj;
+				for (uint32_t j = 0; j < nf; j++) {
+					const uint32_t fi = idx[j];
+					if (!feed.ares[fi] || !live[fi]) continue;
+					const uint32_t w = kf_of(fi).width, h = kf_of(fi).height;
+					Vp8gAlphaDesc ad;
+					if (vp8g_make_alpha_desc(w, h, feed.afilter[fi], L.ares + ao, w, L.aout + ao, w, (uint32_t)s.adescs.size(), &ad) != 0) {
+						feed.err[fi] = EINVAL;  // (cannot happen: the decoder returns filters 0..3 for sizes it accepted)
+						continue;
+					}
+					PTRY(hipMemcpyAsync(d + L.ares + ao, feed.ares[fi], (size_t)w * h, hipMemcpyHostToDevice, stream), "H2D");
+					aplane[j] = Vp8gTensorAlpha{L.aout + ao, w, 0};
+					if (opts) {
+						Vp8gScaleDesc sd;
+						if (vp8g_make_scale_desc_plane(w, h, L.aout + ao, w, opt_of(fi), L.asout + aso, atask, &sd) != 0) {
+							feed.err[fi] = EINVAL;  // (cannot happen: the options were resolved when the chunk was gathered)
+							continue;
+						}
+						s.asdescs.push_back(sd);
+						atask += sd.ntasks;
+						aplane[j] = Vp8gTensorAlpha{L.asout + aso, sd.width, 0};
+						aso = al256(aso + (uint64_t)sd.width * sd.height);
+					}
+					s.adescs.push_back(ad);
+					ao = al256(ao + (uint64_t)w * h);
+				}
+				if (!s.adescs.empty()) {
+					PTRY(hipMemcpyAsync(d + L.adesc, s.adescs.data(), s.adescs.size() * sizeof(Vp8gAlphaDesc), hipMemcpyHostToDevice, stream),
+					     "H2D");
+					if (vp8g_alpha_unfilter_batch_device(s.adescs.data(), (const Vp8gAlphaDesc*)(d + L.adesc), (uint32_t)s.adescs.size(), d, d,
+					                                     stream) != 0) {
+						he = hipGetLastError();
+						if (he == hipSuccess) he = hipErrorInvalidValue;
+						where = "alpha launch";
+						goto fail;
+					}
+				}
+				if (!s.asdescs.empty()) {
+					PTRY(hipMemcpyAsync(d + L.asdesc, s.asdescs.data(), s.asdescs.size() * sizeof(Vp8gScaleDesc), hipMemcpyHostToDevice,
+					                    stream),
+					     "H2D");
+					if (vp8g_scale_batch_device(s.asdescs.data(), (const Vp8gScaleDesc*)(d + L.asdesc), (uint32_t)s.asdescs.size(), d, d,
+					                            stream) != 0) {
+						he = hipGetLastError();
+						if (he == hipSuccess) he = hipErrorInvalidValue;
+						where = "alpha scale launch";
+						goto fail;
+					}
+				}
+			}
 			// -- tensor sink: the chunk's frames (scaled or as reconstructed) into their slots of the
 			// caller's tensor (same stream; nothing but the status word comes back)
 			s.tdescs.clear();
+			s.talpha.clear();
 			if (topt) {
-				auto add = [&](uint32_t fi, uint64_t y, uint64_t u, uint64_t v, uint32_t sy, uint32_t suv) {
+				auto add = [&](uint32_t j, uint64_t y, uint64_t u, uint64_t v, uint32_t sy, uint32_t suv) {
+					const uint32_t fi = idx[j];
+					if (feed.err[fi]) return;  // (a frame whose alpha stage failed above)
 					Vp8gTensorDesc td;
 					if (vp8g_make_tensor_desc(topt, y, u, v, sy, suv, (uint64_t)fi * tslot, 0, &td) != 0) {
 						feed.err[fi] = EINVAL;  // (cannot happen: the size was checked when the chunk was gathered)
@@ -801,24 +905,32 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 					}
 					td.task0 = (uint32_t)s.tdescs.size() * td.ntasks;  // (every image of a tensor has the same task count)
 					s.tdescs.push_back(td);
+					s.talpha.push_back(aplane[j]);
 				};
 				if (opts) {
 					for (size_t q = 0; q < s.sdescs.size(); q++) {
 						const Vp8gScaleDesc& sd = s.sdescs[q];
-						add(idx[sj[q]], sd.p[0].dst, sd.p[1].dst, sd.p[2].dst, sd.p[0].dst_stride, sd.p[1].dst_stride);
+						add(sj[q], sd.p[0].dst, sd.p[1].dst, sd.p[2].dst, sd.p[0].dst_stride, sd.p[1].dst_stride);
 					}
 				} else {
 					for (uint32_t j = 0; j < nf; j++) {
 						const Vp8gFrameDesc& fd = s.descs[j];
-						if (live[idx[j]]) add(idx[j], L.out + fd.out_y, L.out + fd.out_u, L.out + fd.out_v, fd.stride_y, fd.stride_uv);
+						if (live[idx[j]]) add(j, L.out + fd.out_y, L.out + fd.out_u, L.out + fd.out_v, fd.stride_y, fd.stride_uv);
 					}
 				}
 				if (!s.tdescs.empty()) {
 					PTRY(hipMemcpyAsync(d + L.tdesc, s.tdescs.data(), s.tdescs.size() * sizeof(Vp8gTensorDesc), hipMemcpyHostToDevice,
 					                    stream),
 					     "H2D");
-					if (vp8g_tensor_batch_device(s.tdescs.data(), (const Vp8gTensorDesc*)(d + L.tdesc), (uint32_t)s.tdescs.size(), topt,
-					                             d, d_tensor, stream) != 0) {
+					if (alpha)
+						PTRY(hipMemcpyAsync(d + L.talpha, s.talpha.data(), s.talpha.size() * sizeof(Vp8gTensorAlpha), hipMemcpyHostToDevice,
+						                    stream),
+						     "H2D");
+					if ((alpha ? vp8g_tensor_batch_device_a(s.tdescs.data(), (const Vp8gTensorDesc*)(d + L.tdesc), s.talpha.data(),
+					                                        (const Vp8gTensorAlpha*)(d + L.talpha), (uint32_t)s.tdescs.size(), topt, d,
+					                                        d_tensor, stream)
+					           : vp8g_tensor_batch_device(s.tdescs.data(), (const Vp8gTensorDesc*)(d + L.tdesc), (uint32_t)s.tdescs.size(),
+					                                      topt, d, d_tensor, stream)) != 0) {
 						he = hipGetLastError();
 						if (he == hipSuccess) he = hipErrorInvalidValue;
 						where = "tensor launch";
@@ -887,6 +999,7 @@ static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_
 		int first = 0;
 		for (uint32_t i = 0; i < n; i++) {
 			if (!feed.dev[i]) vp8f_packed_free(&feed.pk[i]);  // failed frames (the others were freed per chunk)
+			free(feed.ares[i]);
 			if (status) status[i] = feed.err[i];
 			if (feed.err[i] && !first) first = feed.err[i];
 			if (feed.err[i] && outs) yuv420_free(&outs[i]);
@@ -919,6 +1032,7 @@ fail:
 		if (c.stream) (void)hipStreamDestroy(c.stream);
 	for (uint32_t i = 0; i < n; i++) {
 		if (!feed.dev[i]) vp8f_packed_free(&feed.pk[i]);
+		free(feed.ares[i]);
 		if (outs) yuv420_free(&outs[i]);
 		if (status) status[i] = EIO;
 	}
@@ -951,6 +1065,29 @@ VP8G_API int vp8g_decode_webp_batch_tensor(const ByteSpan* files, uint32_t n, in
 		return -1;
 	}
 	return decode_batch(files, n, filtered, threads, flags, opts, n_opts, nullptr, status, t, (uint8_t*)d_out);
+}
+
+// The extended container (webp_parse_extended) in front of the same pipeline: VP8X files decode, alpha
+// is ignored.
+VP8G_API int vp8g_decode_webp_batch_x(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                      const Vp8gScaleOpt* opts, uint32_t n_opts, Yuv420Image* outs, int* status) {
+	if (opts ? n_opts != 1 && n_opts != n : n_opts != 0) {
+		errno = EINVAL;
+		return -1;
+	}
+	return decode_batch(files, n, filtered, threads, flags, opts, n_opts, outs, status, nullptr, nullptr, true);
+}
+
+VP8G_API int vp8g_decode_webp_batch_tensor_x(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                             const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, uint32_t xflags,
+                                             void* d_out, int* status) {
+	if ((xflags & ~VP8G_X_ALPHA) || !t || !d_out || !vp8g_tensor_slot_size(t) || (opts ? n_opts != 1 && n_opts != n : n_opts != 0) ||
+	    (uintptr_t)d_out % (vp8g_tensor_slot_size(t) / (3ull * t->width * t->height))) {
+		errno = EINVAL;
+		return -1;
+	}
+	return decode_batch(files, n, filtered, threads, flags, opts, n_opts, nullptr, status, t, (uint8_t*)d_out, true,
+	                    (xflags & VP8G_X_ALPHA) != 0);
 }
 
 VP8G_API int vp8g_decode_webp_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, Yuv420Image* outs,

@@ -421,6 +421,9 @@ void make_plane(Vp8gScalePlane* p, uint64_t src, uint32_t sstride, uint32_t W, u
 
 bool expands(const Vp8gScalePlane& p) { return p.src_w < p.dst_w || p.src_h < p.dst_h; }
 
+// a chroma slot of a single-plane descriptor (vp8g_make_scale_desc_plane): no size, no tasks
+bool plane_empty(const Vp8gScalePlane& p) { return !p.ntasks && !p.src_w && !p.src_h && !p.dst_w && !p.dst_h; }
+
 bool plane_ok(const Vp8gScalePlane& p) {
 	if (p.src_w && p.src_h && expands(p)) {  // expand_kernel's plane: exactly what make_plane gives
 		uint32_t fx, fy, fxy, tw = kThreads;
@@ -482,6 +485,24 @@ VP8G_API int vp8g_make_scale_desc(uint32_t width, uint32_t height, uint64_t src_
 	return 0;
 }
 
+// One plane scaled as luma (the A plane of an extended picture: libwebp rescales it with the luma
+// arithmetic, window and target); p[1] and p[2] stay empty (no tasks).
+VP8G_API int vp8g_make_scale_desc_plane(uint32_t width, uint32_t height, uint64_t src, uint32_t stride, const Vp8gScaleOpt* opt,
+                                        uint64_t dst_offset, uint32_t task0, Vp8gScaleDesc* d) {
+	Vp8fScaleGeom g;
+	if (!d || vp8f_scale_resolve(width, height, opt, &g) != 0 || stride < width) {
+		errno = EINVAL;
+		return -1;
+	}
+	memset(d, 0, sizeof(*d));
+	d->width = g.out_w, d->height = g.out_h;
+	d->src_width = width, d->src_height = height, d->crop_left = g.left, d->crop_top = g.top;
+	make_plane(&d->p[0], src + (uint64_t)g.top * stride + g.left, stride, g.win_w, g.win_h, dst_offset, g.out_w, g.out_h);
+	d->task0 = task0;
+	d->ntasks = d->p[0].ntasks;
+	return 0;
+}
+
 VP8G_API int vp8g_scale_batch_device(const Vp8gScaleDesc* h, const Vp8gScaleDesc* d_descs, uint32_t n, const uint8_t* d_src,
                                      uint8_t* d_dst, void* stream) {
 	if (!h || !d_descs || !d_src || !d_dst || n == 0) {
@@ -493,11 +514,13 @@ VP8G_API int vp8g_scale_batch_device(const Vp8gScaleDesc* h, const Vp8gScaleDesc
 	for (uint32_t i = 0; i < n; i++) {
 		const Vp8gScaleDesc& d = h[i];
 		if (d.task0 != total || d.ntasks == 0 || d.ntasks != (uint64_t)d.p[0].ntasks + d.p[1].ntasks + d.p[2].ntasks ||
-		    !plane_ok(d.p[0]) || !plane_ok(d.p[1]) || !plane_ok(d.p[2])) {  // tasks must be numbered image by image
+		    !plane_ok(d.p[0]) || !(plane_ok(d.p[1]) || plane_empty(d.p[1])) ||
+		    !(plane_ok(d.p[2]) || plane_empty(d.p[2]))) {  // tasks must be numbered image by image
 			errno = EINVAL;
 			return -1;
 		}
-		for (uint32_t pi = 0; pi < 3u; pi++) (expands(d.p[pi]) ? any_expand : any_shrink) = true;
+		for (uint32_t pi = 0; pi < 3u; pi++)
+			if (d.p[pi].ntasks) (expands(d.p[pi]) ? any_expand : any_shrink) = true;
 		total += d.ntasks;
 		if (total > 0x7FFFFFFFu) {
 			errno = EINVAL;

@@ -198,6 +198,96 @@ __global__ __launch_bounds__(kThreads) void tensor_kernel(const Vp8gTensorDesc* 
 	}
 }
 
+// ---- alpha as a fourth channel (vp8g_tensor_batch_device_a) ------------------
+
+// The element of the alpha byte a: the byte, or the float nearest to a / 255 (a correctly rounded
+// division, not a multiply by a rounded reciprocal), rounded once more for the 16-bit types.
+template <uint32_t DT>
+DEV uint32_t conv_a(uint32_t a) {
+	if constexpr (DT == VP8G_T_U8) {
+		return a;
+	} else {
+		const float f = __fdiv_rn((float)a, 255.0f);
+		const uint32_t u = __float_as_uint(f);
+		if constexpr (DT == VP8G_T_F32) return u;
+		else if constexpr (DT == VP8G_T_F16) return (uint32_t)__half_as_ushort(__float2half_rn(f));
+		else return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+	}
+}
+
+// The 3-channel kernel's chunks and colour arithmetic, with four elements per pixel (NHWC: runs of 48
+// elements) or a fourth plane (NCHW).  The alpha bytes of a chunk are read one by one (a plane of any
+// stride and alignment); an opaque image reads none.
+template <uint32_t DT, bool PLANAR, bool BGR>
+__global__ __launch_bounds__(kThreads) void tensor_kernel_a(const Vp8gTensorDesc* __restrict__ D, const Vp8gTensorAlpha* __restrict__ A,
+                                                            uint32_t total, TensorParams P, const uint8_t* __restrict__ src,
+                                                            uint8_t* __restrict__ dst) {
+	constexpr uint32_t EB = (uint32_t)elem_bytes(DT);
+	const uint32_t tid = threadIdx.x, W = P.w;
+	for (uint32_t g = blockIdx.x; g < total; g += gridDim.x) {
+		const uint32_t img = g / P.tpi;
+		const uint32_t gc = (g - img * P.tpi) * kThreads + tid;
+		if (gc >= P.chunks) continue;
+		const Vp8gTensorDesc& d = D[img];
+		const Vp8gTensorAlpha al = A[img];
+		const bool opaque = al.src_a == VP8G_T_OPAQUE;
+		const uint32_t y = gc / P.cpr, x0 = (gc - y * P.cpr) * kChunk;
+		const uint32_t a = y ? (y - 1u) >> 1 : 0u, b = y ? min(a + 1u, P.ch - 1u) : 0u;
+		const bool near_a = y == 0 || (y & 1u);
+		const uint8_t* yrow = src + d.src_y + (size_t)y * d.stride_y;
+		const uint8_t* ua = src + d.src_u + (size_t)a * d.stride_uv;
+		const uint8_t* ub = src + d.src_u + (size_t)b * d.stride_uv;
+		const uint8_t* va = src + d.src_v + (size_t)a * d.stride_uv;
+		const uint8_t* vb = src + d.src_v + (size_t)b * d.stride_uv;
+		const uint8_t* arow = opaque ? src : src + al.src_a + (size_t)y * al.stride_a;  // (read only when not opaque)
+		uint8_t* out = dst + d.dst;
+		const size_t pix = (size_t)y * W + x0;
+		if (x0 + kChunk <= W && P.cw >= 8u) {
+			uint32_t c[kChunk], av[kChunk];
+			chunk_rgb(yrow, ua, ub, va, vb, x0, (int)P.cw, near_a, c);
+#pragma unroll
+			for (int i = 0; i < (int)kChunk; i++) av[i] = conv_a<DT>(opaque ? 255u : (uint32_t)arow[x0 + i]);
+			if constexpr (PLANAR) {
+#pragma unroll
+				for (int ch = 0; ch < 3; ch++) {
+					uint32_t e[kChunk];
+#pragma unroll
+					for (int i = 0; i < (int)kChunk; i++) e[i] = conv<DT>(channel<BGR>(c[i], ch), P.scale[ch], P.bias[ch]);
+					store_run<DT, (int)kChunk>(out + (size_t)ch * P.plane + pix * EB, e);
+				}
+				store_run<DT, (int)kChunk>(out + 3u * P.plane + pix * EB, av);
+			} else {
+				uint32_t e[4 * kChunk];
+#pragma unroll
+				for (int i = 0; i < (int)kChunk; i++) {
+#pragma unroll
+					for (int ch = 0; ch < 3; ch++) e[4 * i + ch] = conv<DT>(channel<BGR>(c[i], ch), P.scale[ch], P.bias[ch]);
+					e[4 * i + 3] = av[i];
+				}
+				store_run<DT, 4 * (int)kChunk>(out + pix * 4u * EB, e);
+			}
+			continue;
+		}
+		const uint32_t xe = min(x0 + kChunk, W);
+		for (uint32_t x = x0; x < xe; x++) {
+			const uint32_t col = pixel_rgb(yrow, ua, ub, va, vb, x, P.cw, near_a);
+			const size_t px = (size_t)y * W + x;
+#pragma unroll
+			for (int ch = 0; ch < 4; ch++) {
+				uint8_t* p = PLANAR ? out + (size_t)ch * P.plane + px * EB : out + (px * 4u + (uint32_t)ch) * EB;
+				store_elem<DT>(p, ch < 3 ? conv<DT>(channel<BGR>(col, ch), P.scale[ch], P.bias[ch])
+				                         : conv_a<DT>(opaque ? 255u : (uint32_t)arow[x]));
+			}
+		}
+	}
+}
+
+using KernelFnA = void (*)(const Vp8gTensorDesc*, const Vp8gTensorAlpha*, uint32_t, TensorParams, const uint8_t*, uint8_t*);
+#define VP8G_T_ROW_A(DT) \
+	{ {tensor_kernel_a<DT, false, false>, tensor_kernel_a<DT, false, true>}, {tensor_kernel_a<DT, true, false>, tensor_kernel_a<DT, true, true>} }
+const KernelFnA kKernelsA[4][2][2] = {VP8G_T_ROW_A(VP8G_T_U8), VP8G_T_ROW_A(VP8G_T_F16), VP8G_T_ROW_A(VP8G_T_BF16), VP8G_T_ROW_A(VP8G_T_F32)};
+#undef VP8G_T_ROW_A
+
 using KernelFn = void (*)(const Vp8gTensorDesc*, uint32_t, TensorParams, const uint8_t*, uint8_t*);
 #define VP8G_T_ROW(DT) \
 	{ {tensor_kernel<DT, false, false>, tensor_kernel<DT, false, true>}, {tensor_kernel<DT, true, false>, tensor_kernel<DT, true, true>} }
@@ -275,6 +365,58 @@ VP8G_API int vp8g_tensor_batch_device(const Vp8gTensorDesc* h, const Vp8gTensorD
 	if (e == hipSuccess) {
 		hipLaunchKernelGGL(kKernels[t->dtype][t->layout][t->flags & VP8G_T_BGR], dim3(grid), dim3(kThreads), 0, (hipStream_t)stream,
 		                   d_descs, (uint32_t)total, P, d_src, (uint8_t*)d_dst);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = gate.done(false);
+	if (e != hipSuccess) {
+		vp8g::set_error_text("tensor launch", e);
+		errno = EIO;
+		return -1;
+	}
+	return 0;
+}
+
+VP8G_API uint64_t vp8g_tensor_slot_size_a(const Vp8gTensorOpt* t) {
+	if (!opt_ok(t)) {
+		errno = EINVAL;
+		return 0;
+	}
+	return 4ull * t->width * t->height * (uint64_t)elem_bytes(t->dtype);
+}
+
+VP8G_API int vp8g_tensor_batch_device_a(const Vp8gTensorDesc* h, const Vp8gTensorDesc* d_descs, const Vp8gTensorAlpha* ha,
+                                        const Vp8gTensorAlpha* d_alpha, uint32_t n, const Vp8gTensorOpt* t, const uint8_t* d_src,
+                                        void* d_dst, void* stream) {
+	if (!h || !d_descs || !ha || !d_alpha || !d_src || !d_dst || n == 0 || !opt_ok(t)) {
+		errno = EINVAL;
+		return -1;
+	}
+	const uint32_t eb = (uint32_t)elem_bytes(t->dtype), tpi = tasks_per_image(*t);
+	uint64_t total = 0;
+	bool ok = (uintptr_t)d_dst % eb == 0;
+	for (uint32_t i = 0; ok && i < n; i++) {  // tasks must be numbered image by image
+		ok = h[i].task0 == total && h[i].ntasks == tpi && h[i].stride_y >= t->width && h[i].stride_uv >= (t->width + 1u) / 2u &&
+		     h[i].dst % eb == 0 && (ha[i].src_a == VP8G_T_OPAQUE || ha[i].stride_a >= t->width);
+		total += tpi;
+		if (total > 0x7FFFFFFFu) ok = false;
+	}
+	if (!ok) {
+		errno = EINVAL;
+		return -1;
+	}
+	TensorParams P;
+	memset(&P, 0, sizeof(P));
+	P.w = t->width, P.h = t->height, P.cw = (t->width + 1u) / 2u, P.ch = (t->height + 1u) / 2u;
+	P.cpr = (t->width + kChunk - 1u) / kChunk, P.chunks = P.cpr * t->height, P.tpi = tpi;
+	P.plane = (uint64_t)t->width * t->height * eb;
+	for (int c = 0; c < 3; c++) P.scale[c] = t->scale[c], P.bias[c] = t->bias[c];
+	const int cus = vp8g::device_cus();
+	const uint32_t grid = min((uint32_t)total, (uint32_t)(cus > 0 ? cus : 256) * 16u);
+	vp8g::GateScope gate((hipStream_t)stream);  // (vp8g_device.h: no cross-workgroup launch beside it)
+	hipError_t e = gate.status();
+	if (e == hipSuccess) {
+		hipLaunchKernelGGL(kKernelsA[t->dtype][t->layout][t->flags & VP8G_T_BGR], dim3(grid), dim3(kThreads), 0, (hipStream_t)stream,
+		                   d_descs, d_alpha, (uint32_t)total, P, d_src, (uint8_t*)d_dst);
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess) e = gate.done(false);

@@ -50,6 +50,9 @@ int vp8f_decode_memory(const uint8_t* data, size_t size, Vp8KeyFrameHeader* kf, 
 /* also accept 2/4/8 token partitions (RFC 6386 9.5), which the reference rejects with ENOTSUP
  * (vp8_tokens.c:357-360); SURVEY §8(f4) */
 #define VP8F_MULTI_PARTITION 2u
+/* (the _memory forms only) read the container with webp_parse_extended instead of
+ * webp_parse_simple_lossy: VP8X files decode, their ALPH chunk is not looked at */
+#define VP8F_EXTENDED 4u
 int vp8f_decode_packed(ByteSpan vp8_payload, Vp8gPackedFrame* out, unsigned flags);
 /* container + key-frame header + vp8f_decode_packed; stage codes as vp8f_decode_file */
 int vp8f_decode_packed_memory(const uint8_t* data, size_t size, Vp8gPackedFrame* out, int* stage, unsigned flags);
@@ -113,6 +116,58 @@ void vp8f_scale_factors(uint32_t W, uint32_t H, uint32_t w, uint32_t h, uint32_t
 int vp8f_scale_i420(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint32_t stride_y, uint32_t stride_uv,
                     uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, uint8_t* dy, uint8_t* du, uint8_t* dv,
                     uint32_t dstride_y, uint32_t dstride_uv);
+
+/* ---- extended container (VP8X) and the ALPH chunk (RFC 9649 2.7) ----------- */
+
+/* What webp_parse_extended found.  alph_chunk_offset = 0: no alpha. */
+typedef struct {
+	uint32_t riff_size;
+	size_t actual_size;
+	size_t vp8_chunk_offset;
+	uint32_t vp8_chunk_size;
+	size_t alph_chunk_offset;
+	uint32_t alph_chunk_size;
+	uint32_t extended;       /* the file starts with a VP8X chunk */
+	uint32_t vp8x_flags;     /* its flag byte (ICC 0x20, alpha 0x10, EXIF 0x08, XMP 0x04, animation 0x02) */
+	uint32_t canvas_width, canvas_height;
+} WebPContainerX;
+
+/* The simple layout as webp_parse_simple_lossy reads it, or a VP8X file: the 10-byte VP8X chunk
+ * first, then chunks up to the first 'VP8 ' chunk, which ends the parse as it does in libwebp (what
+ * follows the image -- EXIF, XMP, a late ALPH -- is not looked at).  ICCP, EXIF, 'XMP ' and unknown
+ * chunks are skipped (odd sizes padded); of several ALPH chunks before the image the last counts
+ * (an empty one too: it then fails to decode); an ALPH chunk counts whether or not the VP8X alpha
+ * flag is set, and the flag without a chunk means no alpha (an opaque picture).
+ * riff_size may be smaller than the file (the rest is ignored); a riff_size beyond
+ * the file, a chunk that overruns it, a missing image chunk or a canvas that differs from the VP8
+ * frame size are -1 + EINVAL; the animation flag, ANIM / ANMF and a 'VP8L' image are -1 + ENOTSUP. */
+int webp_parse_extended(ByteSpan file, WebPContainerX* out);
+
+/* Which features of the format an ALPH stream used (tests and the golden script read it). */
+typedef struct {
+	uint32_t raw, lossless;          /* compression 0 / 1 */
+	uint32_t predictor, cross_color, subtract_green, color_index; /* transforms */
+	uint32_t pack_bits[4];           /* colour indexing at 1, 2, 4, 8 bits per pixel */
+	uint32_t multi_group;            /* an entropy image with more than one prefix-code group */
+	uint32_t backrefs, short_dist;   /* LZ77 copies; those through the 120-entry distance map */
+	uint32_t cache_hits;             /* colour cache symbols */
+	uint32_t simple_codes, normal_codes;
+	uint32_t repeat_codes[3];        /* code-length codes 16, 17, 18 */
+} Vp8fAlphaStats;
+
+/* Entropy-decode an ALPH chunk payload (header byte + data) of a w x h picture into residual[w * h]
+ * and *filter (0 none, 1 horizontal, 2 vertical, 3 gradient).  Compression 0 (raw) and 1 (the
+ * RFC's lossless image stream, green channel); pre-processing and reserved bits are ignored.
+ * stats may be NULL.  Reentrant.  0, or -1 + errno: EINVAL for a NULL argument, a size of 0 or beyond
+ * 16383, an unknown compression, a malformed or truncated stream (never an over-read); ENOMEM. */
+int vp8f_alpha_decode(const uint8_t* alph, size_t size, uint32_t w, uint32_t h, uint8_t* residual, uint32_t* filter,
+                      Vp8fAlphaStats* stats);
+
+/* The un-prediction, sequentially (tight planes): alpha = (pred + residual) & 255 with pred = 0 at
+ * (0, 0), the left neighbour on the top row and the neighbour above in the left column for every
+ * filter != 0, else left / above / clip255(left + above - aboveleft) for filters 1 / 2 / 3; filter 0
+ * copies.  0, or -1 + EINVAL. */
+int vp8f_alpha_unfilter(const uint8_t* residual, uint32_t w, uint32_t h, uint32_t filter, uint8_t* out);
 
 /* FNV-1a 64 over a byte buffer (same constants as reference vp8_tokens.c:15-27). */
 uint64_t vp8f_fnv1a64(const void* data, size_t n, uint64_t h);

@@ -47,6 +47,84 @@ int webp_parse_simple_lossy(ByteSpan file, WebPContainer* out) {
 	return 0;
 }
 
+/* RFC 9649 2.7 (extended file format), with libwebp's reading where the RFC leaves a choice
+ * (tests/golden/alpha.json records its verdict on the directed containers). */
+int webp_parse_extended(ByteSpan file, WebPContainerX* out) {
+	if (!out) return -1;
+	memset(out, 0, sizeof(*out));
+	out->actual_size = file.size;
+	if (!file.data || file.size < 20 || memcmp(file.data, "RIFF", 4) != 0 || memcmp(file.data + 8, "WEBP", 4) != 0) {
+		errno = EINVAL;
+		return -1;
+	}
+	if (memcmp(file.data + 12, "VP8X", 4) != 0) {
+		WebPContainer c;
+		if (memcmp(file.data + 12, "VP8L", 4) == 0) {
+			errno = ENOTSUP;
+			return -1;
+		}
+		if (webp_parse_simple_lossy(file, &c) != 0) return -1;
+		out->riff_size = c.riff_size;
+		out->vp8_chunk_offset = c.vp8_chunk_offset, out->vp8_chunk_size = c.vp8_chunk_size;
+		return 0;
+	}
+	out->riff_size = rd_le32(file.data + 4);
+	/* the RIFF payload must lie inside the file; bytes after it are ignored */
+	if (out->riff_size > 0xFFFFFFF6u || (size_t)out->riff_size > file.size - 8u || out->riff_size < 12u) {
+		errno = EINVAL;
+		return -1;
+	}
+	const size_t end = 8u + (size_t)out->riff_size;
+	if (end < 30u || rd_le32(file.data + 16) != 10u) {
+		errno = EINVAL;
+		return -1;
+	}
+	out->extended = 1;
+	out->vp8x_flags = file.data[20];
+	out->canvas_width = 1u + ((uint32_t)file.data[24] | (uint32_t)file.data[25] << 8 | (uint32_t)file.data[26] << 16);
+	out->canvas_height = 1u + ((uint32_t)file.data[27] | (uint32_t)file.data[28] << 8 | (uint32_t)file.data[29] << 16);
+	if (out->vp8x_flags & 0x02u) {
+		errno = ENOTSUP;
+		return -1;
+	}
+	size_t pos = 30;
+	for (;;) {
+		if (end - pos < 8u) { /* no image chunk */
+			errno = EINVAL;
+			return -1;
+		}
+		const uint8_t* chunk = file.data + pos;
+		const uint32_t csize = rd_le32(chunk + 4);
+		if (csize > 0xFFFFFFF6u || (size_t)csize > end - pos - 8u) {
+			errno = EINVAL;
+			return -1;
+		}
+		if (memcmp(chunk, "VP8L", 4) == 0 || memcmp(chunk, "ANIM", 4) == 0 || memcmp(chunk, "ANMF", 4) == 0) {
+			errno = ENOTSUP;
+			return -1;
+		}
+		if (memcmp(chunk, "VP8 ", 4) == 0) {
+			out->vp8_chunk_offset = pos + 8u, out->vp8_chunk_size = csize;
+			break;
+		}
+		if (memcmp(chunk, "ALPH", 4) == 0) out->alph_chunk_offset = pos + 8u, out->alph_chunk_size = csize;
+		const size_t padded = (size_t)csize + (csize & 1u);
+		if (padded > end - pos - 8u) { /* (the pad byte of the last chunk may be missing only for the image) */
+			errno = EINVAL;
+			return -1;
+		}
+		pos += 8u + padded;
+	}
+	Vp8KeyFrameHeader kf;
+	ByteSpan payload = {file.data + out->vp8_chunk_offset, out->vp8_chunk_size};
+	if (vp8_parse_keyframe_header(payload, &kf) != 0) return -1;
+	if (kf.width != out->canvas_width || kf.height != out->canvas_height) {
+		errno = EINVAL;
+		return -1;
+	}
+	return 0;
+}
+
 int vp8_parse_keyframe_header(ByteSpan p, Vp8KeyFrameHeader* out) {
 	if (!out) return -1;
 	memset(out, 0, sizeof(*out));
@@ -105,6 +183,17 @@ out:
 	return rc;
 }
 
+/* the VP8 payload of a file: the simple layout, or with VP8F_EXTENDED the extended one as well */
+static int locate_payload(ByteSpan file, unsigned flags, WebPContainer* c) {
+	if (!(flags & VP8F_EXTENDED)) return webp_parse_simple_lossy(file, c);
+	WebPContainerX x;
+	if (webp_parse_extended(file, &x) != 0) return -1;
+	memset(c, 0, sizeof(*c));
+	c->riff_size = x.riff_size, c->actual_size = x.actual_size;
+	c->vp8_chunk_offset = x.vp8_chunk_offset, c->vp8_chunk_size = x.vp8_chunk_size;
+	return 0;
+}
+
 int vp8f_decode_packed_memory(const uint8_t* data, size_t size, Vp8gPackedFrame* out, int* stage, unsigned flags) {
 	int st = 0, rc = -1;
 	WebPContainer c;
@@ -113,12 +202,12 @@ int vp8f_decode_packed_memory(const uint8_t* data, size_t size, Vp8gPackedFrame*
 	if (!out) {
 		errno = EINVAL;
 		st = 4;
-	} else if (webp_parse_simple_lossy(file, &c) != 0) {
+	} else if (locate_payload(file, flags, &c) != 0) {
 		st = 2;
 	} else {
 		ByteSpan payload = {data + c.vp8_chunk_offset, c.vp8_chunk_size};
 		if (vp8_parse_keyframe_header(payload, &out->kf) != 0 || !out->kf.is_key_frame) st = 3;
-		else if (vp8f_decode_packed(payload, out, flags) != 0) st = 4;
+		else if (vp8f_decode_packed(payload, out, flags & ~VP8F_EXTENDED) != 0) st = 4;
 		else rc = 0;
 	}
 	if (stage) *stage = st;
@@ -134,7 +223,7 @@ int vp8f_token_header_memory(const uint8_t* data, size_t size, Vp8KeyFrameHeader
 	if (!kf || !hdr || !tf || !payload_off || !payload_size) {
 		errno = EINVAL;
 		st = 4;
-	} else if (webp_parse_simple_lossy(file, &c) != 0) {
+	} else if (locate_payload(file, flags, &c) != 0) {
 		st = 2;
 	} else if (c.vp8_chunk_size > 0xFFFFFFF0u) {
 		errno = EFBIG;
@@ -144,7 +233,7 @@ int vp8f_token_header_memory(const uint8_t* data, size_t size, Vp8KeyFrameHeader
 		if (vp8_parse_keyframe_header(payload, kf) != 0 || !kf->is_key_frame) {
 			errno = EINVAL;
 			st = 3;
-		} else if (vp8f_token_header(payload, kf, hdr, tf, flags) != 0) {
+		} else if (vp8f_token_header(payload, kf, hdr, tf, flags & ~VP8F_EXTENDED) != 0) {
 			st = 4;
 		} else {
 			*payload_off = c.vp8_chunk_offset;

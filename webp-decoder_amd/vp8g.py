@@ -162,6 +162,37 @@ class Vp8gTensorDesc(C.Structure):
         "stride_y", "stride_uv", "task0", "ntasks")]
 
 
+class WebPContainerX(C.Structure):
+    """host/vp8_front.h: what webp_parse_extended found (alph_chunk_offset 0 = no alpha)."""
+    _fields_ = [("riff_size", C.c_uint32), ("actual_size", C.c_size_t), ("vp8_chunk_offset", C.c_size_t),
+                ("vp8_chunk_size", C.c_uint32), ("alph_chunk_offset", C.c_size_t), ("alph_chunk_size", C.c_uint32),
+                ("extended", C.c_uint32), ("vp8x_flags", C.c_uint32), ("canvas_width", C.c_uint32),
+                ("canvas_height", C.c_uint32)]
+
+
+ALPHA_STATS = ("raw", "lossless", "predictor", "cross_color", "subtract_green", "color_index", "pack_bits_1",
+               "pack_bits_2", "pack_bits_4", "pack_bits_8", "multi_group", "backrefs", "short_dist", "cache_hits",
+               "simple_codes", "normal_codes", "repeat_16", "repeat_17", "repeat_18")
+
+
+class Vp8fAlphaStats(C.Structure):
+    """host/vp8_front.h: which features of the format an ALPH stream used (counters, in ALPHA_STATS order)."""
+    _fields_ = [(n, C.c_uint32) for n in ALPHA_STATS]
+
+
+class Vp8gAlphaDesc(C.Structure):
+    """include/vp8g.h: per-plane descriptor of the alpha un-prediction kernel."""
+    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64)] + [(n, C.c_uint32) for n in (
+        "width", "height", "src_stride", "dst_stride", "filter", "task0", "ntasks", "reserved")]
+
+
+class Vp8gTensorAlpha(C.Structure):
+    """include/vp8g.h: the alpha plane of one image of the 4-channel tensor kernel (src_a = 2^64 - 1: opaque)."""
+    _fields_ = [("src_a", C.c_uint64), ("stride_a", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+T_OPAQUE = 0xFFFFFFFFFFFFFFFF
+VP8G_X_ALPHA = 1
 VP8G_SCALE_DWEBP_FILTER = 1
 VP8G_SCALE_EXPAND = 4
 
@@ -268,6 +299,13 @@ def host_lib():
         lib.vp8f_scale_filtered.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(Vp8gScaleOpt), C.c_int]
         lib.vp8f_scale_i420.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                         C.POINTER(Vp8gScaleOpt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        lib.webp_parse_simple_lossy.argtypes = [ByteSpan, C.c_void_p]
+        lib.vp8_parse_keyframe_header.argtypes = [ByteSpan, C.POINTER(Vp8KeyFrameHeader)]
+        if hasattr(lib, "webp_parse_extended"):  # (libraries built before the alpha path: A/B of old builds)
+            lib.webp_parse_extended.argtypes = [ByteSpan, C.POINTER(WebPContainerX)]
+            lib.vp8f_alpha_decode.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
+                                              C.POINTER(C.c_uint32), C.POINTER(Vp8fAlphaStats)]
+            lib.vp8f_alpha_unfilter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         lib._typed = True
     return lib
 
@@ -337,6 +375,22 @@ def gpu_lib():
                                                  C.c_void_p, C.c_void_p]
         lib.vp8g_decode_webp_batch_tensor.argtypes = [P(ByteSpan), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
                                                       P(Vp8gScaleOpt), C.c_uint32, P(Vp8gTensorOpt), C.c_void_p, P(C.c_int)]
+        if hasattr(lib, "vp8g_alpha_unfilter_batch_device"):  # (libraries built before the alpha path: A/B of old builds)
+            lib.vp8g_make_scale_desc_plane.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, P(Vp8gScaleOpt), C.c_uint64,
+                                                       C.c_uint32, P(Vp8gScaleDesc)]
+            lib.vp8g_make_alpha_desc.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64,
+                                                 C.c_uint32, C.c_uint32, P(Vp8gAlphaDesc)]
+            lib.vp8g_alpha_unfilter_batch_device.argtypes = [P(Vp8gAlphaDesc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                             C.c_void_p]
+            lib.vp8g_decode_webp_batch_x.argtypes = [P(ByteSpan), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, P(Vp8gScaleOpt),
+                                                     C.c_uint32, P(Yuv420Image), P(C.c_int)]
+            lib.vp8g_decode_webp_batch_tensor_x.argtypes = [P(ByteSpan), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
+                                                            P(Vp8gScaleOpt), C.c_uint32, P(Vp8gTensorOpt), C.c_uint32, C.c_void_p,
+                                                            P(C.c_int)]
+            lib.vp8g_tensor_slot_size_a.argtypes = [P(Vp8gTensorOpt)]
+            lib.vp8g_tensor_slot_size_a.restype = C.c_uint64
+            lib.vp8g_tensor_batch_device_a.argtypes = [P(Vp8gTensorDesc), C.c_void_p, P(Vp8gTensorAlpha), C.c_void_p, C.c_uint32,
+                                                       P(Vp8gTensorOpt), C.c_void_p, C.c_void_p, C.c_void_p]
         lib._typed = True
     return lib
 
@@ -608,6 +662,146 @@ def gpu_decode_webp_batch_scaled(files: list[bytes], scale, filtered: bool = Tru
     return out, list(st)
 
 
+def _c_bytes(data: bytes):
+    buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(data if data else b"\0")
+    return buf, ByteSpan(C.cast(buf, C.POINTER(C.c_uint8)), len(data))
+
+
+def parse_simple(data: bytes):
+    """webp_parse_simple_lossy: (payload offset, payload size); OSError with its errno if refused."""
+    out = (C.c_uint8 * 64)()
+    buf, span = _c_bytes(data)
+    if host_lib().webp_parse_simple_lossy(span, out) != 0:
+        raise OSError(C.get_errno(), "webp_parse_simple_lossy")
+    return int.from_bytes(bytes(out[16:24]), "little"), int.from_bytes(bytes(out[24:28]), "little")
+
+
+def parse_extended(data: bytes) -> dict:
+    """webp_parse_extended: the fields of WebPContainerX as a dict, plus "alpha" (an ALPH chunk was found);
+    OSError with its errno (EINVAL, ENOTSUP) if refused."""
+    c = WebPContainerX()
+    buf, span = _c_bytes(data)
+    if host_lib().webp_parse_extended(span, C.byref(c)) != 0:
+        raise OSError(C.get_errno(), "webp_parse_extended")
+    d = {n: int(getattr(c, n)) for n, _ in WebPContainerX._fields_}
+    d["alpha"] = d["alph_chunk_offset"] != 0
+    return d
+
+
+def alpha_decode_host(alph: bytes, w: int, h: int):
+    """vp8f_alpha_decode of an ALPH chunk payload: (residual plane uint8 [h, w], filter, stats dict);
+    OSError with its errno if the stream does not decode."""
+    res = np.zeros((max(h, 0), max(w, 0)), np.uint8)
+    flt, st = C.c_uint32(), Vp8fAlphaStats()
+    buf, _ = _c_bytes(alph)
+    if host_lib().vp8f_alpha_decode(buf, len(alph), w, h, res.ctypes.data, C.byref(flt), C.byref(st)) != 0:
+        raise OSError(C.get_errno(), "vp8f_alpha_decode")
+    return res, int(flt.value), {n: int(getattr(st, n)) for n in ALPHA_STATS}
+
+
+def host_alpha_unfilter(residual, filter: int) -> np.ndarray:
+    """vp8f_alpha_unfilter (the sequential CPU restatement of the un-prediction) of a uint8 [h, w] plane."""
+    r = np.ascontiguousarray(residual, dtype=np.uint8)
+    out = np.empty_like(r)
+    if r.ndim != 2 or host_lib().vp8f_alpha_unfilter(r.ctypes.data, r.shape[1], r.shape[0], filter, out.ctypes.data) != 0:
+        raise OSError(C.get_errno() or 22, "vp8f_alpha_unfilter")
+    return out
+
+
+def host_alpha_plane(data: bytes):
+    """The alpha plane of an extended .webp on the host (container, ALPH decode, un-prediction): uint8 [h, w],
+    or None for a picture without alpha.  OSError as the stages raise it."""
+    c = parse_extended(data)
+    if not c["alpha"]:
+        return None
+    kf = Vp8KeyFrameHeader()
+    buf, _ = _c_bytes(data[c["vp8_chunk_offset"]:c["vp8_chunk_offset"] + c["vp8_chunk_size"]])
+    host_lib().vp8_parse_keyframe_header(ByteSpan(C.cast(buf, C.POINTER(C.c_uint8)), c["vp8_chunk_size"]), C.byref(kf))
+    res, flt, _ = alpha_decode_host(data[c["alph_chunk_offset"]:c["alph_chunk_offset"] + c["alph_chunk_size"]],
+                                    kf.width, kf.height)
+    return host_alpha_unfilter(res, flt)
+
+
+def gpu_alpha_unfilter(planes, filters, src_pad: int = 0, guard: int = 0, fill: int = 0xEE):
+    """vp8g_alpha_unfilter_batch_device over residual planes (uint8 [h, w] each) of mixed sizes and filters in
+    one launch: the list of un-predicted planes.  src_pad: extra bytes per source row (a padded stride);
+    guard: bytes kept around every destination plane, which the call checks still hold `fill`."""
+    import torch
+    lib = gpu_lib()
+    dev = torch.device("cuda", 0)
+    n = len(planes)
+    descs = (Vp8gAlphaDesc * n)()
+    src_parts, so, do, task0 = [], 0, guard, 0
+    for i, (p, f) in enumerate(zip(planes, filters)):
+        p = np.ascontiguousarray(p, dtype=np.uint8)
+        h, w = p.shape
+        padded = np.full((h, w + src_pad), 0x5A, np.uint8)
+        padded[:, :w] = p
+        src_parts.append(padded.reshape(-1))
+        if lib.vp8g_make_alpha_desc(w, h, f, so, w + src_pad, do, w, task0, C.byref(descs[i])) != 0:
+            raise ValueError(f"vp8g_make_alpha_desc failed: errno={C.get_errno()}")
+        task0 += descs[i].ntasks
+        so += padded.size
+        do += w * h + guard
+    src = torch.from_numpy(np.concatenate(src_parts)).to(dev)
+    dst = torch.full((do,), fill, dtype=torch.uint8, device=dev)
+    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
+    stream = torch.cuda.current_stream(dev)
+    if lib.vp8g_alpha_unfilter_batch_device(descs, C.c_void_p(d_descs.data_ptr()), n, C.c_void_p(src.data_ptr()),
+                                            C.c_void_p(dst.data_ptr()), C.c_void_p(stream.cuda_stream)) != 0:
+        raise RuntimeError(f"vp8g_alpha_unfilter_batch_device failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
+    stream.synchronize()
+    host = dst.cpu().numpy()
+    out, keep = [], np.ones(do, bool)
+    for i, p in enumerate(planes):
+        h, w = np.asarray(p).shape
+        out.append(host[descs[i].dst:descs[i].dst + w * h].reshape(h, w).copy())
+        keep[descs[i].dst:descs[i].dst + w * h] = False
+    if not (host[keep] == fill).all():
+        raise AssertionError("gpu_alpha_unfilter: bytes outside the planes were written")
+    return out
+
+
+def host_scale_plane(plane, opt: Vp8gScaleOpt) -> np.ndarray:
+    """One uint8 [h, w] plane through vp8f_scale_i420 as its luma plane (the A plane: libwebp rescales it with the
+    luma arithmetic and window)."""
+    p = np.ascontiguousarray(plane, dtype=np.uint8)
+    h, w = p.shape
+    i420 = p.tobytes() + bytes(2 * ((w + 1) // 2) * ((h + 1) // 2))
+    out, ow, oh = host_scale(i420, w, h, opt)
+    return np.frombuffer(out, np.uint8, ow * oh).reshape(oh, ow).copy()
+
+
+def gpu_scale_planes(planes, opts):
+    """vp8g_make_scale_desc_plane + vp8g_scale_batch_device over uint8 [h, w] planes (opts: one Vp8gScaleOpt per
+    plane) in one launch: the list of scaled planes."""
+    import torch
+    lib = gpu_lib()
+    dev = torch.device("cuda", 0)
+    n = len(planes)
+    descs = (Vp8gScaleDesc * n)()
+    so = do = task0 = 0
+    for i, (p, opt) in enumerate(zip(planes, opts)):
+        h, w = p.shape
+        if lib.vp8g_make_scale_desc_plane(w, h, so, w, C.byref(opt), do, task0, C.byref(descs[i])) != 0:
+            raise ValueError(f"vp8g_make_scale_desc_plane failed: errno={C.get_errno()}")
+        task0 += descs[i].ntasks
+        so += w * h
+        do += descs[i].width * descs[i].height
+    src = torch.from_numpy(np.concatenate([np.ascontiguousarray(p, dtype=np.uint8).reshape(-1) for p in planes])).to(dev)
+    dst = torch.full((do + 16,), 0xEE, dtype=torch.uint8, device=dev)
+    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
+    stream = torch.cuda.current_stream(dev)
+    if lib.vp8g_scale_batch_device(descs, C.c_void_p(d_descs.data_ptr()), n, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                                   C.c_void_p(stream.cuda_stream)) != 0:
+        raise RuntimeError(f"vp8g_scale_batch_device failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
+    stream.synchronize()
+    host = dst.cpu().numpy()
+    if not (host[do:] == 0xEE).all():
+        raise AssertionError("gpu_scale_planes: bytes after the planes were written")
+    return [host[d.p[0].dst:d.p[0].dst + d.width * d.height].reshape(d.height, d.width).copy() for d in descs]
+
+
 def _dtype_name(dtype) -> str:
     name = dtype if isinstance(dtype, str) else (str(dtype) if str(dtype).startswith("torch.") else np.dtype(dtype).name)
     name = name.replace("torch.", "")
@@ -643,8 +837,8 @@ def tensor_opt(size, dtype, layout: str = "NCHW", mean=None, std=None, scale=Non
                          (C.c_float * 3)(*sc), (C.c_float * 3)(*bi))
 
 
-def _tensor_shape(n: int, opt: Vp8gTensorOpt):
-    return (n, 3, opt.height, opt.width) if opt.layout == T_LAYOUTS["NCHW"] else (n, opt.height, opt.width, 3)
+def _tensor_shape(n: int, opt: Vp8gTensorOpt, channels: int = 3):
+    return (n, channels, opt.height, opt.width) if opt.layout == T_LAYOUTS["NCHW"] else (n, opt.height, opt.width, channels)
 
 
 def _torch_dtype(opt: Vp8gTensorOpt):
@@ -652,13 +846,37 @@ def _torch_dtype(opt: Vp8gTensorOpt):
     return (torch.uint8, torch.float16, torch.bfloat16, torch.float32)[opt.dtype]
 
 
-def host_tensor(i420: bytes, w: int, h: int, opt: Vp8gTensorOpt):
+def host_alpha_channel(alpha, opt: Vp8gTensorOpt):
+    """The fourth channel of the tensor for a uint8 [h, w] alpha plane: the byte, or
+    np.float32(a) / np.float32(255) (255 -> 1.0 exactly) rounded once to the 16-bit element types.  A torch CPU
+    tensor [H, W]."""
+    import torch
+    a = np.ascontiguousarray(alpha, dtype=np.uint8)
+    if opt.dtype == T_DTYPES["uint8"]:
+        return torch.from_numpy(a.copy())
+    f = a.astype(np.float32) / np.float32(255)
+    assert f.dtype == np.float32
+    if opt.dtype == T_DTYPES["float16"]:
+        return torch.from_numpy(f.astype(np.float16))
+    if opt.dtype == T_DTYPES["bfloat16"]:
+        return torch.from_numpy(f).to(torch.bfloat16)
+    return torch.from_numpy(f)
+
+
+def host_tensor(i420: bytes, w: int, h: int, opt: Vp8gTensorOpt, alpha=None):
     """The numpy / torch-CPU restatement of the tensor semantics (include/vp8g.h) for one cropped
     I420 picture: the m08 restatement's RGB (oracle_encode), the channel order, a float32 multiply and
     then a float32 add, one rounding to the element type, the layout.  A torch CPU tensor [3, H, W] or
-    [H, W, 3].  Tests and tools use it as the expected value."""
+    [H, W, 3].  Tests and tools use it as the expected value.
+    alpha: a uint8 [h, w] plane, or "opaque": the 4-channel tensor ([4, H, W] / [H, W, 4]) whose first three
+    channels are the above and whose fourth is host_alpha_channel (§16)."""
     import torch
     assert (w, h) == (opt.width, opt.height)
+    if alpha is not None:
+        rgb3 = host_tensor(i420, w, h, opt)
+        a = host_alpha_channel(np.full((h, w), 255, np.uint8) if isinstance(alpha, str) else alpha, opt)
+        planar = opt.layout == T_LAYOUTS["NCHW"]
+        return torch.cat([rgb3, a.unsqueeze(0 if planar else 2)], dim=0 if planar else 2).contiguous()
     ppm = oracle_encode(i420, w, h, "ppm")
     rgb = np.frombuffer(ppm, np.uint8, w * h * 3, len(ppm) - w * h * 3).reshape(h, w, 3)
     if opt.flags & VP8G_T_BGR:
@@ -679,14 +897,16 @@ def host_tensor(i420: bytes, w: int, h: int, opt: Vp8gTensorOpt):
     return out.permute(2, 0, 1).contiguous() if opt.layout == T_LAYOUTS["NCHW"] else out.contiguous()
 
 
-def gpu_tensor(i420_list, w: int, h: int, opt: Vp8gTensorOpt):
+def gpu_tensor(i420_list, w: int, h: int, opt: Vp8gTensorOpt, alpha=None):
     """vp8g_tensor_batch_device over cropped I420 pictures of one size: upload them, one launch, and the
-    torch.Tensor [N, 3, H, W] or [N, H, W, 3] it leaves on the device."""
+    torch.Tensor [N, 3, H, W] or [N, H, W, 3] it leaves on the device.
+    alpha: a list with one uint8 [h, w] plane or None (opaque) per picture: vp8g_tensor_batch_device_a, the
+    4-channel tensor."""
     import torch
     lib = gpu_lib()
     dev = torch.device("cuda", 0)
     n, fsz, cw, ch = len(i420_list), i420_size(w, h), (w + 1) // 2, (h + 1) // 2
-    slot = lib.vp8g_tensor_slot_size(C.byref(opt))
+    slot = lib.vp8g_tensor_slot_size(C.byref(opt)) if alpha is None else lib.vp8g_tensor_slot_size_a(C.byref(opt))
     if not slot or (w, h) != (opt.width, opt.height) or any(len(b) != fsz for b in i420_list):
         raise ValueError("gpu_tensor: invalid options or picture sizes")
     descs = (Vp8gTensorDesc * n)()
@@ -697,10 +917,33 @@ def gpu_tensor(i420_list, w: int, h: int, opt: Vp8gTensorOpt):
                                      C.byref(descs[i])) != 0:
             raise ValueError("vp8g_make_tensor_desc failed")
         task0 += descs[i].ntasks
-    src = torch.from_numpy(np.frombuffer(b"".join(i420_list), dtype=np.uint8).copy()).to(dev)
     d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
-    out = torch.empty(_tensor_shape(n, opt), dtype=_torch_dtype(opt), device=dev)
     stream = torch.cuda.current_stream(dev)
+    if alpha is not None:
+        if len(alpha) != n:
+            raise ValueError("gpu_tensor: one alpha entry per picture")
+        al, parts, ao = (Vp8gTensorAlpha * n)(), [], n * fsz
+        for i, a in enumerate(alpha):
+            if a is None:
+                al[i] = Vp8gTensorAlpha(T_OPAQUE, 0, 0)
+                continue
+            a = np.ascontiguousarray(a, dtype=np.uint8)
+            if a.shape != (h, w):
+                raise ValueError("gpu_tensor: alpha plane of another size")
+            al[i] = Vp8gTensorAlpha(ao, w, 0)
+            parts.append(a.reshape(-1))
+            ao += w * h
+        src = torch.from_numpy(np.concatenate([np.frombuffer(b"".join(i420_list), dtype=np.uint8)] + parts)).to(dev)
+        d_al = torch.frombuffer(bytearray(bytes(al)), dtype=torch.uint8).to(dev)
+        out = torch.empty(_tensor_shape(n, opt, 4), dtype=_torch_dtype(opt), device=dev)
+        if lib.vp8g_tensor_batch_device_a(descs, C.c_void_p(d_descs.data_ptr()), al, C.c_void_p(d_al.data_ptr()), n, C.byref(opt),
+                                          C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()),
+                                          C.c_void_p(stream.cuda_stream)) != 0:
+            raise RuntimeError(f"vp8g_tensor_batch_device_a failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
+        stream.synchronize()
+        return out
+    src = torch.from_numpy(np.frombuffer(b"".join(i420_list), dtype=np.uint8).copy()).to(dev)
+    out = torch.empty(_tensor_shape(n, opt), dtype=_torch_dtype(opt), device=dev)
     if lib.vp8g_tensor_batch_device(descs, C.c_void_p(d_descs.data_ptr()), n, C.byref(opt), C.c_void_p(src.data_ptr()),
                                     C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)) != 0:
         raise RuntimeError(f"vp8g_tensor_batch_device failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
@@ -708,15 +951,44 @@ def gpu_tensor(i420_list, w: int, h: int, opt: Vp8gTensorOpt):
     return out
 
 
+def gpu_decode_webp_batch_x(files: list[bytes], scale=None, filtered: bool = True, threads: int = 0, device_m05: bool = False,
+                            multi_partition: bool = False):
+    """vp8g_decode_webp_batch_x: gpu_decode_webp_batch_scaled (scale: None, one Vp8gScaleOpt, or a list of one per
+    frame) with the extended container in front; alpha is ignored.  Returns (list of (I420 bytes, w, h) or
+    None, list of errno)."""
+    lib = gpu_lib()
+    n = len(files)
+    bufs = [(C.c_uint8 * max(1, len(b))).from_buffer_copy(b if b else b"\0") for b in files]
+    spans = (ByteSpan * n)(*[ByteSpan(C.cast(bufs[i], C.POINTER(C.c_uint8)), len(files[i])) for i in range(n)])
+    opts = [] if scale is None else (list(scale) if isinstance(scale, (list, tuple)) else [scale])
+    c_opts = (Vp8gScaleOpt * len(opts))(*opts) if opts else None
+    imgs = (Yuv420Image * n)()
+    st = (C.c_int * n)()
+    rc = lib.vp8g_decode_webp_batch_x(spans, n, int(filtered), threads,
+                                      (VP8G_BATCH_DEVICE_M05 if device_m05 else 0)
+                                      | (VP8G_BATCH_MULTI_PARTITION if multi_partition else 0), c_opts, len(opts), imgs, st)
+    en = C.get_errno()
+    if rc != 0 and (all(s == 5 for s in st) or not any(st)):  # EIO: device failure; or the call itself refused
+        raise RuntimeError(f"vp8g_decode_webp_batch_x failed: errno={en} {lib.vp8g_last_error()!r}")
+    out = []
+    for i in range(n):
+        out.append((_image_bytes(imgs[i]), int(imgs[i].width), int(imgs[i].height)) if st[i] == 0 else None)
+        lib.yuv420_free(C.byref(imgs[i]))
+    return out, list(st)
+
+
 def gpu_decode_webp_batch_tensor(files: list[bytes], opt: Vp8gTensorOpt, scale=None, filtered: bool = True, threads: int = 0,
-                                 device_m05: bool = False, multi_partition: bool = False):
+                                 device_m05: bool = False, multi_partition: bool = False, extended: bool = False,
+                                 alpha: bool = False):
     """vp8g_decode_webp_batch_tensor: .webp images decoded, optionally cropped / downscaled (scale: None,
     one Vp8gScaleOpt for every frame, or a list of one per frame), converted and left on the device.
     Returns (torch.Tensor on the device, [N, 3, H, W] or [N, H, W, 3] of the requested dtype, list of
-    errno); the slot of a failed frame is zero.  torch only allocates the tensor: its data_ptr() is
+    errno); the slot of a failed frame is zero.  extended: vp8g_decode_webp_batch_tensor_x (VP8X files decode);
+    alpha: with VP8G_X_ALPHA, the tensor has four channels (R, G, B, A; opaque A for a picture without alpha).  torch only allocates the tensor: its data_ptr() is
     handed to the C call."""
     import time
     import torch
+    extended = extended or alpha  # (alpha arrives through the _x call only)
     lib = gpu_lib()
     n = len(files)
     bufs = [(C.c_uint8 * max(1, len(b))).from_buffer_copy(b if b else b"\0") for b in files]
@@ -726,14 +998,17 @@ def gpu_decode_webp_batch_tensor(files: list[bytes], opt: Vp8gTensorOpt, scale=N
     if not lib.vp8g_tensor_slot_size(C.byref(opt)):
         raise ValueError("gpu_decode_webp_batch_tensor: invalid tensor options")
     dev = torch.device("cuda", 0)
-    out = torch.empty(_tensor_shape(n, opt), dtype=_torch_dtype(opt), device=dev)
+    out = torch.empty(_tensor_shape(n, opt, 4 if alpha else 3), dtype=_torch_dtype(opt), device=dev)
     torch.cuda.synchronize(dev)
     st = (C.c_int * n)()
     t0 = time.perf_counter()
-    rc = lib.vp8g_decode_webp_batch_tensor(spans, n, int(filtered), threads,
-                                           (VP8G_BATCH_DEVICE_M05 if device_m05 else 0)
-                                           | (VP8G_BATCH_MULTI_PARTITION if multi_partition else 0), c_opts, len(opts),
-                                           C.byref(opt), C.c_void_p(out.data_ptr()), st)
+    bflags = (VP8G_BATCH_DEVICE_M05 if device_m05 else 0) | (VP8G_BATCH_MULTI_PARTITION if multi_partition else 0)
+    if extended:  # (routed to the _x call only when asked)
+        rc = lib.vp8g_decode_webp_batch_tensor_x(spans, n, int(filtered), threads, bflags, c_opts, len(opts), C.byref(opt),
+                                                 VP8G_X_ALPHA if alpha else 0, C.c_void_p(out.data_ptr()), st)
+    else:
+        rc = lib.vp8g_decode_webp_batch_tensor(spans, n, int(filtered), threads, bflags, c_opts, len(opts), C.byref(opt),
+                                               C.c_void_p(out.data_ptr()), st)
     gpu_decode_webp_batch_tensor.seconds = time.perf_counter() - t0  # the C call alone
     en = C.get_errno()
     if rc != 0 and (all(s == 5 for s in st) or not any(st)):  # EIO: device failure; or the call itself refused
