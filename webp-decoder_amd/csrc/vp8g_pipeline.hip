@@ -1,20 +1,19 @@
-// vp8g_pipeline.hip -- end-to-end batch decode, .webp bytes -> I420 in host memory
-// (vp8g_decode_webp_batch, include/vp8g.h).
+// vp8g_pipeline.hip -- end-to-end batch decode: .webp bytes in host memory -> I420 images in host memory, or
+// pictures in the caller's device tensor (vp8g_decode_webp_batch and its kin, include/vp8g.h).
 //
-//   worker threads   container + key-frame header + m05 (host/vp8_parse.c, reentrant) into the
-//                    packed wire format, frames handed out in order from an atomic counter and
-//                    kept at most a window ahead of the device
-//   this thread      groups finished frames into chunks; per chunk: H2D of the side arrays, the
-//                    block masks and the non-zero values (~5x less than dense int16), expansion
-//                    to the dense SoA the recon kernel reads, the fused recon(+LF) kernel, D2H
-//                    into the callers' images.  Chunk slots alternate (two per chunk kind), so the device work and
-//                    the copies of one chunk overlap the entropy decoding of the next ones.
+//   worker threads   container + key-frame header + m05 (host/vp8_parse.c, reentrant) into the packed wire format (and
+//                    the ALPH chunk's entropy decode, if alpha is asked for), frames handed out in order from an
+//                    atomic counter and kept at most a window ahead of the device
+//   this thread      groups finished frames into chunks and takes each through the stages of Pipeline: H2D of the
+//                    side arrays, block masks and non-zero values (~5x less than dense int16), expansion to the dense
+//                    SoA, the fused recon(+LF) kernel, then the call's sinks -- crop / rescale, alpha un-prediction, the
+//                    tensor kernel -- and D2H of what the caller gets in host memory.  Chunk slots alternate (two per
+//                    chunk kind), so one chunk's device work and copies overlap the entropy decoding of the next ones.
 //
-// With VP8G_BATCH_DEVICE_M05 the workers only parse the container, the
-// frame header and the first partition's frame-level fields (vp8f_token_header_memory); the
-// chunk uploads the compressed VP8 payloads themselves (the smallest possible wire format), and
-// m05 runs on the device (vp8g_m05.hip, one wavefront per frame) straight into the dense SoA.
-//
+// With VP8G_BATCH_DEVICE_M05 the workers only parse the container, the frame header and the first partition's
+// frame-level fields (vp8f_token_header_memory); the chunk uploads the compressed VP8 payloads themselves and m05 runs
+// on the device (vp8g_m05.hip, one workgroup per frame) straight into the dense SoA -- except for the heaviest frames,
+// which plan_frames leaves to the host threads.
 // The reference decodes one file per process (src/main.c:591-705: m01..m05 then m06/m07); its
 // m05 keeps global state (vp8_tokens.c:382, :625), which is why it cannot be threaded as is.
 #include <errno.h>
@@ -31,6 +30,8 @@
 #include <condition_variable>
 #include <memory>
 #include <mutex>
+#include <new>
+#include <system_error>
 #include <thread>
 #include <vector>
 
@@ -357,7 +358,7 @@ constexpr double kD2HNsPerByte = 0.085;    // download into fresh pageable image
 // (rates measured on the box: tools/e2e_probe.py chunk traces, tools/hybrid_sweep.py; profiles/r02_hybrid.json)
 // download = false (the tensor sink: the pictures stay on the device) prices no download.
 void plan_frames(const ByteSpan* files, uint32_t n, bool tok, uint32_t threads, std::vector<uint8_t>& dev,
-                 std::vector<uint32_t>& order, bool download = true, bool extended = false) {
+                 std::vector<uint32_t>& order, bool download, bool extended) {
 	dev.assign(n, tok ? 1 : 0);
 	order.resize(n);
 	for (uint32_t i = 0; i < n; i++) order[i] = i;
@@ -402,692 +403,691 @@ void plan_frames(const ByteSpan* files, uint32_t n, bool tok, uint32_t threads, 
 		if (!dev[by_size[k]]) order[p++] = by_size[k];
 }
 
-}  // namespace
-
-VP8G_API int vp8g_plan_batch(const ByteSpan* files, uint32_t n, uint32_t threads, uint32_t flags, uint8_t* dev,
-                             uint32_t* order) {
-	if (!files || !dev || !order || n == 0 || (flags & ~(VP8G_BATCH_DEVICE_M05 | VP8G_BATCH_MULTI_PARTITION))) {
-		errno = EINVAL;
-		return -1;
-	}
-	std::vector<uint8_t> d;
-	std::vector<uint32_t> o;
-	uint32_t thr = threads ? threads : default_threads();
-	if (thr > n) thr = n;  // (as vp8g_decode_webp_batch_ex)
-	plan_frames(files, n, (flags & VP8G_BATCH_DEVICE_M05) != 0, thr, d, o);
-	memcpy(dev, d.data(), n);
-	memcpy(order, o.data(), n * sizeof(uint32_t));
-	return 0;
+// What a stage returns: hipSuccess, or the HIP error and the step that met it (vp8g_last_error's text).  capi_status:
+// of one of the library's C entry points, which leave HIP's error, if there was one, behind their -1.
+struct Status {
+	hipError_t he = hipSuccess;
+	const char* where = nullptr;
+	bool ok() const { return he == hipSuccess; }
+};
+inline Status capi_status(int rc, const char* where) {
+	if (rc == 0) return Status{};
+	const hipError_t e = hipGetLastError();
+	return Status{e == hipSuccess ? hipErrorInvalidValue : e, where};
 }
 
-// vp8g_decode_webp_batch_ex, and with `opts` (n_opts = 1 or n) vp8g_decode_webp_batch_scaled: each
-// chunk's frames are then cropped / rescaled on the device (vp8g_scale.hip) from the chunk's
-// reconstruction buffer into a second one (small, unless VP8G_SCALE_EXPAND grows the frames: what a
-// frame grows by counts against the chunk's memory budget), and only that is downloaded.
-// With `topt` (vp8g_decode_webp_batch_tensor; outs = NULL) the sink is the caller's device tensor:
-// each chunk's frames, scaled or not, are written to their slots of d_tensor by the tensor kernel
-// (vp8g_tensor.hip) on the chunk's stream, and only the chunk's status word is downloaded.
-static int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
-                        const Vp8gScaleOpt* opts, uint32_t n_opts, Yuv420Image* outs, int* status,
-                        const Vp8gTensorOpt* topt = nullptr, uint8_t* d_tensor = nullptr, bool extended = false,
-                        bool alpha = false) {
-	const uint64_t tslot = topt ? (alpha ? vp8g_tensor_slot_size_a(topt) : vp8g_tensor_slot_size(topt)) : 0;
-	if (!files || (topt ? !d_tensor || !tslot || outs : !outs) || n == 0 || (alpha && !(topt && extended)) ||
-	    (flags & ~(VP8G_BATCH_DEVICE_M05 | VP8G_BATCH_MULTI_PARTITION))) {
-		errno = EINVAL;
-		return -1;
-	}
-	auto opt_of = [&](uint32_t i) -> const Vp8gScaleOpt* { return opts ? &opts[n_opts == 1 ? 0 : i] : nullptr; };
-	const bool tok = (flags & VP8G_BATCH_DEVICE_M05) != 0;
-	uint32_t chunk_frames_pk = kChunkFrames, chunk_frames_tok = kTokChunkFrames;
-	if (const char* e = getenv("VP8G_CHUNK_FRAMES")) {  // test knob: smaller chunks
-		const long v = atol(e);
-		if (v > 0 && (uint64_t)v < chunk_frames_pk) chunk_frames_pk = (uint32_t)v;
-		if (v > 0 && (uint64_t)v < chunk_frames_tok) chunk_frames_tok = (uint32_t)v;
-	}
-	uint64_t chunk_mbs_tok = kTokChunkMbs, chunk_mbs_pk = kChunkMbs;
-	{
-		// four chunk slots (two per chunk kind): host-m05 chunks ~1.5 KB per MB, device-m05 chunks
-		// ~1.3 KB per MB (+ payloads).  All four stay within ~3/8 of the free device memory, so a
-		// device shared with other work gets smaller chunks instead of a failed allocation (EIO for
-		// every frame); the device-m05 slots get what the (small) host-m05 slots leave.  (Round 5:
-		// the old cap, free / 16384 MBs for every slot, cut 768 device frames into two m05 launches
-		// on a 288-GB card; the second one then waited behind the first whenever their streams
-		// shared a hardware queue -- DESIGN.md §12.)
-		size_t fr = 0, tot = 0;
-		if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr) {
-			const uint64_t budget = (uint64_t)fr / 8u * 3u;
-			const uint64_t floor_mbs = 1u << 15;  // one 4K frame and change
-			const uint64_t cap_pk = budget / (4u * 1536u);
-			if (cap_pk < chunk_mbs_pk) chunk_mbs_pk = cap_pk > floor_mbs ? cap_pk : floor_mbs;
-			const uint64_t pk_bytes = 2u * chunk_mbs_pk * 1536u;
-			const uint64_t cap_tok = budget > pk_bytes ? (budget - pk_bytes) / (2u * 1331u) : 0u;
-			if (cap_tok < chunk_mbs_tok) chunk_mbs_tok = cap_tok > floor_mbs ? cap_tok : floor_mbs;
-		}
-	}
-	for (uint32_t i = 0; outs && i < n; i++) memset(&outs[i], 0, sizeof(outs[i]));
-	std::vector<uint8_t> live(n, 0);  // frame i has its output (an allocated image; a slot of the tensor)
-	if (!threads) threads = default_threads();
-	if (threads > n) threads = n;
+// Where a call's pictures go, and what happens to them on the way (one per entry point).
+struct Sinks {
+	const Vp8gScaleOpt* opts = nullptr;   // crop / rescale on the device (vp8g_scale.hip): one for all frames or one each
+	uint32_t n_opts = 0;
+	Yuv420Image* outs = nullptr;          // I420 images in host memory, or (outs = NULL) ...
+	const Vp8gTensorOpt* topt = nullptr;  // ... the slots of the caller's device tensor (vp8g_tensor.hip)
+	uint8_t* d_tensor = nullptr;
+	bool extended = false;                // the extended container (VP8X) in front
+	bool alpha = false;                   // VP8G_X_ALPHA: ALPH planes become the tensor's fourth channel
+	uint64_t tslot = 0;                   // bytes per tensor slot (decode_batch fills it in)
+	const Vp8gScaleOpt* opt_of(uint32_t i) const { return opts ? &opts[n_opts == 1 ? 0 : i] : nullptr; }
+};
 
+// Device bytes per macroblock at which the memory budget prices a chunk.  Either kind holds per MB (ChunkLayout) ymode,
+// uv_mode, segment_id, has_coeff (4 bytes), bmode (16), the dense coefficients cy, cu, cv, cy2 (512 + 128 + 128 + 32) and
+// the I420 output (384): 1204 bytes.  A host-m05 chunk adds the block masks (kNb * 2 = 50), mb_off (4) and its packed
+// values, priced at 278 bytes (139 values); a device-m05 chunk adds its payloads' bitstream slots, priced at 127 bytes.
+constexpr uint64_t kPkBytesPerMb = 1536, kTokBytesPerMb = 1331;
+// what a frame holds beyond that (a scaled picture larger than the frame, alpha planes), in MBs of the chunk budget
+inline uint64_t extra_mbs(uint64_t bytes) { return (bytes + kPkBytesPerMb - 1) / kPkBytesPerMb; }
+
+// Macroblocks per chunk (at most), by kind: [0] host m05, [1] device m05.  Four chunk slots, two per kind, stay
+// within ~3/8 of the free device memory, so a device shared with other work gets smaller chunks instead of a failed
+// allocation (EIO for every frame); the device-m05 slots get what the (small) host-m05 slots leave.
+struct MbCaps { uint64_t mbs[2]; };
+MbCaps chunk_budget(size_t free_bytes) {
+	MbCaps c{{kChunkMbs, kTokChunkMbs}};
+	if (!free_bytes) return c;  // (unknown: the defaults)
+	const uint64_t budget = (uint64_t)free_bytes / 8u * 3u;
+	const uint64_t floor_mbs = 1u << 15;  // one 4K frame and change
+	const uint64_t cap_pk = budget / (4u * kPkBytesPerMb);
+	if (cap_pk < c.mbs[0]) c.mbs[0] = cap_pk > floor_mbs ? cap_pk : floor_mbs;
+	const uint64_t pk_bytes = 2u * c.mbs[0] * kPkBytesPerMb;
+	const uint64_t cap_tok = budget > pk_bytes ? (budget - pk_bytes) / (2u * kTokBytesPerMb) : 0u;
+	if (cap_tok < c.mbs[1]) c.mbs[1] = cap_tok > floor_mbs ? cap_tok : floor_mbs;
+	return c;
+}
+
+// What a chunk's frames add up to: the sizes its buffer is laid out from.
+struct ChunkShape {
+	uint32_t nf = 0, max_cols = 0, max_rows = 0;
+	uint64_t mbs = 0, vals = 0, bitsb = 0;          // macroblocks; packed values (host m05); bitstream slots (device m05)
+	uint64_t outb = 0, soutb = 0, ab = 0, asb = 0;  // bytes of I420, scaled I420, alpha planes, scaled alpha planes
+};
+
+ChunkLayout make_layout(const ChunkShape& sh, bool tok, const Sinks& sk, uint32_t k_plan) {
+	const uint64_t mbs = sh.mbs, nf = sh.nf;
+	ChunkLayout L;
+	uint64_t o = 0;
+	L.ym = o, o = al256(o + mbs);
+	L.uvm = o, o = al256(o + mbs);
+	L.seg = o, o = al256(o + mbs);
+	L.hasc = o, o = al256(o + mbs);
+	L.bm = o, o = al256(o + mbs * 16);
+	L.masks = o, o = al256(o + (tok ? 0 : mbs * kNb * 2));
+	L.mboff = o, o = al256(o + (tok ? 0 : mbs * 4));
+	L.vals = o, o = al256(o + (tok ? 0 : sh.vals * 2 + 64));  // +64: the expansion may address one past the end
+	L.cy = o, o = al256(o + mbs * 512);
+	L.cu = o, o = al256(o + mbs * 128);
+	L.cv = o, o = al256(o + mbs * 128);
+	L.cy2 = o, o = al256(o + mbs * 32);
+	L.bits = o, o = al256(o + sh.bitsb);
+	L.jobs = o, o = al256(o + (tok ? nf * sizeof(Vp8gTokFrame) : 0));
+	L.desc = o, o = al256(o + nf * sizeof(Vp8gFrameDesc));
+	L.status = o, o = al256(o + 4);
+	// (every frame's column context: the global-context variant for frames too wide for LDS, and
+	// the quad chain kernel, whose rows hand over through device memory)
+	L.gctx = o, o = al256(o + nf * sh.max_cols * vp8g::kCtxBytesPerCol);
+	L.mbox = o, o = al256(o + (k_plan > 1 ? nf * k_plan * sh.max_cols * vp8g::kCtxBytesPerCol : 0));
+	L.gprog = o, o = al256(o + (k_plan > 1 ? nf * k_plan * 4 : 0));
+	L.out = o, o = al256(o + sh.outb);
+	L.sdesc = o, o = al256(o + (sk.opts ? nf * sizeof(Vp8gScaleDesc) : 0));
+	L.sout = o, o = al256(o + sh.soutb);
+	L.tdesc = o, o = al256(o + (sk.topt ? nf * sizeof(Vp8gTensorDesc) : 0));
+	L.ares = o, o = al256(o + sh.ab);
+	L.aout = o, o = al256(o + sh.ab);
+	L.asout = o, o = al256(o + sh.asb);
+	L.adesc = o, o = al256(o + (sk.alpha ? nf * sizeof(Vp8gAlphaDesc) : 0));
+	L.asdesc = o, o = al256(o + (sk.alpha ? nf * sizeof(Vp8gScaleDesc) : 0));
+	L.talpha = o, o = al256(o + (sk.alpha ? nf * sizeof(Vp8gTensorAlpha) : 0));
+	L.total = o;
+	return L;
+}
+
+// One chunk on its way through the stages: the positions [a, b) of the feed's order, all of one kind, of which
+// idx are the frames that decode (chunk position j = frame idx[j]), in slot `s` on its stream.
+struct Chunk {
+	bool tok;  // device m05
+	uint32_t a, b;
+	Slot& s;
+	hipStream_t stream;
+	std::vector<uint32_t> idx;
+	ChunkShape sh;
+	uint32_t nw = 0, k_plan = 1;  // launch geometry: waves per frame workgroup; parts per frame, if the gate allows
+	bool big = false;             //   too wide for the LDS column context
+	ChunkLayout L;
+	std::vector<uint32_t> sj;             // chunk position of each scale descriptor
+	std::vector<Vp8gTensorAlpha> aplane;  // per chunk position: where the tensor kernel finds the frame's alpha
+	hipError_t up_err = hipSuccess;
+	// H2D onto the chunk's stream, to an offset of its buffer; after a failure the rest are skipped.  false: up_status
+	bool up(uint64_t off, const void* src, size_t bytes) {
+		if (up_err == hipSuccess) up_err = hipMemcpyAsync(s.buf + off, src, bytes, hipMemcpyHostToDevice, stream);
+		return up_err == hipSuccess;
+	}
+	Status up_status() const { return Status{up_err, "H2D"}; }
+	template <class T>  // ... of a whole descriptor array
+	bool up(uint64_t off, const std::vector<T>& v) { return up(off, v.data(), v.size() * sizeof(T)); }
+};
+
+// One call's resources and the stages its chunks go through; a finished call, a device failure and a C++ exception
+// all leave through the destructor.  Uploads and kernels run on one stream per chunk slot, downloads by the Copiers:
+// chunk k's D2H overlaps chunk k+1's kernels.  Slots 0/1 alternate between device-m05 chunks, 2/3 between host-m05
+// chunks, so a hybrid batch's host chunks never wait for the (long) device-m05 chunk's slot.
+struct Pipeline {
+	const ByteSpan* files = nullptr;
+	uint32_t n = 0;
+	int filtered = 0;
+	Sinks sk;
+	uint32_t chunk_frames[2] = {kChunkFrames, kTokChunkFrames};  // per chunk (at most), by kind like caps.mbs: [tok]
+	MbCaps caps{{kChunkMbs, kTokChunkMbs}};
+	uint32_t window = 0;    // positions the workers may run ahead of the last launched chunk
+	uint32_t released = 0;  // positions whose chunks are launched (all below this one)
+	bool trace = false;     // VP8G_PIPE_TRACE=1: one stderr line per chunk (kind, frames, MBs, launch / retire times; diagnostics)
+	std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
 	Feed feed;
-	feed.files = files;
-	feed.n = n;
-	feed.fflags = ((flags & VP8G_BATCH_MULTI_PARTITION) ? VP8F_MULTI_PARTITION : 0u) | (extended ? VP8F_EXTENDED : 0u);
-	feed.pk.assign(n, Vp8gPackedFrame{});
-	if (tok) feed.tj.assign(n, TokJob{});
-	feed.err.assign(n, 0);
-	feed.alpha = alpha;
-	feed.ares.assign(n, nullptr);
-	feed.afilter.assign(n, 0);
-	feed.ready.reset(new uint8_t[n]());
-	plan_frames(files, n, tok, threads, feed.dev, feed.order, topt == nullptr, extended);
-	// VP8G_PIPE_TRACE=1: one stderr line per chunk (kind, frames, MBs, launch / retire times; diagnostics)
-	const bool trace = getenv("VP8G_PIPE_TRACE") && atoi(getenv("VP8G_PIPE_TRACE")) != 0;
-	const auto t_start = std::chrono::steady_clock::now();
-	auto ms_now = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(); };
-	if (trace) {
-		uint32_t nd = 0;
-		for (uint32_t i = 0; i < n; i++) nd += feed.dev[i];
-		fprintf(stderr, "[pipe] n=%u threads=%u device_frames=%u host_frames=%u chunk_mbs_tok=%llu chunk_mbs_pk=%llu\n", n,
-		        threads, nd, n - nd, (unsigned long long)chunk_mbs_tok, (unsigned long long)chunk_mbs_pk);
-	}
-	const uint32_t chunk_frames = tok ? chunk_frames_tok : chunk_frames_pk;
-	const uint32_t window = 2 * chunk_frames > 4 * threads ? 2 * chunk_frames : 4 * threads;
-	feed.limit = window;
 	std::vector<std::thread> pool;
-	pool.reserve(threads);
-	for (uint32_t t = 0; t < threads; t++) pool.emplace_back([&feed] { feed.work(); });
-
-	// uploads and kernels on one stream per chunk slot (a long device-m05 chunk and the next
-	// chunk's kernels overlap); downloads by the Copiers: chunk k's D2H overlaps chunk k+1's kernels
-	// slots 0/1 alternate between device-m05 chunks, 2/3 between host-m05 chunks, so a hybrid batch's
-	// host chunks never wait for the (long) device-m05 chunk's slot
 	hipStream_t streams[4] = {nullptr, nullptr, nullptr, nullptr};
 	Copier copiers[2];  // downloads of host-m05 chunks / device-m05 chunks
 	Slot slots[4];
 	uint32_t nchunk[2] = {0, 0};  // chunks so far per kind (host, device)
-	uint32_t released = 0;  // positions whose frames' host data is freed (all below this one)
-	const char* where = nullptr;
-	hipError_t he = hipSuccess;
+	std::vector<uint8_t> live;    // frame i has its output (an allocated image; a slot of the tensor)
 	// The host frames of the last chunks are released by the background freer (g_freer) once the
 	// call has its results: freeing them is when glibc trims the heap those frames grew (GBs of packed data,
 	// ~0.3 s at 1024 4K frames), work the caller need not wait for.
 	bool defer_release = false;
 	std::vector<Vp8gPackedFrame> late;
-	auto release = [&](Slot& s) {
+	bool finished = false;  // every chunk retired (set by the caller); else the destructor takes the failure path,
+	Status failure;         //   with the device failure if that is why
+	~Pipeline() {
+		if (!finished) feed.stop();            // workers waiting for their window leave
+		for (std::thread& t : pool) t.join();  // (before the device buffers they feed are freed)
+		for (Copier& c : copiers) c.stop();
+		const hipStream_t all[6] = {streams[0], streams[1], streams[2], streams[3], copiers[0].stream, copiers[1].stream};
+		if (!finished) {
+			for (Vp8gPackedFrame& p : late) vp8f_packed_free(&p);  // (inline: there is no result to hurry back with)
+			late.clear();
+			for (hipStream_t st : all)
+				if (st) (void)hipStreamSynchronize(st);
+			if (!failure.ok()) vp8g::set_error_text(failure.where ? failure.where : "pipeline", failure.he);
+		}
+		for (Slot& s : slots) {
+			if (s.done) (void)hipEventDestroy(s.done);
+			if (s.kdone) (void)hipEventDestroy(s.kdone);
+			if (s.buf) (void)hipFree(s.buf);
+		}
+		for (hipStream_t st : all)
+			if (st) (void)hipStreamDestroy(st);
+		if (trace && finished) fprintf(stderr, "[pipe] buffers freed at %.1f ms\n", ms_now());
+		try {  // (started last: its heap trimming would contend with the device-memory frees above)
+			if (!late.empty()) g_freer.post(std::move(late));
+		} catch (...) {  // (no thread, no memory: `late` is untouched)
+			for (Vp8gPackedFrame& p : late) vp8f_packed_free(&p);
+		}
+		for (size_t i = 0; i < feed.dev.size(); i++) {  // failed frames (the others were freed per chunk)
+			if (!feed.dev[i]) vp8f_packed_free(&feed.pk[i]);
+			free(feed.ares[i]);
+		}
+	}
+	double ms_now() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(); }
+	const Vp8KeyFrameHeader& kf_of(uint32_t i) const { return feed.dev[i] ? feed.tj[i].kf : feed.pk[i].kf; }
+	const Vp8DecodedFrame& f_of(uint32_t i) const { return feed.dev[i] ? feed.tj[i].hdr : feed.pk[i].f; }
+	// scaled decode: the loop filter per frame (VP8G_SCALE_DWEBP_FILTER), the output image at the scaled size
+	int filtered_of(uint32_t i) const {
+		return sk.opts ? vp8f_scale_filtered(kf_of(i).width, kf_of(i).height, sk.opt_of(i), filtered) : filtered;
+	}
+	int alloc_out(uint32_t i, uint32_t w, uint32_t h) {
+		if (sk.opts && vp8g_scaled_size(w, h, sk.opt_of(i), &w, &h) != 0) return -1;
+		if (!sk.topt && vp8g::alloc_planes(&sk.outs[i], w, h, false) != 0) return -1;
+		live[i] = 1;
+		return 0;
+	}
+	// Plans the batch, starts the workers, creates the device objects.  (No constructor: an exception on the way must
+	// leave a complete object, whose destructor joins the threads that did start.)
+	Status start(const ByteSpan* files_, uint32_t n_, int filtered_, uint32_t threads, uint32_t flags, const Sinks& sinks) {
+		files = files_, n = n_, filtered = filtered_, sk = sinks;
+		const bool tok = (flags & VP8G_BATCH_DEVICE_M05) != 0;
+		const long knob = getenv("VP8G_CHUNK_FRAMES") ? atol(getenv("VP8G_CHUNK_FRAMES")) : 0;  // test knob: smaller chunks
+		for (uint32_t& cf : chunk_frames)
+			if (knob > 0 && (uint64_t)knob < cf) cf = (uint32_t)knob;
+		size_t fr = 0, tot = 0;
+		caps = chunk_budget(hipMemGetInfo(&fr, &tot) == hipSuccess ? fr : 0);
+		live.assign(n, 0);
+		if (!threads) threads = default_threads();
+		if (threads > n) threads = n;
+		feed.files = files, feed.n = n;
+		feed.fflags = ((flags & VP8G_BATCH_MULTI_PARTITION) ? VP8F_MULTI_PARTITION : 0u) | (sk.extended ? VP8F_EXTENDED : 0u);
+		feed.pk.assign(n, Vp8gPackedFrame{});
+		if (tok) feed.tj.assign(n, TokJob{});
+		feed.err.assign(n, 0);
+		feed.alpha = sk.alpha;
+		feed.ares = std::vector<uint8_t*>(n, nullptr);
+		feed.afilter.resize(n);
+		feed.ready.reset(new uint8_t[n]());
+		plan_frames(files, n, tok, threads, feed.dev, feed.order, sk.topt == nullptr, sk.extended);
+		trace = getenv("VP8G_PIPE_TRACE") && atoi(getenv("VP8G_PIPE_TRACE")) != 0;
+		if (trace) {
+			uint32_t nd = 0;
+			for (uint32_t i = 0; i < n; i++) nd += feed.dev[i];
+			fprintf(stderr, "[pipe] n=%u threads=%u device_frames=%u host_frames=%u chunk_mbs_tok=%llu chunk_mbs_pk=%llu\n", n,
+			        threads, nd, n - nd, (unsigned long long)caps.mbs[1], (unsigned long long)caps.mbs[0]);
+		}
+		const uint32_t cf = chunk_frames[tok];
+		window = 2 * cf > 4 * threads ? 2 * cf : 4 * threads;
+		feed.limit = window;
+		pool.reserve(threads);
+		for (uint32_t t = 0; t < threads; t++) pool.emplace_back([this] { feed.work(); });
+		// The device-m05 slots' streams (0, 1) at the lowest stream priority, the others at the default:
+		// HIP keeps a pool of hardware queues per priority, so a host-m05 chunk never sits in one hardware
+		// queue behind a device-m05 kernel (~0.5-1.5 s, one frame's serial bool decoding) -- streams
+		// beyond GPU_MAX_HW_QUEUES share queues, and work on a shared queue runs in order.
+		int least = 0, greatest = 0;
+		if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
+		hipError_t e = hipSuccess;
+		for (int i = 0; i < 4 && e == hipSuccess; i++)
+			e = i < 2 ? hipStreamCreateWithPriority(&streams[i], hipStreamNonBlocking, least)
+			          : hipStreamCreateWithFlags(&streams[i], hipStreamNonBlocking);
+		for (Copier& c : copiers) {
+			if (e == hipSuccess) e = hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking);
+			if (e == hipSuccess) c.th = std::thread([&c] { c.run(); });
+		}
+		if (e != hipSuccess) return Status{e, "stream"};
+		for (Slot& s : slots) {
+			if (e == hipSuccess) e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
+			if (e == hipSuccess) e = hipEventCreateWithFlags(&s.kdone, hipEventDisableTiming);
+		}
+		return Status{e, "event"};
+	}
+	void release(Slot& s) {
 		for (uint32_t i : s.frames) {
 			free(feed.ares[i]);
 			feed.ares[i] = nullptr;
+			if (feed.dev[i]) continue;
+			if (defer_release) late.push_back(feed.pk[i]), memset(&feed.pk[i], 0, sizeof(feed.pk[i]));
+			else vp8f_packed_free(&feed.pk[i]);
 		}
-		for (uint32_t i : s.frames)
-			if (!feed.dev[i]) {
-				if (defer_release) {
-					late.push_back(feed.pk[i]);
-					memset(&feed.pk[i], 0, sizeof(feed.pk[i]));
-				} else {
-					vp8f_packed_free(&feed.pk[i]);
-				}
-			}
 		s.frames.clear();
-	};
-	auto kf_of = [&](uint32_t i) -> const Vp8KeyFrameHeader& { return feed.dev[i] ? feed.tj[i].kf : feed.pk[i].kf; };
-	auto f_of = [&](uint32_t i) -> const Vp8DecodedFrame& { return feed.dev[i] ? feed.tj[i].hdr : feed.pk[i].f; };
-	// scaled decode: the loop filter per frame (VP8G_SCALE_DWEBP_FILTER), the output image at the scaled size
-	auto filtered_of = [&](uint32_t i) -> int {
-		return opts ? vp8f_scale_filtered(kf_of(i).width, kf_of(i).height, opt_of(i), filtered) : filtered;
-	};
-	auto alloc_out = [&](uint32_t i, uint32_t w, uint32_t h) -> int {
-		if (opts && vp8g_scaled_size(w, h, opt_of(i), &w, &h) != 0) return -1;
-		if (!topt && vp8g::alloc_planes(&outs[i], w, h, false) != 0) return -1;
-		live[i] = 1;
-		return 0;
-	};
-	auto finish_slot = [&](Slot& s) -> bool {  // wait for a slot's chunk; false on a device failure
-		if (!s.busy) return true;
+	}
+	// Waits for a slot's chunk, if it has one, and frees the chunk's host data.
+	Status finish_slot(Slot& s) {
+		if (!s.busy) return Status{};
 		s.busy = false;
+		const int si = (int)(&s - slots);
 		const double tw = trace ? ms_now() : 0.0;
-		if ((he = copiers[&s - slots < 2 ? 1 : 0].wait_issued(&s)) != hipSuccess) {
-			where = "D2H";
-			return false;
-		}
-		if ((he = hipEventSynchronize(s.done)) != hipSuccess) {
-			where = "sync";
-			return false;
-		}
-		if (trace) fprintf(stderr, "[pipe] slot %d retired at %.1f ms (waited %.1f ms)\n", (int)(&s - slots), ms_now(), ms_now() - tw);
+		if (hipError_t e = copiers[si < 2 ? 1 : 0].wait_issued(&s); e != hipSuccess) return Status{e, "D2H"};
+		if (hipError_t e = hipEventSynchronize(s.done); e != hipSuccess) return Status{e, "sync"};
+		if (trace) fprintf(stderr, "[pipe] slot %d retired at %.1f ms (waited %.1f ms)\n", si, ms_now(), ms_now() - tw);
 		const double tr = trace ? ms_now() : 0.0;
 		release(s);
-		if (trace) fprintf(stderr, "[pipe] slot %d host data freed in %.1f ms\n", (int)(&s - slots), ms_now() - tr);
-		if (s.status != 0) {
-			where = "kernel status";
-			he = hipErrorLaunchFailure;
-			return false;
+		if (trace) fprintf(stderr, "[pipe] slot %d host data freed in %.1f ms\n", si, ms_now() - tr);
+		return s.status != 0 ? Status{hipErrorLaunchFailure, "kernel status"} : Status{};
+	}
+	// The next chunk's frames and shape: consecutive positions of one kind from c.a, in order, as they finish.  A frame
+	// whose options or size do not suit the sinks fails here (feed.err) and stays out of idx; the others still decode.
+	void gather_chunk(Chunk& c) {
+		ChunkShape& sh = c.sh;
+		uint64_t xmbs = 0;  // what the frames hold beyond their MBs' share (extra_mbs)
+		for (; c.b < n && c.b - c.a < chunk_frames[c.tok] && (feed.dev[feed.order[c.b]] != 0) == c.tok; c.b++) {
+			const uint32_t fi = feed.order[c.b];
+			feed.wait_ready(fi);
+			if (feed.err[fi]) continue;
+			const uint32_t w = kf_of(fi).width, h = kf_of(fi).height;
+			uint32_t sw = w, sh_ = h;  // the picture's size at the sink
+			if (sk.opts && vp8g_scaled_size(w, h, sk.opt_of(fi), &sw, &sh_) != 0) feed.err[fi] = EINVAL;  // options that do not fit it
+			else if (sk.topt && (sw != sk.topt->width || sh_ != sk.topt->height)) feed.err[fi] = EINVAL;  // not the tensor's size
+			if (feed.err[fi]) continue;
+			const Vp8DecodedFrame& f = f_of(fi);
+			const uint64_t ownb = vp8g_i420_size(w, h), sclb = sk.opts ? vp8g_i420_size(sw, sh_) : 0;
+			uint64_t fx = sclb > ownb ? extra_mbs(sclb - ownb) : 0u;  // (0 unless VP8G_SCALE_EXPAND grows it)
+			// alpha planes count against the chunk's memory budget: residual + un-predicted (+ scaled)
+			const uint64_t apl = feed.ares[fi] ? (uint64_t)w * h : 0u;
+			const uint64_t aspl = apl && sk.opts ? (uint64_t)sw * sh_ : 0u;
+			fx += extra_mbs(2u * apl + aspl);
+			if (!c.idx.empty() && sh.mbs + xmbs + f.mb_total + fx > caps.mbs[c.tok]) break;
+			xmbs += fx;
+			if (sk.opts) sh.soutb = al256(sh.soutb + sclb);
+			if (apl) sh.ab = al256(sh.ab + apl), sh.asb = al256(sh.asb + aspl);
+			c.idx.push_back(fi);
+			sh.mbs += f.mb_total;
+			if (c.tok) sh.bitsb += bits_slot(feed.tj[fi].psize);
+			else sh.vals += feed.pk[fi].n_values;
+			sh.outb = al256(sh.outb + ownb);
+			if (f.mb_cols > sh.max_cols) sh.max_cols = f.mb_cols;
+			if (f.mb_rows > sh.max_rows) sh.max_rows = f.mb_rows;
 		}
-		return true;
-	};
-
-#define PTRY(expr, w)                \
-	do {                             \
-		if ((he = (expr)) != hipSuccess) { \
-			where = w;               \
-			goto fail;               \
-		}                            \
-	} while (0)
-
-	// The device-m05 slots' streams (0, 1) at the lowest stream priority, the others at the default:
-	// HIP keeps a pool of hardware queues per priority, so a host-m05 chunk never sits in one hardware
-	// queue behind a device-m05 kernel (~0.5-1.5 s, one frame's serial bool decoding) -- streams
-	// beyond GPU_MAX_HW_QUEUES share queues, and work on a shared queue runs in order.
-	{
-		int least = 0, greatest = 0;
-		if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
-		for (int i = 0; i < 4; i++)
-			PTRY(i < 2 ? hipStreamCreateWithPriority(&streams[i], hipStreamNonBlocking, least)
-			           : hipStreamCreateWithFlags(&streams[i], hipStreamNonBlocking),
-			     "stream");
+		sh.nf = (uint32_t)c.idx.size();
 	}
-	for (Copier& c : copiers) {
-		PTRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking), "stream");
-		c.th = std::thread([&c] { c.run(); });
+	// Launch geometry (the choices vp8g_reconstruct_batch makes).  Split mode (a frame over several co-resident workgroups
+	// that spin on each other) only for a call's only chunk: other slots' streams could hold the CUs a part is waiting for.
+	void plan_launch(Chunk& c) const {
+		const bool alone = c.a == 0 && c.b == n;
+		c.nw = vp8g::pick_waves(0, c.sh.max_rows, c.sh.nf);
+		if (alone && vp8g::pick_split(0, c.sh.nf, 8, c.sh.max_rows) > 1) c.nw = 8;
+		c.big = vp8g::lds_bytes((int)c.nw, c.sh.max_cols, false) > (size_t)vp8g::kMaxLds;
+		c.k_plan = c.big || !alone ? 1u : vp8g::pick_split(0, c.sh.nf, c.nw, c.sh.max_rows);
 	}
-	for (Slot& s : slots) {
-		PTRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming), "event");
-		PTRY(hipEventCreateWithFlags(&s.kdone, hipEventDisableTiming), "event");
-	}
-
-	{
-		uint32_t a = 0;
-		while (a < n) {
-			// -- gather the next chunk: consecutive positions of one kind (device m05 or host m05),
-			// in order, as they finish
-			std::vector<uint32_t> idx;
-			uint64_t mbs = 0, vals = 0, bitsb = 0, outb = 0, soutb = 0, ab = 0, asb = 0;
-			uint64_t xmbs = 0;  // expanding frames: scaled bytes beyond the frame's own size, priced in MBs of the chunk budget
-			uint32_t b = a, max_cols = 0, max_rows = 0;
-			const bool ctok = feed.dev[feed.order[a]] != 0;  // this chunk's kind
-			const uint32_t cframes = ctok ? chunk_frames_tok : chunk_frames_pk;
-			const uint64_t cmbs = ctok ? chunk_mbs_tok : chunk_mbs_pk;
-			while (b < n && b - a < cframes && (feed.dev[feed.order[b]] != 0) == ctok) {
-				const uint32_t fi = feed.order[b];
-				feed.wait_ready(fi);
-				uint32_t sw = 0, sh = 0;
-				if (feed.err[fi] == 0 && opts && vp8g_scaled_size(kf_of(fi).width, kf_of(fi).height, opt_of(fi), &sw, &sh) != 0)
-					feed.err[fi] = EINVAL;  // options that do not fit this frame: the others still decode
-				if (feed.err[fi] == 0 && topt &&
-				    ((opts ? sw : (uint32_t)kf_of(fi).width) != topt->width || (opts ? sh : (uint32_t)kf_of(fi).height) != topt->height))
-					feed.err[fi] = EINVAL;  // not the tensor's picture size
-				if (feed.err[fi] == 0) {
-					const Vp8DecodedFrame& f = f_of(fi);
-					const uint64_t ownb = vp8g_i420_size(kf_of(fi).width, kf_of(fi).height), sclb = opts ? vp8g_i420_size(sw, sh) : 0;
-					uint64_t fx = sclb > ownb ? (sclb - ownb + 1535u) / 1536u : 0u;  // (0 unless VP8G_SCALE_EXPAND grows it)
-					// alpha planes count against the chunk's memory budget: residual + un-predicted (+ scaled)
-					const uint64_t apl = feed.ares[fi] ? (uint64_t)kf_of(fi).width * kf_of(fi).height : 0u;
-					const uint64_t aspl = apl && opts ? (uint64_t)sw * sh : 0u;
-					fx += (2u * apl + aspl + 1535u) / 1536u;
-					if (!idx.empty() && mbs + xmbs + f.mb_total + fx > cmbs) break;
-					xmbs += fx;
-					if (opts) soutb = al256(soutb + sclb);
-					if (apl) ab = al256(ab + apl), asb = al256(asb + aspl);
-					idx.push_back(fi);
-					mbs += f.mb_total;
-					if (ctok) bitsb += bits_slot(feed.tj[fi].psize);
-					else vals += feed.pk[fi].n_values;
-					outb = al256(outb + vp8g_i420_size(kf_of(fi).width, kf_of(fi).height));
-					if (f.mb_cols > max_cols) max_cols = f.mb_cols;
-					if (f.mb_rows > max_rows) max_rows = f.mb_rows;
-				}
-				b++;
+	// Frame descriptors and output images, and the chunk's input onto its stream (a device-m05 chunk's payloads and
+	// m05 jobs, a host-m05 one's side arrays, block masks and packed values); then the descriptors and a zero status word.
+	Status upload_chunk(Chunk& c) {
+		Slot& s = c.s;
+		const ChunkLayout& L = c.L;
+		s.descs.assign(c.sh.nf, Vp8gFrameDesc{});
+		if (c.tok) s.jobs.resize(c.sh.nf);
+		uint64_t mo = 0, po = 0, oo = 0;  // offsets in the chunk: MBs, payload (bitstream bytes / packed values), output bytes
+		for (uint32_t j = 0; j < c.sh.nf && c.up_err == hipSuccess; j++) {
+			const uint32_t fi = c.idx[j];
+			const Vp8KeyFrameHeader& kf = kf_of(fi);
+			const uint64_t mt = f_of(fi).mb_total;
+			if (vp8g::make_desc(&kf, &f_of(fi), filtered_of(fi), mo, oo, &s.descs[j], false) != 0 || alloc_out(fi, kf.width, kf.height) != 0) {
+				feed.err[fi] = errno ? errno : EINVAL;  // (cannot happen for a frame the host front end accepted)
+				s.descs[j].flags = 0;
 			}
-			const uint32_t si = (ctok ? 0u : 2u) + (nchunk[ctok ? 1 : 0]++ & 1u);
-			Slot& s = slots[si];
-			hipStream_t stream = streams[si];
-			if (!finish_slot(s)) goto fail;
-			if (idx.empty()) {
-				a = b;
+			if (c.tok) {
+				const TokJob& t = feed.tj[fi];
+				s.jobs[j] = t.tf;
+				s.jobs[j].data = po;
+				s.jobs[j].mb_offset = mo;
+				c.up(L.bits + po, files[fi].data + t.poff, t.psize);
+				po += bits_slot(t.psize);
+			} else {
+				Vp8gPackedFrame& p = feed.pk[fi];
+				for (uint32_t m = 0; po && m < mt; m++) p.mb_off[m] += (uint32_t)po;  // chunk-relative value offsets
+				c.up(L.ym + mo, p.f.ymode, mt);
+				c.up(L.uvm + mo, p.f.uv_mode, mt);
+				c.up(L.seg + mo, p.f.segment_id, mt);
+				c.up(L.hasc + mo, p.f.has_coeff, mt);
+				c.up(L.bm + mo * 16, p.f.bmode, mt * 16);
+				c.up(L.masks + mo * kNb * 2, p.masks, mt * kNb * 2);
+				c.up(L.mboff + mo * 4, p.mb_off, mt * 4);
+				if (p.n_values) c.up(L.vals + po * 2, p.values, p.n_values * 2);
+				po += p.n_values;
+			}
+			mo += mt;
+			oo = al256(oo + vp8g_i420_size(kf.width, kf.height));
+		}
+		if (c.tok) c.up(L.jobs, s.jobs);
+		if (c.up_err != hipSuccess) return c.up_status();
+		s.frames = c.idx;
+		if (trace)
+			fprintf(stderr, "[pipe] chunk %s slot %u frames=%u mbs=%llu launched at %.1f ms\n", c.tok ? "device-m05" : "host-m05",
+			        (uint32_t)(&s - slots), c.sh.nf, (unsigned long long)c.sh.mbs, ms_now());
+		if (!c.up(L.desc, s.descs)) return c.up_status();
+		return Status{hipMemsetAsync(s.buf + L.status, 0, 4, c.stream), "memset"};
+	}
+	// Expansion (or device m05) + recon(+LF), inside the process-wide launch gate (vp8g_device.h): the split mode only
+	// when no other launch of the library is in flight.
+	Status launch_recon(Chunk& c) {
+		const ChunkLayout& L = c.L;
+		const uint32_t nf = c.sh.nf, max_cols = c.sh.max_cols;
+		uint8_t* d = c.s.buf;
+		hipStream_t stream = c.stream;
+		vp8g::GateScope gate(stream);
+		if (gate.status() != hipSuccess) return Status{gate.status(), "hipStreamWaitEvent(gate)"};
+		const uint32_t k = c.k_plan > 1 && gate.may_cross() ? c.k_plan : 1u;
+		if (k > 1)
+			if (hipError_t e = hipMemsetAsync(d + L.gprog, 0, (size_t)nf * k * 4, stream); e != hipSuccess) return Status{e, "memset"};
+		Vp8gBatchArrays arr{(const int16_t*)(d + L.cy), (const int16_t*)(d + L.cu), (const int16_t*)(d + L.cv), (const int16_t*)(d + L.cy2),
+		                    d + L.ym, d + L.uvm, d + L.seg, d + L.hasc, d + L.bm, /*src=*/nullptr, (uint32_t*)(d + L.status)};
+		if (c.tok) {
+			if (hipError_t e = hipMemsetAsync(d + L.cy, 0, L.cy2 + c.sh.mbs * 32 - L.cy, stream); e != hipSuccess) return Status{e, "memset"};
+			const int rc = vp8g_m05_batch_device(c.s.jobs.data(), (const Vp8gTokFrame*)(d + L.jobs), nf, d + L.bits, &arr, stream);
+			if (rc != 0) return capi_status(rc, "m05 launch");
+		} else {
+			const uint64_t threads_x = c.sh.mbs * 32;
+			hipLaunchKernelGGL(expand_kernel, dim3((uint32_t)((threads_x + 255) / 256)), dim3(256), 0, stream,
+			                   (const uint16_t*)(d + L.masks), (const uint32_t*)(d + L.mboff), (const int16_t*)(d + L.vals),
+			                   (uint32_t)c.sh.mbs, (int16_t*)(d + L.cy), (int16_t*)(d + L.cu), (int16_t*)(d + L.cv), (int16_t*)(d + L.cy2));
+			if (hipError_t e = hipGetLastError(); e != hipSuccess) return Status{e, "expand launch"};
+		}
+		bool ordered = false;
+		const uint32_t wg = c.big || k > 1 ? 0u : vp8g::pick_chain(c.s.descs.data(), nf, max_cols, &ordered);
+		const hipError_t e =
+		    wg  // more frames than CUs: one 16-wave chain of frames per CU
+		        ? vp8g::launch_chain((const Vp8gFrameDesc*)(d + L.desc), nf, arr, d + L.out, max_cols, stream, wg, ordered,
+		                             vp8g::whole_pieces(c.s.descs.data(), nf), d + L.gctx)
+		        : vp8g::launch_frames((const Vp8gFrameDesc*)(d + L.desc), nf, arr, d + L.out, max_cols, c.sh.max_rows,
+		                              c.big ? d + L.gctx : nullptr, stream, c.nw, k, k > 1 ? d + L.mbox : nullptr,
+		                              k > 1 ? (uint32_t*)(d + L.gprog) : nullptr);
+		if (e != hipSuccess) return Status{e, "recon launch"};
+		return Status{gate.done(k > 1), "hipEventRecord(gate)"};
+	}
+	// A batch of scale descriptors (the frames', the alpha planes') to `off` of the chunk's buffer and through the rescaler.
+	Status scale_batch(Chunk& c, const std::vector<Vp8gScaleDesc>& v, uint64_t off, const char* where) {
+		if (v.empty()) return Status{};
+		if (!c.up(off, v)) return c.up_status();
+		uint8_t* d = c.s.buf;
+		return capi_status(vp8g_scale_batch_device(v.data(), (const Vp8gScaleDesc*)(d + off), (uint32_t)v.size(), d, d, c.stream), where);
+	}
+	// Scaled decode: crop / rescale the chunk's frames into the small buffer (same stream).
+	Status launch_scale(Chunk& c) {
+		Slot& s = c.s;
+		s.sdescs.clear();
+		uint64_t so = 0;
+		uint32_t task0 = 0;
+		for (uint32_t j = 0; sk.opts && j < c.sh.nf; j++) {
+			const Vp8gFrameDesc& fd = s.descs[j];
+			if (!live[c.idx[j]]) continue;  // (a frame that failed above)
+			Vp8gScaleDesc sd;
+			if (vp8g_make_scale_desc(fd.width, fd.height, c.L.out + fd.out_y, c.L.out + fd.out_u, c.L.out + fd.out_v, fd.stride_y,
+			                         fd.stride_uv, sk.opt_of(c.idx[j]), c.L.sout + so, task0, &sd) != 0) {
+				feed.err[c.idx[j]] = EINVAL;  // (cannot happen: the options were resolved when the chunk was gathered)
 				continue;
 			}
-			const uint32_t nf = (uint32_t)idx.size();
-			// -- launch geometry (the choices vp8g_reconstruct_batch makes)
-			// Split mode (a frame over several co-resident workgroups that spin on each other) only
-			// for a chunk that is the call's only one: chunks on the other slots' streams -- a long
-			// device-m05 kernel, the other host slot -- could hold the CUs a part is waiting for.
-			const bool alone = a == 0 && b == n;
-			uint32_t nw = vp8g::pick_waves(0, max_rows, nf);
-			if (alone && vp8g::pick_split(0, nf, 8, max_rows) > 1) nw = 8;
-			const bool big = vp8g::lds_bytes((int)nw, max_cols, false) > (size_t)vp8g::kMaxLds;
-			const uint32_t k_plan = big || !alone ? 1u : vp8g::pick_split(0, nf, nw, max_rows);
-			ChunkLayout L;
-			uint64_t o = 0;
-			L.ym = o, o = al256(o + mbs);
-			L.uvm = o, o = al256(o + mbs);
-			L.seg = o, o = al256(o + mbs);
-			L.hasc = o, o = al256(o + mbs);
-			L.bm = o, o = al256(o + mbs * 16);
-			L.masks = o, o = al256(o + (ctok ? 0 : mbs * kNb * 2));
-			L.mboff = o, o = al256(o + (ctok ? 0 : mbs * 4));
-			L.vals = o, o = al256(o + (ctok ? 0 : vals * 2 + 64));  // +64: the expansion may address one past the end
-			L.cy = o, o = al256(o + mbs * 512);
-			L.cu = o, o = al256(o + mbs * 128);
-			L.cv = o, o = al256(o + mbs * 128);
-			L.cy2 = o, o = al256(o + mbs * 32);
-			L.bits = o, o = al256(o + bitsb);
-			L.jobs = o, o = al256(o + (ctok ? nf * sizeof(Vp8gTokFrame) : 0));
-			L.desc = o, o = al256(o + nf * sizeof(Vp8gFrameDesc));
-			L.status = o, o = al256(o + 4);
-			// (every frame's column context: the global-context variant for frames too wide for LDS, and
-			// the quad chain kernel, whose rows hand over through device memory)
-			L.gctx = o, o = al256(o + (uint64_t)nf * max_cols * vp8g::kCtxBytesPerCol);
-			L.mbox = o, o = al256(o + (k_plan > 1 ? (uint64_t)nf * k_plan * max_cols * vp8g::kCtxBytesPerCol : 0));
-			L.gprog = o, o = al256(o + (k_plan > 1 ? (uint64_t)nf * k_plan * 4 : 0));
-			L.out = o, o = al256(o + outb);
-			L.sdesc = o, o = al256(o + (opts ? nf * sizeof(Vp8gScaleDesc) : 0));
-			L.sout = o, o = al256(o + soutb);
-			L.tdesc = o, o = al256(o + (topt ? nf * sizeof(Vp8gTensorDesc) : 0));
-			L.ares = o, o = al256(o + ab);
-			L.aout = o, o = al256(o + ab);
-			L.asout = o, o = al256(o + asb);
-			L.adesc = o, o = al256(o + (alpha ? nf * sizeof(Vp8gAlphaDesc) : 0));
-			L.asdesc = o, o = al256(o + (alpha ? nf * sizeof(Vp8gScaleDesc) : 0));
-			L.talpha = o, o = al256(o + (alpha ? nf * sizeof(Vp8gTensorAlpha) : 0));
-			L.total = o;
-			const double tg = trace ? ms_now() : 0.0;
-			PTRY(grow(s, L.total), "hipMalloc(chunk)");
-			if (trace) fprintf(stderr, "[pipe] slot %u buffer %.1f GB ready at %.1f ms (%.1f ms)\n", si, L.total / 1e9, ms_now(), ms_now() - tg);
-			uint8_t* d = s.buf;
-			// -- descriptors and output images
-			s.descs.assign(nf, Vp8gFrameDesc{});
-			if (ctok) {
-				s.jobs.resize(nf);
-				uint64_t mo = 0, bo = 0, oo = 0;
-				for (uint32_t j = 0; j < nf; j++) {
-					TokJob& t = feed.tj[idx[j]];
-					if (vp8g::make_desc(&t.kf, &t.hdr, filtered_of(idx[j]), mo, oo, &s.descs[j], false) != 0 ||
-					    alloc_out(idx[j], t.kf.width, t.kf.height) != 0) {
-						feed.err[idx[j]] = errno ? errno : EINVAL;  // (cannot happen for a frame the header parse accepted)
-						s.descs[j].flags = 0;
-					}
-					s.jobs[j] = t.tf;
-					s.jobs[j].data = bo;
-					s.jobs[j].mb_offset = mo;
-					PTRY(hipMemcpyAsync(d + L.bits + bo, files[idx[j]].data + t.poff, t.psize, hipMemcpyHostToDevice, stream),
-					     "H2D");
-					mo += t.hdr.mb_total;
-					bo += bits_slot(t.psize);
-					oo = al256(oo + vp8g_i420_size(t.kf.width, t.kf.height));
-				}
-				PTRY(hipMemcpyAsync(d + L.jobs, s.jobs.data(), nf * sizeof(Vp8gTokFrame), hipMemcpyHostToDevice, stream), "H2D");
-			} else {
-				uint64_t mo = 0, vo = 0, oo = 0;
-				for (uint32_t j = 0; j < nf; j++) {
-					Vp8gPackedFrame& p = feed.pk[idx[j]];
-					if (vp8g::make_desc(&p.kf, &p.f, filtered_of(idx[j]), mo, oo, &s.descs[j], false) != 0 ||
-					    alloc_out(idx[j], p.kf.width, p.kf.height) != 0) {
-						feed.err[idx[j]] = errno ? errno : EINVAL;  // (cannot happen for a frame m05 accepted)
-						s.descs[j].flags = 0;
-					}
-					// chunk-relative value offsets
-					if (vo)
-						for (uint32_t m = 0; m < p.f.mb_total; m++) p.mb_off[m] += (uint32_t)vo;
-					const uint64_t mt = p.f.mb_total;
-					PTRY(hipMemcpyAsync(d + L.ym + mo, p.f.ymode, mt, hipMemcpyHostToDevice, stream), "H2D");
-					PTRY(hipMemcpyAsync(d + L.uvm + mo, p.f.uv_mode, mt, hipMemcpyHostToDevice, stream), "H2D");
-					PTRY(hipMemcpyAsync(d + L.seg + mo, p.f.segment_id, mt, hipMemcpyHostToDevice, stream), "H2D");
-					PTRY(hipMemcpyAsync(d + L.hasc + mo, p.f.has_coeff, mt, hipMemcpyHostToDevice, stream), "H2D");
-					PTRY(hipMemcpyAsync(d + L.bm + mo * 16, p.f.bmode, mt * 16, hipMemcpyHostToDevice, stream), "H2D");
-					PTRY(hipMemcpyAsync(d + L.masks + mo * kNb * 2, p.masks, mt * kNb * 2, hipMemcpyHostToDevice, stream), "H2D");
-					PTRY(hipMemcpyAsync(d + L.mboff + mo * 4, p.mb_off, mt * 4, hipMemcpyHostToDevice, stream), "H2D");
-					if (p.n_values)
-						PTRY(hipMemcpyAsync(d + L.vals + vo * 2, p.values, p.n_values * 2, hipMemcpyHostToDevice, stream), "H2D");
-					mo += mt;
-					vo += p.n_values;
-					oo = al256(oo + vp8g_i420_size(p.kf.width, p.kf.height));
-				}
+			s.sdescs.push_back(sd);
+			c.sj.push_back(j);
+			task0 += sd.ntasks;
+			so = al256(so + vp8g_i420_size(sd.width, sd.height));
+		}
+		return scale_batch(c, s.sdescs, c.L.sdesc, "scale launch");
+	}
+	// Alpha sink: the residual planes of the chunk's frames that have one are uploaded, un-predicted (vp8g_alpha.hip) and,
+	// with opts, cropped / rescaled as luma (same stream); c.aplane = where each frame's alpha ends up (opaque if none).
+	Status launch_alpha(Chunk& c) {
+		Slot& s = c.s;
+		const ChunkLayout& L = c.L;
+		uint8_t* d = s.buf;
+		s.adescs.clear();
+		s.asdescs.clear();
+		c.aplane.assign(c.sh.nf, Vp8gTensorAlpha{VP8G_T_OPAQUE, 0, 0});
+		uint64_t ao = 0, aso = 0;
+		uint32_t atask = 0;
+		for (uint32_t j = 0; sk.alpha && j < c.sh.nf && c.up_err == hipSuccess; j++) {
+			const uint32_t fi = c.idx[j];
+			if (!feed.ares[fi] || !live[fi]) continue;
+			const uint32_t w = kf_of(fi).width, h = kf_of(fi).height;
+			Vp8gAlphaDesc ad;
+			if (vp8g_make_alpha_desc(w, h, feed.afilter[fi], L.ares + ao, w, L.aout + ao, w, (uint32_t)s.adescs.size(), &ad) != 0) {
+				feed.err[fi] = EINVAL;  // (cannot happen: the decoder returns filters 0..3 for sizes it accepted)
+				continue;
 			}
-			s.frames = idx;
-			if (trace)
-				fprintf(stderr, "[pipe] chunk %s slot %u frames=%u mbs=%llu launched at %.1f ms\n", ctok ? "device-m05" : "host-m05", si,
-				        nf, (unsigned long long)mbs, ms_now());
-			PTRY(hipMemcpyAsync(d + L.desc, s.descs.data(), nf * sizeof(Vp8gFrameDesc), hipMemcpyHostToDevice, stream), "H2D");
-			PTRY(hipMemsetAsync(d + L.status, 0, 4, stream), "memset");
-			// -- expansion (or device m05) + recon(+LF), inside the process-wide launch gate
-			// (vp8g_device.h): the split mode only when no other launch of the library is in flight
-			{
-				vp8g::GateScope gate(stream);
-				PTRY(gate.status(), "hipStreamWaitEvent(gate)");
-				const uint32_t k = k_plan > 1 && gate.may_cross() ? k_plan : 1u;
-				if (k > 1) PTRY(hipMemsetAsync(d + L.gprog, 0, (size_t)nf * k * 4, stream), "memset");
-				Vp8gBatchArrays arr;
-				arr.coeff_y = (const int16_t*)(d + L.cy);
-				arr.coeff_u = (const int16_t*)(d + L.cu);
-				arr.coeff_v = (const int16_t*)(d + L.cv);
-				arr.coeff_y2 = (const int16_t*)(d + L.cy2);
-				arr.ymode = d + L.ym;
-				arr.uv_mode = d + L.uvm;
-				arr.segment_id = d + L.seg;
-				arr.has_coeff = d + L.hasc;
-				arr.bmode = d + L.bm;
-				arr.src = nullptr;
-				arr.status = (uint32_t*)(d + L.status);
-				if (ctok) {
-					PTRY(hipMemsetAsync(d + L.cy, 0, L.cy2 + mbs * 32 - L.cy, stream), "memset");
-					if (vp8g_m05_batch_device(s.jobs.data(), (const Vp8gTokFrame*)(d + L.jobs), nf, d + L.bits, &arr, stream) != 0) {
-						he = hipGetLastError();
-						if (he == hipSuccess) he = hipErrorInvalidValue;
-						where = "m05 launch";
-						goto fail;
-					}
-				} else {
-					const uint64_t threads_x = mbs * 32;
-					hipLaunchKernelGGL(expand_kernel, dim3((uint32_t)((threads_x + 255) / 256)), dim3(256), 0, stream,
-					                   (const uint16_t*)(d + L.masks), (const uint32_t*)(d + L.mboff),
-					                   (const int16_t*)(d + L.vals), (uint32_t)mbs, (int16_t*)(d + L.cy), (int16_t*)(d + L.cu),
-					                   (int16_t*)(d + L.cv), (int16_t*)(d + L.cy2));
-					PTRY(hipGetLastError(), "expand launch");
+			c.up(L.ares + ao, feed.ares[fi], (size_t)w * h);
+			c.aplane[j] = Vp8gTensorAlpha{L.aout + ao, w, 0};
+			if (sk.opts) {
+				Vp8gScaleDesc sd;
+				if (vp8g_make_scale_desc_plane(w, h, L.aout + ao, w, sk.opt_of(fi), L.asout + aso, atask, &sd) != 0) {
+					feed.err[fi] = EINVAL;  // (cannot happen: the options were resolved when the chunk was gathered)
+					continue;
 				}
-				bool ordered = false;
-				const uint32_t wg = big || k > 1 ? 0u : vp8g::pick_chain(s.descs.data(), nf, max_cols, &ordered);
-				if (wg)  // more frames than CUs: one 16-wave chain of frames per CU
-					PTRY(vp8g::launch_chain((const Vp8gFrameDesc*)(d + L.desc), nf, arr, d + L.out, max_cols, stream, wg, ordered,
-					                        vp8g::whole_pieces(s.descs.data(), nf), d + L.gctx),
-					     "recon launch");
-				else
-					PTRY(vp8g::launch_frames((const Vp8gFrameDesc*)(d + L.desc), nf, arr, d + L.out, max_cols, max_rows,
-					                         big ? d + L.gctx : nullptr, stream, nw, k, k > 1 ? d + L.mbox : nullptr,
-					                         k > 1 ? (uint32_t*)(d + L.gprog) : nullptr),
-					     "recon launch");
-				PTRY(gate.done(k > 1), "hipEventRecord(gate)");
+				s.asdescs.push_back(sd);
+				atask += sd.ntasks;
+				c.aplane[j] = Vp8gTensorAlpha{L.asout + aso, sd.width, 0};
+				aso = al256(aso + (uint64_t)sd.width * sd.height);
 			}
-			// -- scaled decode: crop / downscale the chunk's frames into the small buffer (same stream)
-			s.sdescs.clear();
-			std::vector<uint32_t> sj;  // chunk position of each scale descriptor
-			if (opts) {
-				uint64_t so = 0;
-				uint32_t task0 = 0;
-				for (uint32_t j = 0; j < nf; j++) {
-					const Vp8gFrameDesc& fd = s.descs[j];
-					if (!live[idx[j]]) continue;  // (a frame that failed above)
-					Vp8gScaleDesc sd;
-					if (vp8g_make_scale_desc(fd.width, fd.height, L.out + fd.out_y, L.out + fd.out_u, L.out + fd.out_v, fd.stride_y,
-					                         fd.stride_uv, opt_of(idx[j]), L.sout + so, task0, &sd) != 0) {
-						feed.err[idx[j]] = EINVAL;  // (cannot happen: the options were resolved when the chunk was gathered)
-						continue;
-					}
-					s.sdescs.push_back(sd);
-					sj.push_back(j);
-					task0 += sd.ntasks;
-					so = al256(so + vp8g_i420_size(sd.width, sd.height));
-				}
-				if (!s.sdescs.empty()) {
-					PTRY(hipMemcpyAsync(d + L.sdesc, s.sdescs.data(), s.sdescs.size() * sizeof(Vp8gScaleDesc), hipMemcpyHostToDevice,
-					                    stream),
-					     "H2D");
-					if (vp8g_scale_batch_device(s.sdescs.data(), (const Vp8gScaleDesc*)(d + L.sdesc), (uint32_t)s.sdescs.size(), d, d,
-					                            stream) != 0) {
-						he = hipGetLastError();
-						if (he == hipSuccess) he = hipErrorInvalidValue;
-						where = "scale launch";
-						goto fail;
-					}
-				}
-			}
-			// -- alpha sink: the residual planes of the chunk's frames that have one are uploaded, un-predicted
-			// (vp8g_alpha.hip) and, with opts, cropped / rescaled as luma, all on the chunk's stream;
-			// aplane[chunk position] = where the tensor kernel finds the frame's alpha (opaque if none)
-			s.adescs.clear();
-			s.asdescs.clear();
-			std::vector<Vp8gTensorAlpha> aplane(nf, Vp8gTensorAlpha{VP8G_T_OPAQUE, 0, 0});
-			if (alpha) {
-				uint64_t ao = 0, aso = 0;
-				uint32_t atask = 0;
-				std::vector<uint32_t> aj;
-				for (uint32_t j = 0; j < nf; j++) {
-					const uint32_t fi = idx[j];
-					if (!feed.ares[fi] || !live[fi]) continue;
-					const uint32_t w = kf_of(fi).width, h = kf_of(fi).height;
-					Vp8gAlphaDesc ad;
-					if (vp8g_make_alpha_desc(w, h, feed.afilter[fi], L.ares + ao, w, L.aout + ao, w, (uint32_t)s.adescs.size(), &ad) != 0) {
-						feed.err[fi] = EINVAL;  // (cannot happen: the decoder returns filters 0..3 for sizes it accepted)
-						continue;
-					}
-					PTRY(hipMemcpyAsync(d + L.ares + ao, feed.ares[fi], (size_t)w * h, hipMemcpyHostToDevice, stream), "H2D");
-					aplane[j] = Vp8gTensorAlpha{L.aout + ao, w, 0};
-					if (opts) {
-						Vp8gScaleDesc sd;
-						if (vp8g_make_scale_desc_plane(w, h, L.aout + ao, w, opt_of(fi), L.asout + aso, atask, &sd) != 0) {
-							feed.err[fi] = EINVAL;  // (cannot happen: the options were resolved when the chunk was gathered)
-							continue;
-						}
-						s.asdescs.push_back(sd);
-						atask += sd.ntasks;
-						aplane[j] = Vp8gTensorAlpha{L.asout + aso, sd.width, 0};
-						aso = al256(aso + (uint64_t)sd.width * sd.height);
-					}
-					s.adescs.push_back(ad);
-					ao = al256(ao + (uint64_t)w * h);
-				}
-				if (!s.adescs.empty()) {
-					PTRY(hipMemcpyAsync(d + L.adesc, s.adescs.data(), s.adescs.size() * sizeof(Vp8gAlphaDesc), hipMemcpyHostToDevice, stream),
-					     "H2D");
-					if (vp8g_alpha_unfilter_batch_device(s.adescs.data(), (const Vp8gAlphaDesc*)(d + L.adesc), (uint32_t)s.adescs.size(), d, d,
-					                                     stream) != 0) {
-						he = hipGetLastError();
-						if (he == hipSuccess) he = hipErrorInvalidValue;
-						where = "alpha launch";
-						goto fail;
-					}
-				}
-				if (!s.asdescs.empty()) {
-					PTRY(hipMemcpyAsync(d + L.asdesc, s.asdescs.data(), s.asdescs.size() * sizeof(Vp8gScaleDesc), hipMemcpyHostToDevice,
-					                    stream),
-					     "H2D");
-					if (vp8g_scale_batch_device(s.asdescs.data(), (const Vp8gScaleDesc*)(d + L.asdesc), (uint32_t)s.asdescs.size(), d, d,
-					                            stream) != 0) {
-						he = hipGetLastError();
-						if (he == hipSuccess) he = hipErrorInvalidValue;
-						where = "alpha scale launch";
-						goto fail;
-					}
-				}
-			}
-			// -- tensor sink: the chunk's frames (scaled or as reconstructed) into their slots of the
-			// caller's tensor (same stream; nothing but the status word comes back)
-			s.tdescs.clear();
-			s.talpha.clear();
-			if (topt) {
-				auto add = [&](uint32_t j, uint64_t y, uint64_t u, uint64_t v, uint32_t sy, uint32_t suv) {
-					const uint32_t fi = idx[j];
-					if (feed.err[fi]) return;  // (a frame whose alpha stage failed above)
-					Vp8gTensorDesc td;
-					if (vp8g_make_tensor_desc(topt, y, u, v, sy, suv, (uint64_t)fi * tslot, 0, &td) != 0) {
-						feed.err[fi] = EINVAL;  // (cannot happen: the size was checked when the chunk was gathered)
-						return;
-					}
-					td.task0 = (uint32_t)s.tdescs.size() * td.ntasks;  // (every image of a tensor has the same task count)
-					s.tdescs.push_back(td);
-					s.talpha.push_back(aplane[j]);
-				};
-				if (opts) {
-					for (size_t q = 0; q < s.sdescs.size(); q++) {
-						const Vp8gScaleDesc& sd = s.sdescs[q];
-						add(sj[q], sd.p[0].dst, sd.p[1].dst, sd.p[2].dst, sd.p[0].dst_stride, sd.p[1].dst_stride);
-					}
-				} else {
-					for (uint32_t j = 0; j < nf; j++) {
-						const Vp8gFrameDesc& fd = s.descs[j];
-						if (live[idx[j]]) add(j, L.out + fd.out_y, L.out + fd.out_u, L.out + fd.out_v, fd.stride_y, fd.stride_uv);
-					}
-				}
-				if (!s.tdescs.empty()) {
-					PTRY(hipMemcpyAsync(d + L.tdesc, s.tdescs.data(), s.tdescs.size() * sizeof(Vp8gTensorDesc), hipMemcpyHostToDevice,
-					                    stream),
-					     "H2D");
-					if (alpha)
-						PTRY(hipMemcpyAsync(d + L.talpha, s.talpha.data(), s.talpha.size() * sizeof(Vp8gTensorAlpha), hipMemcpyHostToDevice,
-						                    stream),
-						     "H2D");
-					if ((alpha ? vp8g_tensor_batch_device_a(s.tdescs.data(), (const Vp8gTensorDesc*)(d + L.tdesc), s.talpha.data(),
-					                                        (const Vp8gTensorAlpha*)(d + L.talpha), (uint32_t)s.tdescs.size(), topt, d,
-					                                        d_tensor, stream)
-					           : vp8g_tensor_batch_device(s.tdescs.data(), (const Vp8gTensorDesc*)(d + L.tdesc), (uint32_t)s.tdescs.size(),
-					                                      topt, d, d_tensor, stream)) != 0) {
-						he = hipGetLastError();
-						if (he == hipSuccess) he = hipErrorInvalidValue;
-						where = "tensor launch";
-						goto fail;
-					}
-				}
-			}
-			PTRY(hipEventRecord(s.kdone, stream), "event");
-			// -- D2H into the callers' images, by this kind's Copier once the kernels are done
-			s.d2h.clear();
-			for (size_t q = 0; q < s.sdescs.size() && !topt; q++) {
-				const Vp8gScaleDesc& sd = s.sdescs[q];
-				Yuv420Image& img = outs[idx[sj[q]]];
-				const size_t ysz = (size_t)sd.width * sd.height, uvsz = (size_t)sd.p[1].dst_w * sd.p[1].dst_h;
-				s.d2h.push_back({img.y, d + sd.p[0].dst, ysz});
-				s.d2h.push_back({img.u, d + sd.p[1].dst, uvsz});
-				s.d2h.push_back({img.v, d + sd.p[2].dst, uvsz});
-			}
-			for (uint32_t j = 0; j < nf && !opts && !topt; j++) {
-				const Vp8gFrameDesc& fd = s.descs[j];
-				Yuv420Image& img = outs[idx[j]];
-				if (!img.y) continue;
-				const size_t ysz = (size_t)fd.stride_y * fd.height, uvsz = (size_t)fd.stride_uv * ((fd.height + 1) / 2);
-				s.d2h.push_back({img.y, d + L.out + fd.out_y, ysz});
-				s.d2h.push_back({img.u, d + L.out + fd.out_u, uvsz});
-				s.d2h.push_back({img.v, d + L.out + fd.out_v, uvsz});
-			}
-			s.d2h.push_back({&s.status, d + L.status, 4});
-			copiers[ctok ? 1 : 0].push(&s);
-			s.busy = true;
-			released = b;
-			feed.set_limit(released + window);
-			a = b;
+			s.adescs.push_back(ad);
+			ao = al256(ao + (uint64_t)w * h);
+		}
+		if (s.adescs.empty() || !c.up(L.adesc, s.adescs)) return c.up_status();  // (no plane: no scale descriptor either)
+		const int rc = vp8g_alpha_unfilter_batch_device(s.adescs.data(), (const Vp8gAlphaDesc*)(d + L.adesc), (uint32_t)s.adescs.size(), d, d,
+		                                                c.stream);
+		if (rc != 0) return capi_status(rc, "alpha launch");
+		return scale_batch(c, s.asdescs, L.asdesc, "alpha scale launch");
+	}
+	// One frame of the chunk (position j, its planes at offsets of the chunk's buffer) into its slot of the tensor.
+	void add_tensor_desc(Chunk& c, uint32_t j, uint64_t y, uint64_t u, uint64_t v, uint32_t sy, uint32_t suv) {
+		const uint32_t fi = c.idx[j];
+		if (feed.err[fi]) return;  // (a frame whose alpha stage failed above)
+		Vp8gTensorDesc td;
+		if (vp8g_make_tensor_desc(sk.topt, y, u, v, sy, suv, (uint64_t)fi * sk.tslot, 0, &td) != 0) {
+			feed.err[fi] = EINVAL;  // (cannot happen: the size was checked when the chunk was gathered)
+			return;
+		}
+		td.task0 = (uint32_t)c.s.tdescs.size() * td.ntasks;  // (every image of a tensor has the same task count)
+		c.s.tdescs.push_back(td);
+		c.s.talpha.push_back(c.aplane[j]);
+	}
+	// Tensor sink: the chunk's frames (scaled or as reconstructed) into their slots of the caller's tensor (same stream).
+	Status launch_tensor(Chunk& c) {
+		Slot& s = c.s;
+		const ChunkLayout& L = c.L;
+		uint8_t* d = s.buf;
+		s.tdescs.clear();
+		s.talpha.clear();
+		for (size_t q = 0; sk.topt && sk.opts && q < s.sdescs.size(); q++) {
+			const Vp8gScaleDesc& sd = s.sdescs[q];
+			add_tensor_desc(c, c.sj[q], sd.p[0].dst, sd.p[1].dst, sd.p[2].dst, sd.p[0].dst_stride, sd.p[1].dst_stride);
+		}
+		for (uint32_t j = 0; sk.topt && !sk.opts && j < c.sh.nf; j++) {
+			const Vp8gFrameDesc& fd = s.descs[j];
+			if (live[c.idx[j]]) add_tensor_desc(c, j, L.out + fd.out_y, L.out + fd.out_u, L.out + fd.out_v, fd.stride_y, fd.stride_uv);
+		}
+		if (s.tdescs.empty()) return Status{};
+		const uint32_t nt = (uint32_t)s.tdescs.size();
+		if (!c.up(L.tdesc, s.tdescs) || (sk.alpha && !c.up(L.talpha, s.talpha))) return c.up_status();
+		return capi_status(sk.alpha ? vp8g_tensor_batch_device_a(s.tdescs.data(), (const Vp8gTensorDesc*)(d + L.tdesc), s.talpha.data(),
+		                                                         (const Vp8gTensorAlpha*)(d + L.talpha), nt, sk.topt, d, sk.d_tensor, c.stream)
+		                            : vp8g_tensor_batch_device(s.tdescs.data(), (const Vp8gTensorDesc*)(d + L.tdesc), nt, sk.topt, d,
+		                                                       sk.d_tensor, c.stream),
+		                   "tensor launch");
+	}
+	// D2H into the callers' images (and of the status word, whatever the sink), by this kind's Copier once the
+	// kernels are done; then the workers may run a window ahead of this chunk.
+	void queue_downloads(Chunk& c) {
+		Slot& s = c.s;
+		uint8_t* d = s.buf;
+		s.d2h.clear();
+		for (size_t q = 0; q < s.sdescs.size() && !sk.topt; q++) {
+			const Vp8gScaleDesc& sd = s.sdescs[q];
+			Yuv420Image& img = sk.outs[c.idx[c.sj[q]]];
+			const size_t ysz = (size_t)sd.width * sd.height, uvsz = (size_t)sd.p[1].dst_w * sd.p[1].dst_h;
+			s.d2h.insert(s.d2h.end(), {{img.y, d + sd.p[0].dst, ysz}, {img.u, d + sd.p[1].dst, uvsz}, {img.v, d + sd.p[2].dst, uvsz}});
+		}
+		for (uint32_t j = 0; j < c.sh.nf && !sk.opts && !sk.topt; j++) {
+			const Vp8gFrameDesc& fd = s.descs[j];
+			Yuv420Image& img = sk.outs[c.idx[j]];
+			if (!img.y) continue;
+			const uint8_t* o = d + c.L.out;
+			const size_t ysz = (size_t)fd.stride_y * fd.height, uvsz = (size_t)fd.stride_uv * ((fd.height + 1) / 2);
+			s.d2h.insert(s.d2h.end(), {{img.y, o + fd.out_y, ysz}, {img.u, o + fd.out_u, uvsz}, {img.v, o + fd.out_v, uvsz}});
+		}
+		s.d2h.push_back({&s.status, d + c.L.status, 4});
+		copiers[c.tok ? 1 : 0].push(&s);
+		s.busy = true;
+		released = c.b;
+		feed.set_limit(released + window);
+	}
+	// A gathered chunk (with at least one frame) through its slot's buffer and stream, every stage in enqueue order.
+	Status launch_chunk(Chunk& c) {
+		plan_launch(c);
+		c.L = make_layout(c.sh, c.tok, sk, c.k_plan);
+		const double tg = trace ? ms_now() : 0.0;
+		if (hipError_t e = grow(c.s, c.L.total); e != hipSuccess) return Status{e, "hipMalloc(chunk)"};
+		const uint32_t si = (uint32_t)(&c.s - slots);
+		if (trace) fprintf(stderr, "[pipe] slot %u buffer %.1f GB ready at %.1f ms (%.1f ms)\n", si, c.L.total / 1e9, ms_now(), ms_now() - tg);
+		Status st = upload_chunk(c);
+		if (st.ok()) st = launch_recon(c);
+		// (the scale, alpha and tensor entry points take the launch gate themselves: outside launch_recon's scope)
+		if (st.ok()) st = launch_scale(c);
+		if (st.ok()) st = launch_alpha(c);
+		if (st.ok()) st = launch_tensor(c);
+		if (st.ok()) st = Status{hipEventRecord(c.s.kdone, c.stream), "event"};
+		if (st.ok()) queue_downloads(c);
+		return st;
+	}
+	// Every chunk of the batch, then the slots' last chunks.
+	Status run() {
+		for (uint32_t a = 0; a < n;) {
+			const bool tok = feed.dev[feed.order[a]] != 0;  // this chunk's kind
+			const uint32_t si = (tok ? 0u : 2u) + (nchunk[tok ? 1 : 0]++ & 1u);
+			Chunk c{tok, a, a, slots[si], streams[si]};
+			gather_chunk(c);
+			if (Status st = finish_slot(c.s); !st.ok()) return st;
+			if (!c.idx.empty())  // (else every frame of it failed)
+				if (Status st = launch_chunk(c); !st.ok()) return st;
+			a = c.b;
 		}
 		defer_release = true;
 		for (Slot& s : slots)
-			if (!finish_slot(s)) goto fail;
+			if (Status st = finish_slot(s); !st.ok()) return st;
 		defer_release = false;
-		if (topt) {  // tensor sink: the slot of every failed frame reads as zero bytes
-			bool any = false;
-			for (uint32_t i = 0; i < n; i++)
-				if (feed.err[i]) {
-					PTRY(hipMemsetAsync(d_tensor + (uint64_t)i * tslot, 0, tslot, streams[2]), "memset");
-					any = true;
-				}
-			if (any) PTRY(hipStreamSynchronize(streams[2]), "sync");
+		bool any = false;
+		for (uint32_t i = 0; sk.topt && i < n; i++) {  // tensor sink: the slot of every failed frame reads as zero bytes
+			if (!feed.err[i]) continue;
+			if (hipError_t e = hipMemsetAsync(sk.d_tensor + (uint64_t)i * sk.tslot, 0, sk.tslot, streams[2]); e != hipSuccess)
+				return Status{e, "memset"};
+			any = true;
 		}
+		return any ? Status{hipStreamSynchronize(streams[2]), "sync"} : Status{};
 	}
-	if (trace) fprintf(stderr, "[pipe] all chunks retired at %.1f ms\n", ms_now());
+};
 
-	for (auto& t : pool) t.join();
-	pool.clear();
-	for (Copier& c : copiers) c.stop();
-	for (Slot& s : slots) {
-		if (s.done) (void)hipEventDestroy(s.done);
-		if (s.kdone) (void)hipEventDestroy(s.kdone);
-		if (s.buf) (void)hipFree(s.buf);
-	}
-	for (hipStream_t st : streams) (void)hipStreamDestroy(st);
-	for (Copier& c : copiers) (void)hipStreamDestroy(c.stream);
-	if (trace) fprintf(stderr, "[pipe] buffers freed at %.1f ms\n", ms_now());
-	if (!late.empty()) {  // (started last: its heap trimming would contend with the device-memory frees above)
-		g_freer.post(std::move(late));
-	}
-	{
-		int first = 0;
-		for (uint32_t i = 0; i < n; i++) {
-			if (!feed.dev[i]) vp8f_packed_free(&feed.pk[i]);  // failed frames (the others were freed per chunk)
-			free(feed.ares[i]);
-			if (status) status[i] = feed.err[i];
-			if (feed.err[i] && !first) first = feed.err[i];
-			if (feed.err[i] && outs) yuv420_free(&outs[i]);
-		}
-		if (first) {
-			errno = first;
-			return -1;
-		}
-	}
-	return 0;
-
-fail:
-	feed.stop();
-	for (auto& t : pool) t.join();
-	for (Vp8gPackedFrame& p : late) vp8f_packed_free(&p);
-	for (Copier& c : copiers) c.stop();
-	for (hipStream_t st : streams)
-		if (st) (void)hipStreamSynchronize(st);
-	for (Copier& c : copiers)
-		if (c.stream) (void)hipStreamSynchronize(c.stream);
-	vp8g::set_error_text(where ? where : "pipeline", he);
-	for (Slot& s : slots) {
-		if (s.done) (void)hipEventDestroy(s.done);
-		if (s.kdone) (void)hipEventDestroy(s.kdone);
-		if (s.buf) (void)hipFree(s.buf);
-	}
-	for (hipStream_t st : streams)
-		if (st) (void)hipStreamDestroy(st);
-	for (Copier& c : copiers)
-		if (c.stream) (void)hipStreamDestroy(c.stream);
+bool opts_ok(const Vp8gScaleOpt* opts, uint32_t n_opts, uint32_t n) { return opts ? n_opts == 1 || n_opts == n : n_opts == 0; }
+// a valid option (vp8g_tensor_slot_size: 0 for a NULL or invalid one) and a tensor that starts on an element boundary
+bool tensor_ok(const Vp8gTensorOpt* t, const void* d_out) {
+	return t && d_out && vp8g_tensor_slot_size(t) && (uintptr_t)d_out % (vp8g_tensor_slot_size(t) / (3ull * t->width * t->height)) == 0;
+}
+int fail(int e) { return errno = e, -1; }
+// A call that fails as a whole: no output survives, every frame reports `e`.
+int fail_all(Yuv420Image* outs, uint32_t n, int* status, int e) {
 	for (uint32_t i = 0; i < n; i++) {
-		if (!feed.dev[i]) vp8f_packed_free(&feed.pk[i]);
-		free(feed.ares[i]);
 		if (outs) yuv420_free(&outs[i]);
-		if (status) status[i] = EIO;
+		if (status) status[i] = e;
 	}
-	errno = EIO;
-	return -1;
-#undef PTRY
+	return fail(e);
+}
+
+// The body of every end-to-end entry point.  0, or -1 with errno = the first failed frame's error in index order and
+// status[i] per frame (a failed frame's image is freed, its tensor slot zero).  After a device failure every status is EIO
+// and every output freed; a C++ exception (no memory, no thread) unwinds through ~Pipeline and ends the call alike.
+int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags, Sinks sk, int* status) {
+	sk.tslot = sk.topt ? (sk.alpha ? vp8g_tensor_slot_size_a(sk.topt) : vp8g_tensor_slot_size(sk.topt)) : 0;
+	if (!files || (sk.topt ? !sk.d_tensor || !sk.tslot || sk.outs : !sk.outs) || n == 0 || (sk.alpha && !(sk.topt && sk.extended)) ||
+	    (flags & ~(VP8G_BATCH_DEVICE_M05 | VP8G_BATCH_MULTI_PARTITION)))
+		return fail(EINVAL);
+	for (uint32_t i = 0; sk.outs && i < n; i++) memset(&sk.outs[i], 0, sizeof(sk.outs[i]));
+	std::vector<int> err;  // per frame, once every chunk has retired
+	try {
+		Pipeline p;
+		p.failure = p.start(files, n, filtered, threads, flags, sk);
+		if (p.failure.ok()) p.failure = p.run();
+		p.finished = p.failure.ok();
+		if (p.finished && p.trace) fprintf(stderr, "[pipe] all chunks retired at %.1f ms\n", p.ms_now());
+		if (p.finished) err.swap(p.feed.err);
+	} catch (const std::bad_alloc&) {  // (~Pipeline has run: no copy into `outs` is in flight)
+		return fail_all(sk.outs, n, status, ENOMEM);
+	} catch (const std::system_error& e) {
+		return fail_all(sk.outs, n, status, e.code().value() ? e.code().value() : EAGAIN);
+	}
+	if (err.empty()) return fail_all(sk.outs, n, status, EIO);
+	int first = 0;
+	for (uint32_t i = 0; i < n; i++) {
+		if (status) status[i] = err[i];
+		if (err[i] && !first) first = err[i];
+		if (err[i] && sk.outs) yuv420_free(&sk.outs[i]);
+	}
+	return first ? fail(first) : 0;
+}
+
+}  // namespace
+
+VP8G_API int vp8g_plan_batch(const ByteSpan* files, uint32_t n, uint32_t threads, uint32_t flags, uint8_t* dev,
+                             uint32_t* order) {
+	if (!files || !dev || !order || n == 0 || (flags & ~(VP8G_BATCH_DEVICE_M05 | VP8G_BATCH_MULTI_PARTITION))) return fail(EINVAL);
+	uint32_t thr = threads ? threads : default_threads();
+	if (thr > n) thr = n;  // (as vp8g_decode_webp_batch_ex)
+	std::vector<uint8_t> d;
+	std::vector<uint32_t> o;
+	try {
+		plan_frames(files, n, (flags & VP8G_BATCH_DEVICE_M05) != 0, thr, d, o, true, false);
+	} catch (const std::bad_alloc&) {
+		return fail(ENOMEM);
+	}
+	memcpy(dev, d.data(), n);
+	memcpy(order, o.data(), n * sizeof(uint32_t));
+	return 0;
 }
 
 VP8G_API int vp8g_decode_webp_batch_ex(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
                                        Yuv420Image* outs, int* status) {
-	return decode_batch(files, n, filtered, threads, flags, nullptr, 0, outs, status);
+	return decode_batch(files, n, filtered, threads, flags, Sinks{nullptr, 0, outs}, status);
 }
 
+// With `opts` (n_opts = 1 or n) each chunk's frames are cropped / rescaled on the device (vp8g_scale.hip) into a second
+// buffer (small, unless VP8G_SCALE_EXPAND grows them: that counts against the chunk's budget); only that is downloaded.
 VP8G_API int vp8g_decode_webp_batch_scaled(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
                                            const Vp8gScaleOpt* opts, uint32_t n_opts, Yuv420Image* outs, int* status) {
-	if (!opts || (n_opts != 1 && n_opts != n)) {
-		errno = EINVAL;
-		return -1;
-	}
-	return decode_batch(files, n, filtered, threads, flags, opts, n_opts, outs, status);
+	if (!opts || !opts_ok(opts, n_opts, n)) return fail(EINVAL);
+	return decode_batch(files, n, filtered, threads, flags, Sinks{opts, n_opts, outs}, status);
 }
 
+// The sink is the caller's device tensor: each chunk's frames, scaled or not, are written to their slots of d_out
+// by the tensor kernel (vp8g_tensor.hip) on the chunk's stream, and only the chunk's status word is downloaded.
 VP8G_API int vp8g_decode_webp_batch_tensor(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
                                            const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, void* d_out,
                                            int* status) {
-	// (vp8g_tensor_slot_size: 0 for a NULL or invalid option)
-	if (!t || !d_out || !vp8g_tensor_slot_size(t) || (opts ? n_opts != 1 && n_opts != n : n_opts != 0) ||
-	    (uintptr_t)d_out % (vp8g_tensor_slot_size(t) / (3ull * t->width * t->height))) {
-		errno = EINVAL;
-		return -1;
-	}
-	return decode_batch(files, n, filtered, threads, flags, opts, n_opts, nullptr, status, t, (uint8_t*)d_out);
+	if (!tensor_ok(t, d_out) || !opts_ok(opts, n_opts, n)) return fail(EINVAL);
+	return decode_batch(files, n, filtered, threads, flags, Sinks{opts, n_opts, nullptr, t, (uint8_t*)d_out}, status);
 }
 
 // The extended container (webp_parse_extended) in front of the same pipeline: VP8X files decode, alpha
 // is ignored.
 VP8G_API int vp8g_decode_webp_batch_x(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
                                       const Vp8gScaleOpt* opts, uint32_t n_opts, Yuv420Image* outs, int* status) {
-	if (opts ? n_opts != 1 && n_opts != n : n_opts != 0) {
-		errno = EINVAL;
-		return -1;
-	}
-	return decode_batch(files, n, filtered, threads, flags, opts, n_opts, outs, status, nullptr, nullptr, true);
+	if (!opts_ok(opts, n_opts, n)) return fail(EINVAL);
+	return decode_batch(files, n, filtered, threads, flags, Sinks{opts, n_opts, outs, nullptr, nullptr, /*extended=*/true}, status);
 }
 
+// ... and with VP8G_X_ALPHA the ALPH planes as the tensor's fourth channel.
 VP8G_API int vp8g_decode_webp_batch_tensor_x(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
                                              const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, uint32_t xflags,
                                              void* d_out, int* status) {
-	if ((xflags & ~VP8G_X_ALPHA) || !t || !d_out || !vp8g_tensor_slot_size(t) || (opts ? n_opts != 1 && n_opts != n : n_opts != 0) ||
-	    (uintptr_t)d_out % (vp8g_tensor_slot_size(t) / (3ull * t->width * t->height))) {
-		errno = EINVAL;
-		return -1;
-	}
-	return decode_batch(files, n, filtered, threads, flags, opts, n_opts, nullptr, status, t, (uint8_t*)d_out, true,
-	                    (xflags & VP8G_X_ALPHA) != 0);
+	if ((xflags & ~VP8G_X_ALPHA) || !tensor_ok(t, d_out) || !opts_ok(opts, n_opts, n)) return fail(EINVAL);
+	const Sinks sk{opts, n_opts, nullptr, t, (uint8_t*)d_out, /*extended=*/true, /*alpha=*/(xflags & VP8G_X_ALPHA) != 0};
+	return decode_batch(files, n, filtered, threads, flags, sk, status);
 }
 
 VP8G_API int vp8g_decode_webp_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, Yuv420Image* outs,
