@@ -391,13 +391,76 @@ static void or_edge_census(const uint8_t* q0, int along, int step, int n, int ki
 		else cn[kind][or_hev(q0, step, T) ? 1 : 2]++;
 	}
 }
-static inline void or_walk_edge(uint64_t (*cn)[3], uint8_t* q0, int along, int step, int n, int kind, int limit_or_E, int I,
+/* Arithmetic census of one edge before it is filtered: which clamps of or_common_adjust /
+ * or_mb_adjust the inputs drive.  Paths (ar[path]): 0 simple, 1 normal MB edge with hev, 2 normal MB
+ * edge without hev (or_mb_adjust), 3 normal sub-block edge with hev, 4 normal sub-block edge without
+ * hev (the "inner" common adjust: no p1 - q1 term, p1/q1 updated).  Cell 0 of every path counts the
+ * calls.  Paths 0, 1, 3, 4: [1] p1-q1 > 127, [2] p1-q1 < -128 (outer only), [3] raw a > 127, [4] raw
+ * a < -128, [5] clamped a in 124..127 (a + 4 saturates), [6]/[7] sat8 changes q0 - f1 (low / high),
+ * [8]/[9] sat8 changes p0 + f2, [10]/[11] sat8 changes p1 + a2 or q1 - a2 (inner only).  Path 2:
+ * [1] raw w > 127, [2] raw w < -128, [3]/[4] sat8 changes a p1/q1 tap (low / high), [5]/[6] a p2/q2
+ * tap, [7]/[8] p1-q1 > 127 / < -128, [9]/[10] sat8 changes a p0/q0 tap. */
+#define PX(k) q0[(k) * step]
+static inline void or_sat_count(uint64_t* lo_hi, int v) {
+	if (v < 0) lo_hi[0]++;
+	else if (v > 255) lo_hi[1]++;
+}
+static void or_edge_arith(const uint8_t* q0, int along, int step, int n, int kind, int limit_or_E, int I, int T,
+                          uint64_t ar[OR_AR_PATHS][OR_AR_CELLS]) {
+	for (int i = 0; i < n; i++, q0 += along) {
+		if (!(kind == 0 ? or_simple_ok(q0, step, limit_or_E) : or_normal_ok(q0, step, limit_or_E, I))) continue;
+		const int hev = kind != 0 && or_hev(q0, step, T);
+		const int p2 = PX(-3), p1 = PX(-2), p0 = PX(-1), q0v = PX(0), q1 = PX(1), q2 = PX(2);
+		if (kind == 1 && !hev) {
+			uint64_t* c = ar[2];
+			c[0]++;
+			if (p1 - q1 > 127) c[7]++;
+			if (p1 - q1 < -128) c[8]++;
+			const int raw = sclamp(p1 - q1) + 3 * (q0v - p0), w = sclamp(raw);
+			if (raw > 127) c[1]++;
+			if (raw < -128) c[2]++;
+			int a = (27 * w + 63) >> 7;
+			or_sat_count(c + 9, p0 + a), or_sat_count(c + 9, q0v - a);
+			a = (18 * w + 63) >> 7;
+			or_sat_count(c + 3, p1 + a), or_sat_count(c + 3, q1 - a);
+			a = (9 * w + 63) >> 7;
+			or_sat_count(c + 5, p2 + a), or_sat_count(c + 5, q2 - a);
+			continue;
+		}
+		const int outer = kind == 0 || hev;
+		uint64_t* c = ar[kind == 0 ? 0 : (kind == 1 ? 1 : (hev ? 3 : 4))];
+		c[0]++;
+		if (outer && p1 - q1 > 127) c[1]++;
+		if (outer && p1 - q1 < -128) c[2]++;
+		const int raw = 3 * (q0v - p0) + (outer ? sclamp(p1 - q1) : 0), a = sclamp(raw);
+		if (raw > 127) c[3]++;
+		if (raw < -128) c[4]++;
+		if (a >= 124) c[5]++;
+		const int f1 = sclamp(a + 4) >> 3, f2 = sclamp(a + 3) >> 3;
+		or_sat_count(c + 6, q0v - f1);
+		or_sat_count(c + 8, p0 + f2);
+		if (!outer) {
+			const int a2v = (f1 + 1) >> 1;
+			or_sat_count(c + 10, q1 - a2v), or_sat_count(c + 10, p1 + a2v);
+		}
+	}
+}
+#undef PX
+
+/* what a walk counts besides filtering: the mask/hev table, the arithmetic table, or neither */
+typedef struct {
+	uint64_t (*cn)[3];
+	uint64_t (*ar)[OR_AR_CELLS];
+} OrCensus;
+
+static inline void or_walk_edge(const OrCensus* cs, uint8_t* q0, int along, int step, int n, int kind, int limit_or_E, int I,
                                 int T) {
-	if (cn) or_edge_census(q0, along, step, n, kind, limit_or_E, I, T, cn);
+	if (cs && cs->cn) or_edge_census(q0, along, step, n, kind, limit_or_E, I, T, cs->cn);
+	if (cs && cs->ar) or_edge_arith(q0, along, step, n, kind, limit_or_E, I, T, cs->ar);
 	or_edge(q0, along, step, n, kind, limit_or_E, I, T);
 }
 
-static int or_lf_walk(uint8_t* y, uint8_t* u, uint8_t* v, const Vp8DecodedFrame* d, uint64_t (*cn)[3]) {
+static int or_lf_walk(uint8_t* y, uint8_t* u, uint8_t* v, const Vp8DecodedFrame* d, const OrCensus* cn) {
 	if (!y || !u || !v || !d) {
 		errno = EINVAL;
 		return -1;
@@ -466,7 +529,29 @@ int oracle_loopfilter_census(const uint8_t* y, const uint8_t* u, const uint8_t* 
 		return -1;
 	}
 	memcpy(b, y, ysz), memcpy(b + ysz, u, csz), memcpy(b + ysz + csz, v, csz);
-	const int rc = or_lf_walk(b, b + ysz, b + ysz + csz, d, counts);
+	const OrCensus cs = {counts, NULL};
+	const int rc = or_lf_walk(b, b + ysz, b + ysz + csz, d, &cs);
+	free(b);
+	return rc;
+}
+
+/* As oracle_loopfilter_census, counting into counts[path][cell] of or_edge_arith how often the filter
+ * arithmetic reaches its clamps.  counts is added to, not cleared. */
+int oracle_loopfilter_arith_census(const uint8_t* y, const uint8_t* u, const uint8_t* v, const Vp8DecodedFrame* d,
+                                   uint64_t counts[OR_AR_PATHS][OR_AR_CELLS]) {
+	if (!y || !u || !v || !d || !counts) {
+		errno = EINVAL;
+		return -1;
+	}
+	const size_t ysz = (size_t)d->mb_cols * 16 * d->mb_rows * 16, csz = ysz / 4;
+	uint8_t* b = (uint8_t*)malloc(ysz + 2 * csz);
+	if (!b) {
+		errno = ENOMEM;
+		return -1;
+	}
+	memcpy(b, y, ysz), memcpy(b + ysz, u, csz), memcpy(b + ysz + csz, v, csz);
+	const OrCensus cs = {NULL, counts};
+	const int rc = or_lf_walk(b, b + ysz, b + ysz + csz, d, &cs);
 	free(b);
 	return rc;
 }

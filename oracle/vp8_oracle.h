@@ -32,6 +32,20 @@ int oracle_loopfilter(uint8_t* y, uint8_t* u, uint8_t* v, const Vp8DecodedFrame*
 int oracle_loopfilter_census(const uint8_t* y, const uint8_t* u, const uint8_t* v, const Vp8DecodedFrame* d,
                              uint64_t counts[3][3]);
 
+/* The same walk, counting where the filter arithmetic reaches its clamps, added into
+ * counts[path][cell].  Paths: 0 simple, 1 normal MB edge with hev, 2 normal MB edge without hev (the
+ * MB adjust), 3 normal sub-block edge with hev, 4 normal sub-block edge without hev.  Cell 0 is the
+ * number of filtered positions of the path.  Common adjust (paths 0, 1, 3, 4): 1/2 p1-q1 above 127 /
+ * below -128 (not path 4, which has no such term), 3/4 raw a above 127 / below -128, 5 clamped a in
+ * 124..127, 6/7 sat8 changes q0 - f1 (low / high), 8/9 sat8 changes p0 + f2, 10/11 sat8 changes
+ * p1 + a2 or q1 - a2 (path 4 only).  MB adjust (path 2): 1/2 raw w above 127 / below -128, 3/4 sat8
+ * changes a p1/q1 tap (low / high), 5/6 a p2/q2 tap, 7/8 p1-q1 above 127 / below -128, 9/10 sat8
+ * changes a p0/q0 tap. */
+#define OR_AR_PATHS 5
+#define OR_AR_CELLS 12
+int oracle_loopfilter_arith_census(const uint8_t* y, const uint8_t* u, const uint8_t* v, const Vp8DecodedFrame* d,
+                                   uint64_t counts[OR_AR_PATHS][OR_AR_CELLS]);
+
 /* Full m06(+m07) with crop into a malloc()ed cropped I420 image (free with oracle_image_free). */
 int oracle_reconstruct(const Vp8KeyFrameHeader* kf, const Vp8DecodedFrame* d, Yuv420Image* out, int filtered);
 void oracle_image_free(Yuv420Image* img);

@@ -48,6 +48,20 @@ Kinds on base profile 0 (small coefficients, smooth output: the loop filter fire
   lie_hasc0             has_coeff = 0 on a seeded half of the MBs that do have coefficients
   lie_hasc1             the skip subset zeroed, but has_coeff = 1 on it
   lf00 .. lf15          the loop-filter header overwritten from LF_CASES (below), skip on top
+  sat_mb .. sat_chroma  painted frames (see _paint, _tile): the unfiltered picture is chosen block by
+                        block and the coefficients follow, at q_index 4 where every step is exact; the
+                        normal filter at levels 57..63 meets steps and patterns that take its arithmetic
+                        into the clamps (tests/test_directed.py counts them with the oracle's
+                        arithmetic census):
+                          sat_mb      flat DC_PRED MBs 56..84 apart: w = 2d beyond +-127 on MB edges
+                          sat_sub     flat B_PRED sub-blocks 36..80 apart: a = 3d beyond +-127
+                          sat_hev     +-k patterns beside steps: hev with p1 - q1 and a beyond +-127
+                          sat_ends    the same at 0 and 255: every tap that can leave 0..255 does
+                          sat_sharp   sharpness 3 (interior limit 6): sub-blocks 38..58 apart, MBs, ends
+                          sat_seg     absolute segment levels 63 57 48 30, on both sides of 52 (below
+                                      it flat MBs that pass the mask cannot saturate w); mb, sub, hev
+                          sat_chroma  every design in the chroma planes, luma flat
+                        chroma carries the kind's designs too (8x8 MBs of 4x4 blocks)
 In every kind but the two lies has_coeff / skip_coeff are recomputed from the coefficients.
 
 LF_CASES: simple / normal filter x sharpness 0..7 (case i: simple = i & 1, sharpness = i >> 1), and
@@ -59,6 +73,8 @@ of 15 and of 40 (the hev thresholds).
 smooth_planes(w, h, seed): padded planes for vp8_loopfilter_apply_keyframe -- a seeded random walk
 (steps of a few units, occasional jumps) instead of uniform noise, on which the normal filter's mask
 fails at ~95 % of the positions.
+step_planes(w, h, seed): padded planes painted from the sat_* designs, for the same entry point under
+LF_STEP_CASES (simple and normal filter, levels 57..63, sharpness 0 and > 0).
 """
 import math
 import pathlib
@@ -75,7 +91,10 @@ MIX_WEIGHTS = (0.55, 0.25, 0.20)
 UNIFORM = [f"uni_{a}_{b}" for a in SHAPES for b in SHAPES]
 SPOILERS = [f"spoil_{s}_{r}" for s in ("dc", "cols01") for r in ("luma", "chroma")]
 LF_KINDS = [f"lf{i:02d}" for i in range(16)]
-KINDS = UNIFORM + ["mixed"] + SPOILERS + ["wrap", "bpred_all", "bpred_none", "skip", "lie_hasc0", "lie_hasc1"] + LF_KINDS
+# (appended: build() seeds from KINDS.index(kind), so the kinds before them keep their frames)
+SAT_KINDS = ["sat_mb", "sat_sub", "sat_hev", "sat_ends", "sat_sharp", "sat_seg", "sat_chroma"]
+KINDS = (UNIFORM + ["mixed"] + SPOILERS + ["wrap", "bpred_all", "bpred_none", "skip", "lie_hasc0", "lie_hasc1"] + LF_KINDS
+         + SAT_KINDS)
 
 # (frame level, segmentation_enabled, segmentation_abs, seg_lf_level[4], lf_delta_enabled, lf_ref_delta[0],
 #  lf_mode_delta[0]); per-MB levels (non-B_PRED / B_PRED where they differ) in the comments
@@ -202,10 +221,173 @@ def mb_lf_levels(f):
     return lvl
 
 
+# ---- painted frames: the unfiltered picture is chosen, the coefficients follow ----------------------
+# At q_index 4 with no quantiser deltas every dequantisation factor is 8 (Y2 DC: 16), so a DC
+# coefficient c moves a block by exactly c levels (Y2 DC 4c: the whole MB by c), and one AC coefficient
+# k at natural position 1, 2, 3 (across) or 4, 8, 12 (down) adds a fixed zero-mean pattern, e.g.
+# position 2: +k -k -k +k.  With DC prediction everywhere (B_DC_PRED sub-blocks, DC_PRED MBs and
+# chroma) the reconstruction is clip(mean + pattern) per 4x4 block, whatever the neighbours are.
+
+def _ac_pattern(K, P):
+    """The residual [..., 4, 4] of blocks whose only coefficient is K (ints) at natural position P,
+    dequantised by 8: the inverse DCT of RFC 6386 14.3 restated."""
+    x = np.zeros(K.shape + (16,), np.int64)
+    np.put_along_axis(x, P[..., None], 8 * K[..., None], axis=-1)
+    x = x.reshape(K.shape + (4, 4))
+    mc = lambda v: v + ((v * 20091) >> 16)  # noqa: E731
+    ms = lambda v: (v * 35468) >> 16        # noqa: E731
+
+    def half(v, rnd, sh):  # along the second-to-last axis
+        a, b = v[..., 0, :] + v[..., 2, :], v[..., 0, :] - v[..., 2, :]
+        c, d = ms(v[..., 1, :]) - mc(v[..., 3, :]), mc(v[..., 1, :]) + ms(v[..., 3, :])
+        return np.stack([a + d + rnd, b + c + rnd, b - c + rnd, a - d + rnd], axis=-2) >> sh
+    t = half(x, 0, 0)
+    return np.swapaxes(half(np.swapaxes(t, -1, -2), 4, 3), -1, -2)
+
+
+def _plan(M, K, P):
+    """Pixels of a plane from per-block means, AC coefficients and their positions (grids of 4x4 blocks)."""
+    px = np.clip(M[..., None, None] + _ac_pattern(K, P), 0, 255)
+    return px.transpose(0, 2, 1, 3).reshape(M.shape[0] * 4, M.shape[1] * 4)
+
+
+def _dc_pred(px, n):
+    """DC prediction of every n x n block of the plane from the plane itself (frame edges: 127 above,
+    129 to the left; a 16 / 8 block uses only the edges that exist, a 4x4 sub-block always both)."""
+    h, w = px.shape
+    a = np.full((h + 1, w + 1), 129, np.int64)
+    a[0, :] = 127
+    a[1:, 1:] = px
+    above = a[0:h:n, 1:].reshape(h // n, w // n, n).sum(-1)
+    left = a[1:, 0:w:n].reshape(h // n, n, w // n).sum(1)
+    if n == 4:
+        return (above + left + 4) >> 3
+    both = (above + left + n) >> (5 if n == 16 else 4)
+    one = lambda s: (s + n // 2) >> (4 if n == 16 else 3)  # noqa: E731
+    i, j = np.indices(both.shape)
+    return np.where((i > 0) & (j > 0), both, np.where(i > 0, one(above), np.where(j > 0, one(left), 128)))
+
+
+def _per_mb(grid, b):
+    """A [rows * b, cols * b] grid of blocks as [mb][b * b], blocks in raster order within the MB."""
+    r, c = grid.shape[0] // b, grid.shape[1] // b
+    return grid.reshape(r, b, c, b).transpose(0, 2, 1, 3).reshape(r * c, b * b)
+
+
+def _paint(f, bp, luma, chroma):
+    """Rewrite f so that its unfiltered reconstruction is the painted picture: bp[mb_rows][mb_cols] says
+    which MBs are B_PRED (the others DC_PRED with one mean per MB: their first block's), luma and
+    chroma = (M, K, P) block grids as for _plan (chroma: one triple per plane)."""
+    rows, cols = bp.shape
+    cy, cu, cv, y2 = _coeffs(f)
+    for a in (cy, cu, cv, y2):
+        a[:] = 0
+    f.array("ymode")[:] = np.where(bp, 4, 0).reshape(-1)
+    f.array("bmode")[:] = 0
+    f.array("uv_mode")[:] = 0
+    M, K, P = luma
+    bp4 = np.repeat(np.repeat(bp, 4, 0), 4, 1)
+    M = np.where(bp4, M, np.repeat(np.repeat(M[::4, ::4], 4, 0), 4, 1))
+    px = _plan(M, K, P)
+    np.put_along_axis(cy, _per_mb(P, 4)[..., None], _per_mb(K, 4)[..., None].astype(np.int16), axis=2)
+    cy[:, :, 0] = np.where(bp.reshape(-1, 1), _per_mb(M - _dc_pred(px, 4), 4), 0)
+    y2[:, 0] = np.where(bp, 0, 4 * (M[::4, ::4] - _dc_pred(px, 16))).reshape(-1)
+    for c, (M, K, P) in zip((cu, cv), chroma):
+        np.put_along_axis(c, _per_mb(P, 2)[..., None], _per_mb(K, 2)[..., None].astype(np.int16), axis=2)
+        c[:, :, 0] = _per_mb(M - np.repeat(np.repeat(_dc_pred(_plan(M, K, P), 8), 2, 0), 2, 1), 2)
+    h = f.frame
+    h.q_index = 4
+    h.y1_dc_delta_q = h.y2_dc_delta_q = h.y2_ac_delta_q = h.uv_dc_delta_q = h.uv_ac_delta_q = 0
+
+
+# What a 2 x 2 MB tile of a painted plane holds (bpm = blocks per MB side: 4 luma, 2 chroma).  The step
+# ranges straddle what the filter admits at level 63, sharpness 0 (MB edge 2|p0-q0| + |p1-q1|/2 <= 193,
+# sub-block edge <= 189) and what saturates (w = 2d > 127 from d = 64 between flat MBs, a = 3d > 127
+# from d = 43 between flat sub-blocks):
+#   mb        flat MBs in a checkerboard, neighbours 56..84 apart
+#   sub       flat sub-blocks in a checkerboard, 36..80 apart (subsharp: 38..58, for interior limit <= 8)
+#   hev       across (position 2) or down (position 8) the tile, blocks alternate between two levels
+#             60..78 apart, either with +-k -+k -+k +-k patterns of alternating sign, k 24..31 (p1 - q1
+#             beyond +-128 beside a small p0 - q0), or with one small k 2..6 (hev beside a step: a = 2d)
+#   ends      at 0 or at 255: zig = 0 2k 2k 0 blocks between flat 0 ones (outer taps leave 0..255), tri =
+#             2 0 0 2 between flat 0 ones (the inner p1/q1 tap and the MB adjust's p1/q1 tap leave the
+#             range only from such triples), saw = 6 4 0 0 in every block (the MB adjust's p2/q2 tap),
+#             fine = means within 5 of the end, any position, |k| <= 3
+def _tile(rng, d, i, j, bpm):
+    """(M, K, P, B_PRED) of one tile of design d; i, j = the global block indices of its blocks."""
+    shp = i.shape
+    K, P = np.zeros(shp, np.int64), np.ones(shp, np.int64)
+    if d in ("mb", "sub", "subsharp"):
+        unit = bpm if d == "mb" else 1
+        lo, hi = {"mb": (28, 42), "sub": (18, 40), "subsharp": (19, 29)}[d]
+        hu = rng.integers(lo, hi + 1, (2 * bpm, 2 * bpm))
+        h = hu[(i - i[0, 0]) // unit, (j - j[0, 0]) // unit]
+        s = 1 - 2 * ((i // unit + j // unit) & 1)
+        return int(rng.integers(hi + 1, 255 - hi)) + s * h, K, P, d != "mb"
+    across = int(rng.integers(2))  # the direction in which the blocks alternate (s = +-1), from a drawn phase
+    s = 1 - 2 * (((j if across else i) + int(rng.integers(2))) & 1)
+    if d == "hev":
+        if rng.integers(2):
+            K = -s * rng.integers(24, 32, shp)
+            M = int(rng.integers(72, 184)) + s * rng.integers(30, 40, shp)
+        else:
+            K = np.full(shp, int(rng.integers(2, 7)) * (1 - 2 * int(rng.integers(2))))
+            M = int(rng.integers(50, 206)) + s * rng.integers(28, 39, shp)
+        return M, K, np.full(shp, 2 if across else 8), True
+    assert d == "ends", d
+    top, sub = int(rng.integers(2)), int(rng.integers(4))
+    if sub == 0:    # zig
+        k = rng.integers(20, 32, shp)
+        M, K, P = np.where(s > 0, k, 0), np.where(s > 0, -k, 0), np.full(shp, 2 if across else 8)
+    elif sub == 1:  # tri
+        M, K, P = np.where(s > 0, 1, 0), np.where(s > 0, 1, 0), np.full(shp, 2 if across else 8)
+    elif sub == 2:  # saw
+        M, K, P = np.full(shp, int(rng.integers(1, 3))), np.full(shp, 3), np.full(shp, 1 if across else 4)
+    else:           # fine
+        M, K, P = rng.integers(-2, 6, shp), rng.integers(-3, 4, shp), rng.choice([1, 2, 3, 4, 8, 12], shp)
+    return (255 - M, -K, P, True) if top else (M, K, P, True)
+
+
+def _terrain(rng, designs, rows, cols, bpm):
+    """Block grids (M, K, P) of a plane of rows x cols MBs and its per-MB B_PRED map, every 2 x 2 MB
+    tile of a design drawn from `designs`."""
+    ii, jj = np.indices((rows * bpm, cols * bpm))
+    M, K, P = np.zeros_like(ii), np.zeros_like(ii), np.ones_like(ii)
+    bp = np.zeros((rows, cols), bool)
+    for ti in range(0, rows, 2):
+        for tj in range(0, cols, 2):
+            sl = (slice(ti * bpm, (ti + 2) * bpm), slice(tj * bpm, (tj + 2) * bpm))
+            M[sl], K[sl], P[sl], bp[ti:ti + 2, tj:tj + 2] = _tile(rng, designs[rng.integers(len(designs))], ii[sl], jj[sl], bpm)
+    return (M, K, P), bp
+
+
+# kind -> (tile designs, loop-filter level, sharpness)
+SAT_SPECS = {"sat_mb": (("mb",), 63, 0), "sat_sub": (("sub",), 63, 0), "sat_hev": (("hev",), 60, 0),
+             "sat_ends": (("ends",), 63, 0), "sat_sharp": (("subsharp", "mb", "ends"), 63, 3),
+             "sat_seg": (("mb", "sub", "hev"), 0, 0), "sat_chroma": (("mb", "sub", "hev", "ends"), 63, 0)}
+SAT_SEG_LEVELS = (63, 57, 48, 30)  # sat_seg: absolute segment levels on both sides of what lets w saturate (52)
+
+
+def _sat_frame(rng, f, kind):
+    designs, level, sharp = SAT_SPECS[kind]
+    rows, cols = int(f.frame.mb_rows), int(f.frame.mb_cols)
+    luma, bp = _terrain(rng, designs, rows, cols, 4)
+    if kind == "sat_chroma":  # luma left without coefficients
+        luma, bp = (np.full_like(luma[0], 128), np.zeros_like(luma[1]), luma[2]), np.zeros_like(bp)
+    _paint(f, bp, luma, [_terrain(rng, designs, rows, cols, 2)[0] for _ in range(2)])
+    if kind == "sat_chroma":
+        _coeffs(f)[3][:] = 0
+    h = f.frame
+    h.lf_use_simple, h.lf_sharpness, h.lf_level, h.lf_delta_enabled = 0, sharp, level, 0
+    h.segmentation_enabled = h.segmentation_abs = int(kind == "sat_seg")
+    for i in range(4):
+        h.seg_lf_level[i], h.seg_quant_idx[i] = (SAT_SEG_LEVELS[i], 4) if kind == "sat_seg" else (0, 0)
+
+
 def build(kind, width, height, seed):
     """The directed frame `kind` (one of KINDS) of width x height from `seed`: a vp8g.Frame."""
     rng = np.random.default_rng([KINDS.index(kind), width, height, seed])
-    smooth = kind in ("skip", "lie_hasc0", "lie_hasc1") or kind in LF_KINDS
+    smooth = kind in ("skip", "lie_hasc0", "lie_hasc1") or kind in LF_KINDS + SAT_KINDS
     f = vp8g.synth_frame(width, height, seed, 0 if smooth else 1 + (seed & 1))
     n = f.mb_total
     if kind in UNIFORM:
@@ -263,6 +445,8 @@ def build(kind, width, height, seed):
     elif kind in LF_KINDS:
         _lf_header(f, LF_KINDS.index(kind))
         _zero_mbs(f, _subset(rng, f, 0.25))
+    elif kind in SAT_KINDS:
+        _sat_frame(rng, f, kind)
     else:
         raise KeyError(kind)
     _truth(f)
@@ -294,6 +478,30 @@ def lf_entry_case(case):
     """(frame, planes) of LF case `case` for the m07-alone entry point."""
     f = build(LF_KINDS[case], *LF_ENTRY_SIZE, 40 + case)
     return f, smooth_planes(int(f.frame.mb_cols) * 16, int(f.frame.mb_rows) * 16, 40 + case)
+
+
+def step_planes(width, height, seed):
+    """Padded planes (y, u, v as smooth_planes) painted from every tile design of the sat_* kinds: flat
+    tiles 36..84 apart, +-k patterns beside steps, and the range's ends -- where the filter's
+    intermediates leave [-128, 127] and its taps leave [0, 255]."""
+    rng = np.random.default_rng([0x5A7, width, height, seed])
+    designs = ("mb", "sub", "subsharp", "hev", "hev", "hev", "ends", "ends")  # (MB edges with hev are the rarest)
+    return [_plan(*_terrain(rng, designs, height // 16, width // 16, bpm)[0]).astype(np.uint8).reshape(-1)
+            for bpm in (4, 2, 2)]
+
+
+# vp8_loopfilter_apply_keyframe on step_planes of this picture size: (simple, level, sharpness), one level per MB
+LF_STEP_SIZE = (480, 270)
+LF_STEP_CASES = [(0, 63, 0), (0, 57, 0), (0, 60, 0), (0, 62, 0), (0, 63, 3), (0, 58, 6), (1, 63, 0), (1, 57, 0), (1, 61, 2), (1, 59, 7)]
+
+
+def lf_step_case(case):
+    """(frame, planes) of LF_STEP_CASES[case] for the m07-alone entry point: every MB B_PRED, so every
+    inner edge is filtered."""
+    f = build("sat_sub", *LF_STEP_SIZE, 60 + case)
+    h = f.frame
+    h.lf_use_simple, h.lf_level, h.lf_sharpness = LF_STEP_CASES[case]
+    return f, step_planes(int(h.mb_cols) * 16, int(h.mb_rows) * 16, 60 + case)
 
 
 def same(a, b):

@@ -442,6 +442,18 @@ def fresh(case):
     return _build.__wrapped__(case["name"] if isinstance(case, dict) else case)
 
 
+def directed_stream(kind, width, height, seed):
+    """directed.build(kind, ...) written as a one-partition .webp with the default tables, skip bits at
+    probability 128: (the canonical frame, the stream).  Outside CASES (no golden entry): for a test that
+    needs a directed picture to arrive through the bitstream."""
+    f = directed.build(kind, width, height, seed)
+    prm = _params(_case("", kind, size=(width, height), seed=seed), f, None)
+    data, cs, skipped = write(f, prm)
+    canonical(f, prm, skipped)
+    f.kf.first_partition_len = cs.part0_size
+    return f, data
+
+
 def single_partition():
     return [c for c in CASES if c["log2k"] == 0]
 

@@ -6,6 +6,10 @@
     oracle_loopfilter, counting): every reachable cell >= 1 000 positions over the directed loop-filter
     set, and >= 100 on the frames with sharpness > 0, with deltas, with a level-0 segment; the smooth
     planes of the m07-alone entry pass the normal mask at >= 10 % of the positions;
+  * arithmetic census from the oracle (oracle_loopfilter_arith_census): every reachable clamp of the
+    filter's arithmetic, each sign on its own, >= 100 positions over the sat_* kinds (>= 1 000 for w and
+    the sub-block a), >= 200 on the step planes of the m07-alone entry, and the simple filter's cells
+    >= 100 on the inputs that covered them before; the unreachable cells 0 everywhere;
   * the oracle itself on these frames: equal to the reference where it is built, and to the reference's
     hashes in tests/golden/directed_kat.json everywhere.
 
@@ -19,6 +23,33 @@ Smooth planes (16 cases, 304x176 padded): normal MB edge [38736, 31546, 7446] = 
 edge [73100, 53706, 12330] = 47 % pass.
 For comparison, profiles 1/2 pass the normal mask at ~5 % of positions and uniform noise planes at
 well under 1 %.
+
+Arithmetic census (oracle_loopfilter_arith_census: edge positions at which the filter's arithmetic
+reaches a clamp; -s prints it).  Rows: the five paths of the filter.  Cells of the common adjust
+(simple, hev, and sub-block edge without hev): positions filtered | p1-q1 > 127, < -128 | raw a > 127,
+< -128 | clamped a in 124..127 | sat8 changes q0-f1 low, high | p0+f2 low, high | p1+a2 or q1-a2 low, high.
+Cells of the MB adjust: positions | raw w > 127, < -128 | sat8 changes a p1/q1 tap low, high | a p2/q2 tap
+low, high | sclamp(p1-q1) fires high, low | sat8 changes a p0/q0 tap low, high.  `-` = the path has no such
+cell, `0*` = unreachable (test_unreachable_arith_cells).
+  sat_* kinds but sat_chroma, 320x256, seed 7
+    MB edge, hev            18099 |  246  158 |  1789  1332 |  2161 |  658  584 |  342  616 | -
+    MB edge, no hev         58454 | 4601 4589 |   930   734 |   505   748 | 0* 0* | 0* 0*
+    sub-block edge, hev     65488 |  682  508 |  5916  5173 |  7180 | 1201 1697 | 1573 1541 | -
+    sub-block edge, no hev 159717 |    -    - | 13446 12878 | 13872 |   0*   0* |   0*   0* | 1640  899
+  sat_chroma alone (chroma edges only)
+    MB edge, hev             2033 |   55   25 |   240   161 |   270 |   98   66 |   32   17 | -
+    MB edge, no hev         14713 |  590  551 |    80    71 |    52    41 | 0* 0* | 0* 0*
+    sub-block edge, hev      4708 |   74   62 |   293   298 |   353 |   81   37 |  135   96 | -
+    sub-block edge, no hev  36142 |    -    - |   216   215 |   222 |   0*   0* |   0*   0* |   50    0
+  step_planes, the ten LF_STEP_CASES, 480x272 padded
+    simple                 210867 | 2827 2194 |  5405  4448 |  6577 | 2198 2279 | 2133 2333 | -
+    MB edge, hev            27947 |  406  312 |  3483  2742 |  4003 |  678  556 |  721  407 | -
+    MB edge, no hev         77995 | 3489 3210 |  1785  1544 |   546  1451 | 0* 0* | 0* 0*
+    sub-block edge, hev     86660 | 1728 1308 |  7648  6921 |  9381 | 2878 1801 | 2570 1829 | -
+    sub-block edge, no hev 241616 |    -    - | 16570 15823 | 17241 |   0*   0* |   0*   0* | 3190 2496
+  lf00..lf15 + synthetic profiles 1 and 2 (seed 6), 320x256: what covered the simple filter before
+    simple                 154576 | 7756 7865 |  2764  2665 |  9529 | 4759 5253 | 5025 4883 | -
+  (the same inputs on the normal filter: w beyond +-127 at 1 / 2 positions, a on sub-block edges at 22 / 17)
 """
 import hashlib
 import json
@@ -208,6 +239,159 @@ def test_smooth_planes_pass_the_normal_mask(vp8g):
         print(f"smooth planes, {vp8g.LF_KINDS[kind]}: {tot[kind].tolist()} pass {share:.3f}")
         assert share >= 0.10
     assert tot[0, 0] >= 1000 and tot[0, 2] >= 1000 and tot[1, 1] >= 1000 and tot[2, 1] >= 1000
+
+
+# ---- the filter's saturating arithmetic (oracle_loopfilter_arith_census) -------------------------------
+# (path, cell) of vp8g.LF_ARITH_PATHS / LF_ARITH_CELLS that no input reaches; test_unreachable_arith_cells
+UNREACHABLE = {(2, 7), (2, 8), (2, 9), (2, 10), (4, 6), (4, 7), (4, 8), (4, 9)}
+W_AND_SUB_A = {(2, 1), (2, 2), (3, 3), (3, 4), (4, 3), (4, 4)}  # MB adjust w, sub-block raw a: each sign
+
+
+def arith_cells(vp8g, paths):
+    return [(p, c) for p in paths for c, name in enumerate(vp8g.LF_ARITH_CELLS[p]) if c and name and (p, c) not in UNREACHABLE]
+
+
+def show(vp8g, title, t):
+    print(title)
+    for p, row in enumerate(t):
+        print(f"  {vp8g.LF_ARITH_PATHS[p]:28s}", row.tolist())
+
+
+def check_arith(vp8g, t, paths, floor, floors=()):
+    for p, c in UNREACHABLE:
+        assert t[p, c] == 0, (vp8g.LF_ARITH_PATHS[p], vp8g.LF_ARITH_CELLS[p][c], int(t[p, c]))
+    for p in range(5):  # (a cell the path does not have stays 0, and no cell exceeds the calls)
+        assert all(t[p, c] == 0 for c, name in enumerate(vp8g.LF_ARITH_CELLS[p]) if name is None)
+        assert (t[p, 1:] <= t[p, 0]).all() or p in (2, 4)  # (paths 2 and 4 count two taps per position)
+    for p, c in arith_cells(vp8g, paths):
+        need = dict(floors).get((p, c), floor)
+        assert t[p, c] >= need, (vp8g.LF_ARITH_PATHS[p], vp8g.LF_ARITH_CELLS[p][c], int(t[p, c]), need)
+
+
+def test_unreachable_arith_cells():
+    """The cells no input reaches, each by exhaustive search over the pixels that enter it, under the
+    loosest parameters there are (level 63, sharpness 0: hev threshold 2, MB-edge limit 193).
+
+    MB adjust (MB edge, no hev), sclamp(p1 - q1): |p1 - p0| <= 2 and |q1 - q0| <= 2, so |p1 - q1| <=
+    |p0 - q0| + 4, and the mask's 2|p0 - q0| + |p1 - q1| / 2 <= 193 leaves |p1 - q1| < 128.
+    MB adjust, sat8 on the p0/q0 taps: with d = q0 - p0 > 0, w <= 2d + 4, and p0 + ((27w + 63) >> 7) >= 256
+    would need 74d <= 43.  Searched: every p0, q0 with p1, q1 within 2 of them.
+    Sub-block edge without hev, sat8 on q0 - f1 and p0 + f2: a = 3(q0 - p0) alone, |f| <= (3|d| + 4) >> 3
+    <= |d| moves each pixel toward the other.  Searched: every p0, q0."""
+    sc = lambda v: np.clip(v, -128, 127)  # noqa: E731
+    p0, q0, dp, dq = np.meshgrid(np.arange(256), np.arange(256), np.arange(-2, 3), np.arange(-2, 3), indexing="ij")
+    p1, q1 = p0 + dp, q0 + dq
+    ok = (p1 >= 0) & (p1 <= 255) & (q1 >= 0) & (q1 <= 255) & (2 * abs(p0 - q0) + (abs(p1 - q1) >> 1) <= 193)
+    assert ok.sum() > 500_000  # (the search is not vacuous)
+    assert (abs(p1 - q1)[ok] < 128).all()
+    a27 = (27 * sc(sc(p1 - q1) + 3 * (q0 - p0)) + 63) >> 7
+    assert ((p0 + a27)[ok] >= 0).all() and ((p0 + a27)[ok] <= 255).all()
+    assert ((q0 - a27)[ok] >= 0).all() and ((q0 - a27)[ok] <= 255).all()
+    p0, q0 = np.meshgrid(np.arange(256), np.arange(256), indexing="ij")
+    a = sc(3 * (q0 - p0))
+    f1, f2 = sc(a + 4) >> 3, sc(a + 3) >> 3
+    assert (q0 - f1 >= 0).all() and (q0 - f1 <= 255).all() and (p0 + f2 >= 0).all() and (p0 + f2 <= 255).all()
+
+
+def test_arith_census_of_the_saturating_kinds(vp8g):
+    """Every reachable cell of the normal filter, each sign on its own, >= 100 positions over the sat_*
+    kinds that paint luma (>= 1 000 for the MB adjust's w and the sub-block edges' raw a); sat_chroma,
+    whose luma plane is flat, reaches w and the sub-block a on chroma edges alone; sat_sharp (sharpness
+    3: interior limit 6, where w <= 2 * 55 + 4 and the outer a <= 2 * 55 + 12 stay inside) saturates a = 3d on
+    sub-block edges without hev; sat_seg has segments on both sides of level 52, below which flat MBs that pass
+    the mask cannot saturate w.  If a cell falls short, the inputs change, never the floor."""
+    per = {k: vp8g.oracle_frame_arith_census(D.build(k, *CENSUS_SIZE, 7)) for k in D.SAT_KINDS}
+    luma = sum(c for k, c in per.items() if k != "sat_chroma")
+    show(vp8g, "sat_* kinds but sat_chroma", luma)
+    show(vp8g, "sat_chroma", per["sat_chroma"])
+    check_arith(vp8g, luma, (1, 2, 3, 4), 100, {c: 1000 for c in W_AND_SUB_A})
+    assert luma[0].sum() == 0  # (the normal filter throughout)
+    for k, c in per.items():
+        check_arith(vp8g, c, (), 0)
+    for cell in W_AND_SUB_A:
+        assert per["sat_chroma"][cell] >= 100, (cell, int(per["sat_chroma"][cell]))
+    for cell in ((4, 3), (4, 4)):
+        assert per["sat_sharp"][cell] >= 100, (cell, int(per["sat_sharp"][cell]))
+    f = D.build("sat_sharp", *CENSUS_SIZE, 7)
+    assert f.frame.lf_sharpness > 0
+    f = D.build("sat_seg", *CENSUS_SIZE, 7)
+    lv = D.mb_lf_levels(f)
+    assert f.frame.segmentation_enabled and (lv >= 57).sum() >= 50 and (lv < 52).sum() >= 50
+    assert per["sat_seg"][2, 1] >= 100 and per["sat_seg"][2, 2] >= 100
+    for k in D.SAT_KINDS:
+        f = D.build(k, *CENSUS_SIZE, 7)
+        h = f.frame
+        assert not h.lf_use_simple and (k == "sat_seg" or 57 <= h.lf_level <= 63)
+
+
+def test_saturating_kinds_reconstruct_to_their_plan(vp8g):
+    """The painted kinds are what they say: the oracle's unfiltered luma of sat_sub is the checkerboard of
+    flat sub-blocks the builder planned (each 4x4 block one value, horizontal neighbours 36..80 apart
+    inside a tile)."""
+    f = D.build("sat_sub", *CENSUS_SIZE, 7)
+    w, h = CENSUS_SIZE
+    y = np.frombuffer(vp8g.oracle_reconstruct(f, False), np.uint8)[:w * h].reshape(h // 4, 4, w // 4, 4).astype(int)
+    assert (y == y[:, :1, :, :1]).all()
+    d = abs(np.diff(y[:, 0, :, 0], axis=1))
+    inside = np.arange(1, w // 4) % 8 != 0  # (not across a tile's border)
+    assert d[:, inside].min() >= 36 and d[:, inside].max() <= 80
+
+
+def test_arith_census_of_the_step_planes(vp8g):
+    """The planes of the m07-alone GPU test (directed.lf_step_case): every reachable cell of all five
+    paths >= 200, summed over the cases; simple and normal headers, sharpness 0 and > 0, levels 57..63."""
+    tot = np.zeros((5, 12), np.uint64)
+    for case in range(len(D.LF_STEP_CASES)):
+        f, planes = D.lf_step_case(case)
+        tot += vp8g.oracle_loopfilter_arith_census(planes, f.frame)
+    show(vp8g, "step planes", tot)
+    check_arith(vp8g, tot, range(5), 200)
+    for simple in (0, 1):
+        sh = {s for sm, lvl, s in D.LF_STEP_CASES if sm == simple}
+        assert 0 in sh and max(sh) > 0
+    assert all(57 <= lvl <= 63 for _, lvl, _ in D.LF_STEP_CASES)
+
+
+def test_arith_census_simple_filter_on_the_lf_set(vp8g):
+    """What covers the simple filter's cells today stays: lf00..lf15 plus one simple-filter frame of each
+    of the synthetic profiles 1 and 2 (seed 6: level 14, sharpness 0), >= 100 per cell."""
+    tot = np.zeros((5, 12), np.uint64)
+    for kind in D.LF_KINDS:
+        tot += vp8g.oracle_frame_arith_census(D.build(kind, *CENSUS_SIZE, 7))
+    for profile in (1, 2):
+        f = vp8g.synth_frame(*CENSUS_SIZE, 6, profile)
+        assert f.frame.lf_use_simple
+        tot += vp8g.oracle_frame_arith_census(f)
+    show(vp8g, "lf00..lf15 + profiles 1, 2", tot)
+    check_arith(vp8g, tot, (0,), 100)
+
+
+def test_arith_census_counts_what_the_filter_does(vp8g):
+    """The arithmetic census walks what oracle_loopfilter_census walks (cell 0 of its paths = the mask
+    pass cells of that table), leaves its planes alone, and on hand-made pixels counts the clamps:
+    two flat MBs 70 apart (w = 140) and two flat sub-blocks 50 apart (a = 150), rising and falling."""
+    f, planes = D.lf_step_case(0)
+    keep = [p.copy() for p in planes]
+    a, c = vp8g.oracle_loopfilter_arith_census(planes, f.frame), vp8g.oracle_loopfilter_census(planes, f.frame)
+    assert all(np.array_equal(x, y) for x, y in zip(planes, keep))
+    assert [int(a[p, 0]) for p in range(5)] == [int(c[0, 2]), int(c[1, 1]), int(c[1, 2]), int(c[2, 1]), int(c[2, 2])]
+    f = D.build("sat_sub", 32, 16, 1)  # (every MB B_PRED; level 63, sharpness 0)
+    for row, up in (((60, 110, 120, 190), True), ((190, 140, 130, 60), False)):
+        y = np.empty((16, 32), np.uint8)  # sub-blocks 50 apart at x = 4, 10 apart at x = 8, MBs 70 apart at x = 16
+        y[:, :4], y[:, 4:8], y[:, 8:16], y[:, 16:] = row
+        a = vp8g.oracle_loopfilter_arith_census((y.reshape(-1), np.full(128, 128, np.uint8), np.full(128, 128, np.uint8)), f.frame)
+        assert a[2, 1:3].tolist() == ([16, 0] if up else [0, 16]), a[2].tolist()
+        assert a[4, 3:6].tolist() == ([16, 0, 16] if up else [0, 16, 0]), a[4].tolist()
+        assert not a[2, 3:].any() and not a[4, 6:].any() and not a[[0, 1, 3], 1:].any()
+
+
+def test_saturating_kinds_pass_through_the_stream_writer():
+    """The two kinds the GPU pipeline test sends as .webp: the host front end returns the frame."""
+    import streams as S
+    for kind in ("sat_mb", "sat_seg"):
+        f, data = S.directed_stream(kind, *CENSUS_SIZE, 7)
+        got = S.decode(data)
+        assert got is not None and D.same(f, got), kind
 
 
 @needs_ref

@@ -1,5 +1,5 @@
 """GPU: the directed frames of tests/directed.py through every reconstruction path, byte for byte
-against the oracle (and the uniform kinds and `wrap` against the reference's hashes,
+against the oracle (and the uniform kinds, `wrap` and the sat_* kinds against the reference's hashes,
 tests/golden/directed_kat.json).  tests/test_directed.py proves on the CPU what each kind reaches;
 here is which kernel meets it:
 
@@ -11,6 +11,10 @@ here is which kernel meets it:
       test_quad_chain_directed, and with the mirror split forced test_quad_chain_directed_mirror_split
   device-memory context path (8200 wide), one-column path (16 wide)   test_extreme_dimensions_directed
   m07 alone on planes the filter modifies            test_loopfilter_entry_point_smooth_planes
+  m07 alone on planes that saturate its arithmetic   test_loopfilter_entry_point_step_planes
+  the batch pipeline (.webp in, host and device m05) on two sat_* kinds   test_pipeline_saturating_kinds
+The sat_* kinds (the loop filter's clamps: w and a beyond +-127, taps beyond 0..255; the census is in
+tests/test_directed.py) are part of D.KINDS and so of every test above the m07-alone ones.
 and the launch-mode report itself (test_launch_mode_is_zero_after_an_invalid_call).
 
 Reference path: src/m06_recon/vp8_recon.c:444-684 + src/m07_loopfilter/vp8_loopfilter.c:214-280.
@@ -67,8 +71,8 @@ def last_mode(vp8g):
 def test_single_frame_entry_points_and_small_batch(vp8g, env):
     """Every kind at 320x256 and at an odd size, one workgroup per frame (VP8G_SPLIT=1; launch mode 0):
     the frame kernel's ballot spans one MB, so `mixed` and the spoilers change its iDCT form from MB to
-    MB.  The batch API on all 72 frames; the single-frame entry points on the uniform kinds and `wrap`
-    (held to the reference's hashes too), `mixed`, the spoilers and the has_coeff lies."""
+    MB.  The batch API on all 78 frames; the single-frame entry points on the uniform kinds, `wrap` and
+    the sat_* kinds (held to the reference's hashes too), `mixed`, the spoilers and the has_coeff lies."""
     env["VP8G_SPLIT"] = "1"
     env.pop("VP8G_WAVES", None)
     kat = json.loads((GOLDEN / "directed_kat.json").read_text())["cases"]
@@ -80,9 +84,9 @@ def test_single_frame_entry_points_and_small_batch(vp8g, env):
         assert last_mode(vp8g) == 0
         check(vp8g, frames, labels, outs, filtered)
         for c, f, lab, o in zip(cases, frames, labels, outs):
-            if c[0] in D.UNIFORM + ["wrap"]:
+            if c[0] in D.UNIFORM + ["wrap"] + D.SAT_KINDS:
                 assert hashlib.sha256(o).hexdigest() == kat[lab]["yuvf_sha256" if filtered else "yuv_sha256"], lab
-            if c[0] in D.UNIFORM + D.SPOILERS + ["wrap", "mixed", "lie_hasc0", "lie_hasc1"]:
+            if c[0] in D.UNIFORM + D.SPOILERS + D.SAT_KINDS + ["wrap", "mixed", "lie_hasc0", "lie_hasc1"]:
                 one = vp8g.gpu_reconstruct(f, filtered)
                 assert last_mode(vp8g) == 0
                 assert one == o, f"{lab} filtered={filtered}: single-frame call vs batch, {first_diff(f, one, o)}"
@@ -91,7 +95,7 @@ def test_single_frame_entry_points_and_small_batch(vp8g, env):
 @pytest.mark.parametrize("split,waves", [(3, 8), (8, 0)])
 def test_forced_split_factors(vp8g, env, split, waves):
     """Every kind at 48x1840 (115 MB rows: enough row pairs for eight parts of eight waves) and 52x300,
-    18 frames per call.  VP8G_SPLIT=8: the frames run as split parts (the mode is asserted);
+    39 frames in calls of 18, 18 and 3.  VP8G_SPLIT=8: the frames run as split parts (the mode is asserted);
     VP8G_SPLIT=3 with VP8G_WAVES=8: a waves override keeps the shim from splitting, so this is the
     frame kernel at eight waves per workgroup (mode 0)."""
     env["VP8G_SPLIT"] = str(split)
@@ -112,7 +116,7 @@ def test_forced_split_factors(vp8g, env, split, waves):
 
 @pytest.mark.parametrize("odd", [False, True], ids=["whole", "odd"])
 def test_quad_chain_directed(vp8g, odd):
-    """1 200 slots of the 144 directed frames (every kind at four sizes, filtered at two): the quad
+    """1 200 slots of the 156 directed frames (every kind at four sizes, filtered at two): the quad
     chain's ballot spans four vertically adjacent MBs, separately per role -- uniform frames hold every
     wave to one form at every geometry (last quads of 1..3 rows, cut pieces, one column), `mixed` changes
     the form from step to step inside a chain.  Launch mode: chain + quad."""
@@ -146,21 +150,18 @@ def test_frame_kernel_directed_many_frames(vp8g, odd):
 
 @pytest.mark.parametrize("w,h", [(8200, 40), (16, 2000)])
 def test_extreme_dimensions_directed(vp8g, w, h):
-    """A DC-only, a columns-0-1 and a skip frame where the per-column context lives in device memory
-    (8200 wide) and where a frame is one MB column (16 wide)."""
-    for kind in ("uni_dc_dc", "uni_cols01_cols01", "skip"):
+    """A DC-only, a columns-0-1, a skip and a saturating frame (sat_seg: flat MBs, flat sub-blocks and
+    hev tiles under four segment levels) where the per-column context lives in device memory (8200
+    wide) and where a frame is one MB column (16 wide)."""
+    for kind in ("uni_dc_dc", "uni_cols01_cols01", "skip", "sat_seg"):
         f = D.build(kind, w, h, 3)
         for filtered in (False, True):
             check(vp8g, [f], [f"{kind}/{w}x{h}"], [vp8g.gpu_reconstruct(f, filtered)], filtered)
 
 
-@pytest.mark.parametrize("case", range(16))
-def test_loopfilter_entry_point_smooth_planes(vp8g, case):
-    """vp8_loopfilter_apply_keyframe (m07 alone, in place on a padded image) under every directed
-    loop-filter header, on smooth planes: ~50 % of the normal filter's positions pass the mask
-    (tests/test_directed.py), where the uniform noise of test_gpu_parity's cases passes at < 1 %."""
+def lf_entry_point(vp8g, case, f, planes):
+    """vp8_loopfilter_apply_keyframe on `planes` under f's header against oracle_loopfilter, plane by plane."""
     lib = vp8g.gpu_lib()
-    f, planes = D.lf_entry_case(case)
     w, h = int(f.frame.mb_cols) * 16, int(f.frame.mb_rows) * 16
     img = vp8g.Yuv420Image()
     assert lib.yuv420_alloc(C.byref(img), w, h) == 0
@@ -174,6 +175,35 @@ def test_loopfilter_entry_point_smooth_planes(vp8g, case):
     assert not np.array_equal(exp[0], planes[0])  # (the filter modified the luma plane)
     for name, g, e in zip("YUV", got, exp):
         assert np.array_equal(g, e), (case, name, int(np.flatnonzero(g != e)[0]))
+
+
+@pytest.mark.parametrize("case", range(16))
+def test_loopfilter_entry_point_smooth_planes(vp8g, case):
+    """vp8_loopfilter_apply_keyframe (m07 alone, in place on a padded image) under every directed
+    loop-filter header, on smooth planes: ~50 % of the normal filter's positions pass the mask
+    (tests/test_directed.py), where the uniform noise of test_gpu_parity's cases passes at < 1 %."""
+    lf_entry_point(vp8g, case, *D.lf_entry_case(case))
+
+
+@pytest.mark.parametrize("case", range(len(D.LF_STEP_CASES)))
+def test_loopfilter_entry_point_step_planes(vp8g, case):
+    """The same entry point on planes of flat tiles, +-k patterns beside steps and range ends, under
+    simple and normal headers at levels 57..63, sharpness 0 and > 0: every reachable clamp of the
+    filter's arithmetic fires at >= 200 positions over the cases (tests/test_directed.py)."""
+    lf_entry_point(vp8g, case, *D.lf_step_case(case))
+
+
+@pytest.mark.parametrize("device_m05", [False, True], ids=["host_m05", "device_m05"])
+def test_pipeline_saturating_kinds(vp8g, device_m05):
+    """sat_mb (w beyond +-127 between flat MBs) and sat_seg (segment levels on both sides of where w can
+    saturate; flat sub-blocks and hev tiles) at 320x256, written as .webp by the test stream writer and
+    decoded by the batch pipeline, filtered, against the oracle on the frame the stream carries."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import streams as S
+    built = [S.directed_stream(k, 320, 256, 7) for k in ("sat_mb", "sat_seg")]
+    outs, st = vp8g.gpu_decode_webp_batch([d for _, d in built], True, 2, device_m05=device_m05)
+    assert st == [0, 0], st
+    check(vp8g, [f for f, _ in built], ["sat_mb.webp", "sat_seg.webp"], outs, True)
 
 
 def test_launch_mode_is_zero_after_an_invalid_call(vp8g):

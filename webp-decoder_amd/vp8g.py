@@ -1184,6 +1184,43 @@ def oracle_frame_census(f: Frame) -> np.ndarray:
     return oracle_loopfilter_census((y, u, v), f.frame)
 
 
+# oracle_loopfilter_arith_census (oracle/vp8_oracle.h): counts[LF_ARITH_PATHS][cell]; cell 0 of every path is
+# the number of filtered positions, None marks a cell the path does not have
+LF_ARITH_PATHS = ("simple", "MB edge, hev", "MB edge, no hev (MB adjust)", "sub-block edge, hev", "sub-block edge, no hev")
+_OUTER = ("calls", "p1-q1 > 127", "p1-q1 < -128", "a > 127", "a < -128", "a in 124..127", "q0-f1 < 0", "q0-f1 > 255",
+          "p0+f2 < 0", "p0+f2 > 255", None, None)
+_INNER = _OUTER[:1] + (None, None) + _OUTER[3:10] + ("p1+a2 | q1-a2 < 0", "p1+a2 | q1-a2 > 255")
+_MBADJ = ("calls", "w > 127", "w < -128", "p1/q1 tap < 0", "p1/q1 tap > 255", "p2/q2 tap < 0", "p2/q2 tap > 255",
+          "p1-q1 > 127", "p1-q1 < -128", "p0/q0 tap < 0", "p0/q0 tap > 255", None)
+LF_ARITH_CELLS = (_OUTER, _OUTER, _MBADJ, _OUTER, _INNER)
+
+
+def oracle_loopfilter_arith_census(planes, frame: Vp8DecodedFrame) -> np.ndarray:
+    """oracle_loopfilter_arith_census on padded planes (y, u, v as uint8 arrays; they are not modified):
+    uint64[5][12], per path of the filter how many edge positions drive each clamp of its arithmetic,
+    [LF_ARITH_PATHS][LF_ARITH_CELLS[path]]."""
+    lib = oracle_lib()
+    # bound here, as oracle_loopfilter_census is: an older liboracle.so still serves every other call
+    if not hasattr(lib, "oracle_loopfilter_arith_census"):
+        raise OSError("oracle/liboracle.so has no oracle_loopfilter_arith_census (rebuild it: `make` at the repo root)")
+    lib.oracle_loopfilter_arith_census.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Vp8DecodedFrame), C.c_void_p]
+    counts = np.zeros((len(LF_ARITH_PATHS), len(_OUTER)), dtype=np.uint64)
+    y, u, v = [np.ascontiguousarray(p, dtype=np.uint8) for p in planes]
+    if lib.oracle_loopfilter_arith_census(y.ctypes.data, u.ctypes.data, v.ctypes.data, C.byref(frame),
+                                          counts.ctypes.data) != 0:
+        raise RuntimeError("oracle arithmetic census failed")
+    return counts
+
+
+def oracle_frame_arith_census(f: Frame) -> np.ndarray:
+    """The arithmetic census of the loop filter on the frame's own unfiltered reconstruction."""
+    w, h = int(f.frame.mb_cols) * 16, int(f.frame.mb_rows) * 16
+    y, u, v = np.empty(w * h, np.uint8), np.empty(w * h // 4, np.uint8), np.empty(w * h // 4, np.uint8)
+    if oracle_lib().oracle_recon_padded(C.byref(f.frame), y.ctypes.data, u.ctypes.data, v.ctypes.data, 0) != 0:
+        raise RuntimeError("oracle failed")
+    return oracle_loopfilter_arith_census((y, u, v), f.frame)
+
+
 def ref_lib():
     """oracle/_ref/libref.so: the reference's own m01-m07 compiled here (may be absent)."""
     lib = _load("ref", REPO_DIR / "oracle" / "_ref" / "libref.so")
