@@ -283,6 +283,33 @@ int vp8g_decode_webp_batch_ex(const ByteSpan* files, uint32_t n, int filtered, u
  * every frame on the device).  0, or -1 + EINVAL. */
 int vp8g_plan_batch(const ByteSpan* files, uint32_t n, uint32_t threads, uint32_t flags, uint8_t* dev, uint32_t* order);
 
+/* The recon launch the library would make for a batch of descriptors (host code only, no device call,
+ * the environment is not read; for tests and tools): a device of `cus` compute units, the wave hint
+ * of vp8g_decode_batch_device (0 = none), the six launch switches as values (what VP8G_SPLIT,
+ * VP8G_WAVES, VP8G_CHAIN, VP8G_SPLITCHAIN, VP8G_CHAIN_IL and VP8G_ORDER would say: 0 / 0 / -1 / -1 /
+ * -1 / 1 when unset), the caller (`policy`) and whether the launch gate finds the device free of the
+ * library's other launches (may_cross).  The output base counts as 16-byte aligned.  0, or -1 + EINVAL. */
+#define VP8G_PLAN_REFERENCE 0u /* the reference entry points and vp8g_reconstruct_batch ... */
+#define VP8G_PLAN_PIPELINE 1u  /* ... or a chunk of the end-to-end batch path */
+#define VP8G_PLAN_NO_SPLIT 2u  /* | vp8g_decode_batch_device (asynchronous); a chunk that is not its call's only one */
+typedef struct {
+	uint32_t quad;       /* 1: the quad chain kernel; 0: the frame kernel, one (or `parts`) workgroups per frame */
+	uint32_t waves;      /* per workgroup */
+	uint32_t global_ctx; /* frame kernel: the per-column context in device memory */
+	uint32_t parts;      /* frame kernel: workgroups per frame */
+	uint32_t workgroups; /* the grid */
+	uint32_t ordered, mirror_split, interleave, whole; /* chain: cost-class placement; the modes; the lean instantiation */
+	uint32_t ord_first;  /* frame kernel: cost-balanced placement over this many CUs (0 = batch order) */
+	uint32_t lds_bytes;  /* dynamic LDS per workgroup */
+	uint32_t mode;       /* VP8G_MODE_* as vp8g_last_launch_mode reports it */
+	/* bytes the auxiliary buffers hold for either outcome of the gate: global context, mailboxes + progress
+	 * words, the chain's snapshots, the mirror split's flags */
+	uint64_t gctx_bytes, mbox_bytes, snap_bytes, flags_bytes;
+} Vp8gLaunchPlan;
+int vp8g_plan_launch(const Vp8gFrameDesc* descs, uint32_t n, uint32_t cus, uint32_t waves_hint, uint32_t split, uint32_t waves,
+                     int32_t chain, int32_t splitchain, int32_t chain_il, int32_t order, uint32_t policy, int may_cross,
+                     Vp8gLaunchPlan* out);
+
 /* Device m05 over n frames on `hip_stream`: h_jobs / d_jobs host and device copies of the jobs
  * (data = payload offset in d_bits, 4-aligned, with >= 512 readable bytes after the payload;
  * mb_offset = first MB in the arrays).  Writes ymode, uv_mode, segment_id, has_coeff, bmode and

@@ -1,5 +1,5 @@
 """Helper of tests/test_gpu_batch.py::test_chain_mirror_split_forced (run in a child process with
-VP8G_SPLITCHAIN=1, read once by libvp8g): the chain test's mixed small-frame batch (~7 frames per
+VP8G_SPLITCHAIN=1, set for the whole run): the chain test's mixed small-frame batch (~7 frames per
 workgroup, so every workgroup's list holds many top and bottom segments) decoded with every frame
 of more than four MB rows (more than one quad) split between two workgroups, each slot against the oracle."""
 import pathlib

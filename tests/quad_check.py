@@ -1,6 +1,6 @@
 """Batch decoded by the quad chain kernel (csrc/vp8g_quad.inc: four MB rows per wave; every chain
 batch), every slot against the oracle.  Imported by tests/test_gpu_quad.py,
-and run as a child process there when an environment switch read once by libvp8g must be set
+and run as a child process there when an environment switch of libvp8g must be set for the whole run
 (VP8G_SPLITCHAIN=1: every frame of more than four MB rows split between two workgroups).
 
 Frames (SIZES): widths multiples of 16 (whole 16-B / 8-B row pieces: the kernel's lean instantiation),

@@ -1,8 +1,9 @@
 """Split mode (small batches: one frame worked on by several workgroups that hand MB-row-pair
 context to each other through a device-memory mailbox) vs the oracle, at forced split factors.
 
-VP8G_SPLIT / VP8G_WAVES are read by the shim on every call (webp-decoder_amd/csrc/vp8g_shim.hip
-run_locked); VP8G_SPLIT=1 forces the one-workgroup-per-frame path.
+VP8G_SPLIT / VP8G_WAVES, like the other launch switches, are read on every call
+(webp-decoder_amd/csrc/vp8g_plan.hip knobs_from_env); VP8G_SPLIT=1 forces the
+one-workgroup-per-frame path.
 """
 import os
 

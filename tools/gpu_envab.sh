@@ -1,6 +1,6 @@
 #!/bin/bash
-# one library under several environment settings (env switches are read once per process, so each
-# setting is its own ab_inproc process on the same box): kernel medians per workload
+# one library under several environment settings (each setting is its own ab_inproc process on the
+# same box, set for that whole process): kernel medians per workload
 # Usage: tools/gpu_envab.sh [workloads, default "uhd4 fhd4"]
 set -o pipefail
 mkdir -p gpurun_out/envab

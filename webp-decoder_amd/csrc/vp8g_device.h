@@ -107,7 +107,7 @@ constexpr size_t kChainScratch = (size_t)16 * kQWaveBytes;  // the cost sort's s
 inline size_t chain_lds_bytes(uint32_t list_max) { return (size_t)kQList + 4 * (size_t)list_max; }
 
 // Process-wide launch gate (vp8g_shim.hip).  Launch modes whose workgroups wait on each other across
-// CUs -- split parts (launch_frames with nsplit > 1) and the chain's mirror split -- need every
+// CUs -- split parts (Launch::parts > 1) and the chain's mirror split -- need every
 // workgroup of the launch resident at once.  Beside another kernel of this library (an earlier
 // asynchronous batch on another stream, a pipeline chunk, a device-m05 or writer kernel) some of
 // them could wait for CUs that the others hold while they spin; two such launches side by side
@@ -137,56 +137,88 @@ class GateScope {
 	bool may_cross_ = false;
 };
 
-// Launch the fused recon(+LF) kernel.  `global_ctx` != nullptr selects the variant whose
-// per-column context lives in device memory (frames too wide for LDS); it must hold
-// n_frames * ctx_cols * kCtxBytesPerCol bytes.
-// nsplit > 1 (LDS context, 8 or 16 waves only): each frame is worked on by nsplit workgroups
-// that hand off through `mbox` (n_frames * nsplit * ctx_cols * kCtxBytesPerCol bytes) and
-// `gprog` (n_frames * nsplit words, zeroed before the launch).
-hipError_t launch_frames(const Vp8gFrameDesc* d_descs, uint32_t n_frames, const Vp8gBatchArrays& arrays,
-                         uint8_t* d_out, uint32_t ctx_cols, uint32_t max_mb_rows, uint8_t* global_ctx,
-                         hipStream_t stream, uint32_t waves_hint, uint32_t nsplit, uint8_t* mbox, uint32_t* gprog,
-                         uint32_t ord_first = 0);
-// ord_first != 0 (unsplit launches of more than ord_first frames): workgroup w decodes the frame at
-// position p(w) of the batch sorted by descending cost_class (stable): the first F = ord_first
-// workgroups the F heaviest frames, the next S = min(n - F, F) the S lightest in reverse (so the
-// heaviest frame shares its CU with the lightest), the rest the middle positions heaviest first.
-// pick_order returns F = the CU count when that is worth it (classes differ, more frames than
-// CUs), else 0.
-uint32_t pick_order(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t nsplit);
+// ---- Which kernel a batch runs on (vp8g_plan.hip) --------------------------------
+// The launch switches.  knobs_from_env reads all six from the environment on every call (so a
+// process may change them between calls: tests/test_gpu_split.py), over the compile-time defaults
+// (vp8g_plan.hip: VP8G_CHAIN_DEFAULT, VP8G_SPLITCHAIN_DEFAULT, VP8G_CHAIN_IL_DEFAULT, VP8G_NO_ORDER,
+// VP8G_FORCE_GCTX).
+struct Knobs {
+	uint32_t split;   // VP8G_SPLIT=<k>: workgroups per frame (1 = never split; 0 / unset: automatic)
+	uint32_t waves;   // VP8G_WAVES=<w>: waves per frame workgroup where the caller gives no hint
+	int chain;        // VP8G_CHAIN=0: never the chain; 1: also for batches of at most the CU count; -1: automatic
+	int splitchain;   // VP8G_SPLITCHAIN=0 / 1: the mirror split never / wherever it fits; -1: automatic
+	int chain_il;     // VP8G_CHAIN_IL=0: the two-frame interleave never; else wherever it fits
+	bool order;       // VP8G_ORDER=0 clears it: launch in batch order, no cost-class placement
+	bool force_gctx;  // (build switch only) the frame kernel's column context in device memory always
+};
+extern const Knobs kDefaultKnobs;
+Knobs knobs_from_env();
 
-// Chain mode for n_frames frames on this device: the workgroup count (0 = not applicable: too few
-// frames, a loop-filter-only frame in the batch -- the quad kernel has no such path, the batch runs
-// one workgroup per frame --, more than 1024 MB columns, or VP8G_CHAIN=0), and whether the frames
-// are placed by cost class (*ordered; needs the sort scratch to fit the wave areas).
-uint32_t pick_chain(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t ctx_cols, bool* ordered);
-// Mirror split of a chain launch (vp8g_quad.inc, kSegTop): worth it for ordered batches of at most
-// two frames per workgroup (VP8G_SPLITCHAIN=0 / 1 forces it off / on), and the doubled list must fit.
-bool pick_chain_split(uint32_t n_frames, uint32_t workgroups, bool ordered);
-// Two-frame interleave of a chain launch (vp8g_quad.inc): the frames of a workgroup's list run two
-// at a time with their quads alternating (the quad above is two global quads back), which halves
-// the chain's fill and drain.  Needs every frame of the batch the same size and no mirror split
-// (VP8G_CHAIN_IL=0 / 1 forces it off / on where it fits).
-bool pick_chain_interleave(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t workgroups, bool split);
-// whole_pieces: every frame has whole, aligned 16-B / 8-B row pieces, so launch_chain(..., whole = true)
-// takes the kernel's lean instantiation (the general one adds a byte path for pieces cut by the right
-// edge or unaligned planes).
-bool whole_pieces(const Vp8gFrameDesc* h_descs, uint32_t n_frames);
-// `snap` holds every frame's context, n_frames * ctx_cols * kCtxBytesPerCol bytes, in every mode.
-// split: `flags` holds n_frames words, none equal to `epoch` (a per-launch counter) before the launch.
-hipError_t launch_chain(const Vp8gFrameDesc* d_descs, uint32_t n_frames, const Vp8gBatchArrays& arrays, uint8_t* d_out,
-                        uint32_t ctx_cols, hipStream_t stream, uint32_t workgroups, bool ordered, bool whole, uint8_t* snap,
-                        bool split = false, uint32_t* flags = nullptr, uint32_t epoch = 0, bool interleave = false);
+// What the two callers of plan_launch do differently (DESIGN.md §3.3 has the history of each).
+struct LaunchPolicy {
+	bool may_split;         // split parts without VP8G_SPLIT > 1: the call is synchronous (the host APIs) / the call's only chunk
+	bool hint_plain;        // a non-zero wave hint means exactly that: no split parts, no chain
+	bool env_geometry;      // honours Knobs::split, waves and force_gctx
+	bool split_waves_stay;  // the gate refuses split parts: the whole-frame launch keeps their 8 waves
+	bool placement;         // whole-frame launches of more frames than CUs are placed by cost class
+	bool chain_extras;      // the chain may take the mirror split or the interleave
+	bool snap_in_gctx;      // the chain's snapshots live in the global-context buffer (no buffer of their own)
+};
+constexpr LaunchPolicy kReferencePolicy = {true, true, true, false, true, true, false};   // vp8g_shim.hip (may_split: see run_locked)
+constexpr LaunchPolicy kPipelinePolicy = {true, true, false, true, false, false, true};   // vp8g_pipeline.hip
+
+// One launch: frame_kernel<waves, gctx, parts > 1> over `workgroups` = n * parts workgroups, or the
+// quad chain kernel (vp8g_quad.inc) over one 16-wave workgroup per CU.
+struct Launch {
+	bool quad;        // the quad chain kernel, else the frame kernel
+	bool gctx;        // frame kernel: the variant whose per-column context lives in device memory (frames too wide for LDS)
+	bool ordered, split, interleave;  // chain: placed by cost class; mirror split (kSegTop); two frames interleaved
+	bool whole;       // chain: every frame has whole, aligned 16-B / 8-B row pieces -- the lean instantiation (the
+	                  // general one adds a byte path for pieces cut by the right edge or unaligned planes)
+	uint32_t waves;   // per workgroup
+	uint32_t parts;   // frame kernel: workgroups per frame, handing off through mailboxes (8 or 16 waves, LDS context only)
+	uint32_t workgroups;
+	// ord_first = F != 0 (whole-frame launches of more than F frames): workgroup w decodes the frame at
+	// position p(w) of the batch sorted by descending cost_class (stable): the first F workgroups the F
+	// heaviest frames, the next S = min(n - F, F) the S lightest in reverse (so the heaviest frame
+	// shares its CU with the lightest), the rest the middle positions heaviest first.  F = the CU count.
+	uint32_t ord_first;
+	uint32_t lds;     // dynamic LDS bytes
+	uint32_t mode;    // VP8G_MODE_* (vp8g_last_launch_mode)
+	bool crosses() const { return parts > 1 || split; }  // workgroups wait on each other across CUs (GateScope)
+};
+// Both outcomes of the launch gate, decided before it (so nothing is allocated inside it), and the
+// bytes the auxiliary buffers must hold for either.  Inside the gate, resolve() is all that is left.
+struct LaunchPlan {
+	uint32_t n, ctx_cols, max_rows;  // frames; the largest MB columns / rows of the batch
+	Launch open, shut;               // the gate allows a cross-workgroup launch / does not
+	size_t gctx_bytes;   // every frame's column context (n * ctx_cols * kCtxBytesPerCol)
+	size_t mbox_bytes;   // split parts: parts mailboxes per frame, each one frame's column context ...
+	size_t gprog_bytes;  // ... and one progress word per part, zeroed before the launch
+	size_t snap_bytes;   // chain: every frame's context between waves, and with it the mirror split's snapshots
+	size_t flags_bytes;  // mirror split: one word per frame, none equal to the launch's epoch before it
+	const Launch& resolve(bool may_cross) const { return may_cross ? open : shut; }
+};
+// Pure: no HIP call, no environment.  n_cus: the device's CU count (device_cus(); 0 = unknown: eight
+// waves, no chain, no split).  out_aligned: the output base is 16-byte aligned (else no `whole`).
+LaunchPlan plan_launch(const Vp8gFrameDesc* h_descs, uint32_t n, int n_cus, bool out_aligned, uint32_t waves_hint, const Knobs& knobs,
+                       const LaunchPolicy& policy);
 
 constexpr uint32_t kMaxSplit = 8;
 int device_cus();
-// Workgroups per frame for this batch: split_hint if non-zero, else CUs / frames, capped at
-// kMaxSplit and at one part per CU overall (all parts must be co-resident), 1 if not possible.
-uint32_t pick_split(uint32_t split_hint, uint32_t n_frames, uint32_t nw, uint32_t max_mb_rows);
 
-// Waves per workgroup the launcher would use for this batch (for LDS sizing decisions):
-// waves_hint if non-zero, else 8, or 16 when n_frames <= the device's CU count.
-uint32_t pick_waves(uint32_t waves_hint, uint32_t max_mb_rows, uint32_t n_frames);
+// The buffers a launch may use (device pointers; those the plan sized as 0 bytes may be null).
+struct LaunchBuffers {
+	uint8_t* gctx;
+	uint8_t* mbox;
+	uint32_t* gprog;
+	uint8_t* snap;  // (LaunchPolicy::snap_in_gctx: the caller passes its global-context buffer here as well)
+	uint32_t* flags;
+	uint32_t epoch;  // mirror split: this launch's counter value for `flags`
+};
+// Enqueue launch L of plan P (inside a GateScope).
+hipError_t launch(const LaunchPlan& P, const Launch& L, const Vp8gFrameDesc* d_descs, const Vp8gBatchArrays& arrays, uint8_t* d_out,
+                  const LaunchBuffers& b, hipStream_t stream);
 
 // vp8g_make_frame_desc; dense_coeffs = false skips the check of the coeff_* pointers (packed
 // frames: the coefficients reach the device through the expansion kernel).

@@ -588,7 +588,7 @@ struct Pref {
 // The fused kernel.
 // ---------------------------------------------------------------------------------------------
 // Occupancy target: two workgroups (frames) per CU at NW <= 8 (2*NW waves per CU); one
-// workgroup of 12 or 16 waves per CU for batches smaller than the CU count (pick_waves).  Either
+// workgroup of 12 or 16 waves per CU for batches smaller than the CU count (vp8g_plan.hip).  Either
 // way at most 4 waves per SIMD, i.e. the full 128-VGPR budget.
 template <int NW>
 constexpr int min_waves_per_simd() {
@@ -605,7 +605,7 @@ constexpr int min_waves_per_simd() {
 // ahead of use (MI355X_MICROARCH.md, inter-workgroup visibility: sc1 payload + drained flag).
 // Requires every part of a frame to be resident at once: the host splits only batches of at most
 // one part per CU.
-// The frame workgroup blockIdx.x decodes under the cost-balanced launch order (pick_order in
+// The frame workgroup blockIdx.x decodes under the cost-balanced launch order (ord_first in
 // vp8g_device.h): the position p of this workgroup in the sorted batch, then the frame at that
 // position -- a histogram of the n frames' cost classes gives p's class c and its rank r among
 // the frames of class c, and a block-wide ballot scan over the frames finds the r-th frame of
@@ -1571,17 +1571,16 @@ hipError_t lds_attr() {
 }
 
 template <int NW, bool kG, bool kS>
-hipError_t launch_t(const Vp8gFrameDesc* d_descs, uint32_t n, const Vp8gBatchArrays& arrays, uint8_t* d_out,
-                    uint32_t ctx_cols, uint8_t* gctx, uint32_t nsplit, uint8_t* mbox, uint32_t* gprog, hipStream_t stream,
-                    uint32_t ord_first = 0) {
-	const size_t lds = lds_bytes(NW, ctx_cols, kG);
+hipError_t launch_t(const LaunchPlan& P, const Launch& L, const Vp8gFrameDesc* d_descs, const Vp8gBatchArrays& arrays, uint8_t* d_out,
+                    const LaunchBuffers& b, hipStream_t stream) {
 	auto fn = frame_kernel<NW, kG, kS>;
-	if (lds > 65536) {
+	if (L.lds > 65536) {
 		hipError_t e = lds_attr<NW, kG, kS>();
 		if (e != hipSuccess) return e;
 	}
-	hipLaunchKernelGGL(fn, dim3(n * (kS ? nsplit : 1u)), dim3(NW * 64), lds, stream, d_descs, arrays, d_out, ctx_cols, gctx,
-	                   nsplit, mbox, gprog, kS ? 0u : ord_first);
+	// (the order maps positions >= ord_first: it needs more frames than that)
+	hipLaunchKernelGGL(fn, dim3(L.workgroups), dim3(NW * 64), L.lds, stream, d_descs, arrays, d_out, P.ctx_cols, kG ? b.gctx : nullptr,
+	                   L.parts, kS ? b.mbox : nullptr, kS ? b.gprog : nullptr, kS || L.ord_first >= P.n ? 0u : L.ord_first);
 	return hipGetLastError();
 }
 
@@ -1614,164 +1613,52 @@ int device_cus() {
 	return n_cus;
 }
 
-uint32_t pick_waves(uint32_t waves_hint, uint32_t max_mb_rows, uint32_t n_frames) {
-	static const uint32_t kSupported[] = {1, 2, 4, 8, 12, 16};
-	// default: 8 waves (two frames per CU) when the batch fills the chip; a batch with at most
-	// one frame per CU gets 16 waves per frame instead (twice the MB row pairs in flight)
-	const int n_cus = device_cus();
-	uint32_t want = waves_hint ? waves_hint : (n_cus > 0 && n_frames <= (uint32_t)n_cus ? 16u : 8u);
-	const uint32_t pairs = (max_mb_rows + 1) / 2;
-	if (want > pairs) want = pairs;  // no point in more waves than MB row pairs
-	uint32_t nw = 1;
-	for (uint32_t s : kSupported)
-		if (s <= want) nw = s;
-	return nw;
-}
-
-uint32_t pick_split(uint32_t split_hint, uint32_t n_frames, uint32_t nw, uint32_t max_mb_rows) {
-	if (nw != 8 && nw != 16) return 1;  // split kernels exist for these only
-	const int n_cus = device_cus();
-	const uint32_t pairs = (max_mb_rows + 1) / 2;
-	uint32_t k = split_hint ? split_hint : (n_cus > 0 ? (uint32_t)n_cus / (n_frames ? n_frames : 1u) : 1u);
-	if (k > kMaxSplit) k = kMaxSplit;
-	while (k > 1 && (k - 1) * nw >= pairs) k--;  // every part gets at least one pair
-	// all parts of all frames must be resident together: at most one part per CU
-	if (n_cus <= 0 || (uint64_t)n_frames * k > (uint64_t)n_cus) k = 1;
-	return k ? k : 1;
-}
-
-uint32_t pick_order(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t nsplit) {
-	static const bool off = [] {  // VP8G_ORDER=0: launch in batch order (A/B experiments)
-		const char* e = getenv("VP8G_ORDER");
-		return e && e[0] == '0';
-	}();
-#ifdef VP8G_NO_ORDER  // diagnostic build: batch order always
-	return 0;
-#endif
-	const int n_cus = device_cus();
-	if (off || nsplit > 1 || n_cus <= 0 || n_frames <= (uint32_t)n_cus) return 0;
-	const uint32_t c0 = cost_class(h_descs[0]);
-	for (uint32_t i = 1; i < n_frames; i++)
-		if (cost_class(h_descs[i]) != c0) return (uint32_t)n_cus;
-	return 0;  // uniform batch: the order would be the identity
-}
-
-uint32_t pick_chain(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t ctx_cols, bool* ordered) {
-#ifndef VP8G_CHAIN_DEFAULT  // (A/B builds: -DVP8G_CHAIN_DEFAULT=0)
-#define VP8G_CHAIN_DEFAULT -1
-#endif
-	static const int mode = [] {  // VP8G_CHAIN=0: never (A/B experiments), =1: also for batches <= the CU count
-		const char* e = getenv("VP8G_CHAIN");
-		return e ? atoi(e) : VP8G_CHAIN_DEFAULT;
-	}();
-	*ordered = false;
-	const int n_cus = device_cus();
-	if (mode == 0 || n_cus <= 0 || n_frames == 0 || (mode < 0 && n_frames <= (uint32_t)n_cus)) return 0;
-	// the quad kernel decodes every frame but loop-filter-only ones (frames without whole row pieces
-	// take its byte path at the right edge / for unaligned planes)
-	for (uint32_t i = 0; i < n_frames; i++)
-		if (h_descs[i].mb_cols != 0 && h_descs[i].mb_rows != 0 && (h_descs[i].flags & VP8G_F_LF_ONLY)) return 0;
-	const uint32_t wg = n_frames < (uint32_t)n_cus ? n_frames : (uint32_t)n_cus;
-	const uint32_t list_max = (n_frames + wg - 1) / wg;
-	if (ctx_cols > 1024 || chain_lds_bytes(list_max) > (size_t)kMaxLds) return 0;
-	// cost-class placement when the classes differ and the sort scratch fits the wave areas
-	const uint32_t c0 = cost_class(h_descs[0]);
-	bool differ = false;
-	for (uint32_t i = 1; i < n_frames && !differ; i++) differ = cost_class(h_descs[i]) != c0;
-	*ordered = differ && (size_t)4 * (kCostClasses + n_frames) <= kChainScratch && pick_order(h_descs, n_frames, 1) != 0;
-	return wg;
-}
-
-bool pick_chain_split(uint32_t n_frames, uint32_t workgroups, bool ordered) {
-#ifndef VP8G_SPLITCHAIN_DEFAULT  // (A/B builds: -DVP8G_SPLITCHAIN_DEFAULT=0 / 1)
-#define VP8G_SPLITCHAIN_DEFAULT -1
-#endif
-	static const int mode = [] {  // VP8G_SPLITCHAIN=0: never, =1: whenever it fits (A/B experiments, tests)
-		const char* e = getenv("VP8G_SPLITCHAIN");
-		return e ? atoi(e) : VP8G_SPLITCHAIN_DEFAULT;
-	}();
-	if (mode == 0 || workgroups == 0) return false;
-	const uint32_t list_max = (n_frames + workgroups - 1) / workgroups;
-	if (chain_lds_bytes(2 * list_max) > (size_t)kMaxLds) return false;
-	return mode > 0 || (ordered && list_max <= 2);
-}
-
-bool pick_chain_interleave(const Vp8gFrameDesc* h_descs, uint32_t n_frames, uint32_t workgroups, bool split) {
-#ifndef VP8G_CHAIN_IL_DEFAULT  // (A/B builds: -DVP8G_CHAIN_IL_DEFAULT=0)
-#define VP8G_CHAIN_IL_DEFAULT -1
-#endif
-	static const int mode = [] {  // VP8G_CHAIN_IL=0: never, =1: wherever it fits (A/B experiments, tests)
-		const char* e = getenv("VP8G_CHAIN_IL");
-		return e ? atoi(e) : VP8G_CHAIN_IL_DEFAULT;
-	}();
-	if (mode == 0 || split || workgroups == 0 || n_frames < 2 * workgroups) return false;
-	for (uint32_t i = 1; i < n_frames; i++)
-		if (h_descs[i].mb_cols != h_descs[0].mb_cols || h_descs[i].mb_rows != h_descs[0].mb_rows) return false;
-	if (h_descs[0].mb_rows < 2) return false;
-	const uint32_t list_max = (n_frames + workgroups - 1) / workgroups;
-	return chain_lds_bytes(list_max) <= (size_t)kMaxLds;
-}
-
-bool whole_pieces(const Vp8gFrameDesc* h_descs, uint32_t n_frames) {
-	// every 16-B luma / 8-B chroma row piece inside its frame and aligned (the output base is at least
-	// 16-B aligned): the quad kernel's lean instantiation
-	for (uint32_t i = 0; i < n_frames; i++) {
-		const Vp8gFrameDesc& d = h_descs[i];
-		if (d.mb_cols == 0 || d.mb_rows == 0) continue;
-		if (d.width != 16u * d.mb_cols || ((d.out_y | d.stride_y) & 15u) != 0 || ((d.out_u | d.stride_uv | (d.out_v - d.out_u)) & 7u) != 0)
-			return false;
-	}
-	return true;
-}
-
-hipError_t launch_chain(const Vp8gFrameDesc* d_descs, uint32_t n_frames, const Vp8gBatchArrays& arrays, uint8_t* d_out,
-                        uint32_t ctx_cols, hipStream_t stream, uint32_t workgroups, bool ordered, bool whole, uint8_t* snap,
-                        bool split, uint32_t* flags, uint32_t epoch, bool interleave) {
-	if (n_frames == 0) return hipSuccess;
-	if (!snap || (split && !flags) || (interleave && split)) return hipErrorInvalidValue;
-	const uint32_t list_max = (n_frames + workgroups - 1) / workgroups;
-	const size_t lds = chain_lds_bytes(split ? 2 * list_max : list_max);
+// The two launchers run what the plan says (vp8g_plan.hip decides; nothing is decided here).
+static hipError_t launch_chain(const LaunchPlan& P, const Launch& L, const Vp8gFrameDesc* d_descs, const Vp8gBatchArrays& arrays,
+                               uint8_t* d_out, const LaunchBuffers& b, hipStream_t stream) {
+	if (!b.snap || (L.split && !b.flags) || (L.interleave && L.split)) return hipErrorInvalidValue;
 	static const hipError_t eq1 =
 	    hipFuncSetAttribute((const void*)quad_kernel<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
 	static const hipError_t eq0 =
 	    hipFuncSetAttribute((const void*)quad_kernel<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
 	if (eq1 != hipSuccess) return eq1;
 	if (eq0 != hipSuccess) return eq0;
-	auto fq = whole ? quad_kernel<16, true> : quad_kernel<16, false>;
-	hipLaunchKernelGGL(fq, dim3(workgroups), dim3(16 * 64), lds, stream, d_descs, arrays, d_out, ctx_cols, snap,
-	                   split ? epoch : 1u, split ? flags : nullptr, (ordered ? 1u : 0u) | (split ? 2u : 0u) | (interleave ? 4u : 0u),
-	                   n_frames);
+	auto fq = L.whole ? quad_kernel<16, true> : quad_kernel<16, false>;
+	hipLaunchKernelGGL(fq, dim3(L.workgroups), dim3(16 * 64), L.lds, stream, d_descs, arrays, d_out, P.ctx_cols, b.snap,
+	                   L.split ? b.epoch : 1u, L.split ? b.flags : nullptr,
+	                   (L.ordered ? 1u : 0u) | (L.split ? 2u : 0u) | (L.interleave ? 4u : 0u), P.n);
 	return hipGetLastError();
 }
 
-hipError_t launch_frames(const Vp8gFrameDesc* d_descs, uint32_t n_frames, const Vp8gBatchArrays& arrays,
-                         uint8_t* d_out, uint32_t ctx_cols, uint32_t max_mb_rows, uint8_t* global_ctx,
-                         hipStream_t stream, uint32_t waves_hint, uint32_t nsplit, uint8_t* mbox, uint32_t* gprog,
-                         uint32_t ord_first) {
-	if (n_frames == 0) return hipSuccess;
-	if (ord_first >= n_frames) ord_first = 0;  // (the order maps positions >= ord_first; needs n > ord_first)
-	const uint32_t nw = pick_waves(waves_hint, max_mb_rows, n_frames);
-	const bool g = global_ctx != nullptr;
-	if (nsplit > 1 && !g && (nw == 8 || nw == 16)) {
-		if (!mbox || !gprog) return hipErrorInvalidValue;
-		return nw == 8 ? launch_t<8, false, true>(d_descs, n_frames, arrays, d_out, ctx_cols, nullptr, nsplit, mbox, gprog, stream)
-		               : launch_t<16, false, true>(d_descs, n_frames, arrays, d_out, ctx_cols, nullptr, nsplit, mbox, gprog, stream);
+static hipError_t launch_frames(const LaunchPlan& P, const Launch& L, const Vp8gFrameDesc* d_descs, const Vp8gBatchArrays& arrays,
+                                uint8_t* d_out, const LaunchBuffers& b, hipStream_t stream) {
+	if (L.parts > 1) {  // (split kernels exist for 8 and 16 waves and the LDS context only)
+		if (!b.mbox || !b.gprog || L.gctx || (L.waves != 8 && L.waves != 16)) return hipErrorInvalidValue;
+		return L.waves == 8 ? launch_t<8, false, true>(P, L, d_descs, arrays, d_out, b, stream)
+		                    : launch_t<16, false, true>(P, L, d_descs, arrays, d_out, b, stream);
 	}
-#define VP8G_CASE(N)                                                                                                          \
-	case N:                                                                                                                   \
-		return g ? launch_t<N, true, false>(d_descs, n_frames, arrays, d_out, ctx_cols, global_ctx, 1, nullptr, nullptr, stream, \
-		                                    ord_first)                                                                        \
-		         : launch_t<N, false, false>(d_descs, n_frames, arrays, d_out, ctx_cols, nullptr, 1, nullptr, nullptr, stream, ord_first);
-	switch (nw) {
+	if (L.gctx && !b.gctx) return hipErrorInvalidValue;
+#define VP8G_CASE(N) \
+	case N:          \
+		return L.gctx ? launch_t<N, true, false>(P, L, d_descs, arrays, d_out, b, stream) : launch_t<N, false, false>(P, L, d_descs, arrays, d_out, b, stream);
+	switch (L.waves) {
 		VP8G_CASE(1)
 		VP8G_CASE(2)
 		VP8G_CASE(4)
 		VP8G_CASE(8)
 		VP8G_CASE(12)
-		default:
 		VP8G_CASE(16)
+		default:
+			return hipErrorInvalidValue;
 	}
 #undef VP8G_CASE
 }
 
+hipError_t launch(const LaunchPlan& P, const Launch& L, const Vp8gFrameDesc* d_descs, const Vp8gBatchArrays& arrays, uint8_t* d_out,
+                  const LaunchBuffers& b, hipStream_t stream) {
+	if (P.n == 0) return hipSuccess;
+	return L.quad ? launch_chain(P, L, d_descs, arrays, d_out, b, stream) : launch_frames(P, L, d_descs, arrays, d_out, b, stream);
+}
+
 }  // namespace vp8g
+

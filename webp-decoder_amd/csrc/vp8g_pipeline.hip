@@ -461,7 +461,7 @@ struct ChunkShape {
 	uint64_t outb = 0, soutb = 0, ab = 0, asb = 0;  // bytes of I420, scaled I420, alpha planes, scaled alpha planes
 };
 
-ChunkLayout make_layout(const ChunkShape& sh, bool tok, const Sinks& sk, uint32_t k_plan) {
+ChunkLayout make_layout(const ChunkShape& sh, bool tok, const Sinks& sk, const vp8g::LaunchPlan& plan) {
 	const uint64_t mbs = sh.mbs, nf = sh.nf;
 	ChunkLayout L;
 	uint64_t o = 0;
@@ -484,8 +484,8 @@ ChunkLayout make_layout(const ChunkShape& sh, bool tok, const Sinks& sk, uint32_
 	// (every frame's column context: the global-context variant for frames too wide for LDS, and
 	// the quad chain kernel, whose rows hand over through device memory)
 	L.gctx = o, o = al256(o + nf * sh.max_cols * vp8g::kCtxBytesPerCol);
-	L.mbox = o, o = al256(o + (k_plan > 1 ? nf * k_plan * sh.max_cols * vp8g::kCtxBytesPerCol : 0));
-	L.gprog = o, o = al256(o + (k_plan > 1 ? nf * k_plan * 4 : 0));
+	L.mbox = o, o = al256(o + plan.mbox_bytes);
+	L.gprog = o, o = al256(o + plan.gprog_bytes);
 	L.out = o, o = al256(o + sh.outb);
 	L.sdesc = o, o = al256(o + (sk.opts ? nf * sizeof(Vp8gScaleDesc) : 0));
 	L.sout = o, o = al256(o + sh.soutb);
@@ -509,8 +509,7 @@ struct Chunk {
 	hipStream_t stream;
 	std::vector<uint32_t> idx;
 	ChunkShape sh;
-	uint32_t nw = 0, k_plan = 1;  // launch geometry: waves per frame workgroup; parts per frame, if the gate allows
-	bool big = false;             //   too wide for the LDS column context
+	vp8g::LaunchPlan plan = {};  // the recon launch, for either outcome of the launch gate
 	ChunkLayout L;
 	std::vector<uint32_t> sj;             // chunk position of each scale descriptor
 	std::vector<Vp8gTensorAlpha> aplane;  // per chunk position: where the tensor kernel finds the frame's alpha
@@ -712,31 +711,39 @@ struct Pipeline {
 		}
 		sh.nf = (uint32_t)c.idx.size();
 	}
-	// Launch geometry (the choices vp8g_reconstruct_batch makes).  Split mode (a frame over several co-resident workgroups
-	// that spin on each other) only for a call's only chunk: other slots' streams could hold the CUs a part is waiting for.
-	void plan_launch(Chunk& c) const {
-		const bool alone = c.a == 0 && c.b == n;
-		c.nw = vp8g::pick_waves(0, c.sh.max_rows, c.sh.nf);
-		if (alone && vp8g::pick_split(0, c.sh.nf, 8, c.sh.max_rows) > 1) c.nw = 8;
-		c.big = vp8g::lds_bytes((int)c.nw, c.sh.max_cols, false) > (size_t)vp8g::kMaxLds;
-		c.k_plan = c.big || !alone ? 1u : vp8g::pick_split(0, c.sh.nf, c.nw, c.sh.max_rows);
-	}
-	// Frame descriptors and output images, and the chunk's input onto its stream (a device-m05 chunk's payloads and
-	// m05 jobs, a host-m05 one's side arrays, block masks and packed values); then the descriptors and a zero status word.
-	Status upload_chunk(Chunk& c) {
+	// Frame descriptors and output images of the chunk's frames.
+	void describe_chunk(Chunk& c) {
 		Slot& s = c.s;
-		const ChunkLayout& L = c.L;
 		s.descs.assign(c.sh.nf, Vp8gFrameDesc{});
-		if (c.tok) s.jobs.resize(c.sh.nf);
-		uint64_t mo = 0, po = 0, oo = 0;  // offsets in the chunk: MBs, payload (bitstream bytes / packed values), output bytes
-		for (uint32_t j = 0; j < c.sh.nf && c.up_err == hipSuccess; j++) {
+		uint64_t mo = 0, oo = 0;  // offsets in the chunk: MBs, output bytes
+		for (uint32_t j = 0; j < c.sh.nf; j++) {
 			const uint32_t fi = c.idx[j];
 			const Vp8KeyFrameHeader& kf = kf_of(fi);
-			const uint64_t mt = f_of(fi).mb_total;
 			if (vp8g::make_desc(&kf, &f_of(fi), filtered_of(fi), mo, oo, &s.descs[j], false) != 0 || alloc_out(fi, kf.width, kf.height) != 0) {
 				feed.err[fi] = errno ? errno : EINVAL;  // (cannot happen for a frame the host front end accepted)
 				s.descs[j].flags = 0;
 			}
+			mo += f_of(fi).mb_total;
+			oo = al256(oo + vp8g_i420_size(kf.width, kf.height));
+		}
+	}
+	// The recon launch (vp8g_plan.hip, kPipelinePolicy).  Split mode (a frame over several co-resident workgroups that
+	// spin on each other) only for a call's only chunk: other slots' streams could hold the CUs a part is waiting for.
+	void plan_launch(Chunk& c) const {
+		vp8g::LaunchPolicy pol = vp8g::kPipelinePolicy;
+		pol.may_split = c.a == 0 && c.b == n;
+		c.plan = vp8g::plan_launch(c.s.descs.data(), c.sh.nf, vp8g::device_cus(), true, 0, vp8g::knobs_from_env(), pol);
+	}
+	// The chunk's input onto its stream (a device-m05 chunk's payloads and m05 jobs, a host-m05 one's side arrays, block
+	// masks and packed values); then the descriptors and a zero status word.
+	Status upload_chunk(Chunk& c) {
+		Slot& s = c.s;
+		const ChunkLayout& L = c.L;
+		if (c.tok) s.jobs.resize(c.sh.nf);
+		uint64_t mo = 0, po = 0;  // offsets in the chunk: MBs, payload (bitstream bytes / packed values)
+		for (uint32_t j = 0; j < c.sh.nf && c.up_err == hipSuccess; j++) {
+			const uint32_t fi = c.idx[j];
+			const uint64_t mt = f_of(fi).mb_total;
 			if (c.tok) {
 				const TokJob& t = feed.tj[fi];
 				s.jobs[j] = t.tf;
@@ -758,7 +765,6 @@ struct Pipeline {
 				po += p.n_values;
 			}
 			mo += mt;
-			oo = al256(oo + vp8g_i420_size(kf.width, kf.height));
 		}
 		if (c.tok) c.up(L.jobs, s.jobs);
 		if (c.up_err != hipSuccess) return c.up_status();
@@ -773,14 +779,14 @@ struct Pipeline {
 	// when no other launch of the library is in flight.
 	Status launch_recon(Chunk& c) {
 		const ChunkLayout& L = c.L;
-		const uint32_t nf = c.sh.nf, max_cols = c.sh.max_cols;
+		const uint32_t nf = c.sh.nf;
 		uint8_t* d = c.s.buf;
 		hipStream_t stream = c.stream;
 		vp8g::GateScope gate(stream);
 		if (gate.status() != hipSuccess) return Status{gate.status(), "hipStreamWaitEvent(gate)"};
-		const uint32_t k = c.k_plan > 1 && gate.may_cross() ? c.k_plan : 1u;
-		if (k > 1)
-			if (hipError_t e = hipMemsetAsync(d + L.gprog, 0, (size_t)nf * k * 4, stream); e != hipSuccess) return Status{e, "memset"};
+		const vp8g::Launch& run = c.plan.resolve(gate.may_cross());
+		if (run.parts > 1)
+			if (hipError_t e = hipMemsetAsync(d + L.gprog, 0, c.plan.gprog_bytes, stream); e != hipSuccess) return Status{e, "memset"};
 		Vp8gBatchArrays arr{(const int16_t*)(d + L.cy), (const int16_t*)(d + L.cu), (const int16_t*)(d + L.cv), (const int16_t*)(d + L.cy2),
 		                    d + L.ym, d + L.uvm, d + L.seg, d + L.hasc, d + L.bm, /*src=*/nullptr, (uint32_t*)(d + L.status)};
 		if (c.tok) {
@@ -794,17 +800,11 @@ struct Pipeline {
 			                   (uint32_t)c.sh.mbs, (int16_t*)(d + L.cy), (int16_t*)(d + L.cu), (int16_t*)(d + L.cv), (int16_t*)(d + L.cy2));
 			if (hipError_t e = hipGetLastError(); e != hipSuccess) return Status{e, "expand launch"};
 		}
-		bool ordered = false;
-		const uint32_t wg = c.big || k > 1 ? 0u : vp8g::pick_chain(c.s.descs.data(), nf, max_cols, &ordered);
-		const hipError_t e =
-		    wg  // more frames than CUs: one 16-wave chain of frames per CU
-		        ? vp8g::launch_chain((const Vp8gFrameDesc*)(d + L.desc), nf, arr, d + L.out, max_cols, stream, wg, ordered,
-		                             vp8g::whole_pieces(c.s.descs.data(), nf), d + L.gctx)
-		        : vp8g::launch_frames((const Vp8gFrameDesc*)(d + L.desc), nf, arr, d + L.out, max_cols, c.sh.max_rows,
-		                              c.big ? d + L.gctx : nullptr, stream, c.nw, k, k > 1 ? d + L.mbox : nullptr,
-		                              k > 1 ? (uint32_t*)(d + L.gprog) : nullptr);
-		if (e != hipSuccess) return Status{e, "recon launch"};
-		return Status{gate.done(k > 1), "hipEventRecord(gate)"};
+		// (the gctx region holds the frame kernel's global context or the chain's context between waves: never both)
+		const vp8g::LaunchBuffers bufs = {d + L.gctx, d + L.mbox, (uint32_t*)(d + L.gprog), d + L.gctx, nullptr, 0};
+		if (hipError_t e = vp8g::launch(c.plan, run, (const Vp8gFrameDesc*)(d + L.desc), arr, d + L.out, bufs, stream); e != hipSuccess)
+			return Status{e, "recon launch"};
+		return Status{gate.done(run.crosses()), "hipEventRecord(gate)"};
 	}
 	// A batch of scale descriptors (the frames', the alpha planes') to `off` of the chunk's buffer and through the rescaler.
 	Status scale_batch(Chunk& c, const std::vector<Vp8gScaleDesc>& v, uint64_t off, const char* where) {
@@ -942,8 +942,9 @@ struct Pipeline {
 	}
 	// A gathered chunk (with at least one frame) through its slot's buffer and stream, every stage in enqueue order.
 	Status launch_chunk(Chunk& c) {
+		describe_chunk(c);
 		plan_launch(c);
-		c.L = make_layout(c.sh, c.tok, sk, c.k_plan);
+		c.L = make_layout(c.sh, c.tok, sk, c.plan);
 		const double tg = trace ? ms_now() : 0.0;
 		if (hipError_t e = grow(c.s, c.L.total); e != hipSuccess) return Status{e, "hipMalloc(chunk)"};
 		const uint32_t si = (uint32_t)(&c.s - slots);

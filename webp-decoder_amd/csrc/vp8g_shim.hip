@@ -340,104 +340,48 @@ InLayout in_layout(uint64_t mbs, uint64_t src_bytes) {
 		}                             \
 	} while (0)
 
-// VP8G_SPLIT=<k>: workgroups per frame (1 = never split); unset: automatic for the host APIs.
-uint32_t split_env() {
-	const char* e = getenv("VP8G_SPLIT");
-	return e ? (uint32_t)strtoul(e, nullptr, 10) : 0u;
-}
-
 // Launch over device-resident data with the buffers of the leased context g.  `may_split`: the
 // call completes (stream synchronised) before its lease ends.  Launch modes whose workgroups wait on
 // each other across CUs (split parts, the chain's mirror split) need every workgroup of the launch
-// resident: they are chosen only when the launch gate (vp8g_device.h, GateScope) reports no other
-// launch of the library in flight, and every later launch on another stream is ordered after them.
-int run_locked(DevState& g_dev, const std::vector<Vp8gFrameDesc>& descs, const Vp8gBatchArrays& arr, uint8_t* d_out, hipStream_t s,
+// resident: the plan (vp8g_plan.hip) holds them as the outcome for an open launch gate
+// (vp8g_device.h, GateScope: no other launch of the library in flight), and every later launch on
+// another stream is ordered after them.
+int run_locked(DevState& g, const std::vector<Vp8gFrameDesc>& descs, const Vp8gBatchArrays& arr, uint8_t* d_out, hipStream_t s,
                uint32_t waves_hint, uint8_t* d_descs, bool may_split) {
-	uint32_t max_cols = 0, max_rows = 0;
-	for (const auto& d : descs) {
-		if (d.mb_cols > max_cols) max_cols = d.mb_cols;
-		if (d.mb_rows > max_rows) max_rows = d.mb_rows;
-	}
-	const uint32_t n = (uint32_t)descs.size();
 	g_mode = 0u;  // (a call that fails before its launch reports no mode, not the previous call's)
-	if (g_dev.pending) {  // the previous (asynchronous) launch on this context's buffers comes first
-		HIP_TRY(hipStreamWaitEvent(s, g_dev.done, 0), "hipStreamWaitEvent");
+	if (g.pending) {  // the previous (asynchronous) launch on this context's buffers comes first
+		HIP_TRY(hipStreamWaitEvent(s, g.done, 0), "hipStreamWaitEvent");
 	}
-	if (!waves_hint) {
-		const char* e = getenv("VP8G_WAVES");  // override of the default waves per workgroup
-		if (e) waves_hint = (uint32_t)strtoul(e, nullptr, 10);
-	}
-	const uint32_t env = split_env();
-	// Buffers for every mode this call could pick, before the gate (growing may wait for this context's
-	// previous launch, or release idle contexts' buffers).  A call that the gate then keeps from the
+	vp8g::LaunchPolicy pol = vp8g::kReferencePolicy;
+	pol.may_split = may_split;
+	const vp8g::LaunchPlan P = vp8g::plan_launch(descs.data(), (uint32_t)descs.size(), vp8g::device_cus(), ((uintptr_t)d_out & 15u) == 0,
+	                                             waves_hint, vp8g::knobs_from_env(), pol);
+	// Buffers for either outcome of the gate, before it (growing may wait for this context's previous
+	// launch, or release idle contexts' buffers).  A call that the gate then keeps from the
 	// cross-workgroup modes (another launch in flight) holds mailbox / snapshot memory it did not use
 	// this time: the price of never allocating inside the gate, bounded by trim_idle.
-	uint32_t nw = vp8g::pick_waves(waves_hint, max_rows, n);
-	const bool try_split = (may_split || env > 1) && env != 1 && !waves_hint;
-	const uint32_t nw_split = try_split && vp8g::pick_split(env, n, 8, max_rows) > 1 ? 8u : nw;
-#ifdef VP8G_FORCE_GCTX  // diagnostic: per-column context in device memory for every frame
-	const bool big = true;
-#else
-	const bool big = vp8g::lds_bytes((int)nw, max_cols, false) > (size_t)vp8g::kMaxLds;
-#endif
-	const bool big_split = vp8g::lds_bytes((int)nw_split, max_cols, false) > (size_t)vp8g::kMaxLds;
-	uint8_t* gctx = nullptr;
-	if (big) {
-		const size_t need = descs.size() * (size_t)max_cols * vp8g::kCtxBytesPerCol;
-		HIP_TRY(grow(g_dev, &g_dev.gctx, &g_dev.gctx_cap, need), "hipMalloc(ctx)");
-		gctx = g_dev.gctx;
-	}
-	const uint32_t k_want = !big_split && try_split ? vp8g::pick_split(env, n, nw_split, max_rows) : 1u;
-	if (k_want > 1) {
-		const size_t mb = (size_t)n * k_want * max_cols * vp8g::kCtxBytesPerCol, pb = (size_t)n * k_want * sizeof(uint32_t);
-		HIP_TRY(grow(g_dev, &g_dev.mbox, &g_dev.mbox_cap, mb + pb), "hipMalloc(mailbox)");
-	}
-	bool ordered = false;
-	const uint32_t wg = !big && !waves_hint ? vp8g::pick_chain(descs.data(), n, max_cols, &ordered) : 0u;
-	const bool split_want = wg && vp8g::pick_chain_split(n, wg, ordered);
-	if (wg)  // (the chain's context between waves, and with it the mirror split's snapshots)
-		HIP_TRY(grow(g_dev, &g_dev.snap, &g_dev.snap_cap, (size_t)n * max_cols * vp8g::kCtxBytesPerCol), "hipMalloc(context)");
-	if (split_want) {
-		const size_t old_cap = g_dev.sflags_cap;
-		HIP_TRY(grow(g_dev, &g_dev.sflags, &g_dev.sflags_cap, (size_t)n * sizeof(uint32_t)), "hipMalloc(flags)");
-		if (g_dev.sflags_cap != old_cap) g_dev.epoch = 0;  // (fresh flags: zeroed below)
-	}
-	g_dev.pending = false;
+	HIP_TRY(grow(g, &g.gctx, &g.gctx_cap, P.gctx_bytes), "hipMalloc(ctx)");
+	HIP_TRY(grow(g, &g.mbox, &g.mbox_cap, P.mbox_bytes + P.gprog_bytes), "hipMalloc(mailbox)");
+	HIP_TRY(grow(g, &g.snap, &g.snap_cap, P.snap_bytes), "hipMalloc(context)");
+	const size_t old_cap = g.sflags_cap;
+	HIP_TRY(grow(g, &g.sflags, &g.sflags_cap, P.flags_bytes), "hipMalloc(flags)");
+	if (g.sflags_cap != old_cap) g.epoch = 0;  // (fresh flags: zeroed below)
+	g.pending = false;
 
 	vp8g::GateScope gate(s);
 	HIP_TRY(gate.status(), "hipStreamWaitEvent(gate)");
-	const bool alone = gate.may_cross();
-	// small batches on the host APIs: 8-wave parts, up to kMaxSplit per frame (measured on one 4K
-	// frame: 8 waves x 8 parts 3.9 ms per call, 16 waves x 1..8 parts 8.1..4.7 ms)
-	const uint32_t k = alone && k_want > 1 ? k_want : 1u;
-	bool crossed = k > 1;
-	g_mode = k > 1 ? VP8G_MODE_SPLIT_PARTS : 0u;
-	if (k > 1) {
-		const size_t mb = (size_t)n * k * max_cols * vp8g::kCtxBytesPerCol, pb = (size_t)n * k * sizeof(uint32_t);
-		HIP_TRY(hipMemsetAsync(g_dev.mbox + mb, 0, pb, s), "memset(progress)");
-		HIP_TRY(vp8g::launch_frames((const Vp8gFrameDesc*)d_descs, n, arr, d_out, max_cols, max_rows, nullptr, s, nw_split, k, g_dev.mbox,
-		                            (uint32_t*)(g_dev.mbox + mb), 0),
-		        "launch");
-	} else if (wg) {  // more frames than CUs: one 16-wave chain of frames per CU
-		// mirror split (vp8g_quad.inc, kSegTop): snapshot flags of a fresh epoch
-		const bool split = alone && split_want;
-		if (split && (g_dev.epoch == 0 || ++g_dev.epoch == 0)) {  // (epoch 0 = the zeroed flags: never used)
-			g_dev.epoch = 1;
-			HIP_TRY(hipMemsetAsync(g_dev.sflags, 0, g_dev.sflags_cap, s), "memset(flags)");
-		}
-		crossed = split;
-		const bool il = vp8g::pick_chain_interleave(descs.data(), n, wg, split);  // (1080p batches: two frames interleaved)
-		g_mode = VP8G_MODE_CHAIN | VP8G_MODE_QUAD | (split ? VP8G_MODE_MIRROR_SPLIT : 0u) | (il ? VP8G_MODE_INTERLEAVE : 0u);
-		HIP_TRY(vp8g::launch_chain((const Vp8gFrameDesc*)d_descs, n, arr, d_out, max_cols, s, wg, ordered,
-		                           vp8g::whole_pieces(descs.data(), n) && ((uintptr_t)d_out & 15u) == 0, g_dev.snap, split,
-		                           (uint32_t*)g_dev.sflags, g_dev.epoch, il),
-		        "launch");
-	} else {
-		const uint32_t ord = vp8g::pick_order(descs.data(), n, 1);  // cost-balanced placement (vp8g_device.h)
-		HIP_TRY(vp8g::launch_frames((const Vp8gFrameDesc*)d_descs, n, arr, d_out, max_cols, max_rows, gctx, s, nw, 1, nullptr, nullptr, ord),
-		        "launch");
+	const vp8g::Launch& L = P.resolve(gate.may_cross());
+	g_mode = L.mode;
+	uint32_t* const gprog = (uint32_t*)(g.mbox + P.mbox_bytes);
+	if (L.parts > 1) HIP_TRY(hipMemsetAsync(gprog, 0, P.gprog_bytes, s), "memset(progress)");
+	// mirror split (vp8g_quad.inc, kSegTop): snapshot flags of a fresh epoch
+	if (L.split && (g.epoch == 0 || ++g.epoch == 0)) {  // (epoch 0 = the zeroed flags: never used)
+		g.epoch = 1;
+		HIP_TRY(hipMemsetAsync(g.sflags, 0, g.sflags_cap, s), "memset(flags)");
 	}
-	HIP_TRY(gate.done(crossed), "hipEventRecord(gate)");
+	const vp8g::LaunchBuffers bufs = {g.gctx, g.mbox, gprog, g.snap, (uint32_t*)g.sflags, g.epoch};
+	HIP_TRY(vp8g::launch(P, L, (const Vp8gFrameDesc*)d_descs, arr, d_out, bufs, s), "launch");
+	HIP_TRY(gate.done(L.crosses()), "hipEventRecord(gate)");
 	return 0;
 }
 

@@ -94,6 +94,13 @@ class Vp8gFrameDesc(C.Structure):
     ]
 
 
+class Vp8gLaunchPlan(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in (
+        "quad", "waves", "global_ctx", "parts", "workgroups", "ordered", "mirror_split", "interleave", "whole",
+        "ord_first", "lds_bytes", "mode")] + [(n, C.c_uint64) for n in (
+            "gctx_bytes", "mbox_bytes", "snap_bytes", "flags_bytes")]
+
+
 class Vp8gBatchArrays(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "coeff_y", "coeff_u", "coeff_v", "coeff_y2", "ymode", "uv_mode", "segment_id", "has_coeff",
@@ -312,6 +319,19 @@ def host_lib():
 
 # vp8g_last_launch_mode bits (include/vp8g.h)
 MODE_CHAIN, MODE_MIRROR_SPLIT, MODE_INTERLEAVE, MODE_QUAD, MODE_SPLIT_PARTS = 1, 2, 4, 8, 16
+# vp8g_plan_launch callers
+PLAN_REFERENCE, PLAN_PIPELINE, PLAN_NO_SPLIT = 0, 1, 2
+
+
+def plan_launch(descs, cus: int, *, hint: int = 0, split: int = 0, waves: int = 0, chain: int = -1, splitchain: int = -1,
+                chain_il: int = -1, order: int = 1, policy: int = PLAN_REFERENCE, may_cross: bool = True) -> Vp8gLaunchPlan:
+    """vp8g_plan_launch: the recon launch the library makes for `descs` (a ctypes array of Vp8gFrameDesc)
+    on a device of `cus` CUs.  Host code only: no device call, the environment is not read."""
+    out = Vp8gLaunchPlan()
+    if gpu_lib().vp8g_plan_launch(descs, len(descs), cus, hint, split, waves, chain, splitchain, chain_il, order, policy,
+                                  int(may_cross), C.byref(out)) != 0:
+        raise ValueError(f"vp8g_plan_launch: errno={C.get_errno()}")
+    return out
 
 
 def gpu_lib():
@@ -339,6 +359,10 @@ def gpu_lib():
         lib.vp8g_abi_version.restype = C.c_uint32
         if hasattr(lib, "vp8g_last_launch_mode"):  # (libraries built before round 5 lack it: A/B of old builds)
             lib.vp8g_last_launch_mode.restype = C.c_uint32
+        if hasattr(lib, "vp8g_plan_launch"):  # (A/B of libraries built before it existed)
+            lib.vp8g_plan_launch.argtypes = [P(Vp8gFrameDesc), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                             C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_int,
+                                             P(Vp8gLaunchPlan)]
         lib.yuv420_write_ppm_fd.argtypes = [C.c_int, P(Yuv420Image)]
         lib.yuv420_write_png_fd.argtypes = [C.c_int, P(Yuv420Image)]
         lib.vp8g_encoded_size.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
