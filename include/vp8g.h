@@ -626,6 +626,87 @@ int vp8g_decode_webp_batch_tensor_x(const ByteSpan* files, uint32_t n, int filte
                                     const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, uint32_t xflags,
                                     void* d_out, int* status);
 
+/* ---- Lossless (VP8L) images ----------------------------------------------- */
+
+/* A VP8L stream entropy-decodes on the host (vp8f_lossless_decode, host/vp8_front.h) into an ARGB
+ * residual image and a list of up to four transforms; inverting those runs on the device.  One
+ * transform of an image, as the stream spells it (RFC 9649 4): */
+#define VP8G_L_PREDICTOR 0u
+#define VP8G_L_CROSS_COLOR 1u
+#define VP8G_L_SUBTRACT_GREEN 2u
+#define VP8G_L_COLOR_INDEX 3u
+typedef struct {
+	uint64_t data;    /* byte offset in the source buffer of the sub-image (predictor, cross colour: div_up(xsize, bits) x
+	                   * div_up(height, bits) dwords) or of the colour table (ncolors dwords, prefix-summed); any alignment */
+	uint32_t type;    /* VP8G_L_* */
+	uint32_t bits;    /* predictor, cross colour: 2 .. 9; colour index: 3 / 2 / 1 / 0 for up to 2 / 4 / 16 / 256 colours */
+	uint32_t xsize;   /* the image's width when the transform was read */
+	uint32_t ncolors; /* colour index: 1 .. 256 */
+} Vp8gLosslessTransform;
+
+/* Per-image descriptor (built by vp8g_make_lossless_desc).  128 bytes. */
+typedef struct {
+	uint64_t src;            /* byte offset of the residual image in the source buffer (any alignment): tight dwords,
+	                          * height rows of the last transform's input width (the packed width after colour indexing) */
+	uint64_t dst;            /* byte offset (a multiple of 4) of the tight width x height 0xAARRGGBB output */
+	uint32_t width, height;  /* 1 .. 16383 */
+	uint32_t ntransforms;    /* 0 .. 4, in stream order; inverted last to first */
+	uint32_t task0;          /* this image's workgroup task in the launch (one per image) */
+	Vp8gLosslessTransform tr[4];
+} Vp8gLosslessDesc;
+
+/* 0, or -1 + EINVAL: NULL, a size of 0 or beyond 16383, more than four transforms, a type twice, bits
+ * or ncolors out of range, an xsize that is not the width the stream would have at that point, dst
+ * not a multiple of 4. */
+int vp8g_make_lossless_desc(uint32_t width, uint32_t height, uint64_t src, uint64_t dst, uint32_t ntransforms,
+                            const Vp8gLosslessTransform* tr, uint32_t task0, Vp8gLosslessDesc* out);
+
+/* The kernel's geometry, for tests that aim at its boundaries: out[0] = columns per barrier group (the tile step),
+ * out[1] = rows per wave (a band), out[2] = bands per workgroup round. */
+void vp8g_lossless_geometry(uint32_t out[3]);
+
+/* Invert the transforms of n images of mixed sizes and transform lists in one launch on `hip_stream`.
+ * One 16-wave workgroup per image; the predictor runs as a skewed wavefront (a row per lane, each row
+ * two columns behind the row above), paced by workgroup barriers only: no workgroup waits on another,
+ * nothing spins on memory, there is no timeout path.  Writes only each image's own width x height
+ * dwords (which also serve as its working buffer).  Asynchronous; 0 or -1 + errno (EINVAL: NULL pointer,
+ * n = 0, d_dst not dword-aligned, an invalid or inconsistent descriptor -- checked before any launch;
+ * EIO on a launch failure). */
+int vp8g_lossless_batch_device(const Vp8gLosslessDesc* h_descs, const Vp8gLosslessDesc* d_descs, uint32_t n,
+                               const uint8_t* d_src, uint8_t* d_dst, void* hip_stream);
+
+/* One image of the ARGB tensor kernel: src = byte offset (a multiple of 4) of tight width x height
+ * 0xAARRGGBB dwords, as vp8g_lossless_batch_device leaves them; dst = byte offset of the picture's slot. */
+typedef struct {
+	uint64_t src, dst;
+	uint32_t task0, ntasks;
+} Vp8gTensorArgbDesc;
+
+/* channels = 3 or 4.  0, or -1 + EINVAL. */
+int vp8g_make_tensor_argb_desc(const Vp8gTensorOpt* opt, uint32_t channels, uint64_t src, uint64_t dst_offset, uint32_t task0,
+                               Vp8gTensorArgbDesc* out);
+
+/* vp8g_tensor_batch_device / _a for ARGB sources: channels = 3 writes slots of vp8g_tensor_slot_size
+ * bytes (alpha dropped, as `dwebp -ppm` drops it), channels = 4 slots of vp8g_tensor_slot_size_a bytes.
+ * R, G, B: the arithmetic of vp8g_tensor_batch_device; A: that of vp8g_tensor_batch_device_a. */
+int vp8g_tensor_batch_device_argb(const Vp8gTensorArgbDesc* h_descs, const Vp8gTensorArgbDesc* d_descs, uint32_t n,
+                                  const Vp8gTensorOpt* opt, uint32_t channels, const uint8_t* d_src, void* d_dst,
+                                  void* hip_stream);
+
+/* vp8g_decode_webp_batch_tensor_x, which with VP8G_X_LOSSLESS also decodes lossless files (a simple
+ * 'VP8L' file, or VP8X + 'VP8L'): lossy and lossless files may share a batch and a tensor.  A worker
+ * thread entropy-decodes a lossless frame (vp8f_lossless_decode); its residual image and transform data
+ * are uploaded into the chunk buffer and go through vp8g_lossless_batch_device and
+ * vp8g_tensor_batch_device_argb on the chunk's stream (3 channels without VP8G_X_ALPHA, 4 with).
+ * Scaling a lossless frame is not supported: one whose resolved scale option is not the identity gets
+ * status[i] = ENOTSUP and a zero slot.  A size mismatch with the tensor or a stream that does not
+ * decode is EINVAL.  Without VP8G_X_LOSSLESS: vp8g_decode_webp_batch_tensor_x.  Other xflags bits: EINVAL.
+ * The lossless buffers count against the chunk memory budget; vp8g_plan_batch does not price them. */
+#define VP8G_X_LOSSLESS 2u
+int vp8g_decode_webp_batch_tensor_any(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                      const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, uint32_t xflags,
+                                      void* d_out, int* status);
+
 /* Name of the last HIP error seen by this library in the calling thread ("" if none). */
 const char* vp8g_last_error(void);
 

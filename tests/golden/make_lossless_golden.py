@@ -1,0 +1,263 @@
+#!/usr/bin/env python3
+"""Regenerate tests/golden/lossless/*.webp and tests/golden/lossless.json: the fixtures of the lossless
+(VP8L) path and libwebp's answer for each of them.
+
+The authority is the libwebp installed on the build machine (1.2.2, libwebp.so.7).  A small probe
+(tools/libwebp_lossless_probe.c) is compiled into a temporary directory and linked against it; nothing is
+written outside that directory, tests/golden/lossless/ and lossless.json.
+
+Every fixture is libwebp's LOSSLESS encoding (exact, methods 0 / 4 / 6, several qualities) of a seeded ARGB
+picture of the kinds make_alpha_golden.py draws -- gradient + rectangles + noise, the same with a disc as
+alpha, tiles, regions of mixed statistics, palettes of 2 / 4 / 16 / 40 colours, one colour -- wrapped by hand
+as a simple RIFF/WEBP/VP8L file, as VP8X + VP8L with metadata, or truncated / corrupted.
+For each file lossless.json records libwebp's verdict, the picture size, sha256 of WebPDecodeRGBA's bytes
+and -- where the project's host decoder reads the stream -- the Vp8fAlphaStats it reported, the transforms in
+stream order with their block sizes, and the predictor modes the stream's mode image names.  "uncovered" lists
+the predictor modes, block sizes and counters that no fixture libwebp decodes reaches.
+
+Usage: python tests/golden/make_lossless_golden.py [--check]
+"""
+import hashlib
+import importlib.util
+import json
+import pathlib
+import struct
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = pathlib.Path(__file__).resolve().parent.parent.parent
+OUT = ROOT / "tests" / "golden" / "lossless.json"
+DIR = ROOT / "tests" / "golden" / "lossless"
+LIBWEBP = "/usr/lib/x86_64-linux-gnu/libwebp.so.7"
+INCLUDE = "/opt/conda/include"
+sys.path.insert(0, str(ROOT / "webp-decoder_amd"))
+
+_spec = importlib.util.spec_from_file_location("make_alpha_golden", ROOT / "tests" / "golden" / "make_alpha_golden.py")
+ag = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(ag)
+chunk, riff, vp8x, chunks_of = ag.chunk, ag.riff, ag.vp8x, ag.chunks_of
+
+
+class Probe:
+    def __init__(self, tmp: pathlib.Path):
+        self.tmp = tmp
+        self.exe = tmp / "probe"
+        subprocess.run(["gcc", "-std=c11", "-O2", "-I", INCLUDE, "-o", str(self.exe),
+                        str(ROOT / "tools" / "libwebp_lossless_probe.c"), LIBWEBP], check=True)
+
+    def rgba(self, data: bytes):
+        src, dst = self.tmp / "in.webp", self.tmp / "out.rgba"
+        src.write_bytes(data)
+        r = subprocess.run([str(self.exe), "rgba", str(src), str(dst)], capture_output=True, text=True)
+        if r.returncode != 0:
+            return None
+        w, h, has_alpha = (int(v) for v in r.stdout.split())
+        b = dst.read_bytes()
+        assert len(b) == w * h * 4
+        return {"size": [w, h], "has_alpha": has_alpha, "rgba": hashlib.sha256(b).hexdigest()}
+
+    def lossless(self, argb: np.ndarray, method: int = 4, quality: int = 75) -> bytes:
+        """The VP8L chunk payload libwebp's lossless encoder writes for uint32 [h, w] 0xAARRGGBB pixels."""
+        src, dst = self.tmp / "in.argb", self.tmp / "out.webp"
+        src.write_bytes(argb.astype("<u4").tobytes())
+        h, w = argb.shape
+        subprocess.run([str(self.exe), "lossless", str(w), str(h), str(src), str(method), str(quality), str(dst)], check=True)
+        (tag, payload), = [c for c in chunks_of(dst.read_bytes()) if c[0] == b"VP8L"]
+        return payload
+
+
+def pack(rgba: np.ndarray) -> np.ndarray:
+    p = rgba.astype(np.uint32)
+    return p[:, :, 3] << 24 | p[:, :, 0] << 16 | p[:, :, 1] << 8 | p[:, :, 2]
+
+
+def content(kind: str, w: int, h: int, seed: int) -> np.ndarray:
+    """A seeded uint32 [h, w] 0xAARRGGBB picture."""
+    rng = np.random.default_rng(seed)
+    if kind in ("pic", "smooth"):
+        return pack(ag.picture(w, h, seed, noise=6 if kind == "pic" else 1))
+    if kind == "disc":
+        p = ag.picture(w, h, seed, noise=2)
+        p[:, :, 3] = ag.alpha_content("disc", w, h, seed)
+        return pack(p)
+    if kind in ("tiles", "mixed"):
+        return pack(np.stack([ag.alpha_content(kind, w, h, seed + k) for k in range(3)] + [np.full((h, w), 255, np.uint8)], axis=-1))
+    if kind.startswith("levels"):
+        n = int(kind[6:])
+        _, idx = np.unique(ag.alpha_content(kind, w, h, seed), return_inverse=True)
+        pal = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+        return pal[idx.reshape(h, w) % n]
+    if kind == "one":
+        return np.full((h, w), 0x80C04020, np.uint32)
+    raise ValueError(kind)
+
+
+# (kind, (w, h), (method, quality))
+FIXTURES = [
+    ("pic", (1, 1), (4, 75)), ("pic", (37, 21), (0, 10)), ("pic", (67, 45), (4, 75)), ("pic", (257, 70), (4, 50)),
+    ("smooth", (160, 100), (6, 100)), ("smooth", (192, 128), (4, 75)), ("smooth", (257, 70), (0, 0)),
+    ("disc", (67, 45), (4, 75)), ("disc", (160, 100), (0, 0)), ("disc", (257, 70), (6, 100)),
+    ("tiles", (160, 100), (4, 75)), ("tiles", (67, 45), (6, 100)),
+    ("mixed", (192, 128), (4, 75)), ("mixed", (257, 70), (0, 25)),
+    ("levels2", (37, 21), (4, 75)), ("levels2", (257, 70), (6, 100)),
+    ("levels4", (67, 45), (4, 75)), ("levels4", (37, 21), (0, 10)),
+    ("levels16", (160, 100), (4, 75)), ("levels16", (37, 21), (6, 100)),
+    ("levels40", (192, 128), (4, 75)), ("levels40", (67, 45), (0, 50)),
+    ("one", (1, 1), (4, 75)), ("one", (37, 21), (4, 75)),
+]
+
+
+def fixture_name(kind, size, mq):
+    return f"{kind}_{size[0]}x{size[1]}_m{mq[0]}q{mq[1]}"
+
+
+def build_fixtures(pr: Probe) -> dict:
+    files, payload = {}, {}
+    for kind, (w, h), (m, q) in FIXTURES:
+        name = fixture_name(kind, (w, h), (m, q))
+        payload[name] = pr.lossless(content(kind, w, h, w * 13 + h * 7 + m), m, q)
+        files[name] = riff(chunk(b"VP8L", payload[name]))
+    # VP8X + VP8L
+    p, (w, h) = payload["pic_67x45_m4q75"], (67, 45)
+    files["x_meta"] = riff(vp8x(ag.F_ICC | ag.F_EXIF | ag.F_XMP, w, h) + chunk(b"ICCP", b"icc" * 11) + chunk(b"zzzz", b"odd")
+                           + chunk(b"VP8L", p) + chunk(b"EXIF", b"Exif\0\0II") + chunk(b"XMP ", b"<x/>"))
+    files["x_alpha_flag"] = riff(vp8x(ag.F_ALPHA, w, h) + chunk(b"VP8L", payload["disc_67x45_m4q75"]))
+    files["x_alph_ignored"] = riff(vp8x(ag.F_ALPHA, w, h) + chunk(b"ALPH", bytes([0]) + bytes(w * h)) + chunk(b"VP8L", p))
+    files["x_canvas_mismatch"] = riff(vp8x(0, w + 1, h) + chunk(b"VP8L", p))
+    files["x_anim_flag"] = riff(vp8x(ag.F_ANIM, w, h) + chunk(b"VP8L", p))
+    files["x_anmf"] = riff(vp8x(0, w, h) + chunk(b"ANMF", b"\0" * 16 + chunk(b"VP8L", p)))
+    body = chunk(b"VP8L", p)
+    files["c_riff_small"] = riff(body + b"trailing bytes", len(body) + 4)
+    files["c_riff_big"] = riff(body, len(body) + 4 + 10)
+    files["c_chunk_overrun"] = riff(b"VP8L" + struct.pack("<I", len(p) + 1000) + p)
+    # headers and streams that do not decode
+    files["bad_signature"] = riff(chunk(b"VP8L", b"\x2e" + p[1:]))
+    files["bad_version"] = riff(chunk(b"VP8L", p[:4] + bytes([p[4] | 0x20]) + p[5:]))
+    for name in ("pic_67x45_m4q75", "smooth_160x100_m6q100", "levels4_67x45_m4q75"):
+        q = payload[name]
+        files["bad_trunc_" + name.split("_m")[0]] = riff(chunk(b"VP8L", q[:len(q) // 2]))
+        files["bad_trunc8_" + name.split("_m")[0]] = riff(chunk(b"VP8L", q[:8]))
+    q = payload["smooth_160x100_m6q100"]
+    for k, off in enumerate((5, 7, 10)):  # the transform bits / the first prefix-code headers
+        b = bytearray(q)
+        b[off] ^= 0xFF
+        files[f"bad_corrupt{k}"] = riff(chunk(b"VP8L", bytes(b)))
+    return files
+
+
+# 3840 x 2160 streams for tools/lossless_bench.py's end-to-end leg: (name, kind, (method, quality)).  Written to
+# tests/golden/lossless_bench/NAME.webp; each stays under 600 000 bytes.
+BENCH_DIR = ROOT / "tests" / "golden" / "lossless_bench"
+BENCH = [("uhd_flat", "flat", (4, 75)), ("uhd_bands16", "bands16", (4, 75))]
+
+
+def build_bench(pr: Probe):
+    import vp8g
+    out, doc = {}, {}
+    w, h = 3840, 2160
+    for name, kind, (m, q) in BENCH:
+        if kind == "flat":  # gradients and rectangles without noise, a disc as alpha
+            p = ag.picture(w, h, 21, noise=0)
+            p[:, :, 3] = ag.alpha_content("disc", w, h, 21)
+            argb = pack(p)
+        else:  # sixteen colours in blocks: a colour-indexed stream
+            y, x = np.mgrid[0:h, 0:w]
+            pal = np.random.default_rng(21).integers(0, 1 << 32, 16, dtype=np.uint64).astype(np.uint32)
+            argb = pal[((x // 40 + y // 24) * 7 + (x * y) // 90000) % 16]
+        data = riff(chunk(b"VP8L", pr.lossless(argb, m, q)))
+        assert len(data) < 600000, (name, len(data))
+        got = vp8g.host_lossless_argb(data)
+        assert np.array_equal(got, argb)  # (exact)
+        out[name] = data
+        doc[name] = {"bytes": len(data), "sha256": hashlib.sha256(data).hexdigest(), "size": [w, h], "ours": ours(vp8g, data),
+                     "rgba": hashlib.sha256(vp8g.argb_to_rgba(argb).tobytes()).hexdigest()}
+        del doc[name]["ours"]["stats"]
+    return out, doc
+
+
+TYPE_NAMES = ("predictor", "cross_color", "subtract_green", "color_index")
+
+
+def ours(vp8g, data: bytes) -> dict:
+    """What the project's host decoder says of the file."""
+    try:
+        c = vp8g.parse_any(data)
+    except OSError as e:
+        return {"errno": e.errno}
+    if not c["lossless"]:
+        return {"errno": 0, "lossless": False}
+    try:
+        im = vp8g.lossless_decode_host(data[c["vp8l_chunk_offset"]:c["vp8l_chunk_offset"] + c["vp8l_chunk_size"]])
+    except OSError as e:
+        return {"errno": e.errno}
+    d = {"errno": 0, "stats": im["stats"], "transforms": [], "modes": []}
+    for t in im["transforms"]:
+        d["transforms"].append({"type": TYPE_NAMES[t["type"]], "bits": t["bits"], "ncolors": t["ncolors"]})
+        if t["type"] == vp8g.L_PREDICTOR:
+            d["modes"] = sorted(int(m) for m in np.unique((t["data"] >> 8) & 15))
+    return d
+
+
+def generate():
+    import vp8g
+    with tempfile.TemporaryDirectory() as td:
+        pr = Probe(pathlib.Path(td))
+        files = build_fixtures(pr)
+        entries = {}
+        for name, data in sorted(files.items()):
+            e = {"bytes": len(data), "sha256": hashlib.sha256(data).hexdigest()}
+            d = pr.rgba(data)
+            e["decodes"] = d is not None
+            if d:
+                e.update(d)
+            e["ours"] = ours(vp8g, data)
+            entries[name] = e
+        bench_files, bench_doc = build_bench(pr)
+    good = [e["ours"] for e in entries.values() if e["decodes"] and e["ours"].get("stats")]
+    modes = {m for o in good for m in o["modes"]}
+    pbits = {t["bits"] for o in good for t in o["transforms"] if t["type"] == "predictor"}
+    cbits = {t["bits"] for o in good for t in o["transforms"] if t["type"] == "cross_color"}
+    reached = {n for o in good for n, v in o["stats"].items() if v}
+    why = "not emitted by libwebp 1.2.2's lossless encoder at methods 0 / 4 / 6 on any picture of the set"
+    uncovered = {
+        "predictor_modes": [m for m in range(16) if m not in modes],
+        "predictor_bits": [b for b in range(2, 10) if b not in pbits],
+        "cross_color_bits": [b for b in range(2, 10) if b not in cbits],
+        "stats": [n for n in vp8g.ALPHA_STATS if n not in reached and n != "raw"],
+        "why": why + "; tests/test_gpu_lossless.py reaches every mode and block size with synthetic mode images",
+    }
+    doc = {
+        "about": "libwebp's answers for tests/golden/lossless/*.webp (tests/golden/make_lossless_golden.py; probe tools/libwebp_lossless_probe.c)",
+        "libwebp": "1.2.2 (libwebp.so.7)",
+        "uncovered": uncovered,
+        "files": entries,
+        "bench": bench_doc,
+    }
+    return files, doc, bench_files
+
+
+def main() -> int:
+    files, doc, bench = generate()
+    text = json.dumps(doc, indent=1) + "\n"
+    if "--check" in sys.argv[1:]:
+        same = OUT.exists() and OUT.read_text() == text and all(
+            (DIR / f"{n}.webp").exists() and (DIR / f"{n}.webp").read_bytes() == b for n, b in files.items()) and all(
+            (BENCH_DIR / f"{n}.webp").exists() and (BENCH_DIR / f"{n}.webp").read_bytes() == b for n, b in bench.items())
+        print("lossless golden: identical" if same else "lossless golden: DIFFERS")
+        return 0 if same else 1
+    DIR.mkdir(exist_ok=True)
+    BENCH_DIR.mkdir(exist_ok=True)
+    for n, b in bench.items():
+        (BENCH_DIR / f"{n}.webp").write_bytes(b)
+    for n, b in files.items():
+        (DIR / f"{n}.webp").write_bytes(b)
+    OUT.write_text(text)
+    print(f"wrote {len(files)} fixtures ({sum(len(b) for b in files.values())} bytes) and {OUT} ({len(text)} bytes)")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -110,6 +110,7 @@ struct Freer {
 	std::mutex mu;
 	std::condition_variable cv;
 	std::vector<std::vector<Vp8gPackedFrame>> q;
+	std::vector<std::vector<Vp8fLosslessImage>> ql;  // lossless frames' residual images and transform data
 	bool stop = false;
 	std::thread th;
 	void post(std::vector<Vp8gPackedFrame>&& v) {
@@ -118,15 +119,24 @@ struct Freer {
 		q.push_back(std::move(v));
 		cv.notify_one();
 	}
+	void post(std::vector<Vp8fLosslessImage>&& v) {
+		std::lock_guard<std::mutex> lk(mu);
+		if (!th.joinable()) th = std::thread([this] { run(); });
+		ql.push_back(std::move(v));
+		cv.notify_one();
+	}
 	void run() {
 		std::unique_lock<std::mutex> lk(mu);
 		for (;;) {
-			cv.wait(lk, [this] { return stop || !q.empty(); });
-			if (q.empty()) return;  // (stop with nothing queued)
-			std::vector<Vp8gPackedFrame> v = std::move(q.back());
-			q.pop_back();
+			cv.wait(lk, [this] { return stop || !q.empty() || !ql.empty(); });
+			if (q.empty() && ql.empty()) return;  // (stop with nothing queued)
+			std::vector<Vp8gPackedFrame> v;
+			std::vector<Vp8fLosslessImage> vl;
+			if (!q.empty()) v = std::move(q.back()), q.pop_back();
+			else vl = std::move(ql.back()), ql.pop_back();
 			lk.unlock();
 			for (Vp8gPackedFrame& p : v) vp8f_packed_free(&p);
+			for (Vp8fLosslessImage& im : vl) vp8f_lossless_free(&im);
 			lk.lock();
 		}
 	}
@@ -162,6 +172,9 @@ struct Feed {
 	bool alpha = false;             // also entropy-decode the ALPH chunk (VP8G_X_ALPHA): ares[i] = the residual plane
 	std::vector<uint8_t*> ares;     // (malloc; NULL = no alpha; freed with the frame's host data)
 	std::vector<uint32_t> afilter;
+	bool lossless = false;          // VP8G_X_LOSSLESS: a file whose image chunk is VP8L is entropy-decoded into ll[i]
+	std::vector<uint8_t> is_ll;     // frame i is lossless (it has no kf / pk / tj; it rides in the chunk its position falls in)
+	std::vector<Vp8fLosslessImage> ll;  // (freed with the frame's host data)
 	std::vector<Vp8gPackedFrame> pk;
 	std::vector<TokJob> tj;
 	std::vector<int> err;
@@ -183,15 +196,21 @@ struct Feed {
 			}
 			const uint32_t i = order[pos];
 			int stage = 0, e = 0;
+			WebPContainerL any;
 			if (!files[i].data) e = EINVAL;
-			else if (dev[i]) {
+			else if (lossless && webp_parse_any(files[i], &any) != 0) e = errno ? errno : EINVAL;  // (a lossy file: webp_parse_extended's errno)
+			else if (lossless && any.vp8l_chunk_offset) {
+				is_ll[i] = 1;
+				if (vp8f_lossless_decode(files[i].data + any.vp8l_chunk_offset, any.vp8l_chunk_size, &ll[i], nullptr) != 0)
+					e = errno ? errno : EINVAL;
+			} else if (dev[i]) {
 				TokJob& j = tj[i];
 				if (vp8f_token_header_memory(files[i].data, files[i].size, &j.kf, &j.hdr, &j.tf, &j.poff, &j.psize, &stage,
 				                             fflags) != 0)
 					e = errno ? errno : EINVAL;
 			} else if (vp8f_decode_packed_memory(files[i].data, files[i].size, &pk[i], &stage, fflags) != 0)
 				e = errno ? errno : EINVAL;
-			if (alpha && e == 0) {  // a picture whose ALPH does not decode fails as a whole, as in libwebp
+			if (alpha && e == 0 && !is_ll[i]) {  // a picture whose ALPH does not decode fails as a whole, as in libwebp
 				WebPContainerX x;
 				const Vp8KeyFrameHeader& kf = dev[i] ? tj[i].kf : pk[i].kf;
 				if (webp_parse_extended(files[i], &x) == 0 && x.alph_chunk_offset) {
@@ -252,6 +271,8 @@ struct Slot {
 	std::vector<Vp8gAlphaDesc> adescs;   // alpha sink: the chunk's frames that have an ALPH plane
 	std::vector<Vp8gScaleDesc> asdescs;  //   their alpha planes through the rescaler
 	std::vector<Vp8gTensorAlpha> talpha; //   one per tensor descriptor
+	std::vector<Vp8gLosslessDesc> ldescs;     // lossless sink: the chunk's lossless frames
+	std::vector<Vp8gTensorArgbDesc> ltdescs;  //   and their tensor descriptors
 	std::vector<Vp8gTokFrame> jobs;  // device m05
 	uint32_t status = 0;
 	std::vector<D2H> d2h;          // the chunk's downloads (issued by a Copier)
@@ -330,7 +351,7 @@ struct Copier {
 
 struct ChunkLayout {
 	uint64_t ym, uvm, seg, hasc, bm, masks, mboff, vals, cy, cu, cv, cy2, bits, jobs, desc, status, gctx, mbox, gprog, out,
-	    sdesc, sout, tdesc, ares, aout, asout, adesc, asdesc, talpha, total;
+	    sdesc, sout, tdesc, ares, aout, asout, adesc, asdesc, talpha, lsrc, lout, ldesc, ltdesc, total;
 };
 
 hipError_t grow(Slot& s, size_t need) {
@@ -425,6 +446,7 @@ struct Sinks {
 	uint8_t* d_tensor = nullptr;
 	bool extended = false;                // the extended container (VP8X) in front
 	bool alpha = false;                   // VP8G_X_ALPHA: ALPH planes become the tensor's fourth channel
+	bool lossless = false;                // VP8G_X_LOSSLESS: lossless files decode as well (vp8g_lossless.hip)
 	uint64_t tslot = 0;                   // bytes per tensor slot (decode_batch fills it in)
 	const Vp8gScaleOpt* opt_of(uint32_t i) const { return opts ? &opts[n_opts == 1 ? 0 : i] : nullptr; }
 };
@@ -459,6 +481,8 @@ struct ChunkShape {
 	uint32_t nf = 0, max_cols = 0, max_rows = 0;
 	uint64_t mbs = 0, vals = 0, bitsb = 0;          // macroblocks; packed values (host m05); bitstream slots (device m05)
 	uint64_t outb = 0, soutb = 0, ab = 0, asb = 0;  // bytes of I420, scaled I420, alpha planes, scaled alpha planes
+	uint32_t nl = 0;                                // lossless frames
+	uint64_t lsrcb = 0, loutb = 0;                  // bytes of their residual images + transform data, of their ARGB pictures
 };
 
 ChunkLayout make_layout(const ChunkShape& sh, bool tok, const Sinks& sk, const vp8g::LaunchPlan& plan) {
@@ -496,6 +520,10 @@ ChunkLayout make_layout(const ChunkShape& sh, bool tok, const Sinks& sk, const v
 	L.adesc = o, o = al256(o + (sk.alpha ? nf * sizeof(Vp8gAlphaDesc) : 0));
 	L.asdesc = o, o = al256(o + (sk.alpha ? nf * sizeof(Vp8gScaleDesc) : 0));
 	L.talpha = o, o = al256(o + (sk.alpha ? nf * sizeof(Vp8gTensorAlpha) : 0));
+	L.lsrc = o, o = al256(o + sh.lsrcb);
+	L.lout = o, o = al256(o + sh.loutb);
+	L.ldesc = o, o = al256(o + sh.nl * sizeof(Vp8gLosslessDesc));
+	L.ltdesc = o, o = al256(o + sh.nl * sizeof(Vp8gTensorArgbDesc));
 	L.total = o;
 	return L;
 }
@@ -508,6 +536,7 @@ struct Chunk {
 	Slot& s;
 	hipStream_t stream;
 	std::vector<uint32_t> idx;
+	std::vector<uint32_t> lidx;  // the chunk's lossless frames (not in idx: they have no macroblocks and skip every stage but their own)
 	ChunkShape sh;
 	vp8g::LaunchPlan plan = {};  // the recon launch, for either outcome of the launch gate
 	ChunkLayout L;
@@ -551,6 +580,7 @@ struct Pipeline {
 	// ~0.3 s at 1024 4K frames), work the caller need not wait for.
 	bool defer_release = false;
 	std::vector<Vp8gPackedFrame> late;
+	std::vector<Vp8fLosslessImage> late_ll;  // (the same for lossless frames: 4 bytes per pixel of residuals each)
 	bool finished = false;  // every chunk retired (set by the caller); else the destructor takes the failure path,
 	Status failure;         //   with the device failure if that is why
 	~Pipeline() {
@@ -561,6 +591,8 @@ struct Pipeline {
 		if (!finished) {
 			for (Vp8gPackedFrame& p : late) vp8f_packed_free(&p);  // (inline: there is no result to hurry back with)
 			late.clear();
+			for (Vp8fLosslessImage& im : late_ll) vp8f_lossless_free(&im);
+			late_ll.clear();
 			for (hipStream_t st : all)
 				if (st) (void)hipStreamSynchronize(st);
 			if (!failure.ok()) vp8g::set_error_text(failure.where ? failure.where : "pipeline", failure.he);
@@ -578,9 +610,15 @@ struct Pipeline {
 		} catch (...) {  // (no thread, no memory: `late` is untouched)
 			for (Vp8gPackedFrame& p : late) vp8f_packed_free(&p);
 		}
+		try {
+			if (!late_ll.empty()) g_freer.post(std::move(late_ll));
+		} catch (...) {
+			for (Vp8fLosslessImage& im : late_ll) vp8f_lossless_free(&im);
+		}
 		for (size_t i = 0; i < feed.dev.size(); i++) {  // failed frames (the others were freed per chunk)
 			if (!feed.dev[i]) vp8f_packed_free(&feed.pk[i]);
 			free(feed.ares[i]);
+			vp8f_lossless_free(&feed.ll[i]);
 		}
 	}
 	double ms_now() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(); }
@@ -617,6 +655,9 @@ struct Pipeline {
 		feed.alpha = sk.alpha;
 		feed.ares = std::vector<uint8_t*>(n, nullptr);
 		feed.afilter.resize(n);
+		feed.lossless = sk.lossless;
+		feed.is_ll.assign(n, 0);
+		feed.ll.assign(n, Vp8fLosslessImage{});
 		feed.ready.reset(new uint8_t[n]());
 		plan_frames(files, n, tok, threads, feed.dev, feed.order, sk.topt == nullptr, sk.extended);
 		trace = getenv("VP8G_PIPE_TRACE") && atoi(getenv("VP8G_PIPE_TRACE")) != 0;
@@ -656,6 +697,11 @@ struct Pipeline {
 		for (uint32_t i : s.frames) {
 			free(feed.ares[i]);
 			feed.ares[i] = nullptr;
+			if (feed.is_ll[i]) {
+				if (defer_release) late_ll.push_back(feed.ll[i]), memset(&feed.ll[i], 0, sizeof(feed.ll[i]));
+				else vp8f_lossless_free(&feed.ll[i]);
+				continue;
+			}
 			if (feed.dev[i]) continue;
 			if (defer_release) late.push_back(feed.pk[i]), memset(&feed.pk[i], 0, sizeof(feed.pk[i]));
 			else vp8f_packed_free(&feed.pk[i]);
@@ -685,6 +731,19 @@ struct Pipeline {
 			const uint32_t fi = feed.order[c.b];
 			feed.wait_ready(fi);
 			if (feed.err[fi]) continue;
+			if (feed.is_ll[fi]) {
+				const uint64_t srcb = lossless_src_bytes(feed.ll[fi]), outb = 4ull * feed.ll[fi].width * feed.ll[fi].height;
+				if (int e = lossless_fits(fi)) {
+					feed.err[fi] = e;
+					continue;
+				}
+				const uint64_t fx = extra_mbs(al256(srcb) + al256(outb));
+				if (!(c.idx.empty() && c.lidx.empty()) && sh.mbs + xmbs + fx > caps.mbs[c.tok]) break;
+				xmbs += fx;
+				sh.lsrcb = al256(sh.lsrcb + srcb), sh.loutb = al256(sh.loutb + outb);
+				c.lidx.push_back(fi);
+				continue;
+			}
 			const uint32_t w = kf_of(fi).width, h = kf_of(fi).height;
 			uint32_t sw = w, sh_ = h;  // the picture's size at the sink
 			if (sk.opts && vp8g_scaled_size(w, h, sk.opt_of(fi), &sw, &sh_) != 0) feed.err[fi] = EINVAL;  // options that do not fit it
@@ -697,7 +756,7 @@ struct Pipeline {
 			const uint64_t apl = feed.ares[fi] ? (uint64_t)w * h : 0u;
 			const uint64_t aspl = apl && sk.opts ? (uint64_t)sw * sh_ : 0u;
 			fx += extra_mbs(2u * apl + aspl);
-			if (!c.idx.empty() && sh.mbs + xmbs + f.mb_total + fx > caps.mbs[c.tok]) break;
+			if (!(c.idx.empty() && c.lidx.empty()) && sh.mbs + xmbs + f.mb_total + fx > caps.mbs[c.tok]) break;
 			xmbs += fx;
 			if (sk.opts) sh.soutb = al256(sh.soutb + sclb);
 			if (apl) sh.ab = al256(sh.ab + apl), sh.asb = al256(sh.asb + aspl);
@@ -710,6 +769,34 @@ struct Pipeline {
 			if (f.mb_rows > sh.max_rows) sh.max_rows = f.mb_rows;
 		}
 		sh.nf = (uint32_t)c.idx.size();
+		sh.nl = (uint32_t)c.lidx.size();
+	}
+	// a lossless frame's upload: the residual image and every transform's data, each padded to a dword count
+	static uint64_t lossless_tr_dwords(const Vp8fLosslessImage& im, uint32_t k) {
+		const Vp8fLosslessTransform& t = im.tr[k];
+		if (t.type == VP8F_T_COLOR_INDEX) return t.ncolors;
+		if (t.type == VP8F_T_SUBTRACT_GREEN) return 0;
+		const uint64_t r = (1u << t.bits) - 1u;
+		return ((t.xsize + r) >> t.bits) * ((im.height + r) >> t.bits);
+	}
+	static uint64_t lossless_src_bytes(const Vp8fLosslessImage& im) {
+		uint64_t dw = (uint64_t)im.xsize * im.height;
+		for (uint32_t k = 0; k < im.ntransforms; k++) dw += lossless_tr_dwords(im, k);
+		return 4u * dw;
+	}
+	// 0, or why a lossless frame cannot go to the sink: scaling it is not supported (ENOTSUP for any option that is not
+	// the identity), and it must have the tensor's size
+	int lossless_fits(uint32_t fi) const {
+		const uint32_t w = feed.ll[fi].width, h = feed.ll[fi].height;
+		if (sk.opts) {
+			const Vp8gScaleOpt& o = *sk.opt_of(fi);
+			uint32_t sw = 0, sh_ = 0;
+			if (vp8g_scaled_size(w, h, &o, &sw, &sh_) != 0) return EINVAL;
+			const bool whole = (o.crop_left | o.crop_top | o.crop_w | o.crop_h) == 0 ||
+			                   (o.crop_left == 0 && o.crop_top == 0 && o.crop_w == w && o.crop_h == h);
+			if (!whole || sw != w || sh_ != h) return ENOTSUP;
+		}
+		return sk.topt && w == sk.topt->width && h == sk.topt->height ? 0 : EINVAL;
 	}
 	// Frame descriptors and output images of the chunk's frames.
 	void describe_chunk(Chunk& c) {
@@ -914,6 +1001,51 @@ struct Pipeline {
 		                                                       sk.d_tensor, c.stream),
 		                   "tensor launch");
 	}
+	// Lossless sink: the residual images and transform data of the chunk's lossless frames are uploaded, the transforms
+	// inverted (vp8g_lossless.hip) and the ARGB pictures written to their slots of the tensor (same stream).
+	Status launch_lossless(Chunk& c) {
+		Slot& s = c.s;
+		const ChunkLayout& L = c.L;
+		uint8_t* d = s.buf;
+		s.ldescs.clear();
+		s.ltdescs.clear();
+		s.frames.insert(s.frames.end(), c.lidx.begin(), c.lidx.end());  // (their host data lives until the slot retires)
+		uint64_t so = 0, oo = 0;
+		for (uint32_t fi : c.lidx) {
+			const Vp8fLosslessImage& im = feed.ll[fi];
+			Vp8gLosslessTransform tr[4];
+			const uint64_t src = L.lsrc + so;
+			c.up(src, im.argb, 4u * (size_t)im.xsize * im.height);
+			so += 4u * (uint64_t)im.xsize * im.height;
+			for (uint32_t k = 0; k < im.ntransforms; k++) {
+				const uint64_t bytes = 4u * lossless_tr_dwords(im, k);
+				tr[k] = Vp8gLosslessTransform{L.lsrc + so, im.tr[k].type, im.tr[k].bits, im.tr[k].xsize, im.tr[k].ncolors};
+				if (bytes) c.up(L.lsrc + so, im.tr[k].data, bytes);
+				so += bytes;
+			}
+			so = al256(so);
+			Vp8gLosslessDesc ld;
+			Vp8gTensorArgbDesc td;
+			if (vp8g_make_lossless_desc(im.width, im.height, src, L.lout + oo, im.ntransforms, tr, (uint32_t)s.ldescs.size(), &ld) != 0 ||
+			    vp8g_make_tensor_argb_desc(sk.topt, sk.alpha ? 4u : 3u, L.lout + oo, (uint64_t)fi * sk.tslot, 0, &td) != 0) {
+				feed.err[fi] = EINVAL;  // (cannot happen for a stream the host decoder accepted and a size checked when gathered)
+				continue;
+			}
+			td.task0 = (uint32_t)s.ltdescs.size() * td.ntasks;
+			oo = al256(oo + 4u * (uint64_t)im.width * im.height);
+			s.ldescs.push_back(ld);
+			s.ltdescs.push_back(td);
+			live[fi] = 1;
+		}
+		if (s.ldescs.empty()) return c.up_status();
+		if (!c.up(L.ldesc, s.ldescs) || !c.up(L.ltdesc, s.ltdescs)) return c.up_status();
+		const uint32_t nl = (uint32_t)s.ldescs.size();
+		if (int rc = vp8g_lossless_batch_device(s.ldescs.data(), (const Vp8gLosslessDesc*)(d + L.ldesc), nl, d, d, c.stream); rc != 0)
+			return capi_status(rc, "lossless launch");
+		return capi_status(vp8g_tensor_batch_device_argb(s.ltdescs.data(), (const Vp8gTensorArgbDesc*)(d + L.ltdesc), nl, sk.topt,
+		                                                 sk.alpha ? 4u : 3u, d, sk.d_tensor, c.stream),
+		                   "tensor launch");
+	}
 	// D2H into the callers' images (and of the status word, whatever the sink), by this kind's Copier once the
 	// kernels are done; then the workers may run a window ahead of this chunk.
 	void queue_downloads(Chunk& c) {
@@ -942,19 +1074,24 @@ struct Pipeline {
 	}
 	// A gathered chunk (with at least one frame) through its slot's buffer and stream, every stage in enqueue order.
 	Status launch_chunk(Chunk& c) {
-		describe_chunk(c);
-		plan_launch(c);
+		const bool lossy = !c.idx.empty();  // (else only lossless frames: no recon launch, c.plan stays empty)
+		if (lossy) {
+			describe_chunk(c);
+			plan_launch(c);
+		}
 		c.L = make_layout(c.sh, c.tok, sk, c.plan);
 		const double tg = trace ? ms_now() : 0.0;
 		if (hipError_t e = grow(c.s, c.L.total); e != hipSuccess) return Status{e, "hipMalloc(chunk)"};
 		const uint32_t si = (uint32_t)(&c.s - slots);
 		if (trace) fprintf(stderr, "[pipe] slot %u buffer %.1f GB ready at %.1f ms (%.1f ms)\n", si, c.L.total / 1e9, ms_now(), ms_now() - tg);
-		Status st = upload_chunk(c);
-		if (st.ok()) st = launch_recon(c);
+		Status st = lossy ? upload_chunk(c) : Status{hipMemsetAsync(c.s.buf + c.L.status, 0, 4, c.stream), "memset"};
+		if (!lossy) c.s.descs.clear(), c.s.sdescs.clear();
+		if (st.ok() && lossy) st = launch_recon(c);
 		// (the scale, alpha and tensor entry points take the launch gate themselves: outside launch_recon's scope)
-		if (st.ok()) st = launch_scale(c);
-		if (st.ok()) st = launch_alpha(c);
-		if (st.ok()) st = launch_tensor(c);
+		if (st.ok() && lossy) st = launch_scale(c);
+		if (st.ok() && lossy) st = launch_alpha(c);
+		if (st.ok() && lossy) st = launch_tensor(c);
+		if (st.ok()) st = launch_lossless(c);
 		if (st.ok()) st = Status{hipEventRecord(c.s.kdone, c.stream), "event"};
 		if (st.ok()) queue_downloads(c);
 		return st;
@@ -967,7 +1104,7 @@ struct Pipeline {
 			Chunk c{tok, a, a, slots[si], streams[si]};
 			gather_chunk(c);
 			if (Status st = finish_slot(c.s); !st.ok()) return st;
-			if (!c.idx.empty())  // (else every frame of it failed)
+			if (!c.idx.empty() || !c.lidx.empty())  // (else every frame of it failed)
 				if (Status st = launch_chunk(c); !st.ok()) return st;
 			a = c.b;
 		}
@@ -1007,6 +1144,7 @@ int fail_all(Yuv420Image* outs, uint32_t n, int* status, int e) {
 int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags, Sinks sk, int* status) {
 	sk.tslot = sk.topt ? (sk.alpha ? vp8g_tensor_slot_size_a(sk.topt) : vp8g_tensor_slot_size(sk.topt)) : 0;
 	if (!files || (sk.topt ? !sk.d_tensor || !sk.tslot || sk.outs : !sk.outs) || n == 0 || (sk.alpha && !(sk.topt && sk.extended)) ||
+	    (sk.lossless && !(sk.topt && sk.extended)) ||
 	    (flags & ~(VP8G_BATCH_DEVICE_M05 | VP8G_BATCH_MULTI_PARTITION)))
 		return fail(EINVAL);
 	for (uint32_t i = 0; sk.outs && i < n; i++) memset(&sk.outs[i], 0, sizeof(sk.outs[i]));
@@ -1088,6 +1226,16 @@ VP8G_API int vp8g_decode_webp_batch_tensor_x(const ByteSpan* files, uint32_t n, 
                                              void* d_out, int* status) {
 	if ((xflags & ~VP8G_X_ALPHA) || !tensor_ok(t, d_out) || !opts_ok(opts, n_opts, n)) return fail(EINVAL);
 	const Sinks sk{opts, n_opts, nullptr, t, (uint8_t*)d_out, /*extended=*/true, /*alpha=*/(xflags & VP8G_X_ALPHA) != 0};
+	return decode_batch(files, n, filtered, threads, flags, sk, status);
+}
+
+// ... and with VP8G_X_LOSSLESS lossless files beside the lossy ones.
+VP8G_API int vp8g_decode_webp_batch_tensor_any(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                               const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, uint32_t xflags,
+                                               void* d_out, int* status) {
+	if ((xflags & ~(VP8G_X_ALPHA | VP8G_X_LOSSLESS)) || !tensor_ok(t, d_out) || !opts_ok(opts, n_opts, n)) return fail(EINVAL);
+	const Sinks sk{opts,  n_opts, nullptr, t, (uint8_t*)d_out, /*extended=*/true, /*alpha=*/(xflags & VP8G_X_ALPHA) != 0,
+	               /*lossless=*/(xflags & VP8G_X_LOSSLESS) != 0};
 	return decode_batch(files, n, filtered, threads, flags, sk, status);
 }
 

@@ -282,6 +282,85 @@ __global__ __launch_bounds__(kThreads) void tensor_kernel_a(const Vp8gTensorDesc
 	}
 }
 
+// ---- ARGB sources (vp8g_tensor_batch_device_argb) ------------------------------
+
+// Tight 0xAARRGGBB dwords, as the lossless kernel leaves them.  Source and NHWC destination are both
+// flat in the pixel index, so a thread takes four consecutive pixels of the image (one 16-byte load;
+// NHWC: one run of 4 C elements, NCHW: a run of four per plane), and a workgroup task 1024 of them; the
+// last pixels of an image whose size is no multiple of four go element by element.  The arithmetic on
+// R, G and B is conv<>, that on A conv_a<>.
+constexpr uint32_t kArgbPx = 4;
+
+template <uint32_t DT, bool PLANAR, bool BGR, int C>
+__global__ __launch_bounds__(kThreads) void tensor_kernel_argb(const Vp8gTensorArgbDesc* __restrict__ D, uint32_t total, TensorParams P,
+                                                               const uint8_t* __restrict__ src, uint8_t* __restrict__ dst) {
+	constexpr uint32_t EB = (uint32_t)elem_bytes(DT);
+	const uint32_t npx = P.w * P.h;
+	for (uint32_t g = blockIdx.x; g < total; g += gridDim.x) {
+		const uint32_t img = g / P.tpi;
+		const uint32_t p0 = ((g - img * P.tpi) * kThreads + threadIdx.x) * kArgbPx;
+		if (p0 >= npx) continue;
+		const Vp8gTensorArgbDesc& d = D[img];
+		const uint32_t* in = (const uint32_t*)(src + d.src);
+		uint8_t* out = dst + d.dst;
+		uint32_t c[kArgbPx], e[kArgbPx][4];
+		const uint32_t cnt = min(kArgbPx, npx - p0);
+		if (cnt == kArgbPx) {
+			const u32x4a v = *(const u32x4a*)(in + p0);
+			c[0] = v.x, c[1] = v.y, c[2] = v.z, c[3] = v.w;
+		} else {
+#pragma unroll
+			for (int i = 0; i < (int)kArgbPx; i++) c[i] = (uint32_t)i < cnt ? in[p0 + i] : 0u;
+		}
+#pragma unroll
+		for (int i = 0; i < (int)kArgbPx; i++) {
+			// (channel<> reads r | g << 8 | b << 16)
+			const uint32_t rgb = ((c[i] >> 16) & 255u) | (c[i] & 0xFF00u) | ((c[i] & 255u) << 16);
+#pragma unroll
+			for (int k = 0; k < 3; k++) e[i][k] = conv<DT>(channel<BGR>(rgb, k), P.scale[k], P.bias[k]);
+			e[i][3] = conv_a<DT>(c[i] >> 24);
+		}
+		if (cnt == kArgbPx) {
+			if constexpr (PLANAR) {
+#pragma unroll
+				for (int k = 0; k < C; k++) {
+					const uint32_t r[kArgbPx] = {e[0][k], e[1][k], e[2][k], e[3][k]};
+					store_run<DT, (int)kArgbPx>(out + (size_t)k * P.plane + (size_t)p0 * EB, r);
+				}
+			} else {
+				uint32_t r[kArgbPx * C];
+#pragma unroll
+				for (int i = 0; i < (int)kArgbPx; i++)
+#pragma unroll
+					for (int k = 0; k < C; k++) r[C * i + k] = e[i][k];
+				store_run<DT, (int)kArgbPx * C>(out + (size_t)p0 * C * EB, r);
+			}
+			continue;
+		}
+		for (uint32_t i = 0; i < cnt; i++)
+#pragma unroll
+			for (int k = 0; k < C; k++) {
+				const size_t px = (size_t)p0 + i;
+				uint8_t* p = PLANAR ? out + (size_t)k * P.plane + px * EB : out + (px * C + (uint32_t)k) * EB;
+				store_elem<DT>(p, i == 0 ? e[0][k] : i == 1 ? e[1][k] : e[2][k]);
+			}
+	}
+}
+
+using KernelFnArgb = void (*)(const Vp8gTensorArgbDesc*, uint32_t, TensorParams, const uint8_t*, uint8_t*);
+#define VP8G_T_ROW_ARGB(DT, C) \
+	{ {tensor_kernel_argb<DT, false, false, C>, tensor_kernel_argb<DT, false, true, C>}, \
+	  {tensor_kernel_argb<DT, true, false, C>, tensor_kernel_argb<DT, true, true, C>} }
+const KernelFnArgb kKernelsArgb[2][4][2][2] = {
+    {VP8G_T_ROW_ARGB(VP8G_T_U8, 3), VP8G_T_ROW_ARGB(VP8G_T_F16, 3), VP8G_T_ROW_ARGB(VP8G_T_BF16, 3), VP8G_T_ROW_ARGB(VP8G_T_F32, 3)},
+    {VP8G_T_ROW_ARGB(VP8G_T_U8, 4), VP8G_T_ROW_ARGB(VP8G_T_F16, 4), VP8G_T_ROW_ARGB(VP8G_T_BF16, 4), VP8G_T_ROW_ARGB(VP8G_T_F32, 4)}};
+#undef VP8G_T_ROW_ARGB
+
+uint32_t argb_tasks_per_image(const Vp8gTensorOpt& t) {
+	const uint32_t per = kThreads * kArgbPx;
+	return (t.width * t.height + per - 1u) / per;
+}
+
 using KernelFnA = void (*)(const Vp8gTensorDesc*, const Vp8gTensorAlpha*, uint32_t, TensorParams, const uint8_t*, uint8_t*);
 #define VP8G_T_ROW_A(DT) \
 	{ {tensor_kernel_a<DT, false, false>, tensor_kernel_a<DT, false, true>}, {tensor_kernel_a<DT, true, false>, tensor_kernel_a<DT, true, true>} }
@@ -417,6 +496,58 @@ VP8G_API int vp8g_tensor_batch_device_a(const Vp8gTensorDesc* h, const Vp8gTenso
 	if (e == hipSuccess) {
 		hipLaunchKernelGGL(kKernelsA[t->dtype][t->layout][t->flags & VP8G_T_BGR], dim3(grid), dim3(kThreads), 0, (hipStream_t)stream,
 		                   d_descs, d_alpha, (uint32_t)total, P, d_src, (uint8_t*)d_dst);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = gate.done(false);
+	if (e != hipSuccess) {
+		vp8g::set_error_text("tensor launch", e);
+		errno = EIO;
+		return -1;
+	}
+	return 0;
+}
+
+VP8G_API int vp8g_make_tensor_argb_desc(const Vp8gTensorOpt* t, uint32_t channels, uint64_t src, uint64_t dst_offset, uint32_t task0,
+                                        Vp8gTensorArgbDesc* d) {
+	if (!d || !opt_ok(t) || (channels != 3 && channels != 4) || src % 4u || dst_offset % (uint64_t)elem_bytes(t->dtype)) {
+		errno = EINVAL;
+		return -1;
+	}
+	memset(d, 0, sizeof(*d));
+	d->src = src, d->dst = dst_offset, d->task0 = task0, d->ntasks = argb_tasks_per_image(*t);
+	return 0;
+}
+
+VP8G_API int vp8g_tensor_batch_device_argb(const Vp8gTensorArgbDesc* h, const Vp8gTensorArgbDesc* d_descs, uint32_t n,
+                                           const Vp8gTensorOpt* t, uint32_t channels, const uint8_t* d_src, void* d_dst, void* stream) {
+	if (!h || !d_descs || !d_src || !d_dst || n == 0 || !opt_ok(t) || (channels != 3 && channels != 4)) {
+		errno = EINVAL;
+		return -1;
+	}
+	const uint32_t eb = (uint32_t)elem_bytes(t->dtype), tpi = argb_tasks_per_image(*t);
+	uint64_t total = 0;
+	bool ok = (uintptr_t)d_dst % eb == 0 && (uintptr_t)d_src % 4u == 0;
+	for (uint32_t i = 0; ok && i < n; i++) {  // tasks must be numbered image by image
+		ok = h[i].task0 == total && h[i].ntasks == tpi && h[i].src % 4u == 0 && h[i].dst % eb == 0;
+		total += tpi;
+		if (total > 0x7FFFFFFFu) ok = false;
+	}
+	if (!ok) {
+		errno = EINVAL;
+		return -1;
+	}
+	TensorParams P;
+	memset(&P, 0, sizeof(P));
+	P.w = t->width, P.h = t->height, P.tpi = tpi;
+	P.plane = (uint64_t)t->width * t->height * eb;
+	for (int c = 0; c < 3; c++) P.scale[c] = t->scale[c], P.bias[c] = t->bias[c];
+	const int cus = vp8g::device_cus();
+	const uint32_t grid = min((uint32_t)total, (uint32_t)(cus > 0 ? cus : 256) * 16u);
+	vp8g::GateScope gate((hipStream_t)stream);  // (vp8g_device.h: no cross-workgroup launch beside it)
+	hipError_t e = gate.status();
+	if (e == hipSuccess) {
+		hipLaunchKernelGGL(kKernelsArgb[channels - 3u][t->dtype][t->layout][t->flags & VP8G_T_BGR], dim3(grid), dim3(kThreads), 0,
+		                   (hipStream_t)stream, d_descs, (uint32_t)total, P, d_src, (uint8_t*)d_dst);
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess) e = gate.done(false);

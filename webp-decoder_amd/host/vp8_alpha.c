@@ -5,8 +5,12 @@
  * Compression 1 is a complete decoder of the RFC's lossless image stream (3.4 - 3.7, 5) of implicit
  * size w x h: the four transforms (colour indexing with its 1/2/4/8-bit packing), normal and simple
  * prefix codes, the entropy image, LZ77 backward references with the short-distance map, and the
- * colour cache.  Written from the RFC text.  Only the green channel leaves: it is the residual
+ * colour cache.  Written from the RFC text.  For ALPH only the green channel leaves: it is the residual
  * plane that the un-prediction (on the device: csrc/vp8g_alpha.hip) turns into alpha.
+ *
+ * The same decoder serves lossless main images (VP8L chunks) in two halves: vp8f_lossless_decode
+ * (the 5-byte header, then the entropy half: the residual ARGB image and the transforms, nothing inverted) and
+ * vp8f_lossless_apply (the inverse transforms, sequentially: the restatement of csrc/vp8g_lossless.hip).
  *
  * Reentrant: all state is on the stack or in allocations owned by the call.  Every read of the
  * stream is bounds-checked (a read past the end yields zero bits and marks the stream as ended,
@@ -252,7 +256,8 @@ static int image_decode(BitRd* b, uint32_t w, uint32_t h, int level0, uint32_t**
 		meta_bits = br_read(b, 3) + 2u;
 		meta_w = div_up(w, meta_bits);
 		const uint32_t meta_h = div_up(h, meta_bits);
-		if (b->eos || image_decode(b, meta_w, meta_h, 0, &meta, st) != 0) goto out;
+		if (b->eos) goto bad;
+		if (image_decode(b, meta_w, meta_h, 0, &meta, st) != 0) goto out;
 		uint32_t top = 0;
 		for (size_t i = 0; i < (size_t)meta_w * meta_h; i++) {
 			meta[i] = (meta[i] >> 8) & 0xFFFFu;
@@ -360,15 +365,9 @@ out:
 
 /* ---- transforms --------------------------------------------------------------------------- */
 
-enum { T_PREDICTOR = 0, T_CROSS_COLOR = 1, T_SUBTRACT_GREEN = 2, T_COLOR_INDEX = 3 };
+enum { T_PREDICTOR = VP8F_T_PREDICTOR, T_CROSS_COLOR = VP8F_T_CROSS_COLOR, T_SUBTRACT_GREEN = VP8F_T_SUBTRACT_GREEN, T_COLOR_INDEX = VP8F_T_COLOR_INDEX };
 
-typedef struct {
-	int type;
-	unsigned bits;   /* block size (predictor, cross colour) or pixels per packed pixel (colour index), log2 */
-	uint32_t xsize;  /* image width when the transform was read (its output width) */
-	uint32_t* data;  /* sub-image, or the colour table */
-	uint32_t ncolors;
-} Transform;
+typedef Vp8fLosslessTransform Transform; /* (vp8_front.h) */
 
 static uint32_t add_px(uint32_t a, uint32_t b) {
 	return (((a & 0xFF00FF00u) + (b & 0xFF00FF00u)) & 0xFF00FF00u) | (((a & 0x00FF00FFu) + (b & 0x00FF00FFu)) & 0x00FF00FFu);
@@ -467,29 +466,30 @@ static void inv_color_index(const Transform* t, const uint32_t* src, uint32_t* d
 		}
 }
 
-static int lossless_decode(const uint8_t* data, size_t size, uint32_t w, uint32_t h, uint8_t* residual, Vp8fAlphaStats* st) {
+/* The entropy half: the transforms' headers and data, then the spatially-coded image, of a stream
+ * of implicit size w x h.  On failure *im is left for vp8f_lossless_free. */
+static int lossless_entropy(const uint8_t* data, size_t size, uint32_t w, uint32_t h, Vp8fLosslessImage* im, Vp8fAlphaStats* st) {
 	BitRd b = {data, size, 0, (uint64_t)size * 8u, 0};
-	Transform tr[4];
-	int ntr = 0, rc = -1;
 	unsigned seen = 0;
 	uint32_t xsize = w;
-	uint32_t *pix = NULL, *wide = NULL;
-	memset(tr, 0, sizeof(tr));
+	im->width = w, im->height = h;
 	while (br_read(&b, 1)) {
 		const int type = (int)br_read(&b, 2);
 		if (b.eos || (seen & (1u << type))) goto bad;
 		seen |= 1u << type;
-		Transform* t = &tr[ntr++];
-		t->type = type, t->xsize = xsize;
+		Transform* t = &im->tr[im->ntransforms++];
+		t->type = (uint32_t)type, t->xsize = xsize;
 		if (type == T_PREDICTOR || type == T_CROSS_COLOR) {
 			t->bits = br_read(&b, 3) + 2u;
-			if (b.eos || image_decode(&b, div_up(xsize, t->bits), div_up(h, t->bits), 0, &t->data, st) != 0) goto out;
+			if (b.eos) goto bad;
+			if (image_decode(&b, div_up(xsize, t->bits), div_up(h, t->bits), 0, &t->data, st) != 0) return -1;
 			if (type == T_PREDICTOR) st->predictor++;
 			else st->cross_color++;
 		} else if (type == T_COLOR_INDEX) {
 			t->ncolors = br_read(&b, 8) + 1u;
 			t->bits = t->ncolors > 16 ? 0 : t->ncolors > 4 ? 1 : t->ncolors > 2 ? 2 : 3;
-			if (b.eos || image_decode(&b, t->ncolors, 1, 0, &t->data, st) != 0) goto out;
+			if (b.eos) goto bad;
+			if (image_decode(&b, t->ncolors, 1, 0, &t->data, st) != 0) return -1;
 			for (uint32_t i = 1; i < t->ncolors; i++) t->data[i] = add_px(t->data[i], t->data[i - 1]);
 			xsize = div_up(xsize, t->bits);
 			st->color_index++;
@@ -498,37 +498,62 @@ static int lossless_decode(const uint8_t* data, size_t size, uint32_t w, uint32_
 			st->subtract_green++;
 		}
 	}
-	if (b.eos || image_decode(&b, xsize, h, 1, &pix, st) != 0) goto out;
-	for (int i = ntr - 1; i >= 0; i--) {
-		const Transform* t = &tr[i];
+	im->xsize = xsize;
+	if (b.eos) goto bad;
+	if (image_decode(&b, xsize, h, 1, &im->argb, st) != 0) return -1;
+	st->lossless++;
+	return 0;
+bad:
+	errno = EINVAL;
+	return -1;
+}
+
+/* The inverse half, in place on pix (im->xsize x height on entry, a malloc'ed buffer that colour
+ * indexing replaces); *out = the width x height result. */
+static int lossless_inverse(const Vp8fLosslessImage* im, uint32_t* pix, uint32_t** out) {
+	const uint32_t h = im->height;
+	uint32_t xsize = im->xsize;
+	*out = pix;
+	for (int i = (int)im->ntransforms - 1; i >= 0; i--) {
+		const Transform* t = &im->tr[i];
 		/* (the width the transform works at: everything read after a colour indexing transform sees the
 		 * packed width, which is that transform's input) */
 		switch (t->type) {
 			case T_PREDICTOR: inv_predictor(t, pix, h); break;
 			case T_CROSS_COLOR: inv_cross_color(t, pix, h); break;
 			case T_SUBTRACT_GREEN: inv_subtract_green(pix, (size_t)xsize * h); break;
-			default:
-				wide = (uint32_t*)malloc((size_t)t->xsize * h * sizeof(uint32_t));
+			default: {
+				uint32_t* wide = (uint32_t*)malloc((size_t)t->xsize * h * sizeof(uint32_t));
 				if (!wide) {
 					errno = ENOMEM;
-					goto out;
+					return -1;
 				}
 				inv_color_index(t, pix, wide, h);
 				free(pix);
-				pix = wide, wide = NULL;
+				*out = pix = wide;
 				xsize = t->xsize;
 				break;
+			}
 		}
 	}
-	for (size_t i = 0; i < (size_t)w * h; i++) residual[i] = (uint8_t)(pix[i] >> 8);
-	st->lossless++;
-	rc = 0;
-	goto out;
-bad:
-	errno = EINVAL;
-out:
-	for (int i = 0; i < ntr; i++) free(tr[i].data);
-	free(pix);
+	return 0;
+}
+
+static int lossless_decode(const uint8_t* data, size_t size, uint32_t w, uint32_t h, uint8_t* residual, Vp8fAlphaStats* st) {
+	Vp8fLosslessImage im;
+	memset(&im, 0, sizeof(im));
+	int rc = lossless_entropy(data, size, w, h, &im, st);
+	if (rc == 0) {
+		uint32_t* pix = im.argb;
+		im.argb = NULL;
+		rc = lossless_inverse(&im, pix, &pix);
+		if (rc == 0)
+			for (size_t i = 0; i < (size_t)w * h; i++) residual[i] = (uint8_t)(pix[i] >> 8);
+		free(pix);
+	}
+	const int e = errno;
+	vp8f_lossless_free(&im);
+	errno = e;
 	return rc;
 }
 
@@ -582,4 +607,53 @@ int vp8f_alpha_unfilter(const uint8_t* residual, uint32_t w, uint32_t h, uint32_
 		}
 	}
 	return 0;
+}
+
+void vp8f_lossless_free(Vp8fLosslessImage* im) {
+	if (!im) return;
+	for (int i = 0; i < 4; i++) free(im->tr[i].data);
+	free(im->argb);
+	memset(im, 0, sizeof(*im));
+}
+
+int vp8f_lossless_decode(const uint8_t* data, size_t size, Vp8fLosslessImage* out, Vp8fAlphaStats* stats) {
+	Vp8fAlphaStats local;
+	Vp8fAlphaStats* st = stats ? stats : &local;
+	memset(st, 0, sizeof(*st));
+	if (out) memset(out, 0, sizeof(*out));
+	uint32_t w, h, hint;
+	if (!out || vp8f_lossless_header(data, size, &w, &h, &hint) != 0) {
+		errno = EINVAL;
+		return -1;
+	}
+	if (w > 16383 || h > 16383) { /* (as every other entry point of the project) */
+		errno = EINVAL;
+		return -1;
+	}
+	out->alpha_hint = hint;
+	if (lossless_entropy(data + 5, size - 5, w, h, out, st) != 0) {
+		const int e = errno;
+		vp8f_lossless_free(out);
+		errno = e;
+		return -1;
+	}
+	return 0;
+}
+
+int vp8f_lossless_apply(const Vp8fLosslessImage* im, uint32_t* argb) {
+	if (!im || !argb || !im->argb || im->width == 0 || im->height == 0 || im->xsize == 0 || im->ntransforms > 4) {
+		errno = EINVAL;
+		return -1;
+	}
+	const size_t n = (size_t)im->xsize * im->height;
+	uint32_t* pix = (uint32_t*)malloc(n * sizeof(uint32_t));
+	if (!pix) {
+		errno = ENOMEM;
+		return -1;
+	}
+	memcpy(pix, im->argb, n * sizeof(uint32_t));
+	const int rc = lossless_inverse(im, pix, &pix);
+	if (rc == 0) memcpy(argb, pix, (size_t)im->width * im->height * sizeof(uint32_t));
+	free(pix);
+	return rc;
 }

@@ -169,6 +169,67 @@ int vp8f_alpha_decode(const uint8_t* alph, size_t size, uint32_t w, uint32_t h, 
  * copies.  0, or -1 + EINVAL. */
 int vp8f_alpha_unfilter(const uint8_t* residual, uint32_t w, uint32_t h, uint32_t filter, uint8_t* out);
 
+/* ---- lossless (VP8L) main images (RFC 9649 3) ------------------------------ */
+
+/* webp_parse_extended plus the lossless image chunk.  vp8l_chunk_offset = 0: a lossy file, whose
+ * other fields are those of WebPContainerX; otherwise the image is the 'VP8L' chunk named here and
+ * the vp8 / alph fields are 0 (an ALPH chunk beside a VP8L image is ignored, as libwebp ignores it). */
+typedef struct {
+	uint32_t riff_size;
+	size_t actual_size;
+	size_t vp8_chunk_offset;
+	uint32_t vp8_chunk_size;
+	size_t alph_chunk_offset;
+	uint32_t alph_chunk_size;
+	uint32_t extended;
+	uint32_t vp8x_flags;
+	uint32_t canvas_width, canvas_height;
+	size_t vp8l_chunk_offset;
+	uint32_t vp8l_chunk_size;
+} WebPContainerL;
+
+/* webp_parse_extended, which also accepts a simple RIFF/WEBP/VP8L file (the chunk must lie inside
+ * the file and the RIFF payload; what follows it is ignored) and a VP8X file whose image chunk is
+ * 'VP8L'.  Animation stays -1 + ENOTSUP; a VP8X canvas that differs from the VP8L header's size, or
+ * a VP8L header that does not parse, is -1 + EINVAL. */
+int webp_parse_any(ByteSpan file, WebPContainerL* out);
+
+/* The 5-byte header of a VP8L chunk payload: signature 0x2f, 14 + 14 bits of width - 1 and
+ * height - 1, the alpha hint, a 3-bit version.  0, or -1 + EINVAL (NULL, fewer than 5 bytes, a wrong
+ * signature, a non-zero version). */
+int vp8f_lossless_header(const uint8_t* data, size_t size, uint32_t* width, uint32_t* height, uint32_t* alpha_hint);
+
+enum { VP8F_T_PREDICTOR = 0, VP8F_T_CROSS_COLOR = 1, VP8F_T_SUBTRACT_GREEN = 2, VP8F_T_COLOR_INDEX = 3 };
+
+typedef struct {
+	uint32_t type;    /* VP8F_T_* */
+	uint32_t bits;    /* block size (predictor, cross colour) or pixels per packed pixel (colour index), log2 */
+	uint32_t xsize;   /* image width when the transform was read (its output width) */
+	uint32_t ncolors; /* colour index: entries of the table */
+	uint32_t* data;   /* sub-image of div_up(xsize, bits) x div_up(height, bits), or the colour table, prefix-summed */
+} Vp8fLosslessTransform;
+
+/* What the entropy half leaves: the ARGB residual image (xsize x height: the packed width when a
+ * colour-indexing transform is present, else the width) and the transforms in stream order. */
+typedef struct {
+	uint32_t width, height, alpha_hint;
+	uint32_t xsize;
+	uint32_t ntransforms;
+	uint32_t reserved;
+	uint32_t* argb;
+	Vp8fLosslessTransform tr[4];
+} Vp8fLosslessImage;
+
+/* Entropy-decode a VP8L chunk payload (header + stream) into *out; no inverse transform is applied.
+ * stats may be NULL.  Reentrant.  0, or -1 + errno as vp8f_alpha_decode (EINVAL for a malformed or
+ * truncated stream, never an over-read; ENOMEM), with *out zeroed.  vp8f_lossless_free releases *out. */
+int vp8f_lossless_decode(const uint8_t* data, size_t size, Vp8fLosslessImage* out, Vp8fAlphaStats* stats);
+void vp8f_lossless_free(Vp8fLosslessImage* img);
+
+/* The inverse transforms, sequentially, last to first: argb[width * height] = 0xAARRGGBB.  The
+ * authority the device kernel (csrc/vp8g_lossless.hip) is tested against.  0, or -1 + EINVAL / ENOMEM. */
+int vp8f_lossless_apply(const Vp8fLosslessImage* img, uint32_t* argb);
+
 /* FNV-1a 64 over a byte buffer (same constants as reference vp8_tokens.c:15-27). */
 uint64_t vp8f_fnv1a64(const void* data, size_t n, uint64_t h);
 

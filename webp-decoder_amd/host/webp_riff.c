@@ -125,6 +125,101 @@ int webp_parse_extended(ByteSpan file, WebPContainerX* out) {
 	return 0;
 }
 
+/* (here, not beside the stream decoder in vp8_alpha.c: webp_parse_any needs it, and this file links on its own) */
+int vp8f_lossless_header(const uint8_t* data, size_t size, uint32_t* width, uint32_t* height, uint32_t* alpha_hint) {
+	if (!data || !width || !height || !alpha_hint || size < 5 || data[0] != 0x2f) {
+		errno = EINVAL;
+		return -1;
+	}
+	const uint32_t v = (uint32_t)data[1] | (uint32_t)data[2] << 8 | (uint32_t)data[3] << 16 | (uint32_t)data[4] << 24;
+	if (v >> 29) { /* version */
+		errno = EINVAL;
+		return -1;
+	}
+	*width = (v & 0x3FFFu) + 1u, *height = ((v >> 14) & 0x3FFFu) + 1u, *alpha_hint = (v >> 28) & 1u;
+	return 0;
+}
+
+static void copy_container(WebPContainerL* out, const WebPContainerX* x) {
+	out->riff_size = x->riff_size, out->actual_size = x->actual_size;
+	out->vp8_chunk_offset = x->vp8_chunk_offset, out->vp8_chunk_size = x->vp8_chunk_size;
+	out->alph_chunk_offset = x->alph_chunk_offset, out->alph_chunk_size = x->alph_chunk_size;
+	out->extended = x->extended, out->vp8x_flags = x->vp8x_flags;
+	out->canvas_width = x->canvas_width, out->canvas_height = x->canvas_height;
+}
+
+/* webp_parse_extended's walk, with a 'VP8L' image chunk accepted (simple layout: as libwebp reads it, the
+ * chunk inside the RIFF payload and the file, the rest ignored). */
+int webp_parse_any(ByteSpan file, WebPContainerL* out) {
+	if (!out) return -1;
+	memset(out, 0, sizeof(*out));
+	WebPContainerX x;
+	if (webp_parse_extended(file, &x) == 0) {
+		copy_container(out, &x);
+		return 0;
+	}
+	if (errno != ENOTSUP) {
+		out->actual_size = file.size;
+		return -1;
+	}
+	/* animation, or a lossless image: the file has passed the checks in front of the chunk walk */
+	copy_container(out, &x);
+	out->vp8_chunk_offset = 0, out->vp8_chunk_size = 0, out->alph_chunk_offset = 0, out->alph_chunk_size = 0;
+	size_t pos, end;
+	if (!x.extended) {
+		out->riff_size = rd_le32(file.data + 4);
+		if (out->riff_size > 0xFFFFFFF6u || (size_t)out->riff_size > file.size - 8u || out->riff_size < 12u) {
+			errno = EINVAL;
+			return -1;
+		}
+		pos = 12, end = 8u + (size_t)out->riff_size;
+	} else {
+		if (x.vp8x_flags & 0x02u) {
+			errno = ENOTSUP;
+			return -1;
+		}
+		pos = 30, end = 8u + (size_t)x.riff_size;
+	}
+	for (;;) {
+		if (end - pos < 8u) {
+			errno = EINVAL;
+			return -1;
+		}
+		const uint8_t* chunk = file.data + pos;
+		const uint32_t csize = rd_le32(chunk + 4);
+		if (csize > 0xFFFFFFF6u || (size_t)csize > end - pos - 8u) {
+			errno = EINVAL;
+			return -1;
+		}
+		if (memcmp(chunk, "ANIM", 4) == 0 || memcmp(chunk, "ANMF", 4) == 0) {
+			errno = ENOTSUP;
+			return -1;
+		}
+		if (memcmp(chunk, "VP8L", 4) == 0) {
+			out->vp8l_chunk_offset = pos + 8u, out->vp8l_chunk_size = csize;
+			break;
+		}
+		if (!x.extended || memcmp(chunk, "VP8 ", 4) == 0) { /* (unreachable after webp_parse_extended's verdict) */
+			errno = EINVAL;
+			return -1;
+		}
+		const size_t padded = (size_t)csize + (csize & 1u);
+		if (padded > end - pos - 8u) {
+			errno = EINVAL;
+			return -1;
+		}
+		pos += 8u + padded;
+	}
+	uint32_t w, h, hint;
+	if (vp8f_lossless_header(file.data + out->vp8l_chunk_offset, out->vp8l_chunk_size, &w, &h, &hint) != 0) return -1;
+	if (x.extended && (w != out->canvas_width || h != out->canvas_height)) {
+		errno = EINVAL;
+		return -1;
+	}
+	if (!x.extended) out->canvas_width = w, out->canvas_height = h;
+	return 0;
+}
+
 int vp8_parse_keyframe_header(ByteSpan p, Vp8KeyFrameHeader* out) {
 	if (!out) return -1;
 	memset(out, 0, sizeof(*out));

@@ -198,8 +198,52 @@ class Vp8gTensorAlpha(C.Structure):
     _fields_ = [("src_a", C.c_uint64), ("stride_a", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class WebPContainerL(C.Structure):
+    """host/vp8_front.h: what webp_parse_any found (vp8l_chunk_offset 0 = a lossy file)."""
+    _fields_ = WebPContainerX._fields_ + [("vp8l_chunk_offset", C.c_size_t), ("vp8l_chunk_size", C.c_uint32)]
+
+
+class Vp8fLosslessTransform(C.Structure):
+    """host/vp8_front.h: one transform of a lossless stream, as vp8f_lossless_decode leaves it."""
+    _fields_ = [(n, C.c_uint32) for n in ("type", "bits", "xsize", "ncolors")] + [("data", C.POINTER(C.c_uint32))]
+
+
+class Vp8fLosslessImage(C.Structure):
+    """host/vp8_front.h: the entropy-decoded residual image and the transforms of a lossless stream."""
+    _fields_ = [(n, C.c_uint32) for n in ("width", "height", "alpha_hint", "xsize", "ntransforms", "reserved")] + [
+        ("argb", C.POINTER(C.c_uint32)), ("tr", Vp8fLosslessTransform * 4)]
+
+
+class Vp8gLosslessTransform(C.Structure):
+    """include/vp8g.h: one transform of an image of the lossless kernel (data = byte offset in the source buffer)."""
+    _fields_ = [("data", C.c_uint64)] + [(n, C.c_uint32) for n in ("type", "bits", "xsize", "ncolors")]
+
+
+class Vp8gLosslessDesc(C.Structure):
+    """include/vp8g.h: per-image descriptor of the lossless kernel (vp8g_make_lossless_desc)."""
+    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64)] + [(n, C.c_uint32) for n in (
+        "width", "height", "ntransforms", "task0")] + [("tr", Vp8gLosslessTransform * 4)]
+
+
+class Vp8gTensorArgbDesc(C.Structure):
+    """include/vp8g.h: per-image descriptor of the ARGB tensor kernel (vp8g_make_tensor_argb_desc)."""
+    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("task0", C.c_uint32), ("ntasks", C.c_uint32)]
+
+
+# transform types (RFC 9649 4)
+L_PREDICTOR, L_CROSS_COLOR, L_SUBTRACT_GREEN, L_COLOR_INDEX = 0, 1, 2, 3
+
+
+def lossless_geometry():
+    """vp8g_lossless_geometry: (tile step, band rows, round bands) of the lossless kernel as the library was built --
+    columns per barrier group, rows per wave, bands per workgroup round.  The boundary sizes of the tests come from it."""
+    g = (C.c_uint32 * 3)()
+    gpu_lib().vp8g_lossless_geometry(g)
+    return int(g[0]), int(g[1]), int(g[2])
+
 T_OPAQUE = 0xFFFFFFFFFFFFFFFF
 VP8G_X_ALPHA = 1
+VP8G_X_LOSSLESS = 2
 VP8G_SCALE_DWEBP_FILTER = 1
 VP8G_SCALE_EXPAND = 4
 
@@ -313,6 +357,15 @@ def host_lib():
             lib.vp8f_alpha_decode.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
                                               C.POINTER(C.c_uint32), C.POINTER(Vp8fAlphaStats)]
             lib.vp8f_alpha_unfilter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        if hasattr(lib, "webp_parse_any"):  # (libraries built before the lossless path: A/B of old builds)
+            lib.webp_parse_any.argtypes = [ByteSpan, C.POINTER(WebPContainerL)]
+            lib.vp8f_lossless_header.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                 C.POINTER(C.c_uint32)]
+            lib.vp8f_lossless_decode.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(Vp8fLosslessImage),
+                                                 C.POINTER(Vp8fAlphaStats)]
+            lib.vp8f_lossless_free.argtypes = [C.POINTER(Vp8fLosslessImage)]
+            lib.vp8f_lossless_free.restype = None
+            lib.vp8f_lossless_apply.argtypes = [C.POINTER(Vp8fLosslessImage), C.c_void_p]
         lib._typed = True
     return lib
 
@@ -415,6 +468,20 @@ def gpu_lib():
             lib.vp8g_tensor_slot_size_a.restype = C.c_uint64
             lib.vp8g_tensor_batch_device_a.argtypes = [P(Vp8gTensorDesc), C.c_void_p, P(Vp8gTensorAlpha), C.c_void_p, C.c_uint32,
                                                        P(Vp8gTensorOpt), C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "vp8g_lossless_batch_device"):  # (libraries built before the lossless path: A/B of old builds)
+            lib.vp8g_lossless_geometry.argtypes = [P(C.c_uint32)]
+            lib.vp8g_lossless_geometry.restype = None
+            lib.vp8g_make_lossless_desc.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                    P(Vp8gLosslessTransform), C.c_uint32, P(Vp8gLosslessDesc)]
+            lib.vp8g_lossless_batch_device.argtypes = [P(Vp8gLosslessDesc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]
+            lib.vp8g_make_tensor_argb_desc.argtypes = [P(Vp8gTensorOpt), C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                       P(Vp8gTensorArgbDesc)]
+            lib.vp8g_tensor_batch_device_argb.argtypes = [P(Vp8gTensorArgbDesc), C.c_void_p, C.c_uint32, P(Vp8gTensorOpt),
+                                                          C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.vp8g_decode_webp_batch_tensor_any.argtypes = [P(ByteSpan), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
+                                                              P(Vp8gScaleOpt), C.c_uint32, P(Vp8gTensorOpt), C.c_uint32,
+                                                              C.c_void_p, P(C.c_int)]
         lib._typed = True
     return lib
 
@@ -975,6 +1042,234 @@ def gpu_tensor(i420_list, w: int, h: int, opt: Vp8gTensorOpt, alpha=None):
     return out
 
 
+# ---- lossless (VP8L) images -------------------------------------------------
+
+
+def parse_any(data: bytes) -> dict:
+    """webp_parse_any: the fields of WebPContainerL as a dict, plus "alpha" and "lossless" (the image chunk is
+    VP8L); OSError with its errno (EINVAL, ENOTSUP) if refused."""
+    c = WebPContainerL()
+    buf, span = _c_bytes(data)
+    if host_lib().webp_parse_any(span, C.byref(c)) != 0:
+        raise OSError(C.get_errno(), "webp_parse_any")
+    d = {n: int(getattr(c, n)) for n, _ in WebPContainerL._fields_}
+    d["alpha"] = d["alph_chunk_offset"] != 0
+    d["lossless"] = d["vp8l_chunk_offset"] != 0
+    return d
+
+
+def _sub_shape(t: dict, h: int):
+    r = (1 << t["bits"]) - 1
+    return ((h + r) >> t["bits"], (t["xsize"] + r) >> t["bits"])
+
+
+def lossless_decode_host(data: bytes) -> dict:
+    """vp8f_lossless_decode of a VP8L chunk payload: {"width", "height", "alpha_hint", "residual": uint32
+    [h, xsize], "transforms": [{"type", "bits", "xsize", "ncolors", "data": uint32 array (the sub-image [bh, bw]
+    or the colour table)}, ...] in stream order, "stats": dict}; OSError with its errno if the stream does not decode."""
+    im, st = Vp8fLosslessImage(), Vp8fAlphaStats()
+    buf, _ = _c_bytes(data)
+    lib = host_lib()
+    if lib.vp8f_lossless_decode(buf, len(data), C.byref(im), C.byref(st)) != 0:
+        raise OSError(C.get_errno(), "vp8f_lossless_decode")
+    try:
+        h, xs = int(im.height), int(im.xsize)
+        out = {"width": int(im.width), "height": h, "alpha_hint": int(im.alpha_hint),
+               "residual": np.ctypeslib.as_array(im.argb, (h, xs)).copy(), "transforms": [],
+               "stats": {n: int(getattr(st, n)) for n in ALPHA_STATS}}
+        for k in range(im.ntransforms):
+            t = {n: int(getattr(im.tr[k], n)) for n in ("type", "bits", "xsize", "ncolors")}
+            if t["type"] == L_COLOR_INDEX:
+                t["data"] = np.ctypeslib.as_array(im.tr[k].data, (t["ncolors"],)).copy()
+            elif t["type"] == L_SUBTRACT_GREEN:
+                t["data"] = np.zeros(0, np.uint32)
+            else:
+                t["data"] = np.ctypeslib.as_array(im.tr[k].data, _sub_shape(t, h)).copy()
+            out["transforms"].append(t)
+    finally:
+        lib.vp8f_lossless_free(C.byref(im))
+    return out
+
+
+def lossless_image(residual, transforms, width: int | None = None) -> dict:
+    """An image in lossless_decode_host's form from a uint32 [h, xsize] residual and a list of transforms (dicts
+    with "type", "bits" and, by type, "data" / "ncolors"): xsize is filled in as the stream would have it."""
+    res = np.ascontiguousarray(residual, dtype=np.uint32)
+    h = res.shape[0]
+    packs = [t["bits"] for t in transforms if t["type"] == L_COLOR_INDEX]
+    if width is None:
+        if packs and packs[0]:
+            raise ValueError("lossless_image: give the width of an image with packed pixels")
+        width = res.shape[1]
+    xs, trs = width, []
+    for t in transforms:
+        t = dict(t, xsize=xs, ncolors=int(t.get("ncolors", 0)))
+        t["data"] = np.ascontiguousarray(t.get("data", np.zeros(0, np.uint32)), dtype=np.uint32)
+        if t["type"] == L_COLOR_INDEX:
+            t["ncolors"] = t["data"].size
+            xs = (xs + (1 << t["bits"]) - 1) >> t["bits"]
+        trs.append(t)
+    if xs != res.shape[1]:
+        raise ValueError("lossless_image: residual width does not match the transforms")
+    return {"width": width, "height": h, "alpha_hint": 1, "residual": res, "transforms": trs}
+
+
+def lossless_struct(img: dict):
+    """The Vp8fLosslessImage of an image in lossless_decode_host's form, and the arrays it points into (keep them)."""
+    im = Vp8fLosslessImage()
+    res = np.ascontiguousarray(img["residual"], dtype=np.uint32)
+    keep = [res]
+    if res.shape[0] != img["height"]:
+        raise ValueError("lossless_struct: residual of another height")
+    im.width, im.height, im.xsize, im.ntransforms = img["width"], img["height"], res.shape[1], len(img["transforms"])
+    im.argb = res.ctypes.data_as(C.POINTER(C.c_uint32))
+    for k, t in enumerate(img["transforms"]):
+        d = np.ascontiguousarray(t["data"], dtype=np.uint32)
+        keep.append(d)
+        im.tr[k].type, im.tr[k].bits, im.tr[k].xsize, im.tr[k].ncolors = t["type"], t["bits"], t["xsize"], t["ncolors"]
+        if t["type"] in (L_PREDICTOR, L_CROSS_COLOR) and d.shape != _sub_shape(t, img["height"]):
+            raise ValueError("lossless_struct: sub-image of another size")
+        im.tr[k].data = d.ctypes.data_as(C.POINTER(C.c_uint32)) if d.size else None
+    return im, keep
+
+
+def host_lossless_apply(img: dict) -> np.ndarray:
+    """vp8f_lossless_apply (the sequential CPU restatement of the inverse transforms) of an image in
+    lossless_decode_host's form: uint32 [h, w] 0xAARRGGBB."""
+    im, keep = lossless_struct(img)
+    out = np.empty((img["height"], img["width"]), np.uint32)
+    if host_lib().vp8f_lossless_apply(C.byref(im), out.ctypes.data) != 0:
+        raise OSError(C.get_errno() or 22, "vp8f_lossless_apply")
+    return out
+
+
+def argb_to_rgba(argb) -> np.ndarray:
+    """uint32 [h, w] 0xAARRGGBB -> uint8 [h, w, 4] R, G, B, A (WebPDecodeRGBA's bytes)."""
+    a = np.asarray(argb, dtype=np.uint32)
+    return np.stack([(a >> 16) & 255, (a >> 8) & 255, a & 255, a >> 24], axis=-1).astype(np.uint8)
+
+
+def host_lossless_argb(data: bytes) -> np.ndarray:
+    """A lossless .webp on the host: container, entropy decode, inverse transforms.  uint32 [h, w]."""
+    c = parse_any(data)
+    if not c["lossless"]:
+        raise OSError(22, "not a lossless file")
+    return host_lossless_apply(lossless_decode_host(data[c["vp8l_chunk_offset"]:c["vp8l_chunk_offset"] + c["vp8l_chunk_size"]]))
+
+
+def gpu_lossless_argb(images, src_shift: int = 1, guard: int = 64, fill: int = 0xEE):
+    """vp8g_lossless_batch_device over images in lossless_decode_host's form, of mixed sizes and transform lists, in
+    one launch: the list of uint32 [h, w] pictures.  src_shift: every residual image, sub-image and colour table
+    starts at an offset that is this much off a dword boundary; guard: bytes kept around every output, which the
+    call checks still hold `fill`."""
+    import torch
+    lib = gpu_lib()
+    dev = torch.device("cuda", 0)
+    n = len(images)
+    descs = (Vp8gLosslessDesc * n)()
+    parts, so, do = [], 0, guard
+
+    def put(a):
+        nonlocal so
+        pad = (-so) % 4 + src_shift
+        parts.append(np.full(pad, 0x5A, np.uint8))
+        so += pad
+        off = so
+        b = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1).view(np.uint8)
+        parts.append(b)
+        so += b.size
+        return off
+
+    for i, img in enumerate(images):
+        tr = (Vp8gLosslessTransform * 4)()
+        src = put(img["residual"])
+        for k, t in enumerate(img["transforms"]):
+            tr[k] = Vp8gLosslessTransform(put(t["data"]) if np.asarray(t["data"]).size else 0, t["type"], t["bits"], t["xsize"],
+                                          t["ncolors"])
+        if lib.vp8g_make_lossless_desc(img["width"], img["height"], src, do, len(img["transforms"]), tr, i,
+                                       C.byref(descs[i])) != 0:
+            raise ValueError(f"vp8g_make_lossless_desc failed: errno={C.get_errno()}")
+        do += 4 * img["width"] * img["height"] + guard
+    parts.append(np.full(16, 0x5A, np.uint8))
+    src = torch.from_numpy(np.concatenate(parts)).to(dev)
+    dst = torch.full((do,), fill, dtype=torch.uint8, device=dev)
+    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
+    stream = torch.cuda.current_stream(dev)
+    if lib.vp8g_lossless_batch_device(descs, C.c_void_p(d_descs.data_ptr()), n, C.c_void_p(src.data_ptr()),
+                                      C.c_void_p(dst.data_ptr()), C.c_void_p(stream.cuda_stream)) != 0:
+        raise RuntimeError(f"vp8g_lossless_batch_device failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
+    stream.synchronize()
+    host = dst.cpu().numpy()
+    out, keep = [], np.ones(do, bool)
+    for i, img in enumerate(images):
+        nb = 4 * img["width"] * img["height"]
+        out.append(host[descs[i].dst:descs[i].dst + nb].view(np.uint32).reshape(img["height"], img["width"]).copy())
+        keep[descs[i].dst:descs[i].dst + nb] = False
+    if not (host[keep] == fill).all():
+        raise AssertionError("gpu_lossless_argb: bytes outside the images were written")
+    return out
+
+
+def host_tensor_argb(argb, opt: Vp8gTensorOpt, channels: int = 4):
+    """The numpy / torch-CPU restatement of vp8g_tensor_batch_device_argb for one uint32 [h, w] 0xAARRGGBB picture:
+    R, G, B as host_tensor treats them (the channel order, a float32 multiply and then a float32 add, one rounding),
+    A as host_alpha_channel, the layout.  A torch CPU tensor [C, H, W] or [H, W, C]."""
+    import torch
+    rgba = argb_to_rgba(argb)
+    assert rgba.shape[:2] == (opt.height, opt.width) and channels in (3, 4)
+    rgb = rgba[:, :, :3]
+    if opt.flags & VP8G_T_BGR:
+        rgb = rgb[:, :, ::-1]
+    if opt.dtype == T_DTYPES["uint8"]:
+        out = torch.from_numpy(np.array(rgb))
+    else:
+        scale, bias = np.array(list(opt.scale), np.float32), np.array(list(opt.bias), np.float32)
+        f = rgb.astype(np.float32) * scale + bias  # (two float32 operations, each rounded to nearest)
+        assert f.dtype == np.float32
+        if opt.dtype == T_DTYPES["float16"]:
+            with np.errstate(over="ignore"):
+                out = torch.from_numpy(f.astype(np.float16))
+        elif opt.dtype == T_DTYPES["bfloat16"]:
+            out = torch.from_numpy(f).to(torch.bfloat16)
+        else:
+            out = torch.from_numpy(f)
+    if channels == 4:
+        out = torch.cat([out, host_alpha_channel(rgba[:, :, 3], opt).unsqueeze(2)], dim=2)
+    return out.permute(2, 0, 1).contiguous() if opt.layout == T_LAYOUTS["NCHW"] else out.contiguous()
+
+
+def gpu_tensor_argb(argb_list, opt: Vp8gTensorOpt, channels: int = 4, slot_shift: int = 0):
+    """vp8g_tensor_batch_device_argb over uint32 [h, w] pictures of the tensor's size: upload them, one launch, and the
+    torch.Tensor [N, C, H, W] or [N, H, W, C] it leaves on the device.  slot_shift: the tensor starts this many
+    ELEMENTS into its allocation (a slot that is not 16-byte aligned)."""
+    import torch
+    lib = gpu_lib()
+    dev = torch.device("cuda", 0)
+    n, w, h = len(argb_list), opt.width, opt.height
+    slot = lib.vp8g_tensor_slot_size(C.byref(opt)) if channels == 3 else lib.vp8g_tensor_slot_size_a(C.byref(opt))
+    if not slot or any(np.asarray(a).shape != (h, w) for a in argb_list):
+        raise ValueError("gpu_tensor_argb: invalid options or picture sizes")
+    descs = (Vp8gTensorArgbDesc * n)()
+    task0 = 0
+    for i in range(n):
+        if lib.vp8g_make_tensor_argb_desc(C.byref(opt), channels, i * 4 * w * h, i * slot, task0, C.byref(descs[i])) != 0:
+            raise ValueError("vp8g_make_tensor_argb_desc failed")
+        task0 += descs[i].ntasks
+    src = torch.from_numpy(np.concatenate([np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in argb_list])
+                           .view(np.uint8)).to(dev)
+    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
+    shape = _tensor_shape(n, opt, channels)
+    flat = torch.zeros(int(np.prod(shape)) + slot_shift, dtype=_torch_dtype(opt), device=dev)
+    out = flat[slot_shift:].view(shape)
+    stream = torch.cuda.current_stream(dev)
+    if lib.vp8g_tensor_batch_device_argb(descs, C.c_void_p(d_descs.data_ptr()), n, C.byref(opt), channels,
+                                         C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()),
+                                         C.c_void_p(stream.cuda_stream)) != 0:
+        raise RuntimeError(f"vp8g_tensor_batch_device_argb failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
+    stream.synchronize()
+    return out
+
+
 def gpu_decode_webp_batch_x(files: list[bytes], scale=None, filtered: bool = True, threads: int = 0, device_m05: bool = False,
                             multi_partition: bool = False):
     """vp8g_decode_webp_batch_x: gpu_decode_webp_batch_scaled (scale: None, one Vp8gScaleOpt, or a list of one per
@@ -1003,12 +1298,14 @@ def gpu_decode_webp_batch_x(files: list[bytes], scale=None, filtered: bool = Tru
 
 def gpu_decode_webp_batch_tensor(files: list[bytes], opt: Vp8gTensorOpt, scale=None, filtered: bool = True, threads: int = 0,
                                  device_m05: bool = False, multi_partition: bool = False, extended: bool = False,
-                                 alpha: bool = False):
+                                 alpha: bool = False, lossless: bool = False):
     """vp8g_decode_webp_batch_tensor: .webp images decoded, optionally cropped / downscaled (scale: None,
     one Vp8gScaleOpt for every frame, or a list of one per frame), converted and left on the device.
     Returns (torch.Tensor on the device, [N, 3, H, W] or [N, H, W, 3] of the requested dtype, list of
     errno); the slot of a failed frame is zero.  extended: vp8g_decode_webp_batch_tensor_x (VP8X files decode);
-    alpha: with VP8G_X_ALPHA, the tensor has four channels (R, G, B, A; opaque A for a picture without alpha).  torch only allocates the tensor: its data_ptr() is
+    alpha: with VP8G_X_ALPHA, the tensor has four channels (R, G, B, A; opaque A for a picture without alpha).
+    lossless: vp8g_decode_webp_batch_tensor_any with VP8G_X_LOSSLESS (implies the extended container): lossless
+    (VP8L) files decode beside the lossy ones; one whose scale option is not the identity gets ENOTSUP.  torch only allocates the tensor: its data_ptr() is
     handed to the C call."""
     import time
     import torch
@@ -1027,7 +1324,11 @@ def gpu_decode_webp_batch_tensor(files: list[bytes], opt: Vp8gTensorOpt, scale=N
     st = (C.c_int * n)()
     t0 = time.perf_counter()
     bflags = (VP8G_BATCH_DEVICE_M05 if device_m05 else 0) | (VP8G_BATCH_MULTI_PARTITION if multi_partition else 0)
-    if extended:  # (routed to the _x call only when asked)
+    if lossless:
+        rc = lib.vp8g_decode_webp_batch_tensor_any(spans, n, int(filtered), threads, bflags, c_opts, len(opts), C.byref(opt),
+                                                   VP8G_X_LOSSLESS | (VP8G_X_ALPHA if alpha else 0),
+                                                   C.c_void_p(out.data_ptr()), st)
+    elif extended:  # (routed to the _x call only when asked)
         rc = lib.vp8g_decode_webp_batch_tensor_x(spans, n, int(filtered), threads, bflags, c_opts, len(opts), C.byref(opt),
                                                  VP8G_X_ALPHA if alpha else 0, C.c_void_p(out.data_ptr()), st)
     else:
