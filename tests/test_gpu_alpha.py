@@ -108,7 +108,9 @@ def test_unfilter_refuses_bad_descriptors(vp8g):
 
 # ---- alpha as the fourth channel of the tensor -------------------------------------------------
 
-T_SIZES = [(w, h) for w in (1, 2, 11, 12, 13, 37, 224) for h in (1, 2, 5)] + [(224, 224)]
+# (14, 15: the first widths whose chroma rows, 7 and 8 bytes, sit either side of the chunk path's 8-byte load;
+# 24, 25: two whole chunks, and two with a one-pixel partial chunk after them)
+T_SIZES = [(w, h) for w in (1, 2, 11, 12, 13, 14, 15, 24, 25, 37, 224) for h in (1, 2, 5)] + [(224, 224)]
 
 
 def i420_input(w, h, seed):

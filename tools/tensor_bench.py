@@ -6,15 +6,18 @@
        with vp8g_encode_batch_device in VP8G_ENC_RGB on the same input.  The two write identical
        bytes (checked), so the encoder is the yardstick.
  (ii)  the legs with no predecessor: the same frames -> float16 NCHW, and the data-loader shape, N
-       224x224 I420 pictures (the host rescale of the four frames, replicated) -> float16 NCHW; HIP-event
-       ms and the achieved bytes/s read + written against the achievable HBM rate.
+       224x224 I420 pictures (the host rescale of the four frames, replicated) -> float16 NCHW; and the
+       4-channel kernel (vp8g_tensor_batch_device_a, one random alpha plane per picture): the 4K frames ->
+       uint8 NHWC RGBA, the 224x224 pictures -> float16 NCHW RGBA.  HIP-event ms and the achieved bytes/s
+       read + written against the achievable HBM rate.
  (iii) end to end: vp8g_decode_webp_batch_tensor(4K -> 224x224 float16 NCHW) against
        vp8g_decode_webp_batch_scaled(4K -> 224x224), interleaved call by call.  --parent-lib names a
        libvp8g.so built from the parent commit for the scaled leg (loaded side by side); without it
        the scaled leg runs this tree's library.
 
 Every leg: the cold first call discarded, then the median of the warm runs with min .. max.  Writes
-profiles/tensor_bench.json and prints the table of DESIGN.md §15.
+profiles/tensor_bench.json and prints the table of DESIGN.md §15.  --e2e-frames 0 leaves (iii) out (an A/B of
+the kernels alone: VP8G_LIB=<another build's libvp8g.so> runs the same legs on that library).
 
   python tools/tensor_bench.py [--frames 512] [--runs 12] [--e2e-frames 256] [--e2e-runs 5] [--parent-lib PATH]
 """
@@ -64,16 +67,19 @@ def timed_interleaved(launches, runs, dev):
 
 
 class Source:
-    """n device-resident I420 pictures of one size: slot i <- pictures[i % K] at 256-byte aligned steps."""
+    """n device-resident I420 pictures of one size: slot i <- pictures[i % K] at 256-byte aligned steps, each
+    followed by its alpha plane (w x h random bytes per picture; only the 4-channel legs read it)."""
 
     def __init__(self, pictures, w, h, n, dev):
         self.w, self.h, self.n, self.pictures = w, h, n, pictures
+        self.alphas = [np.random.default_rng(k).integers(0, 256, (h, w), dtype=np.uint8) for k in range(len(pictures))]
         self.i420 = vp8g.i420_size(w, h)
-        self.step = (self.i420 + 255) // 256 * 256
+        self.step = (self.i420 + w * h + 255) // 256 * 256
         self.buf = torch.empty(n * self.step + 16, dtype=torch.uint8, device=dev)
         view = self.buf[:n * self.step].view(n, self.step)
-        for j, p in enumerate(pictures):
+        for j, (p, a) in enumerate(zip(pictures, self.alphas)):
             view[j::len(pictures), :self.i420] = torch.from_numpy(np.frombuffer(p, np.uint8).copy()).to(dev)
+            view[j::len(pictures), self.i420:self.i420 + w * h] = torch.from_numpy(a.reshape(-1)).to(dev)
 
     def planes(self, i):
         cw, ch = (self.w + 1) // 2, (self.h + 1) // 2
@@ -82,11 +88,11 @@ class Source:
 
 
 class TensorLeg:
-    """One vp8g_tensor_batch_device launch over a Source."""
+    """One vp8g_tensor_batch_device launch over a Source; alpha: vp8g_tensor_batch_device_a with the Source's alpha planes."""
 
-    def __init__(self, src, opt, dev):
-        self.lib, self.src, self.opt, self.n = vp8g.gpu_lib(), src, opt, src.n
-        self.slot = self.lib.vp8g_tensor_slot_size(C.byref(opt))
+    def __init__(self, src, opt, dev, alpha=False):
+        self.lib, self.src, self.opt, self.n, self.alpha = vp8g.gpu_lib(), src, opt, src.n, alpha
+        self.slot = (self.lib.vp8g_tensor_slot_size_a if alpha else self.lib.vp8g_tensor_slot_size)(C.byref(opt))
         self.descs = (vp8g.Vp8gTensorDesc * src.n)()
         task0 = 0
         for i in range(src.n):
@@ -95,10 +101,19 @@ class TensorLeg:
                                                   C.byref(self.descs[i])) == 0
             task0 += self.descs[i].ntasks
         self.d_descs = torch.frombuffer(bytearray(bytes(self.descs)), dtype=torch.uint8).to(dev)
-        self.out = torch.empty(vp8g._tensor_shape(src.n, opt), dtype=vp8g._torch_dtype(opt), device=dev)
-        self.bytes = src.n * (src.i420 + self.slot)  # read + written
+        self.al = (vp8g.Vp8gTensorAlpha * src.n)(*[vp8g.Vp8gTensorAlpha(i * src.step + src.i420, src.w, 0) for i in range(src.n)])
+        self.d_al = torch.frombuffer(bytearray(bytes(self.al)), dtype=torch.uint8).to(dev)
+        self.out = torch.empty(vp8g._tensor_shape(src.n, opt, 4 if alpha else 3), dtype=vp8g._torch_dtype(opt), device=dev)
+        self.bytes = src.n * (src.i420 + (src.w * src.h if alpha else 0) + self.slot)  # read + written
 
     def launch(self, stream):
+        if self.alpha:
+            if self.lib.vp8g_tensor_batch_device_a(self.descs, C.c_void_p(self.d_descs.data_ptr()), self.al,
+                                                   C.c_void_p(self.d_al.data_ptr()), self.n, C.byref(self.opt),
+                                                   C.c_void_p(self.src.buf.data_ptr()), C.c_void_p(self.out.data_ptr()),
+                                                   C.c_void_p(stream)) != 0:
+                raise RuntimeError(f"vp8g_tensor_batch_device_a: {self.lib.vp8g_last_error()!r}")
+            return
         if self.lib.vp8g_tensor_batch_device(self.descs, C.c_void_p(self.d_descs.data_ptr()), self.n, C.byref(self.opt),
                                              C.c_void_p(self.src.buf.data_ptr()), C.c_void_p(self.out.data_ptr()),
                                              C.c_void_p(stream)) != 0:
@@ -107,7 +122,8 @@ class TensorLeg:
     def parity(self, picks):
         int_view = {torch.uint8: torch.uint8, torch.float16: torch.int16, torch.bfloat16: torch.int16, torch.float32: torch.int32}
         for i in picks:
-            exp = vp8g.host_tensor(self.src.pictures[i % len(self.src.pictures)], self.src.w, self.src.h, self.opt)
+            k = i % len(self.src.pictures)
+            exp = vp8g.host_tensor(self.src.pictures[k], self.src.w, self.src.h, self.opt, alpha=self.src.alphas[k] if self.alpha else None)
             if not torch.equal(self.out[i].cpu().view(int_view[exp.dtype]), exp.view(int_view[exp.dtype])):
                 return "MISMATCH"
         return f"bit-exact vs host_tensor ({len(picks)} frames)"
@@ -166,7 +182,13 @@ def kernel_legs(args, dev):
     (t,) = timed_interleaved([lambda: f16.launch(stream)], args.runs, dev)
     out["tensor_f16_nchw_4k"] = rate(f16.bytes, t)
     out["tensor_f16_nchw_4k"]["parity"] = f16.parity(picks[:2])
-    del f16, src
+    del f16
+    torch.cuda.empty_cache()
+    u8a = TensorLeg(src, vp8g.tensor_opt((W, H), "uint8", "NHWC"), dev, alpha=True)
+    (t,) = timed_interleaved([lambda: u8a.launch(stream)], args.runs, dev)
+    out["tensor_u8_nhwc_rgba_4k"] = rate(u8a.bytes, t)
+    out["tensor_u8_nhwc_rgba_4k"]["parity"] = u8a.parity(picks[:2])
+    del u8a, src
     torch.cuda.empty_cache()
     sopt = vp8g.scale_opt(scale=(224, 224))
     small = Source([vp8g.host_scale(b, W, H, sopt)[0] for b in full], 224, 224, n, dev)
@@ -174,6 +196,10 @@ def kernel_legs(args, dev):
     (t,) = timed_interleaved([lambda: s16.launch(stream)], args.runs, dev)
     out["tensor_f16_nchw_224"] = rate(s16.bytes, t)
     out["tensor_f16_nchw_224"]["parity"] = s16.parity(picks)
+    s16a = TensorLeg(small, vp8g.tensor_opt((224, 224), "float16", "NCHW", **IMAGENET), dev, alpha=True)
+    (t,) = timed_interleaved([lambda: s16a.launch(stream)], args.runs, dev)
+    out["tensor_f16_nchw_rgba_224"] = rate(s16a.bytes, t)
+    out["tensor_f16_nchw_rgba_224"]["parity"] = s16a.parity(picks)
     return out
 
 
@@ -239,12 +265,14 @@ def e2e_legs(args, dev):
 
 
 def table(res) -> str:
-    k, e = res["kernel"], res["end_to_end"]
+    k, e = res["kernel"], res.get("end_to_end")
     rows = ["| leg | median | min .. max | note |", "|---|---|---|---|"]
     names = (("encoder_rgb_4k", f"vp8g_encode_batch_device, VP8G_ENC_RGB, {k['frames']} 4K frames"),
              ("tensor_u8_nhwc_4k", "tensor kernel, uint8 NHWC, same frames"),
              ("tensor_f16_nchw_4k", "tensor kernel, float16 NCHW, same frames"),
-             ("tensor_f16_nchw_224", f"tensor kernel, float16 NCHW, {k['frames']} x 224x224"))
+             ("tensor_u8_nhwc_rgba_4k", "tensor kernel, uint8 NHWC RGBA, same frames and an alpha plane each"),
+             ("tensor_f16_nchw_224", f"tensor kernel, float16 NCHW, {k['frames']} x 224x224"),
+             ("tensor_f16_nchw_rgba_224", "tensor kernel, float16 NCHW RGBA, same pictures and an alpha plane each"))
     for key, name in names:
         x = k[key]
         note = f"{x['TBs']} TB/s read + written = {x['fraction_of_achievable']} of {HBM_ACHIEVABLE_TBS} TB/s"
@@ -253,6 +281,8 @@ def table(res) -> str:
         if "parity" in x:
             note += f"; {x['parity']}"
         rows.append(f"| {name} | {x['median']} ms | {x['min']} .. {x['max']} | {note} |")
+    if not e:
+        return "\n".join(rows)
     a, b = e["scaled_224_i420_download"], e["tensor_224_f16_nchw"]
     rows.append(f"| end to end, {e['frames']} 4K files: vp8g_decode_webp_batch_scaled -> 224x224 ({a['library']}) | {a['median']} s | "
                 f"{a['min']} .. {a['max']} | {a['MPs']} MP/s of source pixels |")
@@ -265,7 +295,7 @@ def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=512)
     ap.add_argument("--runs", type=int, default=12)
-    ap.add_argument("--e2e-frames", type=int, default=256)
+    ap.add_argument("--e2e-frames", type=int, default=256, help="0: kernel legs only")
     ap.add_argument("--e2e-runs", type=int, default=5)
     ap.add_argument("--parent-lib", default="")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "tensor_bench.json"))
@@ -275,7 +305,8 @@ def main() -> int:
     dev = torch.device("cuda", 0)
     res = {"device": torch.cuda.get_device_name(dev), "kernel": kernel_legs(args, dev)}
     torch.cuda.empty_cache()
-    res["end_to_end"] = e2e_legs(args, dev)
+    if args.e2e_frames:
+        res["end_to_end"] = e2e_legs(args, dev)
     pathlib.Path(args.out).write_text(json.dumps(res, indent=1) + "\n")
     print(table(res))
     return 0

@@ -247,28 +247,18 @@ VP8G_API int vp8g_alpha_unfilter_batch_device(const Vp8gAlphaDesc* h, const Vp8g
 	bool ok = h && d_descs && d_src && d_dst && n > 0 && n <= 0x7FFFFFFFu;
 	bool gradient = false;
 	for (uint32_t i = 0; ok && i < n; i++) ok = desc_ok(h[i]) && h[i].task0 == i, gradient |= h[i].filter == 3;
-	if (!ok) {
-		errno = EINVAL;
-		return -1;
-	}
+	if (!ok) return vp8g::fail(EINVAL);
 	static const hipError_t attr =
 	    hipFuncSetAttribute((const void*)alpha_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-	const int cus = vp8g::device_cus();
 	// the tiles and rings are the gradient's: a launch without one asks for the full-width row only, and two
 	// 16-wave workgroups share a CU; with one, a workgroup's LDS fills more than half a CU's
 	const uint32_t lds = gradient ? (uint32_t)kLdsBytes : (uint32_t)kFull, full_off = gradient ? (uint32_t)kOffFull : 0u;
-	const uint32_t grid = min(n, (uint32_t)(cus > 0 ? cus : 256) * (gradient ? 1u : 2u));
-	vp8g::GateScope gate((hipStream_t)stream);  // (vp8g_device.h: no cross-workgroup launch beside it)
-	hipError_t e = attr != hipSuccess ? attr : gate.status();
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(alpha_kernel, dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, d_descs, n, d_src, d_dst, full_off);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = gate.done(false);
-	if (e != hipSuccess) {
-		vp8g::set_error_text("alpha launch", e);
-		errno = EIO;
-		return -1;
-	}
-	return 0;
+	const uint32_t grid = vp8g::grid_for(n, gradient ? 1u : 2u);
+	return vp8g::gated_launch(
+	    (hipStream_t)stream, "alpha launch",
+	    [&] {
+		    hipLaunchKernelGGL(alpha_kernel, dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, d_descs, n, d_src, d_dst, full_off);
+		    return hipGetLastError();
+	    },
+	    attr);
 }

@@ -1,6 +1,8 @@
 // vp8g_device.h -- internal interface between the C-ABI shim and the gfx950 kernels.
 #pragma once
 
+#include <errno.h>
+
 #include <hip/hip_runtime.h>
 
 #include "vp8g.h"
@@ -106,6 +108,18 @@ constexpr int kQList = kHdrBytes + 16 * kQWaveBytes;         // the chain list (
 constexpr size_t kChainScratch = (size_t)16 * kQWaveBytes;  // the cost sort's scratch: the wave areas
 inline size_t chain_lds_bytes(uint32_t list_max) { return (size_t)kQList + 4 * (size_t)list_max; }
 
+// Record a HIP failure for vp8g_last_error() (calling thread).
+void set_error_text(const char* where, hipError_t e);
+inline int fail(int e) { return errno = e, -1; }
+
+int device_cus();  // the device's CU count; 0 = unknown
+// The grid of a launch whose workgroups loop over `tasks`: per_cu workgroups for every CU, no more than there are tasks.
+inline uint32_t grid_for(uint64_t tasks, uint32_t per_cu) {
+	const int cus = device_cus();
+	const uint64_t cap = (uint64_t)(cus > 0 ? cus : 256) * per_cu;
+	return (uint32_t)(tasks < cap ? tasks : cap);
+}
+
 // Process-wide launch gate (vp8g_shim.hip).  Launch modes whose workgroups wait on each other across
 // CUs -- split parts (Launch::parts > 1) and the chain's mirror split -- need every
 // workgroup of the launch resident at once.  Beside another kernel of this library (an earlier
@@ -136,6 +150,26 @@ class GateScope {
 	hipError_t err_ = hipSuccess;
 	bool may_cross_ = false;
 };
+
+// The rule above has one implementation for every launch that does not cross workgroups (the sink stages, device m05,
+// the digests): `enqueue` (hipError_t(): each launch followed by hipGetLastError(), stopping at the first failure) runs
+// inside a GateScope on `stream` -- gate status, the enqueues, the completion event.  `before` carries an error found ahead
+// of the gate: the scope is still entered, nothing is enqueued, no event recorded.  0, or -1 with errno = EIO and
+// `where` recorded for vp8g_last_error.  The launches that may cross (run_locked in the shim, Pipeline::launch_recon)
+// read may_cross() and hold their own scope.
+template <class F>
+int gated_launch(hipStream_t stream, const char* where, F&& enqueue, hipError_t before = hipSuccess) {
+	hipError_t e;
+	{
+		GateScope gate(stream);
+		e = before != hipSuccess ? before : gate.status();
+		if (e == hipSuccess) e = enqueue();
+		if (e == hipSuccess) e = gate.done(false);
+	}
+	if (e == hipSuccess) return 0;
+	set_error_text(where, e);
+	return fail(EIO);
+}
 
 // ---- Which kernel a batch runs on (vp8g_plan.hip) --------------------------------
 // The launch switches.  knobs_from_env reads all six from the environment on every call (so a
@@ -205,7 +239,6 @@ LaunchPlan plan_launch(const Vp8gFrameDesc* h_descs, uint32_t n, int n_cus, bool
                        const LaunchPolicy& policy);
 
 constexpr uint32_t kMaxSplit = 8;
-int device_cus();
 
 // The buffers a launch may use (device pointers; those the plan sized as 0 bytes may be null).
 struct LaunchBuffers {
@@ -228,8 +261,5 @@ int make_desc(const Vp8KeyFrameHeader* kf, const Vp8DecodedFrame* d, int filtere
 // Planes in the yuv420_alloc layout; init = false leaves them uninitialised (outputs a D2H
 // overwrites completely).
 int alloc_planes(Yuv420Image* img, uint32_t width, uint32_t height, bool init);
-
-// Record a HIP failure for vp8g_last_error() (calling thread).
-void set_error_text(const char* where, hipError_t e);
 
 }  // namespace vp8g

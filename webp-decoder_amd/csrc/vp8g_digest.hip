@@ -80,43 +80,26 @@ __global__ __launch_bounds__(kThreads) void digest_kernel(const Vp8gFrameDesc* _
 
 VP8G_API int vp8g_frame_digests(const Vp8gFrameDesc* h_descs, const Vp8gFrameDesc* d_descs, uint32_t n, const uint8_t* d_out,
                                 uint64_t* d_digests, void* stream) {
-	if (!h_descs || !d_descs || !d_out || !d_digests) {
-		errno = EINVAL;
-		return -1;
-	}
+	if (!h_descs || !d_descs || !d_out || !d_digests) return vp8g::fail(EINVAL);
 	if (n == 0) return 0;
-	if (n > 65535) {  // grid.y limit
-		errno = EINVAL;
-		return -1;
-	}
+	if (n > 65535) return vp8g::fail(EINVAL);  // grid.y limit
 	uint64_t max_len = 0;
 	for (uint32_t i = 0; i < n; i++) {
 		const Vp8gFrameDesc& d = h_descs[i];
 		const uint64_t cw = (d.width + 1) / 2, ch = (d.height + 1) / 2;
 		// the digest covers the contiguous cropped I420 layout vp8g_make_frame_desc produces
 		if (d.stride_y != d.width || d.stride_uv != cw || d.out_u != d.out_y + (uint64_t)d.width * d.height ||
-		    d.out_v != d.out_u + cw * ch) {
-			errno = EINVAL;
-			return -1;
-		}
+		    d.out_v != d.out_u + cw * ch)
+			return vp8g::fail(EINVAL);
 		const uint64_t len = (uint64_t)d.width * d.height + 2 * cw * ch;
 		if (len > max_len) max_len = len;
 	}
 	hipStream_t s = (hipStream_t)stream;
-	vp8g::GateScope gate(s);  // (vp8g_device.h: no cross-workgroup launch beside it)
-	hipError_t e = gate.status();
-	if (e == hipSuccess) e = hipMemsetAsync(d_digests, 0, (size_t)n * 8, s);
-	if (e == hipSuccess) {
+	return vp8g::gated_launch(s, "digest", [&] {
+		const hipError_t e = hipMemsetAsync(d_digests, 0, (size_t)n * 8, s);
+		if (e != hipSuccess) return e;
 		const uint32_t chunks = (uint32_t)((max_len + kChunk - 1) / kChunk);
-		hipLaunchKernelGGL(digest_kernel, dim3(chunks, n), dim3(kThreads), 0, s, d_descs, d_out,
-		                   (unsigned long long*)d_digests);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = gate.done(false);
-	if (e != hipSuccess) {
-		vp8g::set_error_text("digest", e);
-		errno = EIO;
-		return -1;
-	}
-	return 0;
+		hipLaunchKernelGGL(digest_kernel, dim3(chunks, n), dim3(kThreads), 0, s, d_descs, d_out, (unsigned long long*)d_digests);
+		return hipGetLastError();
+	});
 }

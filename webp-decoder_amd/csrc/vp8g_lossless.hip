@@ -338,28 +338,18 @@ VP8G_API int vp8g_lossless_batch_device(const Vp8gLosslessDesc* h, const Vp8gLos
 		ok = desc_ok(h[i]) && h[i].task0 == i;
 		if (ok && h[i].width > maxw) maxw = h[i].width;
 	}
-	if (!ok) {
-		errno = EINVAL;
-		return -1;
-	}
+	if (!ok) return vp8g::fail(EINVAL);
 	constexpr uint32_t kLdsMax = (uint32_t)(kRingDwords + 16384 + 64) * 4u;
 	static const hipError_t attr =
 	    hipFuncSetAttribute((const void*)lossless_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
 	// the rings, and a full-width row as wide as the launch's widest image
 	const uint32_t lds = (uint32_t)(kRingDwords + ((maxw + 64u) & ~63u)) * 4u;
-	const int cus = vp8g::device_cus();
-	const uint32_t grid = min(n, (uint32_t)(cus > 0 ? cus : 256));
-	vp8g::GateScope gate((hipStream_t)stream);  // (vp8g_device.h: no cross-workgroup launch beside it)
-	hipError_t e = attr != hipSuccess ? attr : gate.status();
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(lossless_kernel, dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, d_descs, n, d_src, d_dst);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = gate.done(false);
-	if (e != hipSuccess) {
-		vp8g::set_error_text("lossless launch", e);
-		errno = EIO;
-		return -1;
-	}
-	return 0;
+	return vp8g::gated_launch(
+	    (hipStream_t)stream, "lossless launch",
+	    [&] {
+		    hipLaunchKernelGGL(lossless_kernel, dim3(vp8g::grid_for(n, 1u)), dim3(kThreads), lds, (hipStream_t)stream, d_descs, n, d_src,
+		                       d_dst);
+		    return hipGetLastError();
+	    },
+	    attr);
 }

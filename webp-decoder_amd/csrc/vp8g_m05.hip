@@ -452,10 +452,7 @@ __global__ __launch_bounds__(64 * (1 + kMaxParts)) void m05_kernel(const Vp8gTok
 
 VP8G_API int vp8g_m05_batch_device(const Vp8gTokFrame* h_jobs, const Vp8gTokFrame* d_jobs, uint32_t n,
                                    const uint8_t* d_bits, const Vp8gBatchArrays* arrays, void* hip_stream) {
-	if (!h_jobs || !d_jobs || !d_bits || !arrays || !arrays->status || n == 0) {
-		errno = EINVAL;
-		return -1;
-	}
+	if (!h_jobs || !d_jobs || !d_bits || !arrays || !arrays->status || n == 0) return vp8g::fail(EINVAL);
 	uint32_t max_cols = 0, max_parts = 1;
 	for (uint32_t i = 0; i < n; i++) {
 		const Vp8gTokFrame& j = h_jobs[i];
@@ -464,10 +461,7 @@ VP8G_API int vp8g_m05_batch_device(const Vp8gTokFrame* h_jobs, const Vp8gTokFram
 		          (j.nparts == 1 || j.nparts == 2 || j.nparts == 4 || j.nparts == 8);
 		for (uint32_t p = 0; ok && p < j.nparts; p++)
 			ok = j.part_off[p] >= j.p0_end && j.part_end[p] >= j.part_off[p] && (p == 0 || j.part_off[p] >= j.part_end[p - 1]);
-		if (!ok) {
-			errno = EINVAL;
-			return -1;
-		}
+		if (!ok) return vp8g::fail(EINVAL);
 		if (j.mb_cols > max_cols) max_cols = j.mb_cols;
 		if (j.nparts > max_parts) max_parts = j.nparts;
 	}
@@ -482,21 +476,9 @@ VP8G_API int vp8g_m05_batch_device(const Vp8gTokFrame* h_jobs, const Vp8gTokFram
 	o.hasc = const_cast<uint8_t*>(arrays->has_coeff);
 	o.bmode = const_cast<uint8_t*>(arrays->bmode);
 	o.status = arrays->status;
-	hipError_t e;
-	{
-		vp8g::GateScope gate((hipStream_t)hip_stream);  // (vp8g_device.h: no cross-workgroup launch beside it)
-		e = gate.status();
-		if (e == hipSuccess) {
-			hipLaunchKernelGGL(m05_kernel, dim3(n), dim3(64u * (1u + max_parts)), (kCtlWords + kRing / 4u + 2u * max_cols) * 4u,
-			                   (hipStream_t)hip_stream, d_jobs, d_bits, o);
-			e = hipGetLastError();
-		}
-		if (e == hipSuccess) e = gate.done(false);
-	}
-	if (e != hipSuccess) {
-		vp8g::set_error_text("m05 launch", e);
-		errno = EIO;
-		return -1;
-	}
-	return 0;
+	return vp8g::gated_launch((hipStream_t)hip_stream, "m05 launch", [&] {
+		hipLaunchKernelGGL(m05_kernel, dim3(n), dim3(64u * (1u + max_parts)), (kCtlWords + kRing / 4u + 2u * max_cols) * 4u,
+		                   (hipStream_t)hip_stream, d_jobs, d_bits, o);
+		return hipGetLastError();
+	});
 }

@@ -1128,7 +1128,7 @@ bool opts_ok(const Vp8gScaleOpt* opts, uint32_t n_opts, uint32_t n) { return opt
 bool tensor_ok(const Vp8gTensorOpt* t, const void* d_out) {
 	return t && d_out && vp8g_tensor_slot_size(t) && (uintptr_t)d_out % (vp8g_tensor_slot_size(t) / (3ull * t->width * t->height)) == 0;
 }
-int fail(int e) { return errno = e, -1; }
+using vp8g::fail;
 // A call that fails as a whole: no output survives, every frame reports `e`.
 int fail_all(Yuv420Image* outs, uint32_t n, int* status, int e) {
 	for (uint32_t i = 0; i < n; i++) {

@@ -589,49 +589,30 @@ VP8G_API uint32_t vp8g_make_enc_desc(uint32_t width, uint32_t height, uint32_t f
 
 VP8G_API int vp8g_encode_batch_device(const Vp8gEncDesc* h, const Vp8gEncDesc* d_descs, uint32_t n, const uint8_t* d_src,
                                       uint8_t* d_out, uint8_t* d_work, void* stream) {
-	if (!h || !d_descs || !d_src || !d_out || !d_work || n == 0) {
-		errno = EINVAL;
-		return -1;
-	}
+	if (!h || !d_descs || !d_src || !d_out || !d_work || n == 0) return vp8g::fail(EINVAL);
 	uint32_t total = 0;
 	bool any_png = false;
 	for (uint32_t i = 0; i < n; i++) {
-		if (h[i].span0 != total || h[i].nspans == 0) {  // tasks must be numbered image by image
-			errno = EINVAL;
-			return -1;
-		}
+		if (h[i].span0 != total || h[i].nspans == 0) return vp8g::fail(EINVAL);  // tasks must be numbered image by image
 		total += h[i].nspans;
 		any_png |= h[i].format == VP8G_ENC_PNG;
 	}
 	uint32_t* tab = nullptr;
-	const int cus = vp8g::device_cus();
-	hipError_t e = any_png ? tables_dev(&tab) : hipSuccess;
-	vp8g::GateScope gate((hipStream_t)stream);  // (vp8g_device.h: no cross-workgroup launch beside these)
-	if (e == hipSuccess) e = gate.status();
-	if (e == hipSuccess) {
-		const uint32_t grid = min(total, (uint32_t)(cus > 0 ? cus : 256) * 16u);
-		hipLaunchKernelGGL(enc_write_kernel, dim3(grid), dim3(kPlainThreads), 0, (hipStream_t)stream, d_descs, n, total, d_src,
-		                   d_out);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess && any_png) {
-		const uint32_t grid = min(total, (uint32_t)(cus > 0 ? cus : 256) * 4u);
-		hipLaunchKernelGGL(crc_kernel, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, d_descs, n, total, d_out,
-		                   (uint32_t*)d_work, tab);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess && any_png) {
-		hipLaunchKernelGGL(png_finish_kernel, dim3(n), dim3(kFinThreads), 0, (hipStream_t)stream, d_descs, (const uint32_t*)d_work,
-		                   d_out, tab);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = gate.done(false);
-	if (e != hipSuccess) {
-		vp8g::set_error_text("encode launch", e);
-		errno = EIO;
-		return -1;
-	}
-	return 0;
+	const hipError_t tables = any_png ? tables_dev(&tab) : hipSuccess;
+	const hipStream_t s = (hipStream_t)stream;
+	return vp8g::gated_launch(
+	    s, "encode launch",
+	    [&] {
+		    hipLaunchKernelGGL(enc_write_kernel, dim3(vp8g::grid_for(total, 16u)), dim3(kPlainThreads), 0, s, d_descs, n, total, d_src, d_out);
+		    hipError_t e = hipGetLastError();
+		    if (e != hipSuccess || !any_png) return e;
+		    hipLaunchKernelGGL(crc_kernel, dim3(vp8g::grid_for(total, 4u)), dim3(kThreads), 0, s, d_descs, n, total, d_out, (uint32_t*)d_work,
+		                       tab);
+		    if ((e = hipGetLastError()) != hipSuccess) return e;
+		    hipLaunchKernelGGL(png_finish_kernel, dim3(n), dim3(kFinThreads), 0, s, d_descs, (const uint32_t*)d_work, d_out, tab);
+		    return hipGetLastError();
+	    },
+	    tables);
 }
 
 // ---- the reference's writers: host image -> device -> file bytes -> fd ---------------------

@@ -505,45 +505,32 @@ VP8G_API int vp8g_make_scale_desc_plane(uint32_t width, uint32_t height, uint64_
 
 VP8G_API int vp8g_scale_batch_device(const Vp8gScaleDesc* h, const Vp8gScaleDesc* d_descs, uint32_t n, const uint8_t* d_src,
                                      uint8_t* d_dst, void* stream) {
-	if (!h || !d_descs || !d_src || !d_dst || n == 0) {
-		errno = EINVAL;
-		return -1;
-	}
+	if (!h || !d_descs || !d_src || !d_dst || n == 0) return vp8g::fail(EINVAL);
 	uint64_t total = 0;
 	bool any_shrink = false, any_expand = false;
 	for (uint32_t i = 0; i < n; i++) {
 		const Vp8gScaleDesc& d = h[i];
 		if (d.task0 != total || d.ntasks == 0 || d.ntasks != (uint64_t)d.p[0].ntasks + d.p[1].ntasks + d.p[2].ntasks ||
 		    !plane_ok(d.p[0]) || !(plane_ok(d.p[1]) || plane_empty(d.p[1])) ||
-		    !(plane_ok(d.p[2]) || plane_empty(d.p[2]))) {  // tasks must be numbered image by image
-			errno = EINVAL;
-			return -1;
-		}
+		    !(plane_ok(d.p[2]) || plane_empty(d.p[2])))  // tasks must be numbered image by image
+			return vp8g::fail(EINVAL);
 		for (uint32_t pi = 0; pi < 3u; pi++)
 			if (d.p[pi].ntasks) (expands(d.p[pi]) ? any_expand : any_shrink) = true;
 		total += d.ntasks;
-		if (total > 0x7FFFFFFFu) {
-			errno = EINVAL;
-			return -1;
+		if (total > 0x7FFFFFFFu) return vp8g::fail(EINVAL);
+	}
+	return vp8g::gated_launch((hipStream_t)stream, "scale launch", [&] {
+		hipError_t e = hipSuccess;
+		if (any_shrink) {
+			hipLaunchKernelGGL(scale_kernel, dim3((uint32_t)total), dim3(kThreads), 0, (hipStream_t)stream, d_descs, n, d_src, d_dst);
+			e = hipGetLastError();
 		}
-	}
-	vp8g::GateScope gate((hipStream_t)stream);  // (vp8g_device.h: no cross-workgroup launch beside it)
-	hipError_t e = gate.status();
-	if (e == hipSuccess && any_shrink) {
-		hipLaunchKernelGGL(scale_kernel, dim3((uint32_t)total), dim3(kThreads), 0, (hipStream_t)stream, d_descs, n, d_src, d_dst);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess && any_expand) {  // same grid, same numbering: each kernel returns from the other's tasks
-		hipLaunchKernelGGL(expand_kernel, dim3((uint32_t)total), dim3(kThreads), 0, (hipStream_t)stream, d_descs, n, d_src, d_dst);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = gate.done(false);
-	if (e != hipSuccess) {
-		vp8g::set_error_text("scale launch", e);
-		errno = EIO;
-		return -1;
-	}
-	return 0;
+		if (e == hipSuccess && any_expand) {  // same grid, same numbering: each kernel returns from the other's tasks
+			hipLaunchKernelGGL(expand_kernel, dim3((uint32_t)total), dim3(kThreads), 0, (hipStream_t)stream, d_descs, n, d_src, d_dst);
+			e = hipGetLastError();
+		}
+		return e;
+	});
 }
 
 VP8G_API int yuv420_rescale(const Yuv420Image* img, const Vp8gScaleOpt* opt, Yuv420Image* out) {

@@ -1,5 +1,5 @@
-// vp8g_tensor.hip -- device-resident I420 -> one dense RGB tensor, in the form a model reads
-// (include/vp8g.h: vp8g_tensor_batch_device).
+// vp8g_tensor.hip -- device-resident I420 (and an alpha plane), or ARGB, -> one dense RGB / RGBA tensor, in
+// the form a model reads (include/vp8g.h: vp8g_tensor_batch_device, _a, _argb).
 //
 // The pixels are those of the file encoder (vp8g_rgb.hip: "fancy" 4:2:0 upsampling, libwebp's
 // VP8YuvToRgb; both go through vp8g_rgb_device.h), but the unit of work is a run of pixels of one
@@ -7,15 +7,19 @@
 // unaligned 8-byte load per chroma row and plane, one 12-byte luma load), converts them to the
 // element type -- out = u8 * scale[c] + bias[c], a rounded multiply and then a rounded add -- and
 // stores them:
-//   NHWC  one run of 36 elements;
-//   NCHW  three runs of 12 elements, one per plane; neighbouring lanes hold neighbouring chunks of
+//   NHWC  one run of 12 C elements;
+//   NCHW  C runs of 12 elements, one per plane; neighbouring lanes hold neighbouring chunks of
 //         the row, so each plane's stores are contiguous across the lanes of a wave.
+// C = 3, or 4 with alpha as the fourth channel (the byte, or a / 255; scale and bias never touch it): one
+// kernel, tensor_kernel<.., C>, whose alpha parts sit under `if constexpr (C == 4)`.
 // A run whose address is dword-aligned goes out as 16- / 8- / 4-byte stores; runs of a row that
 // starts off a dword boundary (an odd slot start, an odd width) go out element by element, as do
 // the pixels of a row's last, partial chunk and of images narrower than 15 pixels (chroma rows
-// shorter than the 8-byte load).  Every store lies inside the image's own 3 * w * h elements.
+// shorter than the 8-byte load).  Every store lies inside the image's own C * w * h elements.
 // No LDS and no barriers.  A workgroup task is 256 consecutive chunks of one image; the dtype,
-// layout and channel order are template parameters picked on the host.
+// layout, channel order and channel count are template parameters picked on the host.
+// ARGB sources (lossless images) have a kernel of their own further down; the three entry points share
+// one host path, launch_tensor.
 #include <errno.h>
 #include <string.h>
 
@@ -121,9 +125,26 @@ DEV void store_run(uint8_t* p, const uint32_t (&e)[R]) {
 	}
 }
 
-template <uint32_t DT, bool PLANAR, bool BGR>
-__global__ __launch_bounds__(kThreads) void tensor_kernel(const Vp8gTensorDesc* __restrict__ D, uint32_t total, TensorParams P,
-                                                          const uint8_t* __restrict__ src, uint8_t* __restrict__ dst) {
+// The element of the alpha byte a: the byte, or the float nearest to a / 255 (a correctly rounded
+// division, not a multiply by a rounded reciprocal), rounded once more for the 16-bit types.
+template <uint32_t DT>
+DEV uint32_t conv_a(uint32_t a) {
+	if constexpr (DT == VP8G_T_U8) {
+		return a;
+	} else {
+		const float f = __fdiv_rn((float)a, 255.0f);
+		const uint32_t u = __float_as_uint(f);
+		if constexpr (DT == VP8G_T_F32) return u;
+		else if constexpr (DT == VP8G_T_F16) return (uint32_t)__half_as_ushort(__float2half_rn(f));
+		else return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+	}
+}
+
+template <uint32_t DT, bool PLANAR, bool BGR, int C>
+__global__ __launch_bounds__(kThreads) void tensor_kernel(const Vp8gTensorDesc* __restrict__ D, const Vp8gTensorAlpha* __restrict__ A,
+                                                          uint32_t total, TensorParams P, const uint8_t* __restrict__ src,
+                                                          uint8_t* __restrict__ dst) {
+	static_assert(C == 3 || C == 4, "RGB, or RGB and alpha");
 	constexpr uint32_t EB = (uint32_t)elem_bytes(DT);
 	const uint32_t tid = threadIdx.x, W = P.w;
 	for (uint32_t g = blockIdx.x; g < total; g += gridDim.x) {
@@ -141,6 +162,16 @@ __global__ __launch_bounds__(kThreads) void tensor_kernel(const Vp8gTensorDesc* 
 		const uint8_t* ub = src + d.src_u + (size_t)b * d.stride_uv;
 		const uint8_t* va = src + d.src_v + (size_t)a * d.stride_uv;
 		const uint8_t* vb = src + d.src_v + (size_t)b * d.stride_uv;
+		// C == 4: the alpha bytes of a chunk are read one by one (a plane of any stride and alignment), where
+		// their elements are stored; an opaque image reads none.  C == 3 never reads A.
+		[[maybe_unused]] bool opaque = true;
+		[[maybe_unused]] const uint8_t* arow = src;
+		if constexpr (C == 4) {
+			const Vp8gTensorAlpha al = A[img];
+			opaque = al.src_a == VP8G_T_OPAQUE;
+			if (!opaque) arow = src + al.src_a + (size_t)y * al.stride_a;
+		}
+		[[maybe_unused]] auto alpha = [&](uint32_t x) { return conv_a<DT>(opaque ? 255u : (uint32_t)arow[x]); };
 		uint8_t* out = dst + d.dst;
 		const size_t pix = (size_t)y * W + x0;  // the chunk's first pixel in the image
 		if (x0 + kChunk <= W && P.cw >= 8u) {
@@ -148,13 +179,14 @@ __global__ __launch_bounds__(kThreads) void tensor_kernel(const Vp8gTensorDesc* 
 			chunk_rgb(yrow, ua, ub, va, vb, x0, (int)P.cw, near_a, c);
 			if constexpr (PLANAR) {
 #pragma unroll
-				for (int ch = 0; ch < 3; ch++) {
+				for (int ch = 0; ch < C; ch++) {
 					uint32_t e[kChunk];
 #pragma unroll
-					for (int i = 0; i < (int)kChunk; i++) e[i] = conv<DT>(channel<BGR>(c[i], ch), P.scale[ch], P.bias[ch]);
+					for (int i = 0; i < (int)kChunk; i++)
+						e[i] = ch < 3 ? conv<DT>(channel<BGR>(c[i], ch), P.scale[ch % 3], P.bias[ch % 3]) : alpha(x0 + (uint32_t)i);
 					store_run<DT, (int)kChunk>(out + (size_t)ch * P.plane + pix * EB, e);
 				}
-			} else if constexpr (DT == VP8G_T_U8) {
+			} else if constexpr (C == 3 && DT == VP8G_T_U8) {
 				// 12 pixels -> 36 bytes -> 9 dwords (4 pixels = 3 dwords), as the file encoder packs them
 				uint8_t* p = out + pix * 3u;
 				if (BGR) {
@@ -175,12 +207,14 @@ __global__ __launch_bounds__(kThreads) void tensor_kernel(const Vp8gTensorDesc* 
 					for (int i = 0; i < 3 * (int)kChunk; i++) p[i] = (uint8_t)(c[i / 3] >> (8 * (i % 3)));
 				}
 			} else {
-				uint32_t e[3 * kChunk];
+				uint32_t e[C * kChunk];
 #pragma unroll
-				for (int i = 0; i < (int)kChunk; i++)
+				for (int i = 0; i < (int)kChunk; i++) {
 #pragma unroll
-					for (int ch = 0; ch < 3; ch++) e[3 * i + ch] = conv<DT>(channel<BGR>(c[i], ch), P.scale[ch], P.bias[ch]);
-				store_run<DT, 3 * (int)kChunk>(out + pix * 3u * EB, e);
+					for (int ch = 0; ch < 3; ch++) e[C * i + ch] = conv<DT>(channel<BGR>(c[i], ch), P.scale[ch], P.bias[ch]);
+					if constexpr (C == 4) e[4 * i + 3] = alpha(x0 + (uint32_t)i);
+				}
+				store_run<DT, C * (int)kChunk>(out + pix * (uint32_t)C * EB, e);
 			}
 			continue;
 		}
@@ -190,93 +224,9 @@ __global__ __launch_bounds__(kThreads) void tensor_kernel(const Vp8gTensorDesc* 
 			const uint32_t col = pixel_rgb(yrow, ua, ub, va, vb, x, P.cw, near_a);
 			const size_t px = (size_t)y * W + x;
 #pragma unroll
-			for (int ch = 0; ch < 3; ch++) {
-				uint8_t* p = PLANAR ? out + (size_t)ch * P.plane + px * EB : out + (px * 3u + (uint32_t)ch) * EB;
-				store_elem<DT>(p, conv<DT>(channel<BGR>(col, ch), P.scale[ch], P.bias[ch]));
-			}
-		}
-	}
-}
-
-// ---- alpha as a fourth channel (vp8g_tensor_batch_device_a) ------------------
-
-// The element of the alpha byte a: the byte, or the float nearest to a / 255 (a correctly rounded
-// division, not a multiply by a rounded reciprocal), rounded once more for the 16-bit types.
-template <uint32_t DT>
-DEV uint32_t conv_a(uint32_t a) {
-	if constexpr (DT == VP8G_T_U8) {
-		return a;
-	} else {
-		const float f = __fdiv_rn((float)a, 255.0f);
-		const uint32_t u = __float_as_uint(f);
-		if constexpr (DT == VP8G_T_F32) return u;
-		else if constexpr (DT == VP8G_T_F16) return (uint32_t)__half_as_ushort(__float2half_rn(f));
-		else return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-	}
-}
-
-// The 3-channel kernel's chunks and colour arithmetic, with four elements per pixel (NHWC: runs of 48
-// elements) or a fourth plane (NCHW).  The alpha bytes of a chunk are read one by one (a plane of any
-// stride and alignment); an opaque image reads none.
-template <uint32_t DT, bool PLANAR, bool BGR>
-__global__ __launch_bounds__(kThreads) void tensor_kernel_a(const Vp8gTensorDesc* __restrict__ D, const Vp8gTensorAlpha* __restrict__ A,
-                                                            uint32_t total, TensorParams P, const uint8_t* __restrict__ src,
-                                                            uint8_t* __restrict__ dst) {
-	constexpr uint32_t EB = (uint32_t)elem_bytes(DT);
-	const uint32_t tid = threadIdx.x, W = P.w;
-	for (uint32_t g = blockIdx.x; g < total; g += gridDim.x) {
-		const uint32_t img = g / P.tpi;
-		const uint32_t gc = (g - img * P.tpi) * kThreads + tid;
-		if (gc >= P.chunks) continue;
-		const Vp8gTensorDesc& d = D[img];
-		const Vp8gTensorAlpha al = A[img];
-		const bool opaque = al.src_a == VP8G_T_OPAQUE;
-		const uint32_t y = gc / P.cpr, x0 = (gc - y * P.cpr) * kChunk;
-		const uint32_t a = y ? (y - 1u) >> 1 : 0u, b = y ? min(a + 1u, P.ch - 1u) : 0u;
-		const bool near_a = y == 0 || (y & 1u);
-		const uint8_t* yrow = src + d.src_y + (size_t)y * d.stride_y;
-		const uint8_t* ua = src + d.src_u + (size_t)a * d.stride_uv;
-		const uint8_t* ub = src + d.src_u + (size_t)b * d.stride_uv;
-		const uint8_t* va = src + d.src_v + (size_t)a * d.stride_uv;
-		const uint8_t* vb = src + d.src_v + (size_t)b * d.stride_uv;
-		const uint8_t* arow = opaque ? src : src + al.src_a + (size_t)y * al.stride_a;  // (read only when not opaque)
-		uint8_t* out = dst + d.dst;
-		const size_t pix = (size_t)y * W + x0;
-		if (x0 + kChunk <= W && P.cw >= 8u) {
-			uint32_t c[kChunk], av[kChunk];
-			chunk_rgb(yrow, ua, ub, va, vb, x0, (int)P.cw, near_a, c);
-#pragma unroll
-			for (int i = 0; i < (int)kChunk; i++) av[i] = conv_a<DT>(opaque ? 255u : (uint32_t)arow[x0 + i]);
-			if constexpr (PLANAR) {
-#pragma unroll
-				for (int ch = 0; ch < 3; ch++) {
-					uint32_t e[kChunk];
-#pragma unroll
-					for (int i = 0; i < (int)kChunk; i++) e[i] = conv<DT>(channel<BGR>(c[i], ch), P.scale[ch], P.bias[ch]);
-					store_run<DT, (int)kChunk>(out + (size_t)ch * P.plane + pix * EB, e);
-				}
-				store_run<DT, (int)kChunk>(out + 3u * P.plane + pix * EB, av);
-			} else {
-				uint32_t e[4 * kChunk];
-#pragma unroll
-				for (int i = 0; i < (int)kChunk; i++) {
-#pragma unroll
-					for (int ch = 0; ch < 3; ch++) e[4 * i + ch] = conv<DT>(channel<BGR>(c[i], ch), P.scale[ch], P.bias[ch]);
-					e[4 * i + 3] = av[i];
-				}
-				store_run<DT, 4 * (int)kChunk>(out + pix * 4u * EB, e);
-			}
-			continue;
-		}
-		const uint32_t xe = min(x0 + kChunk, W);
-		for (uint32_t x = x0; x < xe; x++) {
-			const uint32_t col = pixel_rgb(yrow, ua, ub, va, vb, x, P.cw, near_a);
-			const size_t px = (size_t)y * W + x;
-#pragma unroll
-			for (int ch = 0; ch < 4; ch++) {
-				uint8_t* p = PLANAR ? out + (size_t)ch * P.plane + px * EB : out + (px * 4u + (uint32_t)ch) * EB;
-				store_elem<DT>(p, ch < 3 ? conv<DT>(channel<BGR>(col, ch), P.scale[ch], P.bias[ch])
-				                         : conv_a<DT>(opaque ? 255u : (uint32_t)arow[x]));
+			for (int ch = 0; ch < C; ch++) {
+				uint8_t* p = PLANAR ? out + (size_t)ch * P.plane + px * EB : out + (px * (uint32_t)C + (uint32_t)ch) * EB;
+				store_elem<DT>(p, ch < 3 ? conv<DT>(channel<BGR>(col, ch), P.scale[ch % 3], P.bias[ch % 3]) : alpha(x));
 			}
 		}
 	}
@@ -348,29 +298,15 @@ __global__ __launch_bounds__(kThreads) void tensor_kernel_argb(const Vp8gTensorA
 }
 
 using KernelFnArgb = void (*)(const Vp8gTensorArgbDesc*, uint32_t, TensorParams, const uint8_t*, uint8_t*);
-#define VP8G_T_ROW_ARGB(DT, C) \
-	{ {tensor_kernel_argb<DT, false, false, C>, tensor_kernel_argb<DT, false, true, C>}, \
-	  {tensor_kernel_argb<DT, true, false, C>, tensor_kernel_argb<DT, true, true, C>} }
-const KernelFnArgb kKernelsArgb[2][4][2][2] = {
-    {VP8G_T_ROW_ARGB(VP8G_T_U8, 3), VP8G_T_ROW_ARGB(VP8G_T_F16, 3), VP8G_T_ROW_ARGB(VP8G_T_BF16, 3), VP8G_T_ROW_ARGB(VP8G_T_F32, 3)},
-    {VP8G_T_ROW_ARGB(VP8G_T_U8, 4), VP8G_T_ROW_ARGB(VP8G_T_F16, 4), VP8G_T_ROW_ARGB(VP8G_T_BF16, 4), VP8G_T_ROW_ARGB(VP8G_T_F32, 4)}};
-#undef VP8G_T_ROW_ARGB
-
-uint32_t argb_tasks_per_image(const Vp8gTensorOpt& t) {
-	const uint32_t per = kThreads * kArgbPx;
-	return (t.width * t.height + per - 1u) / per;
-}
-
-using KernelFnA = void (*)(const Vp8gTensorDesc*, const Vp8gTensorAlpha*, uint32_t, TensorParams, const uint8_t*, uint8_t*);
-#define VP8G_T_ROW_A(DT) \
-	{ {tensor_kernel_a<DT, false, false>, tensor_kernel_a<DT, false, true>}, {tensor_kernel_a<DT, true, false>, tensor_kernel_a<DT, true, true>} }
-const KernelFnA kKernelsA[4][2][2] = {VP8G_T_ROW_A(VP8G_T_U8), VP8G_T_ROW_A(VP8G_T_F16), VP8G_T_ROW_A(VP8G_T_BF16), VP8G_T_ROW_A(VP8G_T_F32)};
-#undef VP8G_T_ROW_A
-
-using KernelFn = void (*)(const Vp8gTensorDesc*, uint32_t, TensorParams, const uint8_t*, uint8_t*);
-#define VP8G_T_ROW(DT) \
-	{ {tensor_kernel<DT, false, false>, tensor_kernel<DT, false, true>}, {tensor_kernel<DT, true, false>, tensor_kernel<DT, true, true>} }
-const KernelFn kKernels[4][2][2] = {VP8G_T_ROW(VP8G_T_U8), VP8G_T_ROW(VP8G_T_F16), VP8G_T_ROW(VP8G_T_BF16), VP8G_T_ROW(VP8G_T_F32)};
+using KernelFn = void (*)(const Vp8gTensorDesc*, const Vp8gTensorAlpha*, uint32_t, TensorParams, const uint8_t*, uint8_t*);
+// [C - 3][dtype][layout][bgr]
+#define VP8G_T_ROW(K, DT, C) { {K<DT, false, false, C>, K<DT, false, true, C>}, {K<DT, true, false, C>, K<DT, true, true, C>} }
+#define VP8G_T_TABLE(K) \
+	{ {VP8G_T_ROW(K, VP8G_T_U8, 3), VP8G_T_ROW(K, VP8G_T_F16, 3), VP8G_T_ROW(K, VP8G_T_BF16, 3), VP8G_T_ROW(K, VP8G_T_F32, 3)}, \
+	  {VP8G_T_ROW(K, VP8G_T_U8, 4), VP8G_T_ROW(K, VP8G_T_F16, 4), VP8G_T_ROW(K, VP8G_T_BF16, 4), VP8G_T_ROW(K, VP8G_T_F32, 4)} }
+const KernelFn kKernels[2][4][2][2] = VP8G_T_TABLE(tensor_kernel);
+const KernelFnArgb kKernelsArgb[2][4][2][2] = VP8G_T_TABLE(tensor_kernel_argb);
+#undef VP8G_T_TABLE
 #undef VP8G_T_ROW
 
 bool opt_ok(const Vp8gTensorOpt* t) {
@@ -388,23 +324,62 @@ uint32_t tasks_per_image(const Vp8gTensorOpt& t) {
 	return (chunks + kThreads - 1u) / kThreads;
 }
 
-}  // namespace
+uint32_t argb_tasks_per_image(const Vp8gTensorOpt& t) {
+	const uint32_t per = kThreads * kArgbPx;
+	return (t.width * t.height + per - 1u) / per;
+}
 
-VP8G_API uint64_t vp8g_tensor_slot_size(const Vp8gTensorOpt* t) {
+uint64_t slot_size(const Vp8gTensorOpt* t, uint64_t channels) {
 	if (!opt_ok(t)) {
 		errno = EINVAL;
 		return 0;
 	}
-	return 3ull * t->width * t->height * (uint64_t)elem_bytes(t->dtype);
+	return channels * t->width * t->height * (uint64_t)elem_bytes(t->dtype);
 }
+
+// What the three entry points share.  ptrs_ok: the caller's own pointer and argument checks.  The option and the
+// tensor's base are checked here, then every descriptor: tasks numbered image by image, tpi(*t) each, the slot on an
+// element boundary, and desc_ok(i), the entry point's own conditions.  table is [dtype][layout][bgr];
+// args... are the kernel's leading (descriptor) arguments.  (P.cw .. P.chunks describe the I420 kernel's chunks; the
+// ARGB kernel does not read them.)
+template <class Desc, class Ok, class Kernel, class... Args>
+int launch_tensor(bool ptrs_ok, const Desc* h, uint32_t n, const Vp8gTensorOpt* t, uint32_t (*tpi_of)(const Vp8gTensorOpt&),
+                  const uint8_t* d_src, void* d_dst, void* stream, Ok&& desc_ok, const Kernel (&table)[4][2][2], Args... args) {
+	if (!ptrs_ok || !h || !d_src || !d_dst || n == 0 || !opt_ok(t)) return vp8g::fail(EINVAL);
+	const uint32_t eb = (uint32_t)elem_bytes(t->dtype), tpi = tpi_of(*t);
+	uint64_t total = 0;
+	bool ok = (uintptr_t)d_dst % eb == 0;
+	for (uint32_t i = 0; ok && i < n; i++) {  // tasks must be numbered image by image
+		ok = h[i].task0 == total && h[i].ntasks == tpi && h[i].dst % eb == 0 && desc_ok(i);
+		total += tpi;
+		if (total > 0x7FFFFFFFu) ok = false;
+	}
+	if (!ok) return vp8g::fail(EINVAL);
+	TensorParams P;
+	memset(&P, 0, sizeof(P));
+	P.w = t->width, P.h = t->height, P.cw = (t->width + 1u) / 2u, P.ch = (t->height + 1u) / 2u;
+	P.cpr = (t->width + kChunk - 1u) / kChunk, P.chunks = P.cpr * t->height, P.tpi = tpi;
+	P.plane = (uint64_t)t->width * t->height * eb;
+	for (int c = 0; c < 3; c++) P.scale[c] = t->scale[c], P.bias[c] = t->bias[c];
+	return vp8g::gated_launch((hipStream_t)stream, "tensor launch", [&] {
+		hipLaunchKernelGGL(table[t->dtype][t->layout][t->flags & VP8G_T_BGR], dim3(vp8g::grid_for(total, 16u)), dim3(kThreads), 0,
+		                   (hipStream_t)stream, args..., (uint32_t)total, P, d_src, (uint8_t*)d_dst);
+		return hipGetLastError();
+	});
+}
+
+bool strides_ok(const Vp8gTensorDesc& d, const Vp8gTensorOpt& t) { return d.stride_y >= t.width && d.stride_uv >= (t.width + 1u) / 2u; }
+
+}  // namespace
+
+VP8G_API uint64_t vp8g_tensor_slot_size(const Vp8gTensorOpt* t) { return slot_size(t, 3); }
+
+VP8G_API uint64_t vp8g_tensor_slot_size_a(const Vp8gTensorOpt* t) { return slot_size(t, 4); }
 
 VP8G_API int vp8g_make_tensor_desc(const Vp8gTensorOpt* t, uint64_t src_y, uint64_t src_u, uint64_t src_v, uint32_t stride_y,
                                    uint32_t stride_uv, uint64_t dst_offset, uint32_t task0, Vp8gTensorDesc* d) {
-	if (!d || !opt_ok(t) || stride_y < t->width || stride_uv < (t->width + 1u) / 2u ||
-	    dst_offset % (uint64_t)elem_bytes(t->dtype)) {
-		errno = EINVAL;
-		return -1;
-	}
+	if (!d || !opt_ok(t) || stride_y < t->width || stride_uv < (t->width + 1u) / 2u || dst_offset % (uint64_t)elem_bytes(t->dtype))
+		return vp8g::fail(EINVAL);
 	memset(d, 0, sizeof(*d));
 	d->src_y = src_y, d->src_u = src_u, d->src_v = src_v, d->dst = dst_offset;
 	d->stride_y = stride_y, d->stride_uv = stride_uv;
@@ -414,105 +389,24 @@ VP8G_API int vp8g_make_tensor_desc(const Vp8gTensorOpt* t, uint64_t src_y, uint6
 
 VP8G_API int vp8g_tensor_batch_device(const Vp8gTensorDesc* h, const Vp8gTensorDesc* d_descs, uint32_t n, const Vp8gTensorOpt* t,
                                       const uint8_t* d_src, void* d_dst, void* stream) {
-	if (!h || !d_descs || !d_src || !d_dst || n == 0 || !opt_ok(t)) {
-		errno = EINVAL;
-		return -1;
-	}
-	const uint32_t eb = (uint32_t)elem_bytes(t->dtype), tpi = tasks_per_image(*t);
-	uint64_t total = 0;
-	bool ok = (uintptr_t)d_dst % eb == 0;
-	for (uint32_t i = 0; ok && i < n; i++) {  // tasks must be numbered image by image
-		ok = h[i].task0 == total && h[i].ntasks == tpi && h[i].stride_y >= t->width && h[i].stride_uv >= (t->width + 1u) / 2u &&
-		     h[i].dst % eb == 0;
-		total += tpi;
-		if (total > 0x7FFFFFFFu) ok = false;
-	}
-	if (!ok) {
-		errno = EINVAL;
-		return -1;
-	}
-	TensorParams P;
-	memset(&P, 0, sizeof(P));
-	P.w = t->width, P.h = t->height, P.cw = (t->width + 1u) / 2u, P.ch = (t->height + 1u) / 2u;
-	P.cpr = (t->width + kChunk - 1u) / kChunk, P.chunks = P.cpr * t->height, P.tpi = tpi;
-	P.plane = (uint64_t)t->width * t->height * eb;
-	for (int c = 0; c < 3; c++) P.scale[c] = t->scale[c], P.bias[c] = t->bias[c];
-	const int cus = vp8g::device_cus();
-	const uint32_t grid = min((uint32_t)total, (uint32_t)(cus > 0 ? cus : 256) * 16u);
-	vp8g::GateScope gate((hipStream_t)stream);  // (vp8g_device.h: no cross-workgroup launch beside it)
-	hipError_t e = gate.status();
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(kKernels[t->dtype][t->layout][t->flags & VP8G_T_BGR], dim3(grid), dim3(kThreads), 0, (hipStream_t)stream,
-		                   d_descs, (uint32_t)total, P, d_src, (uint8_t*)d_dst);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = gate.done(false);
-	if (e != hipSuccess) {
-		vp8g::set_error_text("tensor launch", e);
-		errno = EIO;
-		return -1;
-	}
-	return 0;
-}
-
-VP8G_API uint64_t vp8g_tensor_slot_size_a(const Vp8gTensorOpt* t) {
-	if (!opt_ok(t)) {
-		errno = EINVAL;
-		return 0;
-	}
-	return 4ull * t->width * t->height * (uint64_t)elem_bytes(t->dtype);
+	return launch_tensor(
+	    d_descs != nullptr, h, n, t, tasks_per_image, d_src, d_dst, stream, [&](uint32_t i) { return strides_ok(h[i], *t); }, kKernels[0],
+	    d_descs, (const Vp8gTensorAlpha*)nullptr);
 }
 
 VP8G_API int vp8g_tensor_batch_device_a(const Vp8gTensorDesc* h, const Vp8gTensorDesc* d_descs, const Vp8gTensorAlpha* ha,
                                         const Vp8gTensorAlpha* d_alpha, uint32_t n, const Vp8gTensorOpt* t, const uint8_t* d_src,
                                         void* d_dst, void* stream) {
-	if (!h || !d_descs || !ha || !d_alpha || !d_src || !d_dst || n == 0 || !opt_ok(t)) {
-		errno = EINVAL;
-		return -1;
-	}
-	const uint32_t eb = (uint32_t)elem_bytes(t->dtype), tpi = tasks_per_image(*t);
-	uint64_t total = 0;
-	bool ok = (uintptr_t)d_dst % eb == 0;
-	for (uint32_t i = 0; ok && i < n; i++) {  // tasks must be numbered image by image
-		ok = h[i].task0 == total && h[i].ntasks == tpi && h[i].stride_y >= t->width && h[i].stride_uv >= (t->width + 1u) / 2u &&
-		     h[i].dst % eb == 0 && (ha[i].src_a == VP8G_T_OPAQUE || ha[i].stride_a >= t->width);
-		total += tpi;
-		if (total > 0x7FFFFFFFu) ok = false;
-	}
-	if (!ok) {
-		errno = EINVAL;
-		return -1;
-	}
-	TensorParams P;
-	memset(&P, 0, sizeof(P));
-	P.w = t->width, P.h = t->height, P.cw = (t->width + 1u) / 2u, P.ch = (t->height + 1u) / 2u;
-	P.cpr = (t->width + kChunk - 1u) / kChunk, P.chunks = P.cpr * t->height, P.tpi = tpi;
-	P.plane = (uint64_t)t->width * t->height * eb;
-	for (int c = 0; c < 3; c++) P.scale[c] = t->scale[c], P.bias[c] = t->bias[c];
-	const int cus = vp8g::device_cus();
-	const uint32_t grid = min((uint32_t)total, (uint32_t)(cus > 0 ? cus : 256) * 16u);
-	vp8g::GateScope gate((hipStream_t)stream);  // (vp8g_device.h: no cross-workgroup launch beside it)
-	hipError_t e = gate.status();
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(kKernelsA[t->dtype][t->layout][t->flags & VP8G_T_BGR], dim3(grid), dim3(kThreads), 0, (hipStream_t)stream,
-		                   d_descs, d_alpha, (uint32_t)total, P, d_src, (uint8_t*)d_dst);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = gate.done(false);
-	if (e != hipSuccess) {
-		vp8g::set_error_text("tensor launch", e);
-		errno = EIO;
-		return -1;
-	}
-	return 0;
+	return launch_tensor(
+	    d_descs && ha && d_alpha, h, n, t, tasks_per_image, d_src, d_dst, stream,
+	    [&](uint32_t i) { return strides_ok(h[i], *t) && (ha[i].src_a == VP8G_T_OPAQUE || ha[i].stride_a >= t->width); },
+	    kKernels[1], d_descs, d_alpha);
 }
 
 VP8G_API int vp8g_make_tensor_argb_desc(const Vp8gTensorOpt* t, uint32_t channels, uint64_t src, uint64_t dst_offset, uint32_t task0,
                                         Vp8gTensorArgbDesc* d) {
-	if (!d || !opt_ok(t) || (channels != 3 && channels != 4) || src % 4u || dst_offset % (uint64_t)elem_bytes(t->dtype)) {
-		errno = EINVAL;
-		return -1;
-	}
+	if (!d || !opt_ok(t) || (channels != 3 && channels != 4) || src % 4u || dst_offset % (uint64_t)elem_bytes(t->dtype))
+		return vp8g::fail(EINVAL);
 	memset(d, 0, sizeof(*d));
 	d->src = src, d->dst = dst_offset, d->task0 = task0, d->ntasks = argb_tasks_per_image(*t);
 	return 0;
@@ -520,41 +414,7 @@ VP8G_API int vp8g_make_tensor_argb_desc(const Vp8gTensorOpt* t, uint32_t channel
 
 VP8G_API int vp8g_tensor_batch_device_argb(const Vp8gTensorArgbDesc* h, const Vp8gTensorArgbDesc* d_descs, uint32_t n,
                                            const Vp8gTensorOpt* t, uint32_t channels, const uint8_t* d_src, void* d_dst, void* stream) {
-	if (!h || !d_descs || !d_src || !d_dst || n == 0 || !opt_ok(t) || (channels != 3 && channels != 4)) {
-		errno = EINVAL;
-		return -1;
-	}
-	const uint32_t eb = (uint32_t)elem_bytes(t->dtype), tpi = argb_tasks_per_image(*t);
-	uint64_t total = 0;
-	bool ok = (uintptr_t)d_dst % eb == 0 && (uintptr_t)d_src % 4u == 0;
-	for (uint32_t i = 0; ok && i < n; i++) {  // tasks must be numbered image by image
-		ok = h[i].task0 == total && h[i].ntasks == tpi && h[i].src % 4u == 0 && h[i].dst % eb == 0;
-		total += tpi;
-		if (total > 0x7FFFFFFFu) ok = false;
-	}
-	if (!ok) {
-		errno = EINVAL;
-		return -1;
-	}
-	TensorParams P;
-	memset(&P, 0, sizeof(P));
-	P.w = t->width, P.h = t->height, P.tpi = tpi;
-	P.plane = (uint64_t)t->width * t->height * eb;
-	for (int c = 0; c < 3; c++) P.scale[c] = t->scale[c], P.bias[c] = t->bias[c];
-	const int cus = vp8g::device_cus();
-	const uint32_t grid = min((uint32_t)total, (uint32_t)(cus > 0 ? cus : 256) * 16u);
-	vp8g::GateScope gate((hipStream_t)stream);  // (vp8g_device.h: no cross-workgroup launch beside it)
-	hipError_t e = gate.status();
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(kKernelsArgb[channels - 3u][t->dtype][t->layout][t->flags & VP8G_T_BGR], dim3(grid), dim3(kThreads), 0,
-		                   (hipStream_t)stream, d_descs, (uint32_t)total, P, d_src, (uint8_t*)d_dst);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = gate.done(false);
-	if (e != hipSuccess) {
-		vp8g::set_error_text("tensor launch", e);
-		errno = EIO;
-		return -1;
-	}
-	return 0;
+	return launch_tensor(
+	    d_descs && (channels == 3 || channels == 4) && (uintptr_t)d_src % 4u == 0, h, n, t, argb_tasks_per_image, d_src, d_dst, stream,
+	    [&](uint32_t i) { return h[i].src % 4u == 0; }, kKernelsArgb[channels == 4u], d_descs);
 }
