@@ -381,7 +381,9 @@ int vp8g_encode_batch_device(const Vp8gEncDesc* h_descs, const Vp8gEncDesc* d_de
 /* libwebp's `use_cropping` / `use_scaling` decoder options (dwebp -crop x y w h -scale w h), bit-exact
  * to libwebp 1.2.2's rescaler.  All-zero = identity.
  *   crop    (crop_left, crop_top, crop_w, crop_h), all 0 = the full picture; else w, h >= 1,
- *           left + w <= width, top + h <= height; left and top are rounded down to even.
+ *           left + w <= width, top + h <= height; left and top are rounded down to even for I420
+ *           (libwebp keeps the window aligned with chroma) -- but NOT for an ARGB picture of a lossless
+ *           file, whose window starts where it is given (vp8g_scale_argb_batch_device).
  *   scale   scaled_w x scaled_h; one of them 0 = derived from the other with a ceiling
  *           (h = (src_h * w + src_w - 1) / src_w over the cropped size); both 0 = crop only.
  * Without VP8G_SCALE_EXPAND, DOWNSCALE ONLY: scaled_w <= the (cropped) width and scaled_h <= the
@@ -693,16 +695,77 @@ int vp8g_tensor_batch_device_argb(const Vp8gTensorArgbDesc* h_descs, const Vp8gT
                                   const Vp8gTensorOpt* opt, uint32_t channels, const uint8_t* d_src, void* d_dst,
                                   void* hip_stream);
 
+/* ---- Crop + rescale of ARGB pictures (lossless files), exact to libwebp ---- */
+
+/* libwebp applies a Vp8gScaleOpt to a lossless picture as follows, and so does this: the window is taken as
+ * given (NO even rounding of its origin; see Vp8gScaleOpt); its pixels are alpha-premultiplied; each of the
+ * four byte channels is rescaled exactly as a luma plane of vp8g_scale_batch_device (shrinking and, with
+ * VP8G_SCALE_EXPAND, expanding, per axis); the output pixels are un-premultiplied.  A crop without a target size
+ * copies the window's pixels untouched.  VP8G_SCALE_DWEBP_FILTER means nothing here and is ignored.
+ * Per-picture descriptor (built by vp8g_make_scale_argb_desc).  1200 bytes. */
+typedef struct {
+	uint64_t src;                        /* byte offset (a multiple of 4) of the tight src_width x src_height 0xAARRGGBB picture */
+	uint64_t work;                       /* byte offset (a multiple of 16) of this picture's planes in the work buffer */
+	uint64_t dst;                        /* byte offset (a multiple of 4) of the tight width x height 0xAARRGGBB output */
+	uint64_t work_bytes;                 /* bytes at `work`: four window planes, then four scaled planes (0: crop only) */
+	uint32_t width, height;              /* output size */
+	uint32_t src_width, src_height;      /* the picture the options were resolved against */
+	uint32_t crop_left, crop_top, win_w, win_h;  /* the resolved window, origin as given */
+	uint32_t plane_stride, out_stride;   /* bytes per row of a window plane / a scaled plane: win_w / width rounded up to 16 */
+	uint32_t nplanes, plane0;            /* 4, or 0 for a crop without a target size; this picture's first plane descriptor in the launch */
+	uint32_t split_task0, split_ntasks;  /* this picture's workgroup tasks in the split launch, ... */
+	uint32_t scale_task0, scale_ntasks;  /* ... in the rescaler's (the sum over its planes), ... */
+	uint32_t merge_task0, merge_ntasks;  /* ... and in the merge launch */
+	uint32_t reserved[2];
+	Vp8gScaleDesc plane[4];              /* B, G, R, A as vp8g_make_scale_desc_plane makes them: work buffer -> work buffer */
+} Vp8gScaleArgbDesc;
+
+/* Bytes of the work buffer one picture's planes need (a multiple of 16; 0 for a crop without a target size), or
+ * 0 + EINVAL for options that do not fit the picture (as vp8g_scaled_size). */
+uint64_t vp8g_scale_argb_work_size(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt);
+
+/* Bytes at the START of the work buffer that a launch of n pictures keeps for itself (the rescaler's plane
+ * descriptors); every picture's work_offset lies at or beyond it. */
+uint64_t vp8g_scale_argb_head_size(uint32_t n);
+
+/* Fill the descriptor of one width x height ARGB picture at `src` of the source buffer; its planes go to work_offset
+ * of the work buffer (vp8g_scale_argb_work_size bytes), the scaled picture to dst_offset of the output buffer.  The
+ * four counters are the launch's running totals before this picture: planes (out->nplanes each), split tasks, rescaler
+ * tasks, merge tasks (out->*_ntasks each).  0, or -1 + EINVAL (NULL, options that do not fit, a misaligned offset). */
+int vp8g_make_scale_argb_desc(uint32_t width, uint32_t height, uint64_t src, const Vp8gScaleOpt* opt, uint64_t work_offset,
+                              uint64_t dst_offset, uint32_t plane0, uint32_t split_task0, uint32_t scale_task0,
+                              uint32_t merge_task0, Vp8gScaleArgbDesc* out);
+
+/* Crop + rescale n device-resident ARGB pictures of mixed sizes and options on `hip_stream`: the split launch, the
+ * rescaler's one or two launches (vp8g_scale_batch_device over the planes), the merge launch.  h_descs / d_descs: host
+ * and device copies of the descriptors.  d_src and d_dst dword-aligned, d_work 16-byte aligned.  Reads only the
+ * windows' pixels; writes only the pictures' own output dwords, their work regions and the head of d_work.
+ * Asynchronous; 0 or -1 + errno.  The host copies are checked before anything is launched -- EINVAL: NULL or
+ * misaligned pointer, n = 0, a descriptor that is not what vp8g_make_scale_argb_desc gives (a window outside the
+ * picture, ...), counters that do not number the pictures in order, a work region inside the head or overlapping
+ * another's; ENOMEM.  EIO on a launch failure.  d_dst may feed vp8g_tensor_batch_device_argb on the same stream with
+ * no host copy in between, and d_src may be the output of vp8g_lossless_batch_device. */
+int vp8g_scale_argb_batch_device(const Vp8gScaleArgbDesc* h_descs, const Vp8gScaleArgbDesc* d_descs, uint32_t n,
+                                 const uint8_t* d_src, uint8_t* d_work, uint8_t* d_dst, void* hip_stream);
+
 /* vp8g_decode_webp_batch_tensor_x, which with VP8G_X_LOSSLESS also decodes lossless files (a simple
  * 'VP8L' file, or VP8X + 'VP8L'): lossy and lossless files may share a batch and a tensor.  A worker
  * thread entropy-decodes a lossless frame (vp8f_lossless_decode); its residual image and transform data
  * are uploaded into the chunk buffer and go through vp8g_lossless_batch_device and
  * vp8g_tensor_batch_device_argb on the chunk's stream (3 channels without VP8G_X_ALPHA, 4 with).
- * Scaling a lossless frame is not supported: one whose resolved scale option is not the identity gets
- * status[i] = ENOTSUP and a zero slot.  A size mismatch with the tensor or a stream that does not
+ * Without VP8G_X_LOSSLESS_SCALE a lossless frame is not scaled: one whose resolved scale option is not the
+ * identity gets status[i] = ENOTSUP and a zero slot.  A size mismatch with the tensor or a stream that does not
  * decode is EINVAL.  Without VP8G_X_LOSSLESS: vp8g_decode_webp_batch_tensor_x.  Other xflags bits: EINVAL.
- * The lossless buffers count against the chunk memory budget; vp8g_plan_batch does not price them. */
+ * The lossless buffers count against the chunk memory budget; vp8g_plan_batch does not price them.
+ *   VP8G_X_LOSSLESS_SCALE (needs VP8G_X_LOSSLESS, else EINVAL)  a lossless frame's option is applied as libwebp
+ *                  applies it to such a file (vp8g_scale_argb_batch_device above: the window's origin as given,
+ *                  bit-exact RGBA): the transform kernel's picture goes through vp8g_scale_argb_batch_device and
+ *                  then the tensor kernel on the chunk's stream; a frame whose option is the identity goes as
+ *                  without the flag.  An option that does not fit the frame, or whose result is not the tensor's
+ *                  size, is EINVAL.  The planes and the scaled picture count against the chunk memory budget.
+ *                  Lossy frames of the batch are scaled as ever (their window's origin rounded down to even). */
 #define VP8G_X_LOSSLESS 2u
+#define VP8G_X_LOSSLESS_SCALE 16u
 int vp8g_decode_webp_batch_tensor_any(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
                                       const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, uint32_t xflags,
                                       void* d_out, int* status);

@@ -273,6 +273,7 @@ struct Slot {
 	std::vector<Vp8gTensorAlpha> talpha; //   one per tensor descriptor
 	std::vector<Vp8gLosslessDesc> ldescs;     // lossless sink: the chunk's lossless frames
 	std::vector<Vp8gTensorArgbDesc> ltdescs;  //   and their tensor descriptors
+	std::vector<Vp8gScaleArgbDesc> lsdescs;   //   those of them that are cropped / rescaled (VP8G_X_LOSSLESS_SCALE)
 	std::vector<Vp8gTokFrame> jobs;  // device m05
 	uint32_t status = 0;
 	std::vector<D2H> d2h;          // the chunk's downloads (issued by a Copier)
@@ -351,7 +352,8 @@ struct Copier {
 
 struct ChunkLayout {
 	uint64_t ym, uvm, seg, hasc, bm, masks, mboff, vals, cy, cu, cv, cy2, bits, jobs, desc, status, gctx, mbox, gprog, out,
-	    sdesc, sout, tdesc, ares, aout, asout, adesc, asdesc, talpha, lsrc, lout, ldesc, ltdesc, total;
+	    sdesc, sout, tdesc, ares, aout, asout, adesc, asdesc, talpha, lsrc, lout, ldesc, ltdesc, lswork, lsout,
+	    lsdesc, total;
 };
 
 hipError_t grow(Slot& s, size_t need) {
@@ -447,6 +449,7 @@ struct Sinks {
 	bool extended = false;                // the extended container (VP8X) in front
 	bool alpha = false;                   // VP8G_X_ALPHA: ALPH planes become the tensor's fourth channel
 	bool lossless = false;                // VP8G_X_LOSSLESS: lossless files decode as well (vp8g_lossless.hip)
+	bool lossless_scale = false;          // VP8G_X_LOSSLESS_SCALE: ... and are cropped / rescaled (vp8g_scale_argb.hip)
 	uint64_t tslot = 0;                   // bytes per tensor slot (decode_batch fills it in)
 	const Vp8gScaleOpt* opt_of(uint32_t i) const { return opts ? &opts[n_opts == 1 ? 0 : i] : nullptr; }
 };
@@ -483,6 +486,8 @@ struct ChunkShape {
 	uint64_t outb = 0, soutb = 0, ab = 0, asb = 0;  // bytes of I420, scaled I420, alpha planes, scaled alpha planes
 	uint32_t nl = 0;                                // lossless frames
 	uint64_t lsrcb = 0, loutb = 0;                  // bytes of their residual images + transform data, of their ARGB pictures
+	uint32_t nls = 0;                               // those of them that are cropped / rescaled
+	uint64_t lsworkb = 0, lsoutb = 0;               // bytes of their planes in the rescaler's work buffer, of their scaled pictures
 };
 
 ChunkLayout make_layout(const ChunkShape& sh, bool tok, const Sinks& sk, const vp8g::LaunchPlan& plan) {
@@ -524,6 +529,9 @@ ChunkLayout make_layout(const ChunkShape& sh, bool tok, const Sinks& sk, const v
 	L.lout = o, o = al256(o + sh.loutb);
 	L.ldesc = o, o = al256(o + sh.nl * sizeof(Vp8gLosslessDesc));
 	L.ltdesc = o, o = al256(o + sh.nl * sizeof(Vp8gTensorArgbDesc));
+	L.lswork = o, o = al256(o + (sh.nls ? vp8g_scale_argb_head_size(sh.nls) + sh.lsworkb : 0));
+	L.lsout = o, o = al256(o + sh.lsoutb);
+	L.lsdesc = o, o = al256(o + sh.nls * sizeof(Vp8gScaleArgbDesc));
 	L.total = o;
 	return L;
 }
@@ -737,10 +745,17 @@ struct Pipeline {
 					feed.err[fi] = e;
 					continue;
 				}
-				const uint64_t fx = extra_mbs(al256(srcb) + al256(outb));
+				// a frame that is cropped / rescaled also holds its planes and its scaled picture
+				Vp8fScaleGeom g;
+				const bool scaled = !lossless_whole(fi, &g);
+				const uint64_t workb = scaled ? vp8g_scale_argb_work_size(feed.ll[fi].width, feed.ll[fi].height, sk.opt_of(fi)) : 0u;
+				const uint64_t soutb = scaled ? 4ull * g.out_w * g.out_h : 0u;
+				const uint64_t fx = extra_mbs(al256(srcb) + al256(outb) + al256(workb) + al256(soutb) +
+				                              (scaled ? 4u * sizeof(Vp8gScaleDesc) + sizeof(Vp8gScaleArgbDesc) : 0u));
 				if (!(c.idx.empty() && c.lidx.empty()) && sh.mbs + xmbs + fx > caps.mbs[c.tok]) break;
 				xmbs += fx;
 				sh.lsrcb = al256(sh.lsrcb + srcb), sh.loutb = al256(sh.loutb + outb);
+				if (scaled) sh.nls++, sh.lsworkb = al256(sh.lsworkb + workb), sh.lsoutb = al256(sh.lsoutb + soutb);
 				c.lidx.push_back(fi);
 				continue;
 			}
@@ -784,11 +799,25 @@ struct Pipeline {
 		for (uint32_t k = 0; k < im.ntransforms; k++) dw += lossless_tr_dwords(im, k);
 		return 4u * dw;
 	}
-	// 0, or why a lossless frame cannot go to the sink: scaling it is not supported (ENOTSUP for any option that is not
-	// the identity), and it must have the tensor's size
-	int lossless_fits(uint32_t fi) const {
+	// Whether a lossless frame goes to the tensor as it is: without VP8G_X_LOSSLESS_SCALE always (lossless_fits has let
+	// only identities pass); with it when there is no option, or one that resolves (*g, libwebp's rules for such a file:
+	// the window's origin as given) to the whole picture and no target size -- a target equal to the picture's size still
+	// takes libwebp's premultiply, rescale, un-premultiply.  An option that does not fit: true.
+	bool lossless_whole(uint32_t fi, Vp8fScaleGeom* g) const {
 		const uint32_t w = feed.ll[fi].width, h = feed.ll[fi].height;
-		if (sk.opts) {
+		if (!sk.opts || !sk.lossless_scale || vp8f_scale_resolve_argb(w, h, sk.opt_of(fi), g) != 0) return true;
+		return !g->scaling && g->win_w == w && g->win_h == h;
+	}
+	// 0, or why a lossless frame cannot go to the sink: without VP8G_X_LOSSLESS_SCALE scaling it is not supported (ENOTSUP
+	// for any option that is not the identity); with it the option must fit the frame; and the result must have the
+	// tensor's size
+	int lossless_fits(uint32_t fi) const {
+		uint32_t w = feed.ll[fi].width, h = feed.ll[fi].height;
+		if (sk.opts && sk.lossless_scale) {
+			Vp8fScaleGeom g;
+			if (vp8f_scale_resolve_argb(w, h, sk.opt_of(fi), &g) != 0) return EINVAL;
+			w = g.out_w, h = g.out_h;
+		} else if (sk.opts) {
 			const Vp8gScaleOpt& o = *sk.opt_of(fi);
 			uint32_t sw = 0, sh_ = 0;
 			if (vp8g_scaled_size(w, h, &o, &sw, &sh_) != 0) return EINVAL;
@@ -1002,15 +1031,22 @@ struct Pipeline {
 		                   "tensor launch");
 	}
 	// Lossless sink: the residual images and transform data of the chunk's lossless frames are uploaded, the transforms
-	// inverted (vp8g_lossless.hip) and the ARGB pictures written to their slots of the tensor (same stream).
+	// inverted (vp8g_lossless.hip) and the ARGB pictures written to their slots of the tensor (same stream); with
+	// VP8G_X_LOSSLESS_SCALE the pictures whose option is not the identity pass through vp8g_scale_argb_batch_device between
+	// the two, and the tensor kernel reads their scaled copies.
 	Status launch_lossless(Chunk& c) {
 		Slot& s = c.s;
 		const ChunkLayout& L = c.L;
 		uint8_t* d = s.buf;
 		s.ldescs.clear();
 		s.ltdescs.clear();
+		s.lsdescs.clear();
 		s.frames.insert(s.frames.end(), c.lidx.begin(), c.lidx.end());  // (their host data lives until the slot retires)
 		uint64_t so = 0, oo = 0;
+		// cropped / rescaled frames (VP8G_X_LOSSLESS_SCALE): offsets in the rescaler's work buffer (L.lswork, its head
+		// first) and in the scaled pictures (L.lsout); the running counters of vp8g_make_scale_argb_desc
+		uint64_t wo = vp8g_scale_argb_head_size(c.sh.nls), po = 0;
+		uint32_t planes = 0, t_split = 0, t_scale = 0, t_merge = 0;
 		for (uint32_t fi : c.lidx) {
 			const Vp8fLosslessImage& im = feed.ll[fi];
 			Vp8gLosslessTransform tr[4];
@@ -1026,8 +1062,14 @@ struct Pipeline {
 			so = al256(so);
 			Vp8gLosslessDesc ld;
 			Vp8gTensorArgbDesc td;
+			Vp8gScaleArgbDesc sd;
+			Vp8fScaleGeom g;
+			const bool scaled = !lossless_whole(fi, &g);
+			const uint64_t pic = scaled ? L.lsout + po : L.lout + oo;  // what the tensor kernel reads
 			if (vp8g_make_lossless_desc(im.width, im.height, src, L.lout + oo, im.ntransforms, tr, (uint32_t)s.ldescs.size(), &ld) != 0 ||
-			    vp8g_make_tensor_argb_desc(sk.topt, sk.alpha ? 4u : 3u, L.lout + oo, (uint64_t)fi * sk.tslot, 0, &td) != 0) {
+			    (scaled && vp8g_make_scale_argb_desc(im.width, im.height, L.lout + oo, sk.opt_of(fi), wo, L.lsout + po, planes, t_split,
+			                                         t_scale, t_merge, &sd) != 0) ||
+			    vp8g_make_tensor_argb_desc(sk.topt, sk.alpha ? 4u : 3u, pic, (uint64_t)fi * sk.tslot, 0, &td) != 0) {
 				feed.err[fi] = EINVAL;  // (cannot happen for a stream the host decoder accepted and a size checked when gathered)
 				continue;
 			}
@@ -1035,13 +1077,24 @@ struct Pipeline {
 			oo = al256(oo + 4u * (uint64_t)im.width * im.height);
 			s.ldescs.push_back(ld);
 			s.ltdescs.push_back(td);
+			if (scaled) {
+				s.lsdescs.push_back(sd);
+				planes += sd.nplanes, t_split += sd.split_ntasks, t_scale += sd.scale_ntasks, t_merge += sd.merge_ntasks;
+				wo = al256(wo + sd.work_bytes), po = al256(po + 4u * (uint64_t)sd.width * sd.height);
+			}
 			live[fi] = 1;
 		}
 		if (s.ldescs.empty()) return c.up_status();
-		if (!c.up(L.ldesc, s.ldescs) || !c.up(L.ltdesc, s.ltdescs)) return c.up_status();
+		if (!c.up(L.ldesc, s.ldescs) || !c.up(L.ltdesc, s.ltdescs) || !(s.lsdescs.empty() || c.up(L.lsdesc, s.lsdescs)))
+			return c.up_status();
 		const uint32_t nl = (uint32_t)s.ldescs.size();
 		if (int rc = vp8g_lossless_batch_device(s.ldescs.data(), (const Vp8gLosslessDesc*)(d + L.ldesc), nl, d, d, c.stream); rc != 0)
 			return capi_status(rc, "lossless launch");
+		if (!s.lsdescs.empty())
+			if (int rc = vp8g_scale_argb_batch_device(s.lsdescs.data(), (const Vp8gScaleArgbDesc*)(d + L.lsdesc), (uint32_t)s.lsdescs.size(),
+			                                          d, d + L.lswork, d, c.stream);
+			    rc != 0)
+				return capi_status(rc, "lossless scale launch");
 		return capi_status(vp8g_tensor_batch_device_argb(s.ltdescs.data(), (const Vp8gTensorArgbDesc*)(d + L.ltdesc), nl, sk.topt,
 		                                                 sk.alpha ? 4u : 3u, d, sk.d_tensor, c.stream),
 		                   "tensor launch");
@@ -1233,9 +1286,11 @@ VP8G_API int vp8g_decode_webp_batch_tensor_x(const ByteSpan* files, uint32_t n, 
 VP8G_API int vp8g_decode_webp_batch_tensor_any(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
                                                const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, uint32_t xflags,
                                                void* d_out, int* status) {
-	if ((xflags & ~(VP8G_X_ALPHA | VP8G_X_LOSSLESS)) || !tensor_ok(t, d_out) || !opts_ok(opts, n_opts, n)) return fail(EINVAL);
+	if ((xflags & ~(VP8G_X_ALPHA | VP8G_X_LOSSLESS | VP8G_X_LOSSLESS_SCALE)) ||
+	    ((xflags & VP8G_X_LOSSLESS_SCALE) && !(xflags & VP8G_X_LOSSLESS)) || !tensor_ok(t, d_out) || !opts_ok(opts, n_opts, n))
+		return fail(EINVAL);
 	const Sinks sk{opts,  n_opts, nullptr, t, (uint8_t*)d_out, /*extended=*/true, /*alpha=*/(xflags & VP8G_X_ALPHA) != 0,
-	               /*lossless=*/(xflags & VP8G_X_LOSSLESS) != 0};
+	               /*lossless=*/(xflags & VP8G_X_LOSSLESS) != 0, /*lossless_scale=*/(xflags & VP8G_X_LOSSLESS_SCALE) != 0};
 	return decode_batch(files, n, filtered, threads, flags, sk, status);
 }
 

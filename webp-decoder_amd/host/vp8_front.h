@@ -117,6 +117,23 @@ int vp8f_scale_i420(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint32
                     uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, uint8_t* dy, uint8_t* du, uint8_t* dv,
                     uint32_t dstride_y, uint32_t dstride_uv);
 
+/* vp8f_scale_resolve for an ARGB picture (a lossless file): the same rules, but the window's origin is
+ * taken as given -- libwebp rounds it down to even only where there is chroma to stay aligned with. */
+int vp8f_scale_resolve_argb(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, Vp8fScaleGeom* g);
+
+/* libwebp's alpha premultiply of n 0xAARRGGBB pixels in place (inverse = 0), or its inverse (1).  A is
+ * kept; a == 255 leaves the pixel, a == 0 makes the whole pixel 0; otherwise each of R, G, B becomes
+ * (x * scale + 2^23) >> 24 with scale = a * 65793 (65793 = 2^24 / 255), or (255 << 24) / a for the inverse. */
+void vp8f_argb_mult_row(uint32_t* px, uint32_t n, int inverse);
+
+/* Crop + rescale a tight width x height 0xAARRGGBB picture into `out` (tight, the resolved output size),
+ * bit-exact to libwebp's decoder options on a lossless file: the window's rows are premultiplied, each of
+ * the four byte channels is rescaled exactly as a luma plane above, and the output rows are
+ * un-premultiplied.  Without a target size (crop only) the window's pixels are copied untouched.
+ * VP8G_SCALE_DWEBP_FILTER means nothing here and is ignored.  Sequential; reentrant.  0, or -1 + errno
+ * (EINVAL as vp8f_scale_resolve_argb, ENOMEM). */
+int vp8f_argb_scale(const uint32_t* argb, uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, uint32_t* out);
+
 /* ---- extended container (VP8X) and the ALPH chunk (RFC 9649 2.7) ----------- */
 
 /* What webp_parse_extended found.  alph_chunk_offset = 0: no alpha. */

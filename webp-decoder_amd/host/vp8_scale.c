@@ -40,7 +40,8 @@
 static uint32_t mult_fix(uint32_t x, uint32_t y) { return (uint32_t)(((uint64_t)x * y + (1ull << 31)) >> 32); }
 static uint32_t mult_floor(uint32_t x, uint32_t y) { return (uint32_t)(((uint64_t)x * y) >> 32); }
 
-int vp8f_scale_resolve(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, Vp8fScaleGeom* g) {
+/* snap: the window's origin is rounded down to even (I420), or taken as given (ARGB) */
+static int resolve(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, Vp8fScaleGeom* g, int snap) {
 	if (!opt || !g || width == 0 || height == 0 || width > SCALE_MAX_DIM || height > SCALE_MAX_DIM ||
 	    (opt->flags & ~(VP8G_SCALE_DWEBP_FILTER | VP8G_SCALE_EXPAND)))
 		goto bad;
@@ -48,12 +49,12 @@ int vp8f_scale_resolve(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt,
 		const int expand = (opt->flags & VP8G_SCALE_EXPAND) != 0;
 		uint32_t left = 0, top = 0, ww = width, wh = height;
 		if (opt->crop_left | opt->crop_top | opt->crop_w | opt->crop_h) {
-			/* libwebp's rules: the size as given, the origin snapped down to even; the bounds
-			 * are checked with the caller's own values */
+			/* libwebp's rules: the size as given, the origin snapped down to even (I420 only);
+			 * the bounds are checked with the caller's own values */
 			if (opt->crop_w == 0 || opt->crop_h == 0 || (uint64_t)opt->crop_left + opt->crop_w > width ||
 			    (uint64_t)opt->crop_top + opt->crop_h > height)
 				goto bad;
-			left = opt->crop_left & ~1u, top = opt->crop_top & ~1u;
+			left = snap ? opt->crop_left & ~1u : opt->crop_left, top = snap ? opt->crop_top & ~1u : opt->crop_top;
 			ww = opt->crop_w, wh = opt->crop_h;
 		}
 		uint32_t ow = opt->scaled_w, oh = opt->scaled_h;
@@ -75,6 +76,14 @@ int vp8f_scale_resolve(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt,
 bad:
 	errno = EINVAL;
 	return -1;
+}
+
+int vp8f_scale_resolve(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, Vp8fScaleGeom* g) {
+	return resolve(width, height, opt, g, 1);
+}
+
+int vp8f_scale_resolve_argb(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, Vp8fScaleGeom* g) {
+	return resolve(width, height, opt, g, 0);
 }
 
 int vp8f_scale_filtered(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, int filtered) {
@@ -224,5 +233,85 @@ int vp8f_scale_i420(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint32
 	scale_plane(u + co, stride_uv, cw, ch, du, dstride_uv, ocw, och, work);
 	scale_plane(v + co, stride_uv, cw, ch, dv, dstride_uv, ocw, och, work);
 	free(work);
+	return 0;
+}
+
+/* ---- ARGB pictures (lossless files): libwebp's 4-channel rescaler ------------------------------
+ *
+ * libwebp rescales the rows of a VP8L picture as four interleaved byte channels, each with exactly the
+ * single-plane arithmetic above, between an alpha premultiply and its inverse.  The
+ * window's origin is taken as given (no even rounding: there is no chroma to stay aligned with), and a
+ * crop without a target size copies the window's pixels untouched. */
+
+#define ARGB_MFIX 24
+#define ARGB_HALF (1u << (ARGB_MFIX - 1))
+#define ARGB_KINV_255 ((1u << ARGB_MFIX) / 255u) /* 65793 */
+
+void vp8f_argb_mult_row(uint32_t* px, uint32_t n, int inverse) {
+	for (uint32_t x = 0; x < n; x++) {
+		const uint32_t p = px[x], a = p >> 24;
+		if (a == 255u) continue;
+		if (a == 0u) {
+			px[x] = 0;
+			continue;
+		}
+		const uint32_t scale = inverse ? (255u << ARGB_MFIX) / a : a * ARGB_KINV_255;
+		uint32_t out = p & 0xFF000000u;
+		for (int s = 0; s < 24; s += 8) {
+			/* (premultiply: 255 * 255 * 65793 + 2^23 < 2^32; the inverse's product needs 64 bits in general) */
+			const uint64_t v = ((uint64_t)((p >> s) & 255u) * scale + ARGB_HALF) >> ARGB_MFIX;
+			out |= (uint32_t)(v & 255u) << s;
+		}
+		px[x] = out;
+	}
+}
+
+int vp8f_argb_scale(const uint32_t* argb, uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, uint32_t* out) {
+	Vp8fScaleGeom g;
+	if (!argb || !out || vp8f_scale_resolve_argb(width, height, opt, &g) != 0) {
+		errno = EINVAL;
+		return -1;
+	}
+	const uint32_t* win = argb + (size_t)g.top * width + g.left;
+	if (!g.scaling) { /* crop only: libwebp emits the window's rows as they are */
+		for (uint32_t y = 0; y < g.win_h; y++) memcpy(out + (size_t)y * g.win_w, win + (size_t)y * width, (size_t)g.win_w * 4u);
+		return 0;
+	}
+	const size_t wsz = (size_t)g.win_w * g.win_h, osz = (size_t)g.out_w * g.out_h;
+	uint32_t* row = (uint32_t*)malloc(((size_t)g.win_w + 2u * g.out_w) * sizeof(uint32_t));
+	uint8_t* planes = (uint8_t*)malloc(4u * (wsz + osz));
+	if (!row || !planes) {
+		free(row), free(planes);
+		errno = ENOMEM;
+		return -1;
+	}
+	/* premultiply the window's rows; channel c of a pixel is byte c of the dword: B, G, R, A */
+	for (uint32_t y = 0; y < g.win_h; y++) {
+		memcpy(row, win + (size_t)y * width, (size_t)g.win_w * 4u);
+		vp8f_argb_mult_row(row, g.win_w, 0);
+		for (uint32_t x = 0; x < g.win_w; x++)
+			for (uint32_t c = 0; c < 4u; c++) planes[c * wsz + (size_t)y * g.win_w + x] = (uint8_t)(row[x] >> (8u * c));
+	}
+	uint8_t* scaled = planes + 4u * wsz;
+	for (uint32_t c = 0; c < 4u; c++)
+		scale_plane(planes + c * wsz, g.win_w, g.win_w, g.win_h, scaled + c * osz, g.out_w, g.out_w, g.out_h, row + g.win_w);
+	int ok = 1;
+	for (uint32_t y = 0; y < g.out_h; y++) {
+		uint32_t* o = out + (size_t)y * g.out_w;
+		for (uint32_t x = 0; x < g.out_w; x++) {
+			const size_t i = (size_t)y * g.out_w + x;
+			const uint32_t b = scaled[i], gr = scaled[osz + i], r = scaled[2u * osz + i], a = scaled[3u * osz + i];
+			/* every channel is the same monotone function of sums in which colour <= alpha holds termwise: the
+			 * inverse below therefore stays within a byte */
+			ok &= b <= a && gr <= a && r <= a;
+			o[x] = a << 24 | r << 16 | gr << 8 | b;
+		}
+		vp8f_argb_mult_row(o, g.out_w, 1);
+	}
+	free(row), free(planes);
+	if (!ok) { /* (never) */
+		errno = ERANGE;
+		return -1;
+	}
 	return 0;
 }

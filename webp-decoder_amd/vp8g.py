@@ -230,6 +230,14 @@ class Vp8gTensorArgbDesc(C.Structure):
     _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("task0", C.c_uint32), ("ntasks", C.c_uint32)]
 
 
+class Vp8gScaleArgbDesc(C.Structure):
+    """include/vp8g.h: per-picture descriptor of the ARGB crop / rescale (vp8g_make_scale_argb_desc)."""
+    _fields_ = [(n, C.c_uint64) for n in ("src", "work", "dst", "work_bytes")] + [(n, C.c_uint32) for n in (
+        "width", "height", "src_width", "src_height", "crop_left", "crop_top", "win_w", "win_h", "plane_stride", "out_stride",
+        "nplanes", "plane0", "split_task0", "split_ntasks", "scale_task0", "scale_ntasks", "merge_task0", "merge_ntasks")] + [
+        ("reserved", C.c_uint32 * 2), ("plane", Vp8gScaleDesc * 4)]
+
+
 # transform types (RFC 9649 4)
 L_PREDICTOR, L_CROSS_COLOR, L_SUBTRACT_GREEN, L_COLOR_INDEX = 0, 1, 2, 3
 
@@ -244,6 +252,7 @@ def lossless_geometry():
 T_OPAQUE = 0xFFFFFFFFFFFFFFFF
 VP8G_X_ALPHA = 1
 VP8G_X_LOSSLESS = 2
+VP8G_X_LOSSLESS_SCALE = 16
 VP8G_SCALE_DWEBP_FILTER = 1
 VP8G_SCALE_EXPAND = 4
 
@@ -273,6 +282,7 @@ assert C.sizeof(Vp8gScalePlane) == 80
 assert C.sizeof(Vp8gScaleDesc) == 272
 assert C.sizeof(Vp8gTensorOpt) == 44
 assert C.sizeof(Vp8gTensorDesc) == 48
+assert C.sizeof(Vp8gScaleArgbDesc) == 1200
 
 VP8G_F_LOOPFILTER = 1
 VP8G_F_SIMPLE = 2
@@ -366,6 +376,11 @@ def host_lib():
             lib.vp8f_lossless_free.argtypes = [C.POINTER(Vp8fLosslessImage)]
             lib.vp8f_lossless_free.restype = None
             lib.vp8f_lossless_apply.argtypes = [C.POINTER(Vp8fLosslessImage), C.c_void_p]
+        if hasattr(lib, "vp8f_argb_scale"):  # (libraries built before the scaled lossless path: A/B of old builds)
+            lib.vp8f_scale_resolve_argb.argtypes = lib.vp8f_scale_resolve.argtypes
+            lib.vp8f_argb_mult_row.argtypes = [C.c_void_p, C.c_uint32, C.c_int]
+            lib.vp8f_argb_mult_row.restype = None
+            lib.vp8f_argb_scale.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Vp8gScaleOpt), C.c_void_p]
         lib._typed = True
     return lib
 
@@ -482,6 +497,15 @@ def gpu_lib():
             lib.vp8g_decode_webp_batch_tensor_any.argtypes = [P(ByteSpan), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
                                                               P(Vp8gScaleOpt), C.c_uint32, P(Vp8gTensorOpt), C.c_uint32,
                                                               C.c_void_p, P(C.c_int)]
+        if hasattr(lib, "vp8g_scale_argb_batch_device"):  # (libraries built before the scaled lossless path)
+            lib.vp8g_scale_argb_work_size.argtypes = [C.c_uint32, C.c_uint32, P(Vp8gScaleOpt)]
+            lib.vp8g_scale_argb_work_size.restype = C.c_uint64
+            lib.vp8g_scale_argb_head_size.argtypes = [C.c_uint32]
+            lib.vp8g_scale_argb_head_size.restype = C.c_uint64
+            lib.vp8g_make_scale_argb_desc.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, P(Vp8gScaleOpt), C.c_uint64, C.c_uint64,
+                                                      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(Vp8gScaleArgbDesc)]
+            lib.vp8g_scale_argb_batch_device.argtypes = [P(Vp8gScaleArgbDesc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p]
         lib._typed = True
     return lib
 
@@ -1210,6 +1234,91 @@ def gpu_lossless_argb(images, src_shift: int = 1, guard: int = 64, fill: int = 0
     return out
 
 
+def scaled_size_argb(w: int, h: int, opt: Vp8gScaleOpt):
+    """vp8f_scale_resolve_argb: ((left, top, win_w, win_h), (out_w, out_h)) of `opt` on a w x h ARGB picture -- the
+    window's origin as given, not rounded to even; ValueError if invalid."""
+    g = Vp8fScaleGeom()
+    if host_lib().vp8f_scale_resolve_argb(w, h, C.byref(opt), C.byref(g)) != 0:
+        raise ValueError(f"invalid scale options for {w}x{h}")
+    return (int(g.left), int(g.top), int(g.win_w), int(g.win_h)), (int(g.out_w), int(g.out_h))
+
+
+def host_argb_mult(argb, inverse: bool = False) -> np.ndarray:
+    """vp8f_argb_mult_row: libwebp's alpha premultiply (or its inverse) of uint32 0xAARRGGBB pixels; a copy."""
+    a = np.array(argb, dtype=np.uint32)
+    flat = np.ascontiguousarray(a.reshape(-1))
+    host_lib().vp8f_argb_mult_row(flat.ctypes.data, flat.size, int(inverse))
+    return flat.reshape(a.shape)
+
+
+def host_scale_argb(argb, opt: Vp8gScaleOpt) -> np.ndarray:
+    """vp8f_argb_scale (the sequential CPU restatement of libwebp's crop / rescale of a lossless picture) of a uint32
+    [h, w] 0xAARRGGBB picture: uint32 [h', w'].  OSError with its errno (EINVAL) if the option does not fit."""
+    a = np.ascontiguousarray(argb, dtype=np.uint32)
+    h, w = a.shape
+    g = Vp8fScaleGeom()
+    lib = host_lib()
+    if lib.vp8f_scale_resolve_argb(w, h, C.byref(opt), C.byref(g)) != 0:
+        raise OSError(C.get_errno() or 22, "vp8f_scale_resolve_argb")
+    out = np.empty((g.out_h, g.out_w), np.uint32)
+    if lib.vp8f_argb_scale(a.ctypes.data, w, h, C.byref(opt), out.ctypes.data) != 0:
+        raise OSError(C.get_errno() or 22, "vp8f_argb_scale")
+    return out
+
+
+def gpu_scale_argb(argb_list, opts, src_shift: int = 1, guard: int = 64, fill: int = 0xEE):
+    """vp8g_make_scale_argb_desc + vp8g_scale_argb_batch_device over uint32 [h, w] 0xAARRGGBB pictures of mixed sizes
+    (opts: one Vp8gScaleOpt per picture) in one launch: the list of scaled uint32 [h', w'] pictures.  src_shift: every
+    source picture starts this many DWORDS off a 16-byte boundary; guard (a multiple of 16): bytes kept around every
+    picture's work region and every output, which the call checks still hold `fill`."""
+    import torch
+    lib = gpu_lib()
+    dev = torch.device("cuda", 0)
+    n = len(argb_list)
+    descs = (Vp8gScaleArgbDesc * n)()
+    parts, so = [], 0
+    wo, do = int(lib.vp8g_scale_argb_head_size(n)) + guard, guard
+    planes = t_split = t_scale = t_merge = 0
+    for i, (a, opt) in enumerate(zip(argb_list, opts)):
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        h, w = a.shape
+        pad = (-so) % 16 + 4 * src_shift
+        parts += [np.full(pad, 0x5A, np.uint8), a.reshape(-1).view(np.uint8)]
+        if lib.vp8g_make_scale_argb_desc(w, h, so + pad, C.byref(opt), wo, do, planes, t_split, t_scale, t_merge,
+                                         C.byref(descs[i])) != 0:
+            raise ValueError(f"vp8g_make_scale_argb_desc failed: errno={C.get_errno()}")
+        d = descs[i]
+        assert d.work_bytes == lib.vp8g_scale_argb_work_size(w, h, C.byref(opt))
+        so += pad + a.size * 4
+        planes, t_split, t_scale, t_merge = planes + d.nplanes, t_split + d.split_ntasks, t_scale + d.scale_ntasks, t_merge + d.merge_ntasks
+        wo += d.work_bytes + guard
+        do += (4 * d.width * d.height + 15) // 16 * 16 + guard
+    parts.append(np.full(16, 0x5A, np.uint8))
+    src = torch.from_numpy(np.concatenate(parts)).to(dev)
+    work = torch.full((wo,), fill, dtype=torch.uint8, device=dev)
+    dst = torch.full((do,), fill, dtype=torch.uint8, device=dev)
+    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
+    stream = torch.cuda.current_stream(dev)
+    if lib.vp8g_scale_argb_batch_device(descs, C.c_void_p(d_descs.data_ptr()), n, C.c_void_p(src.data_ptr()),
+                                        C.c_void_p(work.data_ptr()), C.c_void_p(dst.data_ptr()),
+                                        C.c_void_p(stream.cuda_stream)) != 0:
+        raise RuntimeError(f"vp8g_scale_argb_batch_device failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
+    stream.synchronize()
+    hw, hd = work.cpu().numpy(), dst.cpu().numpy()
+    out, keep_w, keep_d = [], np.ones(wo, bool), np.ones(do, bool)
+    keep_w[:int(lib.vp8g_scale_argb_head_size(n))] = False
+    for d in descs:
+        nb = 4 * d.width * d.height
+        out.append(hd[d.dst:d.dst + nb].view(np.uint32).reshape(d.height, d.width).copy())
+        keep_d[d.dst:d.dst + nb] = False
+        keep_w[d.work:d.work + d.work_bytes] = False
+    if not (hd[keep_d] == fill).all():
+        raise AssertionError("gpu_scale_argb: bytes outside the outputs were written")
+    if not (hw[keep_w] == fill).all():
+        raise AssertionError("gpu_scale_argb: bytes outside the work regions were written")
+    return out
+
+
 def host_tensor_argb(argb, opt: Vp8gTensorOpt, channels: int = 4):
     """The numpy / torch-CPU restatement of vp8g_tensor_batch_device_argb for one uint32 [h, w] 0xAARRGGBB picture:
     R, G, B as host_tensor treats them (the channel order, a float32 multiply and then a float32 add, one rounding),
@@ -1298,15 +1407,18 @@ def gpu_decode_webp_batch_x(files: list[bytes], scale=None, filtered: bool = Tru
 
 def gpu_decode_webp_batch_tensor(files: list[bytes], opt: Vp8gTensorOpt, scale=None, filtered: bool = True, threads: int = 0,
                                  device_m05: bool = False, multi_partition: bool = False, extended: bool = False,
-                                 alpha: bool = False, lossless: bool = False):
+                                 alpha: bool = False, lossless: bool = False, lossless_scale: bool = False):
     """vp8g_decode_webp_batch_tensor: .webp images decoded, optionally cropped / downscaled (scale: None,
     one Vp8gScaleOpt for every frame, or a list of one per frame), converted and left on the device.
     Returns (torch.Tensor on the device, [N, 3, H, W] or [N, H, W, 3] of the requested dtype, list of
     errno); the slot of a failed frame is zero.  extended: vp8g_decode_webp_batch_tensor_x (VP8X files decode);
     alpha: with VP8G_X_ALPHA, the tensor has four channels (R, G, B, A; opaque A for a picture without alpha).
     lossless: vp8g_decode_webp_batch_tensor_any with VP8G_X_LOSSLESS (implies the extended container): lossless
-    (VP8L) files decode beside the lossy ones; one whose scale option is not the identity gets ENOTSUP.  torch only allocates the tensor: its data_ptr() is
-    handed to the C call."""
+    (VP8L) files decode beside the lossy ones; one whose scale option is not the identity gets ENOTSUP, unless
+    lossless_scale (VP8G_X_LOSSLESS_SCALE; needs lossless): then a lossless file's option is applied as libwebp applies
+    it to such a file -- the crop window's origin as given, not rounded to even, and RGBA bit-exact to libwebp's
+    (host_scale_argb) -- and only an option that does not fit the file, or whose result is not the tensor's size, fails
+    (EINVAL).  torch only allocates the tensor: its data_ptr() is handed to the C call."""
     import time
     import torch
     extended = extended or alpha  # (alpha arrives through the _x call only)
@@ -1324,9 +1436,10 @@ def gpu_decode_webp_batch_tensor(files: list[bytes], opt: Vp8gTensorOpt, scale=N
     st = (C.c_int * n)()
     t0 = time.perf_counter()
     bflags = (VP8G_BATCH_DEVICE_M05 if device_m05 else 0) | (VP8G_BATCH_MULTI_PARTITION if multi_partition else 0)
-    if lossless:
+    if lossless or lossless_scale:
         rc = lib.vp8g_decode_webp_batch_tensor_any(spans, n, int(filtered), threads, bflags, c_opts, len(opts), C.byref(opt),
-                                                   VP8G_X_LOSSLESS | (VP8G_X_ALPHA if alpha else 0),
+                                                   (VP8G_X_LOSSLESS if lossless else 0) | (VP8G_X_ALPHA if alpha else 0)
+                                                   | (VP8G_X_LOSSLESS_SCALE if lossless_scale else 0),
                                                    C.c_void_p(out.data_ptr()), st)
     elif extended:  # (routed to the _x call only when asked)
         rc = lib.vp8g_decode_webp_batch_tensor_x(spans, n, int(filtered), threads, bflags, c_opts, len(opts), C.byref(opt),
