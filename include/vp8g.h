@@ -770,6 +770,91 @@ int vp8g_decode_webp_batch_tensor_any(const ByteSpan* files, uint32_t n, int fil
                                       const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, uint32_t xflags,
                                       void* d_out, int* status);
 
+/* ---- Animated files (ANIM / ANMF), composited on the device --------------- */
+
+/* An animation is a list of frames, each a rectangle of the canvas with a blend and a disposal rule; what is
+ * shown for frame k -- canvas k -- is what libwebp's WebPAnimDecoder (MODE_RGBA) composes (the rules:
+ * vp8f_anim_compose, host/vp8_front.h).  Frames depend on each other, pixels do not: a thread of the compositor
+ * keeps a few pixels of the canvas in registers and walks the frame list, reading each frame's pixels once and
+ * writing every canvas's elements once, already in the tensor's dtype and layout; the canvas never touches memory.
+ * A key frame starts from an empty canvas, so the frames from one key frame to the next -- a segment -- are
+ * composed independently of the others.
+ * One frame (vp8g_make_anim_desc completes it).  40 bytes. */
+#define VP8G_ANIM_BLEND 1u     /* alpha-blend over the canvas (else overwrite) */
+#define VP8G_ANIM_DISPOSE 2u   /* the rectangle is cleared to transparent after the frame */
+#define VP8G_ANIM_HAS_ALPHA 4u /* the frame's bitstream carries alpha (key-frame rule only) */
+#define VP8G_ANIM_KEY 8u       /* set by vp8g_make_anim_desc */
+typedef struct {
+	uint64_t src;                 /* byte offset (a multiple of 4) in the source buffer of the frame's tight width x height
+	                               * 0xAARRGGBB dwords, not premultiplied */
+	uint32_t x, y, width, height; /* its rectangle on the canvas; x and y even */
+	uint32_t flags;               /* VP8G_ANIM_* */
+	uint32_t seg_first, seg_end;  /* in record s of an animation: segment s is frames [seg_first, seg_end) (s < nsegs) */
+	uint32_t reserved;
+} Vp8gAnimFrame;
+
+/* Per-animation descriptor (built by vp8g_make_anim_desc).  48 bytes. */
+typedef struct {
+	uint64_t frames;                /* byte offset (a multiple of 8) in the source buffer of the device copy of the records */
+	const Vp8gAnimFrame* h_frames;  /* their host copy, which the entry point checks before it launches (the kernel never
+	                                 * reads this field); it must stay valid until vp8g_anim_compose_batch_device returns */
+	uint64_t dst;                   /* byte offset of canvas 0 in the output buffer; canvas k follows k canvas sizes later */
+	uint32_t width, height;         /* the canvas, 1 .. 16383 */
+	uint32_t nframes, nsegs;
+	uint32_t task0, ntasks;         /* this animation's workgroup tasks in the launch: nsegs x tiles of the canvas */
+} Vp8gAnimDesc;
+
+/* The kernel's geometry, for tests that aim at its boundaries: out[0] = adjacent pixels of a canvas row per thread,
+ * out[1] = pixels per task (a tile: 256 threads' pixels in row-major order), out[2] = the most frames a task walks
+ * (0: no limit -- the records are read through the scalar cache as the walk reaches them, not staged). */
+void vp8g_anim_geometry(uint32_t out[3]);
+
+/* Complete the nframes records of one animation (in: src, the rectangle, BLEND / DISPOSE / HAS_ALPHA; out: VP8G_ANIM_KEY
+ * by libwebp's rule and the segment table) and fill its descriptor: records at frames_offset of the source buffer,
+ * canvas k at dst_offset + k * channels * width * height * element size, tasks from task0.  0, or -1 + EINVAL: NULL,
+ * no frames, a canvas or rectangle of 0 or beyond 16383, a rectangle outside the canvas, an odd x or y, an unknown flag
+ * bit (VP8G_ANIM_KEY included), src not a multiple of 4, frames_offset not a multiple of 8, more than 2^31 tasks. */
+int vp8g_make_anim_desc(uint32_t width, uint32_t height, Vp8gAnimFrame* frames, uint32_t nframes, uint64_t frames_offset,
+                        uint64_t dst_offset, uint32_t task0, Vp8gAnimDesc* out);
+
+/* Compose n animations of mixed canvas sizes and frame counts in one launch on `hip_stream`.  opt gives the element
+ * type, layout, channel order, scale and bias (its width and height are not read: every animation has its canvas size
+ * in its descriptor); channels = 3 (alpha dropped after compositing) or 4.  R, G, B and A of every element are those
+ * vp8g_tensor_batch_device_argb writes for the composed canvas.  For animations of one canvas size, canvas k of
+ * animation i lands in slot first[i] + k of a dense [N, ...] tensor when dst = first[i] * the slot size.
+ * h_descs / d_descs: host and device copies of the descriptors (tasks numbered animation by animation, a task per
+ * segment and tile).  No workgroup waits on another, nothing spins on memory, there is no timeout path.  Writes only
+ * the animations' own canvases.  Asynchronous; 0 or -1 + errno.  The host copies are checked before anything is
+ * launched -- EINVAL: NULL pointer, n = 0, channels, an invalid option, d_src not 8-byte aligned, d_dst or a dst
+ * offset off the element size, a descriptor or record that is not what vp8g_make_anim_desc gives (a rectangle
+ * outside the canvas, an odd offset, a key flag or segment table that does not follow the rule, ...), task counters
+ * that do not number the animations in order, canvases that are not laid out in order without overlap.  EIO on a
+ * launch failure.  d_src may be the output of vp8g_lossless_batch_device, or the uint8 / NHWC / BGR 4-channel tensor
+ * of vp8g_tensor_batch_device_a / _argb (whose bytes are these dwords), on the same stream with no host copy between. */
+int vp8g_anim_compose_batch_device(const Vp8gAnimDesc* h_descs, const Vp8gAnimDesc* d_descs, uint32_t n,
+                                   const Vp8gTensorOpt* opt, uint32_t channels, const uint8_t* d_src, void* d_dst,
+                                   void* hip_stream);
+
+/* Canvas size, frame count and loop count (0 = forever) of n files, so that a caller can size the tensor: a file
+ * that webp_parse_anim refuses (a still picture included) has nframes[i] = 0 and status[i] = EINVAL.  Any output
+ * array but nframes may be NULL.  0, or -1 + errno (EINVAL: NULL arguments, n = 0; else the first refused file's). */
+int vp8g_anim_info(const ByteSpan* files, uint32_t n, uint32_t* canvas_w, uint32_t* canvas_h, uint32_t* nframes,
+                   uint32_t* loop_count, int* status);
+
+/* Decode n animated files into a dense tensor of canvases: file i owns the nframes[i] slots (of vp8g_tensor_slot_size
+ * bytes for channels = 3, vp8g_tensor_slot_size_a for 4) from slot first[i] = nframes[0] + ... + nframes[i - 1] on, in
+ * frame order; d_out holds the sum of all nframes slots.  Every frame's payload is wrapped in memory as a file of its
+ * own ('VP8 ' alone, VP8X + ALPH + 'VP8 ', or 'VP8L') and decoded by vp8g_decode_webp_batch_tensor_any (filtered, threads
+ * and flags as there; VP8G_X_ALPHA | VP8G_X_LOSSLESS) into a uint8 / NHWC / BGR 4-channel staging tensor, one call per
+ * distinct frame size; then one launch of vp8g_anim_compose_batch_device composes every file.  Frames are not scaled.
+ * timestamps (may be NULL; one per slot): the cumulative end time of each frame in ms, as WebPAnimDecoderGetNext
+ * returns it.  status[i]: 0; EINVAL for a file that is no animation (no slots), whose canvas is not t->width x
+ * t->height, or one of whose frames does not decode (its errno) -- all slots of such a file are zero bytes and the
+ * other files still decode.  Returns after all device work is complete.  0, or -1 + errno: the first failed file's;
+ * EINVAL for bad arguments (nothing is launched); ENOMEM; EIO for a device failure (every status EIO). */
+int vp8g_decode_webp_anim_tensor(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                 const Vp8gTensorOpt* t, uint32_t channels, void* d_out, uint32_t* timestamps, int* status);
+
 /* Name of the last HIP error seen by this library in the calling thread ("" if none). */
 const char* vp8g_last_error(void);
 

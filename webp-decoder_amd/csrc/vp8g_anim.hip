@@ -1,0 +1,460 @@
+// vp8g_anim.hip -- the compositor of animated files: frames (tight 0xAARRGGBB pictures on the device) -> every
+// canvas of every animation, as elements of a dense tensor (include/vp8g.h: vp8g_anim_compose_batch_device and
+// the end-to-end vp8g_decode_webp_anim_tensor).  The rules are libwebp's WebPAnimDecoder, restated
+// sequentially in host/vp8_anim.c.
+//
+// Frames depend on each other, pixels do not.  A thread owns kPx adjacent pixels of one canvas row and keeps their
+// canvas values in registers while it walks a segment -- the frames from one key frame (an empty canvas) up to the
+// next: per frame it reads its pixels of the frame's rectangle (one 16-byte load when all four lie inside), blends
+// or overwrites, converts the four pixels to the element type (conv / conv_a of vp8g_tensor_device.h, only when one
+// of them changed) and stores them into that frame's canvas, then clears what the frame's disposal clears.  The
+// canvas itself is never in memory: F frames on a W x H canvas read every frame pixel once and write F * W * H
+// pixels once.
+// A workgroup task is (segment, tile): 256 consecutive four-pixel pieces of the canvas in row-major order, for one
+// segment; segments are independent, so a long animation on a small canvas still spreads over the device.  The
+// frame records are the same for every thread of a task and are read with wave-uniform addresses (scalar loads).
+// No LDS, no barriers, no workgroup waits on another, nothing spins on memory.
+#include <errno.h>
+#include <string.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "vp8g_device.h"
+#include "vp8g_tensor_device.h"
+#include "../host/vp8_front.h"
+
+#define VP8G_API extern "C" __attribute__((visibility("default")))
+#define DEV __device__ __forceinline__
+
+namespace {
+
+using namespace vp8g_tensor;
+
+constexpr uint32_t kThreads = 256;
+constexpr uint32_t kPx = 4;  // adjacent pixels of a row per thread
+constexpr uint32_t kMaxDim = 16383;
+constexpr uint32_t kInFlags = VP8G_ANIM_BLEND | VP8G_ANIM_DISPOSE | VP8G_ANIM_HAS_ALPHA;
+
+struct AnimParams {
+	float scale[3], bias[3];
+};
+
+// libwebp's non-premultiplied blend of source pixel s over canvas pixel d (host/vp8_anim.c: blend_pixel)
+DEV uint32_t blend_pixel(uint32_t s, uint32_t d) {
+	const uint32_t sa = s >> 24;
+	if (sa == 255u) return s;
+	if (sa == 0u) return d;
+	const uint32_t dfa = ((d >> 24) * (256u - sa)) >> 8;
+	const uint32_t ba = sa + dfa;  // 1 .. 255
+	const uint32_t scale = (1u << 24) / ba;
+	uint32_t out = ba << 24;
+#pragma unroll
+	for (int sh = 0; sh < 24; sh += 8) out |= (((((s >> sh) & 255u) * sa + ((d >> sh) & 255u) * dfa) * scale) >> 24) << sh;
+	return out;
+}
+
+template <uint32_t DT, bool PLANAR, bool BGR, int C>
+__global__ __launch_bounds__(kThreads) void anim_kernel(const Vp8gAnimDesc* __restrict__ D, uint32_t n, uint32_t total, AnimParams P,
+                                                        const uint8_t* __restrict__ src, uint8_t* __restrict__ dst) {
+	static_assert(C == 3 || C == 4, "RGB, or RGB and alpha");
+	constexpr uint32_t EB = (uint32_t)elem_bytes(DT);
+	const uint32_t tid = threadIdx.x;
+	for (uint32_t g = blockIdx.x; g < total; g += gridDim.x) {
+		// the animation of task g: the last one whose task0 is not beyond it (tasks are numbered animation by animation)
+		uint32_t lo = 0, hi = n;
+		while (hi - lo > 1u) {
+			const uint32_t mid = (lo + hi) >> 1;
+			if (D[mid].task0 <= g) lo = mid;
+			else hi = mid;
+		}
+		const Vp8gAnimDesc& d = D[lo];
+		const uint32_t W = d.width, H = d.height;
+		const uint32_t cpr = (W + kPx - 1u) / kPx, pieces = cpr * H, tpc = (pieces + kThreads - 1u) / kThreads;
+		const uint32_t t = g - d.task0, seg = t / tpc;
+		const uint32_t gc = (t - seg * tpc) * kThreads + tid;
+		if (gc >= pieces) continue;
+		const uint32_t y = gc / cpr, x0 = (gc - y * cpr) * kPx;
+		const uint32_t cnt = min(kPx, W - x0);
+		const Vp8gAnimFrame* const R = (const Vp8gAnimFrame*)(src + d.frames);
+		const uint32_t f0 = R[seg].seg_first, f1 = R[seg].seg_end;
+		const uint64_t plane = (uint64_t)W * H * EB;  // one NCHW plane; a canvas is C of them
+		const size_t pix = (size_t)y * W + x0;        // the piece's first pixel in the canvas
+		uint32_t c[kPx] = {0u, 0u, 0u, 0u};           // the canvas under this thread, after the last frame's disposal
+		uint32_t e[kPx][4];
+		uint32_t cleared = 0;  // bit j: the previous frame's disposal has just cleared pixel j
+		for (uint32_t k = f0; k < f1; k++) {
+			const Vp8gAnimFrame& r = R[k];
+			const uint32_t ry = y - r.y, rx = x0 - r.x;  // (unsigned: a pixel left of / above the rectangle compares as beyond it)
+			uint32_t m = 0;  // bit j: pixel j lies in the frame's rectangle
+			if (ry < r.height) {
+#pragma unroll
+				for (uint32_t j = 0; j < kPx; j++) m |= (rx + j < r.width ? 1u : 0u) << j;
+			}
+			if (m) {
+				const uint32_t* const row = (const uint32_t*)(src + r.src) + (size_t)ry * r.width;
+				uint32_t s[kPx] = {0u, 0u, 0u, 0u};
+				if (m == 15u) {
+					const u32x4a v = *(const u32x4a*)(row + rx);
+					s[0] = v.x, s[1] = v.y, s[2] = v.z, s[3] = v.w;
+				} else {
+#pragma unroll
+					for (uint32_t j = 0; j < kPx; j++)
+						if ((m >> j) & 1u) s[j] = row[rx + j];
+				}
+				// blended only where the frame blends, is no key frame (k != f0: a segment starts at its only key frame)
+				// and the canvas below was not just cleared
+				const bool blends = (r.flags & VP8G_ANIM_BLEND) && k != f0;
+#pragma unroll
+				for (uint32_t j = 0; j < kPx; j++)
+					if ((m >> j) & 1u) c[j] = (blends && !((cleared >> j) & 1u)) ? blend_pixel(s[j], c[j]) : s[j];
+			}
+			if (k == f0 || m || cleared) {
+#pragma unroll
+				for (uint32_t j = 0; j < kPx; j++) {
+					// (channel<> reads r | g << 8 | b << 16)
+					const uint32_t rgb = ((c[j] >> 16) & 255u) | (c[j] & 0xFF00u) | ((c[j] & 255u) << 16);
+#pragma unroll
+					for (int q = 0; q < 3; q++) e[j][q] = conv<DT>(channel<BGR>(rgb, q), P.scale[q], P.bias[q]);
+					e[j][3] = conv_a<DT>(c[j] >> 24);
+				}
+			}
+			uint8_t* const out = dst + d.dst + (uint64_t)k * C * plane;
+			if (cnt == kPx) {
+				if constexpr (PLANAR) {
+#pragma unroll
+					for (int q = 0; q < C; q++) {
+						const uint32_t run[kPx] = {e[0][q], e[1][q], e[2][q], e[3][q]};
+						store_run<DT, (int)kPx>(out + (size_t)q * plane + pix * EB, run);
+					}
+				} else {
+					uint32_t run[kPx * C];
+#pragma unroll
+					for (int j = 0; j < (int)kPx; j++)
+#pragma unroll
+						for (int q = 0; q < C; q++) run[C * j + q] = e[j][q];
+					store_run<DT, (int)kPx * C>(out + pix * C * EB, run);
+				}
+			} else {
+				// a row's last, partial piece: element by element
+#pragma unroll
+				for (uint32_t j = 0; j < kPx - 1u; j++)
+					if (j < cnt)
+#pragma unroll
+						for (int q = 0; q < C; q++) {
+							uint8_t* p = PLANAR ? out + (size_t)q * plane + (pix + j) * EB : out + ((pix + j) * C + (uint32_t)q) * EB;
+							store_elem<DT>(p, e[j][q]);
+						}
+			}
+			cleared = (r.flags & VP8G_ANIM_DISPOSE) ? m : 0u;
+#pragma unroll
+			for (uint32_t j = 0; j < kPx; j++)
+				if ((cleared >> j) & 1u) c[j] = 0u;
+		}
+	}
+}
+
+using KernelFn = void (*)(const Vp8gAnimDesc*, uint32_t, uint32_t, AnimParams, const uint8_t*, uint8_t*);
+// [C - 3][dtype][layout][bgr]
+#define VP8G_A_ROW(DT, C) { {anim_kernel<DT, false, false, C>, anim_kernel<DT, false, true, C>}, {anim_kernel<DT, true, false, C>, anim_kernel<DT, true, true, C>} }
+const KernelFn kKernels[2][4][2][2] = {{VP8G_A_ROW(VP8G_T_U8, 3), VP8G_A_ROW(VP8G_T_F16, 3), VP8G_A_ROW(VP8G_T_BF16, 3), VP8G_A_ROW(VP8G_T_F32, 3)},
+                                       {VP8G_A_ROW(VP8G_T_U8, 4), VP8G_A_ROW(VP8G_T_F16, 4), VP8G_A_ROW(VP8G_T_BF16, 4), VP8G_A_ROW(VP8G_T_F32, 4)}};
+#undef VP8G_A_ROW
+
+uint32_t tiles_of(uint32_t w, uint32_t h) { return (((w + kPx - 1u) / kPx) * h + kThreads - 1u) / kThreads; }
+
+bool full(const Vp8gAnimFrame& f, uint32_t w, uint32_t h) { return f.width == w && f.height == h; }
+
+// libwebp's key-frame rule for frame k, given the frames before it with their VP8G_ANIM_KEY set
+bool is_key(const Vp8gAnimFrame* f, uint32_t k, uint32_t w, uint32_t h) {
+	if (k == 0) return true;
+	const Vp8gAnimFrame &c = f[k], &p = f[k - 1];
+	if ((!(c.flags & VP8G_ANIM_HAS_ALPHA) || !(c.flags & VP8G_ANIM_BLEND)) && full(c, w, h)) return true;
+	return (p.flags & VP8G_ANIM_DISPOSE) && (full(p, w, h) || (p.flags & VP8G_ANIM_KEY));
+}
+
+bool rect_ok(const Vp8gAnimFrame& f, uint32_t w, uint32_t h) {
+	return f.width >= 1 && f.height >= 1 && f.x <= w && f.y <= h && f.width <= w - f.x && f.height <= h - f.y && !(f.x & 1u) && !(f.y & 1u) &&
+	       f.src % 4u == 0;
+}
+
+// A descriptor and its host records as vp8g_make_anim_desc leaves them.
+bool desc_ok(const Vp8gAnimDesc& d) {
+	if (!d.h_frames || d.width < 1 || d.height < 1 || d.width > kMaxDim || d.height > kMaxDim || d.nframes < 1 || d.frames % 8u) return false;
+	const Vp8gAnimFrame* f = d.h_frames;
+	uint32_t segs = 0;
+	for (uint32_t k = 0; k < d.nframes; k++) {
+		if (!rect_ok(f[k], d.width, d.height) || (f[k].flags & ~(kInFlags | VP8G_ANIM_KEY))) return false;
+		const bool key = is_key(f, k, d.width, d.height);
+		if (key != ((f[k].flags & VP8G_ANIM_KEY) != 0)) return false;
+		if (key) {
+			if (segs && f[segs - 1].seg_end != k) return false;
+			if (f[segs].seg_first != k) return false;
+			segs++;
+		}
+	}
+	return f[segs - 1].seg_end == d.nframes && d.nsegs == segs && (uint64_t)segs * tiles_of(d.width, d.height) == d.ntasks;
+}
+
+}  // namespace
+
+// (tests/test_gpu_anim.py takes its boundary sizes from here, through vp8g.anim_geometry())
+VP8G_API void vp8g_anim_geometry(uint32_t out[3]) { out[0] = kPx, out[1] = kPx * kThreads, out[2] = 0u; }
+
+VP8G_API int vp8g_make_anim_desc(uint32_t width, uint32_t height, Vp8gAnimFrame* frames, uint32_t nframes, uint64_t frames_offset,
+                                 uint64_t dst_offset, uint32_t task0, Vp8gAnimDesc* out) {
+	if (!out || !frames || nframes == 0 || width < 1 || height < 1 || width > kMaxDim || height > kMaxDim || frames_offset % 8u)
+		return vp8g::fail(EINVAL);
+	for (uint32_t k = 0; k < nframes; k++)
+		if (!rect_ok(frames[k], width, height) || (frames[k].flags & ~kInFlags)) return vp8g::fail(EINVAL);
+	uint32_t segs = 0;
+	for (uint32_t k = 0; k < nframes; k++) {
+		frames[k].seg_first = frames[k].seg_end = frames[k].reserved = 0;
+		if (!is_key(frames, k, width, height)) continue;
+		frames[k].flags |= VP8G_ANIM_KEY;
+		if (segs) frames[segs - 1].seg_end = k;  // (record s < k is complete by now: s <= its segment's first frame)
+		frames[segs++].seg_first = k;
+	}
+	frames[segs - 1].seg_end = nframes;
+	const uint64_t ntasks = (uint64_t)segs * tiles_of(width, height);
+	if (ntasks + task0 > 0x7FFFFFFFu) return vp8g::fail(EINVAL);
+	memset(out, 0, sizeof(*out));
+	out->frames = frames_offset, out->h_frames = frames, out->dst = dst_offset;
+	out->width = width, out->height = height, out->nframes = nframes, out->nsegs = segs;
+	out->task0 = task0, out->ntasks = (uint32_t)ntasks;
+	return 0;
+}
+
+VP8G_API int vp8g_anim_compose_batch_device(const Vp8gAnimDesc* h, const Vp8gAnimDesc* d_descs, uint32_t n, const Vp8gTensorOpt* t,
+                                            uint32_t channels, const uint8_t* d_src, void* d_dst, void* stream) {
+	if (!h || !d_descs || !d_src || !d_dst || n == 0 || (channels != 3 && channels != 4) || !vp8g_tensor_slot_size(t) ||
+	    (uintptr_t)d_src % 8u)
+		return vp8g::fail(EINVAL);
+	const uint32_t eb = (uint32_t)elem_bytes(t->dtype);
+	uint64_t total = 0, dst_end = 0;
+	bool ok = (uintptr_t)d_dst % eb == 0;
+	for (uint32_t i = 0; ok && i < n; i++) {  // tasks numbered animation by animation, canvases laid out in order
+		ok = desc_ok(h[i]) && h[i].task0 == total && h[i].dst % eb == 0 && h[i].dst >= dst_end;
+		total += h[i].ntasks;
+		dst_end = h[i].dst + (uint64_t)h[i].nframes * channels * h[i].width * h[i].height * eb;
+		if (total > 0x7FFFFFFFu) ok = false;
+	}
+	if (!ok) return vp8g::fail(EINVAL);
+	AnimParams P;
+	for (int c = 0; c < 3; c++) P.scale[c] = t->scale[c], P.bias[c] = t->bias[c];
+	return vp8g::gated_launch((hipStream_t)stream, "anim launch", [&] {
+		hipLaunchKernelGGL(kKernels[channels == 4u][t->dtype][t->layout][t->flags & VP8G_T_BGR], dim3(vp8g::grid_for(total, 8u)), dim3(kThreads), 0,
+		                   (hipStream_t)stream, d_descs, n, (uint32_t)total, P, d_src, (uint8_t*)d_dst);
+		return hipGetLastError();
+	});
+}
+
+// ---- end to end ------------------------------------------------------------------------------
+
+namespace {
+
+void put32(std::vector<uint8_t>& v, uint32_t x) {
+	for (int i = 0; i < 4; i++) v.push_back((uint8_t)(x >> (8 * i)));
+}
+void put_chunk(std::vector<uint8_t>& v, const char* tag, const uint8_t* p, uint32_t n) {
+	v.insert(v.end(), tag, tag + 4);
+	put32(v, n);
+	v.insert(v.end(), p, p + n);
+	if (n & 1u) v.push_back(0);
+}
+// One frame's payload as a file of its own: 'VP8 ' alone, VP8X + ALPH + 'VP8 ', or 'VP8L'.
+std::vector<uint8_t> wrap_frame(const uint8_t* file, const WebPAnimFrame& f) {
+	std::vector<uint8_t> v = {'R', 'I', 'F', 'F', 0, 0, 0, 0, 'W', 'E', 'B', 'P'};
+	if (f.vp8l_offset) {
+		put_chunk(v, "VP8L", file + f.vp8l_offset, f.vp8l_size);
+	} else {
+		if (f.alph_offset) {
+			const uint32_t w = f.width - 1u, h = f.height - 1u;
+			const uint8_t x[10] = {0x10, 0, 0, 0, (uint8_t)w, (uint8_t)(w >> 8), (uint8_t)(w >> 16), (uint8_t)h, (uint8_t)(h >> 8), (uint8_t)(h >> 16)};
+			put_chunk(v, "VP8X", x, 10);
+			put_chunk(v, "ALPH", file + f.alph_offset, f.alph_size);
+		}
+		put_chunk(v, "VP8 ", file + f.vp8_offset, f.vp8_size);
+	}
+	const uint32_t riff = (uint32_t)v.size() - 8u;
+	for (int i = 0; i < 4; i++) v[4 + i] = (uint8_t)(riff >> (8 * i));
+	return v;
+}
+
+struct DevBuf {  // device memory for the length of one call
+	uint8_t* p = nullptr;
+	~DevBuf() {
+		if (p) (void)hipFree(p);
+	}
+};
+
+uint64_t al256(uint64_t v) { return (v + 255u) & ~(uint64_t)255u; }
+
+int fail_all(int* status, uint32_t n, int e) {
+	for (uint32_t i = 0; status && i < n; i++) status[i] = e;
+	return vp8g::fail(e);
+}
+
+int anim_tensor(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags, const Vp8gTensorOpt* t, uint32_t channels,
+                uint8_t* d_out, uint32_t* timestamps, int* status) {
+	const uint64_t slot = channels == 4u ? vp8g_tensor_slot_size_a(t) : vp8g_tensor_slot_size(t);
+	struct File {
+		WebPAnimInfo info;
+		std::vector<WebPAnimFrame> fr;
+		uint32_t first = 0;       // its first slot
+		uint32_t ref0 = 0;        // its first frame in `refs` (files without an error)
+		int err = 0;
+	};
+	std::vector<File> fs(n);
+	uint32_t slots = 0;
+	for (uint32_t i = 0; i < n; i++) {
+		File& f = fs[i];
+		f.first = slots;
+		if (webp_parse_anim(files[i], &f.info, nullptr, 0) != 0) {
+			f.err = EINVAL;
+			continue;
+		}
+		f.fr.resize(f.info.nframes);
+		if (webp_parse_anim(files[i], &f.info, f.fr.data(), f.info.nframes) != 0) return fail_all(status, n, EINVAL);  // (cannot differ)
+		if (f.info.canvas_width != t->width || f.info.canvas_height != t->height) f.err = EINVAL;
+		uint32_t ts = 0;
+		for (uint32_t k = 0; timestamps && k < f.info.nframes; k++) timestamps[slots + k] = ts += f.fr[k].duration;
+		if ((uint64_t)slots + f.info.nframes > 0x7FFFFFFFu) return fail_all(status, n, EINVAL);
+		slots += f.info.nframes;
+	}
+	// every frame of the files still standing, grouped by frame size: one staging tensor and one decode call per size
+	struct Ref {
+		uint32_t file, frame;
+		uint64_t src;  // of its picture in the staging buffer
+	};
+	std::vector<Ref> refs;
+	for (uint32_t i = 0; i < n; i++) {
+		if (fs[i].err) continue;
+		fs[i].ref0 = (uint32_t)refs.size();
+		for (uint32_t k = 0; k < fs[i].info.nframes; k++) refs.push_back({i, k, 0});
+	}
+	auto frame_of = [&](uint32_t q) -> const WebPAnimFrame& { return fs[refs[q].file].fr[refs[q].frame]; };
+	auto size_of = [&](uint32_t q) { return ((uint64_t)frame_of(q).width << 32) | frame_of(q).height; };
+	std::vector<uint32_t> order(refs.size());
+	for (uint32_t q = 0; q < order.size(); q++) order[q] = q;
+	std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return size_of(a) < size_of(b); });
+	uint64_t stage = 0;
+	for (size_t a = 0; a < order.size(); a++) {
+		if (a && size_of(order[a]) != size_of(order[a - 1])) stage = al256(stage);  // (a group's pictures back to back: the slots of its tensor)
+		refs[order[a]].src = stage;
+		stage += 4ull * frame_of(order[a]).width * frame_of(order[a]).height;
+	}
+	const uint64_t rec_off = al256(stage), desc_off = al256(rec_off + refs.size() * sizeof(Vp8gAnimFrame));
+	DevBuf buf;
+	if (!refs.empty()) {
+		if (hipError_t e = hipMalloc((void**)&buf.p, desc_off + n * sizeof(Vp8gAnimDesc)); e != hipSuccess) {
+			(void)hipGetLastError();
+			return fail_all(status, n, e == hipErrorOutOfMemory ? ENOMEM : EIO);
+		}
+	}
+	for (size_t a = 0; a < order.size();) {
+		size_t b = a;
+		while (b < order.size() && size_of(order[b]) == size_of(order[a])) b++;
+		std::vector<std::vector<uint8_t>> wrapped;
+		std::vector<ByteSpan> spans;
+		for (size_t q = a; q < b; q++) wrapped.push_back(wrap_frame(files[refs[order[q]].file].data, frame_of(order[q])));
+		for (auto& w : wrapped) spans.push_back(ByteSpan{w.data(), w.size()});
+		Vp8gTensorOpt st;
+		memset(&st, 0, sizeof(st));
+		st.width = frame_of(order[a]).width, st.height = frame_of(order[a]).height;
+		st.dtype = VP8G_T_U8, st.layout = VP8G_T_NHWC, st.flags = VP8G_T_BGR;  // B, G, R, A bytes: the 0xAARRGGBB dword
+		std::vector<int> err(b - a, 0);
+		const int rc = vp8g_decode_webp_batch_tensor_any(spans.data(), (uint32_t)(b - a), filtered, threads, flags, nullptr, 0, &st,
+		                                                 VP8G_X_ALPHA | VP8G_X_LOSSLESS, buf.p + refs[order[a]].src, err.data());
+		const int en = errno;
+		bool any = false, all_io = true;
+		for (int e : err) any |= e != 0, all_io &= e == EIO;
+		if (rc != 0 && (!any || all_io)) return fail_all(status, n, en == EINVAL || en == ENOMEM ? en : EIO);
+		for (size_t q = a; q < b; q++)
+			if (err[q - a] && !fs[refs[order[q]].file].err) fs[refs[order[q]].file].err = err[q - a];
+		a = b;
+	}
+	// the files whose frames all decoded: records and descriptors, one launch
+	std::vector<Vp8gAnimFrame> recs;
+	std::vector<uint32_t> good, rec0;
+	for (uint32_t i = 0; i < n; i++) {
+		const File& f = fs[i];
+		if (f.err) continue;
+		good.push_back(i), rec0.push_back((uint32_t)recs.size());
+		for (uint32_t k = 0; k < f.info.nframes; k++) {
+			const WebPAnimFrame& a = f.fr[k];
+			Vp8gAnimFrame r;
+			memset(&r, 0, sizeof(r));
+			r.src = refs[f.ref0 + k].src, r.x = a.x, r.y = a.y, r.width = a.width, r.height = a.height;
+			r.flags = (a.blend ? VP8G_ANIM_BLEND : 0u) | (a.dispose ? VP8G_ANIM_DISPOSE : 0u) | (a.has_alpha ? VP8G_ANIM_HAS_ALPHA : 0u);
+			recs.push_back(r);
+		}
+	}
+	std::vector<Vp8gAnimDesc> descs(good.size());
+	uint32_t task0 = 0;
+	for (size_t j = 0; j < good.size(); j++) {  // (recs no longer moves: the descriptors point into it)
+		const File& f = fs[good[j]];
+		if (vp8g_make_anim_desc(t->width, t->height, recs.data() + rec0[j], f.info.nframes, rec_off + rec0[j] * sizeof(Vp8gAnimFrame),
+		                        (uint64_t)f.first * slot, task0, &descs[j]) != 0)
+			return fail_all(status, n, EINVAL);
+		task0 += descs[j].ntasks;
+	}
+	hipError_t e = hipSuccess;
+	const char* where = "anim";
+	for (uint32_t i = 0; e == hipSuccess && i < n; i++)
+		if (fs[i].err && !fs[i].fr.empty()) e = hipMemsetAsync(d_out + (uint64_t)fs[i].first * slot, 0, (uint64_t)fs[i].info.nframes * slot, nullptr), where = "memset";
+	if (e == hipSuccess && !descs.empty()) {
+		e = hipMemcpyAsync(buf.p + rec_off, recs.data(), recs.size() * sizeof(Vp8gAnimFrame), hipMemcpyHostToDevice, nullptr), where = "upload";
+		if (e == hipSuccess)
+			e = hipMemcpyAsync(buf.p + desc_off, descs.data(), descs.size() * sizeof(Vp8gAnimDesc), hipMemcpyHostToDevice, nullptr);
+		if (e == hipSuccess && vp8g_anim_compose_batch_device(descs.data(), (const Vp8gAnimDesc*)(buf.p + desc_off), (uint32_t)descs.size(), t, channels,
+		                                                      buf.p, d_out, nullptr) != 0) {
+			if (errno != EIO) return fail_all(status, n, errno);
+			(void)hipStreamSynchronize(nullptr);
+			return fail_all(status, n, EIO);
+		}
+	}
+	if (e == hipSuccess) e = hipStreamSynchronize(nullptr), where = "sync";
+	if (e != hipSuccess) {
+		vp8g::set_error_text(where, e);
+		return fail_all(status, n, EIO);
+	}
+	int first = 0;
+	for (uint32_t i = 0; i < n; i++) {
+		if (status) status[i] = fs[i].err;
+		if (fs[i].err && !first) first = fs[i].err;
+	}
+	return first ? vp8g::fail(first) : 0;
+}
+
+}  // namespace
+
+VP8G_API int vp8g_anim_info(const ByteSpan* files, uint32_t n, uint32_t* canvas_w, uint32_t* canvas_h, uint32_t* nframes, uint32_t* loop_count,
+                            int* status) {
+	if (!files || !nframes || n == 0) return vp8g::fail(EINVAL);
+	int first = 0;
+	for (uint32_t i = 0; i < n; i++) {
+		WebPAnimInfo info;
+		const int e = webp_parse_anim(files[i], &info, nullptr, 0) == 0 ? 0 : EINVAL;  // (a refused file: info is zero)
+		if (canvas_w) canvas_w[i] = info.canvas_width;
+		if (canvas_h) canvas_h[i] = info.canvas_height;
+		nframes[i] = info.nframes;
+		if (loop_count) loop_count[i] = info.loop_count;
+		if (status) status[i] = e;
+		if (e && !first) first = e;
+	}
+	return first ? vp8g::fail(first) : 0;
+}
+
+VP8G_API int vp8g_decode_webp_anim_tensor(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                          const Vp8gTensorOpt* t, uint32_t channels, void* d_out, uint32_t* timestamps, int* status) {
+	if (!files || n == 0 || !d_out || (channels != 3 && channels != 4) || !vp8g_tensor_slot_size(t) ||
+	    (uintptr_t)d_out % (uint32_t)elem_bytes(t->dtype) || (flags & ~(VP8G_BATCH_DEVICE_M05 | VP8G_BATCH_MULTI_PARTITION)))
+		return vp8g::fail(EINVAL);
+	try {
+		return anim_tensor(files, n, filtered, threads, flags, t, channels, (uint8_t*)d_out, timestamps, status);
+	} catch (const std::bad_alloc&) {
+		return fail_all(status, n, ENOMEM);
+	}
+}

@@ -247,6 +247,69 @@ void vp8f_lossless_free(Vp8fLosslessImage* img);
  * authority the device kernel (csrc/vp8g_lossless.hip) is tested against.  0, or -1 + EINVAL / ENOMEM. */
 int vp8f_lossless_apply(const Vp8fLosslessImage* img, uint32_t* argb);
 
+/* ---- animation (ANIM / ANMF chunks, RFC 9649 2.7.1.1) ---------------------- */
+
+/* What webp_parse_anim found in the file as a whole. */
+typedef struct {
+	uint32_t canvas_width, canvas_height;
+	uint32_t bgcolor;    /* the ANIM chunk's background colour as stored; the compositor ignores it, as libwebp's does */
+	uint32_t loop_count; /* 0 = forever */
+	uint32_t nframes;    /* frames of the file (which may be more than the caller had room for) */
+	uint32_t vp8x_flags;
+} WebPAnimInfo;
+
+/* One ANMF chunk.  The rectangle's size is that of the frame's bitstream, whatever the ANMF header names (libwebp's reading).
+ * Spans are payload offsets in the file and payload sizes; a size of 0 = no such sub-chunk.  An image is
+ * 'VP8 ' (with an optional 'ALPH' in front) or 'VP8L'.  80 bytes. */
+typedef struct {
+	size_t offset;                               /* the ANMF payload (its 16 header bytes first) */
+	size_t alph_offset, vp8_offset, vp8l_offset;
+	uint32_t size, alph_size, vp8_size, vp8l_size;
+	uint32_t x, y, width, height;                /* x, y even */
+	uint32_t duration;                           /* ms */
+	uint32_t blend;                              /* 1: alpha-blend over the canvas, 0: overwrite */
+	uint32_t dispose;                            /* 1: the rectangle is cleared to transparent after the frame */
+	uint32_t has_alpha;                          /* an ALPH chunk, or the alpha bit of the VP8L header */
+} WebPAnimFrame;
+
+/* The animated layout: 'VP8X' with the animation flag, one 'ANIM', then 'ANMF' chunks (metadata and unknown
+ * chunks between them skipped; a second ANIM ignored).  *info is always filled on success; frames (may be NULL
+ * with max_frames = 0: count only) receives the first max_frames frames in file order.  The verdict is that of
+ * libwebp's WebPAnimDecoderNew (tests/golden/anim.json records it for the directed files): -1 + EINVAL for a file
+ * that is not an animation (a still picture, the flag without frames, ANMF without the flag), a reserved VP8X flag
+ * bit, a canvas beyond 16383 in either dimension (this decoder's limit, not libwebp's), a RIFF payload beyond
+ * the file, a chunk that overruns it, an ANMF before ANIM or shorter than its header, a top-level image chunk,
+ * an ALPH without an image, behind its image or in front of a VP8L, a frame whose bitstream header does not parse,
+ * or whose rectangle (the bitstream's size at the ANMF's offset) leaves the canvas.  libwebp reads what follows a frame's
+ * image inside the ANMF as chunks of the top level, and so does this: unknown chunks there are skipped, an image there
+ * is refused, and an ANMF in which nothing recognised comes first is no frame at all (it is dropped where its content
+ * passes as top-level chunks, refused where an image follows or where it ends the file). */
+int webp_parse_anim(ByteSpan file, WebPAnimInfo* info, WebPAnimFrame* frames, uint32_t max_frames);
+
+/* One frame as the compositor sees it: a tight width x height 0xAARRGGBB picture (not premultiplied: the bytes
+ * WebPDecodeRGBA gives) and where it goes.  key is filled by vp8f_anim_keyframes. */
+typedef struct {
+	const uint32_t* argb;
+	uint32_t x, y, width, height;
+	uint32_t blend, dispose, has_alpha;
+	uint32_t key;
+} Vp8fAnimFrame;
+
+/* libwebp's key-frame rule (WebPAnimDecoder): frame 0 is a key frame; frame k is one if it covers the canvas and
+ * has no alpha or does not blend, or if frame k - 1 disposes to background and covered the canvas or was a key
+ * frame.  Sets frames[k].key.  0, or -1 + EINVAL (NULL, n = 0, a canvas of 0 or beyond 16383, an empty rectangle
+ * or one outside the canvas). */
+int vp8f_anim_keyframes(uint32_t canvas_w, uint32_t canvas_h, Vp8fAnimFrame* frames, uint32_t n);
+
+/* The n canvases of an animation, sequentially, as WebPAnimDecoder (MODE_RGBA) composes them: canvases[k] (tight
+ * canvas_w x canvas_h dwords each, 0xAARRGGBB) is what is shown for frame k.  A key frame starts from an all-zero
+ * canvas, any other from the previous canvas after its disposal; the frame's pixels overwrite its rectangle, except
+ * that a pixel is blended over the canvas below (non-premultiplied, libwebp's fixed-point formula; source alpha 255
+ * keeps the source, 0 keeps the canvas pixel whole) when the frame blends, is no key frame, and the canvas pixel was
+ * not just cleared by the previous frame's disposal.  The key flags are computed here (frames[k].key is not read).
+ * The authority the device kernel (csrc/vp8g_anim.hip) is tested against.  0, or -1 + EINVAL / ENOMEM. */
+int vp8f_anim_compose(uint32_t canvas_w, uint32_t canvas_h, const Vp8fAnimFrame* frames, uint32_t n, uint32_t* canvases);
+
 /* FNV-1a 64 over a byte buffer (same constants as reference vp8_tokens.c:15-27). */
 uint64_t vp8f_fnv1a64(const void* data, size_t n, uint64_t h);
 

@@ -220,6 +220,123 @@ int webp_parse_any(ByteSpan file, WebPContainerL* out) {
 	return 0;
 }
 
+static uint32_t rd_le24(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16); }
+
+/* The sub-chunks of one frame from *pos on, in a RIFF payload that ends at `end`, as libwebp's demuxer walks them: an
+ * optional ALPH, then 'VP8 ' or 'VP8L'; the walk stops in front of the first chunk that is neither (or a second of
+ * either kind) and leaves *pos there.  1 = a frame, 0 = nothing it recognises came first (libwebp drops such a frame
+ * without a word), -1 = refused. */
+static int anim_frame_chunks(const uint8_t* data, size_t* at, size_t end, WebPAnimFrame* f) {
+	uint32_t bw = 0, bh = 0, hint = 0;
+	size_t pos = *at;
+	for (;;) {
+		if (end - pos < 8u) return -1; /* (a frame's walk needs a chunk header to look at, and one after each chunk it took) */
+		const uint8_t* chunk = data + pos;
+		const uint32_t csize = rd_le32(chunk + 4);
+		if (csize > 0xFFFFFFF6u) return -1;
+		const size_t padded = (size_t)csize + (csize & 1u);
+		if (padded > end - pos - 8u) return -1;
+		const int is_vp8 = memcmp(chunk, "VP8 ", 4) == 0, is_vp8l = memcmp(chunk, "VP8L", 4) == 0;
+		if (memcmp(chunk, "ALPH", 4) == 0) {
+			if (f->alph_offset) break;
+			f->alph_offset = pos + 8u, f->alph_size = csize;
+		} else if (is_vp8 || is_vp8l) {
+			if (is_vp8l && f->alph_offset) return -1;
+			if (f->vp8_offset || f->vp8l_offset) break;
+			if (is_vp8) {
+				Vp8KeyFrameHeader kf;
+				ByteSpan payload = {chunk + 8, csize};
+				if (vp8_parse_keyframe_header(payload, &kf) != 0) return -1;
+				bw = kf.width, bh = kf.height;
+				f->vp8_offset = pos + 8u, f->vp8_size = csize;
+			} else {
+				if (vp8f_lossless_header(chunk + 8, csize, &bw, &bh, &hint) != 0) return -1;
+				f->vp8l_offset = pos + 8u, f->vp8l_size = csize;
+			}
+			f->width = bw, f->height = bh; /* (the bitstream's size counts, whatever the ANMF header names: as in libwebp) */
+		} else {
+			break;
+		}
+		pos += 8u + padded;
+		if (pos == end) break;
+	}
+	*at = pos;
+	if (!f->alph_offset && !f->vp8_offset && !f->vp8l_offset) return 0;
+	/* an ALPH alone, or one behind its image */
+	if (!f->vp8_offset && !f->vp8l_offset) return -1;
+	if (f->alph_offset && f->alph_offset > (f->vp8_offset ? f->vp8_offset : f->vp8l_offset)) return -1;
+	f->has_alpha = f->alph_offset ? 1u : hint;
+	return 1;
+}
+
+static int parse_anim(ByteSpan file, WebPAnimInfo* info, WebPAnimFrame* frames, uint32_t max_frames) {
+	if (!file.data || file.size < 20 || memcmp(file.data, "RIFF", 4) != 0 || memcmp(file.data + 8, "WEBP", 4) != 0) return -1;
+	const uint32_t riff_size = rd_le32(file.data + 4);
+	/* the RIFF payload must lie inside the file; bytes after it are ignored */
+	if (riff_size < 22u || riff_size > 0xFFFFFFF6u || (size_t)riff_size > file.size - 8u) return -1; /* (a VP8X chunk at the least) */
+	const size_t end = 8u + (size_t)riff_size;
+	if (memcmp(file.data + 12, "VP8X", 4) != 0) return -1; /* a still picture */
+	const uint32_t xsize = rd_le32(file.data + 16);
+	if (xsize < 10u || xsize > 0xFFFFFFF6u || (size_t)xsize + (xsize & 1u) > end - 20u) return -1;
+	info->vp8x_flags = file.data[20];
+	info->canvas_width = 1u + rd_le24(file.data + 24), info->canvas_height = 1u + rd_le24(file.data + 27);
+	/* (libwebp's limit is the canvas area; this decoder's is the size of a tensor's picture) */
+	if (info->canvas_width > 16383u || info->canvas_height > 16383u) return -1;
+	if (!(info->vp8x_flags & 0x02u) || (info->vp8x_flags & ~0x3Eu)) return -1;
+	size_t pos = 20u + (size_t)xsize + (xsize & 1u);
+	uint32_t anims = 0, n = 0;
+	while (pos != end) {
+		if (end - pos < 8u) return -1;
+		const uint8_t* chunk = file.data + pos;
+		const uint32_t csize = rd_le32(chunk + 4);
+		if (csize > 0xFFFFFFF6u) return -1;
+		const size_t padded = (size_t)csize + (csize & 1u);
+		if (padded > end - pos - 8u) return -1;
+		if (memcmp(chunk, "VP8X", 4) == 0 || memcmp(chunk, "VP8 ", 4) == 0 || memcmp(chunk, "VP8L", 4) == 0 ||
+		    memcmp(chunk, "ALPH", 4) == 0)
+			return -1;
+		if (memcmp(chunk, "ANIM", 4) == 0) {
+			if (padded < 6u) return -1;
+			if (anims++ == 0) info->bgcolor = rd_le32(chunk + 8), info->loop_count = (uint32_t)chunk[12] | (uint32_t)chunk[13] << 8;
+		} else if (memcmp(chunk, "ANMF", 4) == 0) {
+			if (anims == 0 || padded < 16u) return -1;
+			WebPAnimFrame f;
+			memset(&f, 0, sizeof(f));
+			const uint8_t* p = chunk + 8;
+			f.offset = pos + 8u, f.size = csize;
+			f.x = 2u * rd_le24(p), f.y = 2u * rd_le24(p + 3), f.width = 1u + rd_le24(p + 6), f.height = 1u + rd_le24(p + 9);
+			f.duration = rd_le24(p + 12);
+			f.dispose = p[15] & 1u, f.blend = (p[15] & 2u) ? 0u : 1u;
+			size_t at = pos + 24u;
+			const int got = anim_frame_chunks(file.data, &at, end, &f);
+			if (got < 0 || at > pos + 8u + padded) return -1; /* (a sub-chunk that runs past the ANMF's own end) */
+			if (got > 0) {
+				if ((uint64_t)f.x + f.width > info->canvas_width || (uint64_t)f.y + f.height > info->canvas_height) return -1;
+				if (n < max_frames) frames[n] = f;
+				if (++n == 0) return -1;
+			}
+			/* libwebp goes on from where the frame's walk stopped, not from the ANMF's end: what follows the image
+			 * inside the ANMF is read as chunks of the top level (an unknown one is skipped, an image refused) */
+			pos = at;
+			continue;
+		}
+		pos += 8u + padded;
+	}
+	if (n == 0) return -1;
+	info->nframes = n;
+	return 0;
+}
+
+int webp_parse_anim(ByteSpan file, WebPAnimInfo* info, WebPAnimFrame* frames, uint32_t max_frames) {
+	if (info) memset(info, 0, sizeof(*info));
+	if (!info || (max_frames && !frames) || parse_anim(file, info, frames, max_frames) != 0) {
+		if (info) memset(info, 0, sizeof(*info));
+		errno = EINVAL; /* (every refusal is this one) */
+		return -1;
+	}
+	return 0;
+}
+
 int vp8_parse_keyframe_header(ByteSpan p, Vp8KeyFrameHeader* out) {
 	if (!out) return -1;
 	memset(out, 0, sizeof(*out));

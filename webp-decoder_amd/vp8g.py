@@ -238,6 +238,35 @@ class Vp8gScaleArgbDesc(C.Structure):
         ("reserved", C.c_uint32 * 2), ("plane", Vp8gScaleDesc * 4)]
 
 
+class WebPAnimInfo(C.Structure):
+    """host/vp8_front.h: what webp_parse_anim found in an animated file as a whole."""
+    _fields_ = [(n, C.c_uint32) for n in ("canvas_width", "canvas_height", "bgcolor", "loop_count", "nframes", "vp8x_flags")]
+
+
+class WebPAnimFrame(C.Structure):
+    """host/vp8_front.h: one ANMF chunk (payload offsets and sizes of its sub-chunks; a size of 0 = absent)."""
+    _fields_ = [(n, C.c_size_t) for n in ("offset", "alph_offset", "vp8_offset", "vp8l_offset")] + [(n, C.c_uint32) for n in (
+        "size", "alph_size", "vp8_size", "vp8l_size", "x", "y", "width", "height", "duration", "blend", "dispose", "has_alpha")]
+
+
+class Vp8fAnimFrame(C.Structure):
+    """host/vp8_front.h: one frame as vp8f_anim_compose sees it."""
+    _fields_ = [("argb", C.c_void_p)] + [(n, C.c_uint32) for n in ("x", "y", "width", "height", "blend", "dispose", "has_alpha", "key")]
+
+
+class Vp8gAnimFrame(C.Structure):
+    """include/vp8g.h: one frame record of the compositor kernel (vp8g_make_anim_desc completes it)."""
+    _fields_ = [("src", C.c_uint64)] + [(n, C.c_uint32) for n in ("x", "y", "width", "height", "flags", "seg_first", "seg_end", "reserved")]
+
+
+class Vp8gAnimDesc(C.Structure):
+    """include/vp8g.h: per-animation descriptor of the compositor kernel (vp8g_make_anim_desc)."""
+    _fields_ = [("frames", C.c_uint64), ("h_frames", C.c_void_p), ("dst", C.c_uint64)] + [(n, C.c_uint32) for n in (
+        "width", "height", "nframes", "nsegs", "task0", "ntasks")]
+
+
+ANIM_BLEND, ANIM_DISPOSE, ANIM_HAS_ALPHA, ANIM_KEY = 1, 2, 4, 8  # VP8G_ANIM_*
+
 # transform types (RFC 9649 4)
 L_PREDICTOR, L_CROSS_COLOR, L_SUBTRACT_GREEN, L_COLOR_INDEX = 0, 1, 2, 3
 
@@ -283,6 +312,7 @@ assert C.sizeof(Vp8gScaleDesc) == 272
 assert C.sizeof(Vp8gTensorOpt) == 44
 assert C.sizeof(Vp8gTensorDesc) == 48
 assert C.sizeof(Vp8gScaleArgbDesc) == 1200
+assert C.sizeof(WebPAnimFrame) == 80 and C.sizeof(Vp8gAnimFrame) == 40 and C.sizeof(Vp8gAnimDesc) == 48
 
 VP8G_F_LOOPFILTER = 1
 VP8G_F_SIMPLE = 2
@@ -381,6 +411,10 @@ def host_lib():
             lib.vp8f_argb_mult_row.argtypes = [C.c_void_p, C.c_uint32, C.c_int]
             lib.vp8f_argb_mult_row.restype = None
             lib.vp8f_argb_scale.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Vp8gScaleOpt), C.c_void_p]
+        if hasattr(lib, "webp_parse_anim"):  # (libraries built before the animation path: A/B of old builds)
+            lib.webp_parse_anim.argtypes = [ByteSpan, C.POINTER(WebPAnimInfo), C.POINTER(WebPAnimFrame), C.c_uint32]
+            lib.vp8f_anim_keyframes.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(Vp8fAnimFrame), C.c_uint32]
+            lib.vp8f_anim_compose.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(Vp8fAnimFrame), C.c_uint32, C.c_void_p]
         lib._typed = True
     return lib
 
@@ -506,6 +540,16 @@ def gpu_lib():
                                                       C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(Vp8gScaleArgbDesc)]
             lib.vp8g_scale_argb_batch_device.argtypes = [P(Vp8gScaleArgbDesc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                          C.c_void_p, C.c_void_p]
+        if hasattr(lib, "vp8g_anim_compose_batch_device"):  # (libraries built before the animation path)
+            lib.vp8g_anim_geometry.argtypes = [P(C.c_uint32)]
+            lib.vp8g_anim_geometry.restype = None
+            lib.vp8g_make_anim_desc.argtypes = [C.c_uint32, C.c_uint32, P(Vp8gAnimFrame), C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                P(Vp8gAnimDesc)]
+            lib.vp8g_anim_compose_batch_device.argtypes = [P(Vp8gAnimDesc), C.c_void_p, C.c_uint32, P(Vp8gTensorOpt), C.c_uint32,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.vp8g_anim_info.argtypes = [P(ByteSpan), C.c_uint32, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), P(C.c_int)]
+            lib.vp8g_decode_webp_anim_tensor.argtypes = [P(ByteSpan), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, P(Vp8gTensorOpt),
+                                                         C.c_uint32, C.c_void_p, P(C.c_uint32), P(C.c_int)]
         lib._typed = True
     return lib
 
@@ -1377,6 +1421,230 @@ def gpu_tensor_argb(argb_list, opt: Vp8gTensorOpt, channels: int = 4, slot_shift
         raise RuntimeError(f"vp8g_tensor_batch_device_argb failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
     stream.synchronize()
     return out
+
+
+# ---- animated files ---------------------------------------------------------
+
+
+def parse_anim(data: bytes) -> dict:
+    """webp_parse_anim: {"canvas": [w, h], "loop_count", "bgcolor", "vp8x_flags", "frames": [{the fields of
+    WebPAnimFrame}, ...]}; OSError with EINVAL if refused (a still picture included)."""
+    info = WebPAnimInfo()
+    buf, span = _c_bytes(data)
+    lib = host_lib()
+    if lib.webp_parse_anim(span, C.byref(info), None, 0) != 0:
+        raise OSError(C.get_errno(), "webp_parse_anim")
+    fr = (WebPAnimFrame * info.nframes)()
+    if lib.webp_parse_anim(span, C.byref(info), fr, info.nframes) != 0:
+        raise OSError(C.get_errno(), "webp_parse_anim")
+    return {"canvas": [int(info.canvas_width), int(info.canvas_height)], "loop_count": int(info.loop_count),
+            "bgcolor": int(info.bgcolor), "vp8x_flags": int(info.vp8x_flags),
+            "frames": [{n: int(getattr(f, n)) for n, _ in WebPAnimFrame._fields_} for f in fr]}
+
+
+def wrap_anim_frame(data: bytes, f: dict) -> bytes:
+    """One frame of parse_anim(data) as a file of its own: 'VP8 ' alone, VP8X + ALPH + 'VP8 ', or 'VP8L' (what the
+    end-to-end entry hands to the still-picture decoder)."""
+    def chunk(tag, off, n):
+        return tag + n.to_bytes(4, "little") + data[off:off + n] + (b"\0" if n & 1 else b"")
+    if f["vp8l_size"]:
+        body = chunk(b"VP8L", f["vp8l_offset"], f["vp8l_size"])
+    else:
+        body = chunk(b"VP8 ", f["vp8_offset"], f["vp8_size"])
+        if f["alph_size"] or f["alph_offset"]:
+            x = bytes([0x10, 0, 0, 0]) + (f["width"] - 1).to_bytes(3, "little") + (f["height"] - 1).to_bytes(3, "little")
+            body = b"VP8X" + (10).to_bytes(4, "little") + x + chunk(b"ALPH", f["alph_offset"], f["alph_size"]) + body
+    return b"RIFF" + (len(body) + 4).to_bytes(4, "little") + b"WEBP" + body
+
+
+def host_still_argb(data: bytes) -> np.ndarray:
+    """A still .webp (lossy, lossy with alpha, or lossless) on the host as uint32 [h, w] 0xAARRGGBB, the bytes
+    WebPDecodeRGBA gives: the lossless restatement, or the oracle's reconstruction (loop filter on) and RGB conversion
+    with the alpha plane of host_alpha_plane (255 without one)."""
+    c = parse_any(data)
+    if c["lossless"]:
+        return host_lossless_argb(data)
+    kf, fr, st = Vp8KeyFrameHeader(), Vp8DecodedFrame(), C.c_int(0)
+    p = data[c["vp8_chunk_offset"]:c["vp8_chunk_offset"] + c["vp8_chunk_size"]]
+    simple = b"RIFF" + (len(p) + (len(p) & 1) + 12).to_bytes(4, "little") + b"WEBPVP8 " + len(p).to_bytes(4, "little") + p + (
+        b"\0" if len(p) & 1 else b"")
+    buf, _ = _c_bytes(simple)
+    if host_lib().vp8f_decode_memory(buf, len(simple), C.byref(kf), C.byref(fr), C.byref(st)) != 0:
+        raise OSError(C.get_errno() or 22, f"vp8f_decode_memory (stage {st.value})")
+    f = Frame(kf, fr)
+    w, h = f.width, f.height
+    ppm = oracle_encode(oracle_reconstruct(f, True), w, h, "ppm")
+    f.free()
+    rgb = np.frombuffer(ppm, np.uint8)[len(ppm) - 3 * w * h:].reshape(h, w, 3).astype(np.uint32)
+    a = host_alpha_plane(data) if c["extended"] else None
+    a = np.full((h, w), 255, np.uint32) if a is None else a.astype(np.uint32)
+    return a << 24 | rgb[:, :, 0] << 16 | rgb[:, :, 1] << 8 | rgb[:, :, 2]
+
+
+def host_anim_frames(data: bytes):
+    """An animated file's frames decoded on the host: ([w, h] of the canvas, list of frames in host_anim_compose's
+    form, list of cumulative end times in ms)."""
+    a = parse_anim(data)
+    frames, ts, t = [], [], 0
+    for f in a["frames"]:
+        frames.append({"argb": host_still_argb(wrap_anim_frame(data, f)), "x": f["x"], "y": f["y"], "blend": f["blend"],
+                       "dispose": f["dispose"], "has_alpha": f["has_alpha"]})
+        t += f["duration"]
+        ts.append(t)
+    return a["canvas"], frames, ts
+
+
+def _anim_host_structs(frames):
+    fr = (Vp8fAnimFrame * len(frames))()
+    keep = []
+    for k, f in enumerate(frames):
+        a = np.ascontiguousarray(f["argb"], dtype=np.uint32)
+        keep.append(a)
+        fr[k] = Vp8fAnimFrame(a.ctypes.data, f["x"], f["y"], a.shape[1], a.shape[0], int(f["blend"]), int(f["dispose"]),
+                              int(f["has_alpha"]), 0)
+    return fr, keep
+
+
+def host_anim_compose(canvas_w: int, canvas_h: int, frames):
+    """vp8f_anim_compose (the sequential CPU restatement of libwebp's WebPAnimDecoder) over frames given as dicts
+    {"argb": uint32 [h, w], "x", "y", "blend", "dispose", "has_alpha"}: (uint32 [F, canvas_h, canvas_w] canvases,
+    list of key-frame flags).  OSError with its errno (EINVAL) for a frame outside the canvas."""
+    fr, keep = _anim_host_structs(frames)
+    out = np.empty((len(frames), canvas_h, canvas_w), np.uint32)
+    lib = host_lib()
+    if lib.vp8f_anim_compose(canvas_w, canvas_h, fr, len(frames), out.ctypes.data) != 0:
+        raise OSError(C.get_errno() or 22, "vp8f_anim_compose")
+    if lib.vp8f_anim_keyframes(canvas_w, canvas_h, fr, len(frames)) != 0:
+        raise OSError(C.get_errno() or 22, "vp8f_anim_keyframes")
+    return out, [int(f.key) for f in fr]
+
+
+def anim_geometry():
+    """vp8g_anim_geometry: (pixels per thread, pixels per task, frames per task or 0 for no limit) of the compositor
+    kernel as the library was built.  The boundary sizes of the tests come from it."""
+    g = (C.c_uint32 * 3)()
+    gpu_lib().vp8g_anim_geometry(g)
+    return int(g[0]), int(g[1]), int(g[2])
+
+
+def anim_records(frames, srcs):
+    """The Vp8gAnimFrame array of frames in host_anim_compose's form whose pictures sit at byte offsets srcs."""
+    rec = (Vp8gAnimFrame * len(frames))()
+    for k, f in enumerate(frames):
+        h, w = np.asarray(f["argb"]).shape
+        rec[k] = Vp8gAnimFrame(srcs[k], f["x"], f["y"], w, h, (ANIM_BLEND if f["blend"] else 0) | (ANIM_DISPOSE if f["dispose"] else 0)
+                               | (ANIM_HAS_ALPHA if f["has_alpha"] else 0), 0, 0, 0)
+    return rec
+
+
+def gpu_anim_compose(anims, opt: Vp8gTensorOpt, channels: int = 4, src_shift: int = 1, guard: int = 64, fill: int = 0xEE,
+                     mutate=None, ptr_shift=(0, 0)):
+    """vp8g_make_anim_desc + vp8g_anim_compose_batch_device over animations [(canvas_w, canvas_h, frames in
+    host_anim_compose's form), ...] of mixed canvases and frame counts in one launch: the list of torch CPU tensors
+    [F, C, H, W] or [F, H, W, C] of opt's dtype (opt's width and height are not read).  src_shift: every frame picture
+    starts this many DWORDS off a 16-byte boundary; guard (a multiple of 8): bytes kept in front of, between and behind
+    the animations' canvases, which the call checks still hold `fill` (an animation's canvases are contiguous: a write
+    into a neighbouring canvas shows in the comparison).  mutate(descs, records): called on the host descriptors and the
+    list of record arrays before the upload; ptr_shift: bytes added to the source and output pointers handed to the call
+    (both for tests of the entry point's checks: a refusal raises ValueError)."""
+    import torch
+    lib = gpu_lib()
+    dev = torch.device("cuda", 0)
+    n, eb = len(anims), T_ELEM[opt.dtype]
+    descs = (Vp8gAnimDesc * n)()
+    parts, so, do, task0, recs, rec_at = [], 0, guard, 0, [], []
+
+    def put(b, align, shift=0):
+        nonlocal so
+        pad = (-so) % align + shift
+        parts.append(np.full(pad, 0x5A, np.uint8))
+        so += pad + b.size
+        parts.append(b)
+        return so - b.size
+
+    for i, (cw, ch, frames) in enumerate(anims):
+        srcs = [put(np.ascontiguousarray(f["argb"], dtype=np.uint32).reshape(-1).view(np.uint8), 16, 4 * src_shift) for f in frames]
+        rec = anim_records(frames, srcs)
+        rec_at.append(put(np.zeros(C.sizeof(rec), np.uint8), 8))  # (filled in below, once vp8g_make_anim_desc has completed it)
+        recs.append((rec, len(parts) - 1))
+        if lib.vp8g_make_anim_desc(cw, ch, rec, len(frames), rec_at[i], do, task0, C.byref(descs[i])) != 0:
+            raise ValueError(f"vp8g_make_anim_desc failed: errno={C.get_errno()}")
+        task0 += descs[i].ntasks
+        do += len(frames) * channels * cw * ch * eb + guard
+    for rec, at in recs:
+        parts[at] = np.frombuffer(bytes(rec), np.uint8)
+    parts.append(np.full(16, 0x5A, np.uint8))
+    src = torch.from_numpy(np.concatenate(parts)).to(dev)
+    dst = torch.full((do,), fill, dtype=torch.uint8, device=dev)
+    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
+    if mutate:  # (after the device copies are made: the kernel never sees what a test breaks in the host copies)
+        mutate(descs, [r for r, _ in recs])
+    stream = torch.cuda.current_stream(dev)
+    if lib.vp8g_anim_compose_batch_device(descs, C.c_void_p(d_descs.data_ptr()), n, C.byref(opt), channels,
+                                          C.c_void_p(src.data_ptr() + ptr_shift[0]), C.c_void_p(dst.data_ptr() + ptr_shift[1]),
+                                          C.c_void_p(stream.cuda_stream)) != 0:
+        en = C.get_errno()
+        if en == 22:
+            raise ValueError("vp8g_anim_compose_batch_device: EINVAL")
+        raise RuntimeError(f"vp8g_anim_compose_batch_device failed: errno={en} {lib.vp8g_last_error()!r}")
+    stream.synchronize()
+    host = dst.cpu()
+    out, keep = [], np.ones(do, bool)
+    for i, (cw, ch, frames) in enumerate(anims):
+        nb = len(frames) * channels * cw * ch * eb
+        shape = (len(frames), channels, ch, cw) if opt.layout == T_LAYOUTS["NCHW"] else (len(frames), ch, cw, channels)
+        out.append(host[descs[i].dst:descs[i].dst + nb].clone().view(_torch_dtype(opt)).view(shape))
+        keep[descs[i].dst:descs[i].dst + nb] = False
+    if not (host.numpy()[keep] == fill).all():
+        raise AssertionError("gpu_anim_compose: bytes outside the canvases were written")
+    return out
+
+
+def anim_info(files: list[bytes]):
+    """vp8g_anim_info: (list of {"canvas": [w, h], "nframes", "loop_count"}, list of errno) -- a refused file has no frames."""
+    lib = gpu_lib()
+    n = len(files)
+    bufs = [(C.c_uint8 * max(1, len(b))).from_buffer_copy(b if b else b"\0") for b in files]
+    spans = (ByteSpan * n)(*[ByteSpan(C.cast(bufs[i], C.POINTER(C.c_uint8)), len(files[i])) for i in range(n)])
+    cw, ch, nf, lc = ((C.c_uint32 * n)() for _ in range(4))
+    st = (C.c_int * n)()
+    lib.vp8g_anim_info(spans, n, cw, ch, nf, lc, st)
+    return [{"canvas": [int(cw[i]), int(ch[i])], "nframes": int(nf[i]), "loop_count": int(lc[i])} for i in range(n)], list(st)
+
+
+def gpu_decode_webp_anim_tensor(files: list[bytes], opt: Vp8gTensorOpt, alpha: bool = True, filtered: bool = True, threads: int = 0,
+                                device_m05: bool = False, multi_partition: bool = False, prefill=None):
+    """vp8g_decode_webp_anim_tensor: animated .webp files decoded and composited on the device into one dense tensor
+    of canvases, [sum of frames, C, H, W] or [.., H, W, C] with C = 4 (alpha) or 3.  Returns (the torch.Tensor on the
+    device, each file's first slot, the timestamps (cumulative end time in ms of every slot), list of errno); the
+    slots of a failed file are zero, and a file that is no animation has none.  torch only allocates the tensor
+    (prefill: a value it is filled with before the call, for tests of the zero slots)."""
+    import time
+    import torch
+    lib = gpu_lib()
+    n = len(files)
+    info, _ = anim_info(files)
+    first = [sum(a["nframes"] for a in info[:i]) for i in range(n)]
+    total = sum(a["nframes"] for a in info)
+    bufs = [(C.c_uint8 * max(1, len(b))).from_buffer_copy(b if b else b"\0") for b in files]
+    spans = (ByteSpan * n)(*[ByteSpan(C.cast(bufs[i], C.POINTER(C.c_uint8)), len(files[i])) for i in range(n)])
+    channels = 4 if alpha else 3
+    dev = torch.device("cuda", 0)
+    out = torch.empty(_tensor_shape(max(total, 1), opt, channels), dtype=_torch_dtype(opt), device=dev)
+    if prefill is not None:
+        out.fill_(prefill)
+    torch.cuda.synchronize(dev)
+    ts = (C.c_uint32 * max(total, 1))()
+    st = (C.c_int * n)()
+    t0 = time.perf_counter()
+    rc = lib.vp8g_decode_webp_anim_tensor(spans, n, int(filtered), threads,
+                                          (VP8G_BATCH_DEVICE_M05 if device_m05 else 0) | (VP8G_BATCH_MULTI_PARTITION if multi_partition else 0),
+                                          C.byref(opt), channels, C.c_void_p(out.data_ptr()), ts, st)
+    gpu_decode_webp_anim_tensor.seconds = time.perf_counter() - t0  # the C call alone
+    en = C.get_errno()
+    if rc != 0 and (all(s == 5 for s in st) or not any(st)):  # EIO: device failure; or the call itself refused
+        raise RuntimeError(f"vp8g_decode_webp_anim_tensor failed: errno={en} {lib.vp8g_last_error()!r}")
+    return out[:total], first, list(ts)[:total], list(st)
 
 
 def gpu_decode_webp_batch_x(files: list[bytes], scale=None, filtered: bool = True, threads: int = 0, device_m05: bool = False,
