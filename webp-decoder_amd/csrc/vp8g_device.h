@@ -51,7 +51,7 @@ constexpr int kWaveBytes = 2 * kHalfBytes;
 // Workgroup header.
 constexpr int kProgress = 0;      // 16 x u32 progress words (one per wave)
 constexpr int kBpTable = 64;      // B_PRED predictor table: 11 modes x 16 px x {perm selectors, byte
-                                  // mask, dot weights, bias | shift}
+                                  // mask, dot weights, bias}
 constexpr int kBpModes = 11;      // modes 0..9 + one constant-128 entry for out-of-range modes
 constexpr int kBpEntry = 16;      // bytes per (mode, pixel) entry
 constexpr int kDqTable = kBpTable + kBpModes * 16 * kBpEntry;  // 4 segments x 6 int16 dequant factors

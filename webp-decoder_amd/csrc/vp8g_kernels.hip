@@ -115,7 +115,8 @@ constexpr int kBS = 4 * kTP - 8;  // B_PRED: tile offset from sub-block (i, j) t
 // as v_perm selectors (pos & 7) plus a byte mask picking the high half (pos >= 8) of E: one
 // perm pair + one bfi fetches all three, one signed v_dot4 over the bytes biased by -128 weighs
 // them (avg3 weights (1, 2, 1); TM_PRED = sat8(L + A - P) is the same dot with weights
-// (1, -1, 1) over the positions (L_r, P, A_c)); DC_PRED is a direct sum.
+// (4, -4, 4) over the positions (L_r, P, A_c), which the avg3 modes' >> 2 divides out again); DC_PRED
+// is a direct sum.
 // Entry kBpModes-1 (all positions 128) serves out-of-range modes.
 // Edge index notation of the builders: 0..3 = L3..L0, 4 = P, 5..12 = A0..A7.
 // ---------------------------------------------------------------------------------------------
@@ -162,13 +163,14 @@ constexpr BpTab make_bptab() {
 				sel |= (uint32_t)(pos[k] & 7) << (8 * k);
 				if (pos[k] >= 8) mask |= 0xFFu << (8 * k);
 			}
-			// weights (signed bytes) and bias / shift of the one dot-product formula:
-			// value = (sdot4(E_xyz - 128, w) + bias) >> sh  (avg3: (1, 2, 1), 514, 2; TM: (1, -1, 1), 128, 0)
+			// weights (signed bytes) and bias of the one dot-product formula:
+			// value = (sdot4(E_xyz - 128, w) + bias) >> 2  (avg3: (1, 2, 1), 514; TM: (4, -4, 4), 512 -- four
+			// times L + A - P, so the shift every mode shares is exact for it; |dot| <= 4 * 3 * 128)
 			const bool tm = m == 1;
 			t.v[(m * 16 + p) * 4] = sel;
-			t.v[(m * 16 + p) * 4 + 1] = mask | ((tm ? 0u : 2u) << 24);  // byte 3: the shift (x3's byte 3 is unused)
-			t.v[(m * 16 + p) * 4 + 2] = tm ? 0x0001FF01u : 0x00010201u;
-			t.v[(m * 16 + p) * 4 + 3] = tm ? 128u : 514u;
+			t.v[(m * 16 + p) * 4 + 1] = mask;
+			t.v[(m * 16 + p) * 4 + 2] = tm ? 0x0004FC04u : 0x00010201u;
+			t.v[(m * 16 + p) * 4 + 3] = tm ? 512u : 514u;
 		}
 	return t;
 }
@@ -1292,8 +1294,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void frame_kerne
 							const uint32_t hi = __builtin_amdgcn_perm(a47, a03, tb.x);
 							const uint32_t x3 = (hi & tb.y) | (lo & ~tb.y);  // bytes 0..2 = x, y, z
 							// directional modes and TM in one signed dot product over the byte-biased edge
-							const int vdir = sat8(__builtin_amdgcn_sdot4((int)(x3 ^ 0x00808080u), (int)tb.z, (int)tb.w, false) >>
-							                      (tb.y >> 24));
+							const int vdir = sat8(__builtin_amdgcn_sdot4((int)(x3 ^ 0x00808080u), (int)tb.z, (int)tb.w, false) >> 2);
 							const int vdc = (int)((__builtin_amdgcn_sad_u8(a03, 0u, __builtin_amdgcn_sad_u8(lw, 0u, 4u))) >> 3);
 							const int pred = mode == 0 ? vdc : vdir;
 							const int px = sat8(pred + rv);

@@ -144,19 +144,20 @@ DEV void lf_mb_chroma(const LfLine& L, bool en, bool mb_v, bool mb_h, bool inner
 }
 
 // Paired pixel stores (role 0's luma rows and both roles' chroma rows, in both instantiations): a
-// lane keeps its piece of an even MB column for one step, and at the odd column the lanes l and
-// l ^ 1 (same piece column) trade halves, so that one store instruction writes each of the two rows
-// as two adjacent pieces -- 32 B of luma / 16 B of chroma from two lanes instead of two 16-B / 8-B
-// pieces a step apart.
+// lane keeps its piece of an even MB column for one step and stores at the odd column.  Luma (16-B
+// pieces, the most a lane stores): the lanes l and l ^ 1 (same piece column) trade halves, so that
+// one store instruction writes each of the two rows as two adjacent pieces -- 32 B from two lanes
+// instead of two 16-B pieces a step apart.  Chroma (8-B pieces): the kept piece and the current one
+// are 16 adjacent bytes of the lane's own row and go out as one 16-B store, with no exchange.
 //
 // A step's vector-memory operations, in issue order (vmcnt counts in issue order, and the step loop's
 // `s_waitcnt vmcnt(N)` are written against this list): the context load (1, after the side info), the
-// next step's prefetch (5, after the residual), the pixel stores (7: role 0's luma as two paired
-// stores, role 1's luma, four paired chroma) and quarter 3's context stores (3): 16 in all.  The
-// single stores of a last column come on top, in few steps; more operations in flight only make a
-// wait stricter than it has to be.
+// next step's prefetch (5, after the residual), the pixel stores (5: role 0's luma as two paired
+// stores, role 1's luma, one chroma store per role) and quarter 3's context stores (3): 14 in all.
+// The single stores of a last column come on top, in few steps; more operations in flight only make
+// a wait stricter than it has to be.
 constexpr int kQPrefLoads = 5;
-constexpr int kQStoresPerStep = 7 + 3;
+constexpr int kQStoresPerStep = 5 + 3;
 // Cache policy of the pixel stores: write-through (sc1).  With 32-B luma / 16-B chroma pieces a
 // write-back L2 still refilled the partly written lines from HBM (1 564 B read per MB against 820);
 // sc1 writes them straight through (DESIGN.md §3.1, r05p2).
@@ -179,15 +180,6 @@ DEV void pair_swap(const u32x4& held, const u32x4& cur, u32x4& dA, u32x4& dB) {
 	    VP8G_SELSWAP("%4", "%12", "%8") VP8G_SELSWAP("%5", "%13", "%9") VP8G_SELSWAP("%6", "%14", "%10") VP8G_SELSWAP("%7", "%15", "%11")
 	    : "=&v"(dA.x), "=&v"(dA.y), "=&v"(dA.z), "=&v"(dA.w), "=&v"(dB.x), "=&v"(dB.y), "=&v"(dB.z), "=&v"(dB.w)
 	    : "v"(held.x), "v"(held.y), "v"(held.z), "v"(held.w), "v"(cur.x), "v"(cur.y), "v"(cur.z), "v"(cur.w), "s"(kEvenLanes)
-	    : "vcc", "scc");
-}
-DEV void pair_swap(const u32x2& held, const u32x2& cur, u32x2& dA, u32x2& dB) {
-	asm("s_mov_b64 vcc, %8\n\ts_nop 1\n\t"
-	    VP8G_SELSWAP("%0", "%4", "%6") VP8G_SELSWAP("%1", "%5", "%7")
-	    "s_not_b64 vcc, vcc\n\t"
-	    VP8G_SELSWAP("%2", "%6", "%4") VP8G_SELSWAP("%3", "%7", "%5")
-	    : "=&v"(dA.x), "=&v"(dA.y), "=&v"(dB.x), "=&v"(dB.y)
-	    : "v"(held.x), "v"(held.y), "v"(cur.x), "v"(cur.y), "s"(kEvenLanes)
 	    : "vcc", "scc");
 }
 #undef VP8G_SELSWAP
@@ -541,9 +533,9 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 		asm volatile("" : "+v"(cb0), "+v"(cb1), "+v"(sbase), "+v"(csh1));
 		QPref cur = qprefetch(lane0, 0);
 		// Everything of the setup drained before the step loop (once per quad): with nothing outstanding
-		// on entry, the waits the compiler places in the loop are set by its back edge alone -- vmcnt(14)
-		// and (13) for the side byte and the modes at the top (the rest of the prefetch and the previous
-		// step's ten stores are younger), vmcnt(12) and (11) for the coefficients (the context load is
+		// on entry, the waits the compiler places in the loop are set by its back edge alone -- vmcnt(12)
+		// and (11) for the side byte and the modes at the top (the rest of the prefetch and the previous
+		// step's eight stores are younger), vmcnt(9) and (8) for the coefficients (the context load is
 		// younger too); the context load itself is covered by the publish's wait.  (Dummy operations to
 		// match the back edge's count were fragile: the compiler merged identical ones and placed scratch
 		// reloads after them, and the loop then waited vmcnt(0) -- every store of the previous step -- at
@@ -1000,7 +992,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 								const uint32_t lo = __builtin_amdgcn_perm(ey, lw, tb.x);
 								const uint32_t hi = __builtin_amdgcn_perm(a47, a03, tb.x);
 								const uint32_t x3 = (hi & tb.y) | (lo & ~tb.y);
-								const int vdir = sat8(__builtin_amdgcn_sdot4((int)(x3 ^ 0x00808080u), (int)tb.z, (int)tb.w, false) >> (tb.y >> 24));
+								const int vdir = sat8(__builtin_amdgcn_sdot4((int)(x3 ^ 0x00808080u), (int)tb.z, (int)tb.w, false) >> 2);
 								const int vdc = (int)((__builtin_amdgcn_sad_u8(a03, 0u, __builtin_amdgcn_sad_u8(lw, 0u, 4u))) >> 3);
 								const int pred = mode == 0 ? vdc : vdir;
 								const int px = sat8(pred + rv);
@@ -1048,7 +1040,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 							const uint32_t lo = __builtin_amdgcn_perm(ey, lwv[gg], tb[gg].x);
 							const uint32_t hi = __builtin_amdgcn_perm(a47[gg], a03[gg], tb[gg].x);
 							const uint32_t x3 = (hi & tb[gg].y) | (lo & ~tb[gg].y);
-							const int vdir = sat8(__builtin_amdgcn_sdot4((int)(x3 ^ 0x00808080u), (int)tb[gg].z, (int)tb[gg].w, false) >> (tb[gg].y >> 24));
+							const int vdir = sat8(__builtin_amdgcn_sdot4((int)(x3 ^ 0x00808080u), (int)tb[gg].z, (int)tb[gg].w, false) >> 2);
 							const int vdc = (int)((__builtin_amdgcn_sad_u8(a03[gg], 0u, __builtin_amdgcn_sad_u8(lwv[gg], 0u, 4u))) >> 3);
 							const int pred = md[gg] == 0 ? vdc : vdir;
 							const int px = sat8(pred + rv[gg]);
@@ -1183,7 +1175,8 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 				cutC(oC0, cC0, nC0, bC0), cutC(oC1, cC1, nC1, bC1);
 			}
 			{
-				// The pixel stores, paired over two MB columns (pair_swap above).
+				// The pixel stores, paired over two MB columns (luma: pair_swap above; chroma: the lane's own
+				// two pieces).
 				// piece columns and the last column a role stores itself (the last MB's rows below its top
 				// strip go out with its own stores below)
 				// (general instantiation: a last column cut by the right edge goes byte by byte, so the
@@ -1197,38 +1190,33 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 				auto swp = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, false); };
 				uint32_t sgl = 0;  // bit per piece: an even last column, stored alone
 				const bool near_end = __ballot(act && cu + 2u >= C) != 0ull;  // (wave-uniform: most steps skip the test)
-				// (held = the previous step's piece: at an odd column that is the even column's; A stores
+				// (held = the previous step's piece: at an odd column that is the even column's; luma: A stores
 				// the even lane's row -- its kept piece, then the odd lane's current one --, B the odd lane's)
-				auto pair = [&](uint32_t o, uint32_t col, uint32_t lastc, uint32_t w, auto cur, auto& held, uint32_t& oA, auto& dA, uint32_t& oB,
-				                auto& dB, uint32_t bit) {
-					pair_swap(held, cur, dA, dB);
-					// (bit selects, not branches: the column parity differs between the lanes of a role)
-					const uint32_t oP = swp(o), odd = 0u - (col & 1u);
-					const uint32_t e = isE ? o - w : oP, f = isE ? oP - w : o;
-					oA = (e & odd) | (kNoStore & ~odd);
-					oB = (f & odd) | (kNoStore & ~odd);
+				// (bit selects, not branches: the column parity differs between the lanes of a role)
+				auto single = [&](uint32_t o, uint32_t col, uint32_t lastc, uint32_t odd, uint32_t bit) {
 					if (near_end) sgl |= (col == lastc ? ~odd & bit : 0u) & (o < kNoStore ? bit : 0u);
-					held = cur;
 				};
 				{  // role 0's luma row
 					const u32x4 cur = u32x4{ya0.x, ya0.y, yb0.x, yb0.y};
-					uint32_t oA, oB;
 					u32x4 dA, dB;
-					pair(oY0, cY0, lY0, 16u, cur, hY0, oA, dA, oB, dB, 1u);
-					qst128(rY, oA, dA);
-					qst128(rY, oB, dB);
+					pair_swap(hY0, cur, dA, dB);
+					const uint32_t oP = swp(oY0), odd = 0u - (cY0 & 1u);
+					const uint32_t e = isE ? oY0 - 16u : oP, f = isE ? oP - 16u : oY0;
+					single(oY0, cY0, lY0, odd, 1u);
+					hY0 = cur;
+					qst128(rY, (e & odd) | (kNoStore & ~odd), dA);
+					qst128(rY, (f & odd) | (kNoStore & ~odd), dB);
 				}
 				qst128(rY, oY1, u32x4{ya1.x, ya1.y, yb1.x, yb1.y});
-				{  // both roles' chroma rows
-					uint32_t oA, oB, oA1, oB1;
-					u32x2 dA, dB, dA1, dB1;
-					pair(oC0, cC0, lC0, 8u, cv0, hC0, oA, dA, oB, dB, 2u);
-					pair(oC1, cC1, lC1, 8u, cv1, hC1, oA1, dA1, oB1, dB1, 4u);
-					qst64(rC, oA, dA);
-					qst64(rC, oB, dB);
-					qst64(rC, oA1, dA1);
-					qst64(rC, oB1, dB1);
-				}
+				// both roles' chroma rows: the kept piece and the current one, from the lane that owns them
+				auto own = [&](uint32_t o, uint32_t col, uint32_t lastc, const u32x2& cur, u32x2& held, uint32_t bit) {
+					const uint32_t odd = 0u - (col & 1u);
+					single(o, col, lastc, odd, bit);
+					qst128(rC, ((o - 8u) & odd) | (kNoStore & ~odd), u32x4{held.x, held.y, cur.x, cur.y});
+					held = cur;
+				};
+				own(oC0, cC0, lC0, cv0, hC0, 2u);
+				own(oC1, cC1, lC1, cv1, hC1, 4u);
 				if (near_end && __ballot(sgl != 0u) != 0ull) {  // (a quarter at its last column: rare)
 					qst128(rY, (sgl & 1u) ? oY0 : kNoStore, u32x4{ya0.x, ya0.y, yb0.x, yb0.y});
 					qst64(rC, (sgl & 2u) ? oC0 : kNoStore, cv0);
