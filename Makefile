@@ -18,7 +18,8 @@ HOST_SRC := $(PKG)/host/webp_riff.c $(PKG)/host/vp8_parse.c $(PKG)/host/vp8_synt
 HOST_HDR := $(PKG)/host/vp8_front.h $(PKG)/host/vp8_bool.h $(PKG)/host/vp8_tables.inc include/vp8g.h
 HIP_SRC := $(PKG)/csrc/vp8g_kernels.hip $(PKG)/csrc/vp8g_plan.hip $(PKG)/csrc/vp8g_shim.hip $(PKG)/csrc/vp8g_rgb.hip $(PKG)/csrc/vp8g_pipeline.hip $(PKG)/csrc/vp8g_m05.hip \
 	$(PKG)/csrc/vp8g_digest.hip $(PKG)/csrc/vp8g_scale.hip $(PKG)/csrc/vp8g_tensor.hip $(PKG)/csrc/vp8g_alpha.hip \
-	$(PKG)/csrc/vp8g_lossless.hip $(PKG)/csrc/vp8g_scale_argb.hip $(PKG)/csrc/vp8g_anim.hip
+	$(PKG)/csrc/vp8g_lossless.hip $(PKG)/csrc/vp8g_scale_argb.hip $(PKG)/csrc/vp8g_scale_argb_fused.hip \
+	$(PKG)/csrc/vp8g_anim.hip
 HIP_HDR := $(PKG)/csrc/vp8g_device.h include/vp8g.h $(PKG)/host/vp8_front.h $(PKG)/csrc/vp8g_quad.inc $(PKG)/csrc/vp8g_rgb_device.h \
 	$(PKG)/csrc/vp8g_tensor_device.h
 # libvp8g links the host front end (the end-to-end batch path runs m05 on worker threads)

@@ -770,6 +770,59 @@ int vp8g_decode_webp_batch_tensor_any(const ByteSpan* files, uint32_t n, int fil
                                       const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, uint32_t xflags,
                                       void* d_out, int* status);
 
+/* ---- Crop + shrink of ARGB pictures straight into a tensor: the fused route ---- */
+
+/* What vp8g_scale_argb_batch_device followed by vp8g_tensor_batch_device_argb computes, in ONE launch and without a work
+ * buffer, for the pictures that expand in neither axis (win_w >= width and win_h >= height, equality included): each
+ * window pixel is read once, premultiplied into LDS, the four byte channels are rescaled together, and the result is
+ * un-premultiplied, converted (R, G, B: scale and bias; A: a / 255) and stored as elements of the picture's slot.
+ * Per-picture descriptor (built by vp8g_make_scale_argb_tensor_desc).  96 bytes. */
+typedef struct {
+	uint64_t src;                    /* byte offset (a multiple of 4) of the tight src_width x src_height 0xAARRGGBB picture */
+	uint64_t dst;                    /* byte offset (a multiple of the element size) of the picture's slot in the output */
+	uint32_t width, height;          /* output size: the slot is channels x width x height elements */
+	uint32_t src_width, src_height;  /* the picture the options were resolved against */
+	uint32_t crop_left, crop_top, win_w, win_h;  /* the resolved window, origin as given */
+	uint32_t fx, fy, fxy;            /* as Vp8gScalePlane */
+	uint32_t group;                  /* lanes sharing one output column (power of two, <= 64) */
+	uint32_t tile_w, run_h;          /* output columns (256 / group) and output rows per task */
+	uint32_t tiles_x;                /* tasks per row of tiles */
+	uint32_t pitch, block_rows;      /* LDS staging: bytes per source row segment (a multiple of 16), rows per block */
+	uint32_t task0, ntasks;          /* this picture's workgroup tasks in the launch */
+	uint32_t reserved;
+} Vp8gScaleArgbTensorDesc;
+
+/* The fused kernel's geometry, for tests that aim at its boundaries: out[0] = pixels per 16-byte load, out[1] = pixels of
+ * the longest row segment a task can stage (a picture whose tiles need more is not this kernel's), out[2] = source rows
+ * per run (about: a task takes max(1, out[2] * height / win_h) output rows). */
+void vp8g_scale_argb_fused_geometry(uint32_t out[3]);
+
+/* Fill the descriptor of one width x height ARGB picture at `src` of the source buffer, scaled by `opt` (resolved as
+ * vp8g_make_scale_argb_desc resolves it: the window's origin as given, VP8G_SCALE_DWEBP_FILTER ignored) into the slot at
+ * dst_offset of the output; its tasks start at task0.  0, or -1 + errno: EINVAL as vp8g_make_scale_argb_desc (NULL,
+ * options that do not fit the picture, src not a multiple of 4); ENOTSUP for valid options that are not the fused
+ * kernel's -- an axis that expands, a crop without a target size (a plain copy), a tile whose row segment is longer than
+ * vp8g_scale_argb_fused_geometry's out[1] (only where win_w exceeds 2046 x width) -- which is how a caller chooses between
+ * this route and the planar one. */
+int vp8g_make_scale_argb_tensor_desc(uint32_t width, uint32_t height, uint64_t src, const Vp8gScaleOpt* opt, uint64_t dst_offset,
+                                     uint32_t task0, Vp8gScaleArgbTensorDesc* out);
+
+/* Crop + shrink n device-resident ARGB pictures of mixed sizes, windows and targets into their slots of d_dst in one
+ * launch on `hip_stream`.  opt gives the element type, layout, channel order, scale and bias (its width and height are
+ * not read: every picture has its output size in its descriptor); channels = 3 (alpha dropped after the un-premultiply,
+ * as MODE_RGB drops it) or 4.  Every element is the one vp8g_tensor_batch_device_argb writes for the picture
+ * vp8g_scale_argb_batch_device makes.  h_descs / d_descs: host and device copies of the descriptors (d_descs 8-byte
+ * aligned).  Reads only the windows' pixels and writes only the pictures' own slots.  No workgroup waits on another,
+ * nothing spins on memory.  Asynchronous; 0 or -1 + errno.  The host copies are checked before anything is launched --
+ * EINVAL: NULL or misaligned pointer (d_src to 4 bytes, d_dst to the element size), n = 0, channels, an invalid option,
+ * a descriptor that is not byte for byte what vp8g_make_scale_argb_tensor_desc gives, tasks that do not number the
+ * pictures in order, a dst offset off the element size, slots that overlap; ENOMEM.  EIO on a launch failure.  d_src may
+ * be the uint8 / NHWC / BGR 4-channel tensor of vp8g_anim_compose_batch_device or the output of
+ * vp8g_lossless_batch_device, on the same stream with no host copy between. */
+int vp8g_scale_argb_tensor_batch_device(const Vp8gScaleArgbTensorDesc* h_descs, const Vp8gScaleArgbTensorDesc* d_descs, uint32_t n,
+                                        const Vp8gTensorOpt* opt, uint32_t channels, const uint8_t* d_src, void* d_dst,
+                                        void* hip_stream);
+
 /* ---- Animated files (ANIM / ANMF), composited on the device --------------- */
 
 /* An animation is a list of frames, each a rectangle of the canvas with a blend and a disposal rule; what is
@@ -846,7 +899,8 @@ int vp8g_anim_info(const ByteSpan* files, uint32_t n, uint32_t* canvas_w, uint32
  * frame order; d_out holds the sum of all nframes slots.  Every frame's payload is wrapped in memory as a file of its
  * own ('VP8 ' alone, VP8X + ALPH + 'VP8 ', or 'VP8L') and decoded by vp8g_decode_webp_batch_tensor_any (filtered, threads
  * and flags as there; VP8G_X_ALPHA | VP8G_X_LOSSLESS) into a uint8 / NHWC / BGR 4-channel staging tensor, one call per
- * distinct frame size; then one launch of vp8g_anim_compose_batch_device composes every file.  Frames are not scaled.
+ * distinct frame size; then one launch of vp8g_anim_compose_batch_device composes every file.  Nothing is scaled here
+ * (vp8g_decode_webp_anim_tensor_scaled below decodes to a target size).
  * timestamps (may be NULL; one per slot): the cumulative end time of each frame in ms, as WebPAnimDecoderGetNext
  * returns it.  status[i]: 0; EINVAL for a file that is no animation (no slots), whose canvas is not t->width x
  * t->height, or one of whose frames does not decode (its errno) -- all slots of such a file are zero bytes and the
@@ -854,6 +908,28 @@ int vp8g_anim_info(const ByteSpan* files, uint32_t n, uint32_t* canvas_w, uint32
  * EINVAL for bad arguments (nothing is launched); ENOMEM; EIO for a device failure (every status EIO). */
 int vp8g_decode_webp_anim_tensor(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
                                  const Vp8gTensorOpt* t, uint32_t channels, void* d_out, uint32_t* timestamps, int* status);
+
+/* vp8g_decode_webp_anim_tensor to a target size.  Scaled canvas k of a file is canvas k exactly as
+ * above (the frames are never scaled before compositing: blending does not commute with rescaling), cropped and rescaled
+ * as libwebp crops and rescales an RGBA picture that has alpha (vp8g_scale_argb_batch_device: the window's origin as
+ * given, premultiply, the plane rescaler per byte channel, un-premultiply; a crop without a target size copies pixels
+ * untouched; a target equal to the window is NOT the identity on translucent pixels; VP8G_SCALE_EXPAND for a larger
+ * target; VP8G_SCALE_DWEBP_FILTER ignored); with 3 channels alpha is dropped after the un-premultiply.
+ * opts: n_opts = 0 (the identity), 1 (one option for every file) or n; file i's option is resolved against its own canvas
+ * and must give t->width x t->height, so canvases of different sizes may share one tensor.  An option that does not fit the
+ * canvas, or whose result is not the tensor's size, is status[i] = EINVAL.  Slots, timestamps, the zero slots and errno of
+ * a failed file, and the return value are those of vp8g_decode_webp_anim_tensor.
+ * The frames decode as there.  A file whose option is the identity on a canvas of the tensor's size is composed straight
+ * into d_out.  The others are composed at full size into a device staging buffer (uint8 / NHWC / BGR / 4 channels: the
+ * ARGB dwords) and rescaled from there into d_out: by vp8g_scale_argb_tensor_batch_device, or -- the options its maker
+ * answers ENOTSUP for -- by vp8g_scale_argb_batch_device and vp8g_tensor_batch_device_argb.  The canvases are staged in
+ * groups of whole animations in file order: a group's canvas bytes (4 x canvas x frames per file) stay within stage_bytes
+ * (0 = 256 MiB), but a group always holds at least one animation -- ONE ANIMATION'S CANVASES ARE ALWAYS STAGED TOGETHER,
+ * whatever they take.  The grouping does not change a byte of the output.  A staging allocation that fails is ENOMEM
+ * (every status ENOMEM). */
+int vp8g_decode_webp_anim_tensor_scaled(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                        const Vp8gScaleOpt* opts, uint32_t n_opts, uint64_t stage_bytes, const Vp8gTensorOpt* t,
+                                        uint32_t channels, void* d_out, uint32_t* timestamps, int* status);
 
 /* Name of the last HIP error seen by this library in the calling thread ("" if none). */
 const char* vp8g_last_error(void);

@@ -1,7 +1,8 @@
 // vp8g_anim.hip -- the compositor of animated files: frames (tight 0xAARRGGBB pictures on the device) -> every
 // canvas of every animation, as elements of a dense tensor (include/vp8g.h: vp8g_anim_compose_batch_device and
-// the end-to-end vp8g_decode_webp_anim_tensor).  The rules are libwebp's WebPAnimDecoder, restated
-// sequentially in host/vp8_anim.c.
+// the end-to-end vp8g_decode_webp_anim_tensor and vp8g_decode_webp_anim_tensor_scaled, which composes at full size
+// into a staging buffer and rescales from there: vp8g_scale_argb_fused.hip).  The rules are
+// libwebp's WebPAnimDecoder, restated sequentially in host/vp8_anim.c.
 //
 // Frames depend on each other, pixels do not.  A thread owns kPx adjacent pixels of one canvas row and keeps their
 // canvas values in registers while it walks a segment -- the frames from one key frame (an empty canvas) up to the
@@ -296,8 +297,30 @@ int fail_all(int* status, uint32_t n, int e) {
 	return vp8g::fail(e);
 }
 
-int anim_tensor(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags, const Vp8gTensorOpt* t, uint32_t channels,
-                uint8_t* d_out, uint32_t* timestamps, int* status) {
+// How a file's canvases reach the tensor (vp8g_decode_webp_anim_tensor_scaled).
+enum Route {
+	kDirect,  // composed straight into the tensor: the identity on a canvas of the tensor's size
+	kFused,   // composed into the staging buffer, then vp8g_scale_argb_tensor_batch_device
+	kPlanar,  // ... then vp8g_scale_argb_batch_device and vp8g_tensor_batch_device_argb (what the fused maker answers ENOTSUP for)
+};
+
+constexpr uint64_t kStageDefault = 256ull << 20;  // canvas bytes per staging group when the caller gives 0
+
+// The route of a cw x ch canvas under `o` into t's size, or -1 (EINVAL): an option that does not fit the canvas or
+// whose result is not the tensor's size.
+int route_of(uint32_t cw, uint32_t ch, const Vp8gScaleOpt& o, const Vp8gTensorOpt& t) {
+	Vp8fScaleGeom g;
+	if (vp8f_scale_resolve_argb(cw, ch, &o, &g) != 0 || g.out_w != t.width || g.out_h != t.height) return -1;
+	if (!g.scaling && g.left == 0 && g.top == 0 && g.win_w == cw && g.win_h == ch) return kDirect;
+	Vp8gScaleArgbTensorDesc d;
+	if (vp8g_make_scale_argb_tensor_desc(cw, ch, 0, &o, 0, 0, &d) == 0) return kFused;
+	return errno == ENOTSUP ? kPlanar : -1;
+}
+
+// opts / n_opts / stage_bytes: vp8g_decode_webp_anim_tensor_scaled's; n_opts = 0 is vp8g_decode_webp_anim_tensor (every
+// file kDirect, no staging).
+int anim_tensor(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags, const Vp8gScaleOpt* opts, uint32_t n_opts,
+                uint64_t stage_bytes, const Vp8gTensorOpt* t, uint32_t channels, uint8_t* d_out, uint32_t* timestamps, int* status) {
 	const uint64_t slot = channels == 4u ? vp8g_tensor_slot_size_a(t) : vp8g_tensor_slot_size(t);
 	struct File {
 		WebPAnimInfo info;
@@ -305,6 +328,8 @@ int anim_tensor(const ByteSpan* files, uint32_t n, int filtered, uint32_t thread
 		uint32_t first = 0;       // its first slot
 		uint32_t ref0 = 0;        // its first frame in `refs` (files without an error)
 		int err = 0;
+		int route = kDirect;
+		Vp8gScaleOpt opt;         // (routes other than kDirect)
 	};
 	std::vector<File> fs(n);
 	uint32_t slots = 0;
@@ -317,7 +342,13 @@ int anim_tensor(const ByteSpan* files, uint32_t n, int filtered, uint32_t thread
 		}
 		f.fr.resize(f.info.nframes);
 		if (webp_parse_anim(files[i], &f.info, f.fr.data(), f.info.nframes) != 0) return fail_all(status, n, EINVAL);  // (cannot differ)
-		if (f.info.canvas_width != t->width || f.info.canvas_height != t->height) f.err = EINVAL;
+		if (n_opts) {
+			f.opt = opts[n_opts == 1u ? 0u : i];
+			f.route = route_of(f.info.canvas_width, f.info.canvas_height, f.opt, *t);
+			if (f.route < 0) f.err = EINVAL;
+		} else if (f.info.canvas_width != t->width || f.info.canvas_height != t->height) {
+			f.err = EINVAL;
+		}
 		uint32_t ts = 0;
 		for (uint32_t k = 0; timestamps && k < f.info.nframes; k++) timestamps[slots + k] = ts += f.fr[k].duration;
 		if ((uint64_t)slots + f.info.nframes > 0x7FFFFFFFu) return fail_all(status, n, EINVAL);
@@ -391,29 +422,140 @@ int anim_tensor(const ByteSpan* files, uint32_t n, int filtered, uint32_t thread
 			recs.push_back(r);
 		}
 	}
+	// the files composed straight into the tensor first, then the others in file order: descriptor q of the device array
+	// belongs to file by_route[q]
+	std::vector<uint32_t> by_route, rec_of(n, 0);
+	for (size_t j = 0; j < good.size(); j++) rec_of[good[j]] = rec0[j];
+	for (uint32_t i : good)
+		if (fs[i].route == kDirect) by_route.push_back(i);
+	const uint32_t ndirect = (uint32_t)by_route.size();
+	for (uint32_t i : good)
+		if (fs[i].route != kDirect) by_route.push_back(i);
 	std::vector<Vp8gAnimDesc> descs(good.size());
 	uint32_t task0 = 0;
-	for (size_t j = 0; j < good.size(); j++) {  // (recs no longer moves: the descriptors point into it)
-		const File& f = fs[good[j]];
-		if (vp8g_make_anim_desc(t->width, t->height, recs.data() + rec0[j], f.info.nframes, rec_off + rec0[j] * sizeof(Vp8gAnimFrame),
-		                        (uint64_t)f.first * slot, task0, &descs[j]) != 0)
+	for (uint32_t j = 0; j < ndirect; j++) {  // (recs no longer moves: the descriptors point into it)
+		const File& f = fs[by_route[j]];
+		if (vp8g_make_anim_desc(t->width, t->height, recs.data() + rec_of[by_route[j]], f.info.nframes,
+		                        rec_off + rec_of[by_route[j]] * sizeof(Vp8gAnimFrame), (uint64_t)f.first * slot, task0, &descs[j]) != 0)
 			return fail_all(status, n, EINVAL);
 		task0 += descs[j].ntasks;
 	}
+	// ---- the scaled files: full-size canvases composed into a staging buffer, group by group (whole animations, canvas bytes
+	// up to `cap`), then rescaled into the tensor.  Every descriptor is made before the records are uploaded:
+	// vp8g_make_anim_desc completes them.
+	struct Group {
+		uint32_t q0, q1;  // its files: by_route[q0 .. q1)
+		uint32_t nf, np;  // its canvases on the fused and on the planar route
+		uint64_t o_fd, o_pd, o_td, o_sc, o_work, bytes;  // offsets in the staging buffer; canvases from 0
+	};
+	const uint64_t cap = stage_bytes ? stage_bytes : kStageDefault;
+	auto canvas_bytes = [&](uint32_t i) { return 4ull * fs[i].info.canvas_width * fs[i].info.canvas_height; };
+	const uint64_t scaled_px = 4ull * t->width * t->height;  // one scaled ARGB picture of the planar route
+	std::vector<Group> groups;
+	for (uint32_t q = ndirect; q < by_route.size();) {
+		Group g = {q, q, 0, 0, 0, 0, 0, 0, 0, 0};
+		uint64_t cb = 0, off = 0, work = 0;
+		uint32_t a_task = 0;
+		while (g.q1 < by_route.size()) {  // whole animations, at least one
+			const File& f = fs[by_route[g.q1]];
+			const uint64_t b = canvas_bytes(by_route[g.q1]) * f.info.nframes;
+			if (g.q1 > g.q0 && cb + b > cap) break;
+			if (vp8g_make_anim_desc(f.info.canvas_width, f.info.canvas_height, recs.data() + rec_of[by_route[g.q1]], f.info.nframes,
+			                        rec_off + rec_of[by_route[g.q1]] * sizeof(Vp8gAnimFrame), off, a_task, &descs[g.q1]) != 0)
+				return fail_all(status, n, EINVAL);
+			a_task += descs[g.q1].ntasks;
+			cb += b, off = al256(off + b);
+			if (f.route == kFused) g.nf += f.info.nframes;
+			else g.np += f.info.nframes, work += f.info.nframes * vp8g_scale_argb_work_size(f.info.canvas_width, f.info.canvas_height, &f.opt);
+			g.q1++;
+		}
+		g.o_fd = off;
+		g.o_pd = al256(g.o_fd + g.nf * sizeof(Vp8gScaleArgbTensorDesc));
+		g.o_td = al256(g.o_pd + g.np * sizeof(Vp8gScaleArgbDesc));
+		g.o_sc = al256(g.o_td + g.np * sizeof(Vp8gTensorArgbDesc));
+		g.o_work = al256(g.o_sc + g.np * scaled_px);
+		g.bytes = g.o_work + (g.np ? vp8g_scale_argb_head_size(g.np) + work : 0u);
+		groups.push_back(g);
+		q = g.q1;
+	}
+	// a launch entry point failed: EINVAL / ENOMEM before it launched anything, or EIO
+	auto launch_failed = [&]() {
+		const int en = errno;
+		(void)hipStreamSynchronize(nullptr);  // (uploads from this call's vectors may be in flight)
+		return fail_all(status, n, en);
+	};
+	Vp8gAnimDesc* const d_descs = (Vp8gAnimDesc*)(buf.p + desc_off);
 	hipError_t e = hipSuccess;
 	const char* where = "anim";
 	for (uint32_t i = 0; e == hipSuccess && i < n; i++)
 		if (fs[i].err && !fs[i].fr.empty()) e = hipMemsetAsync(d_out + (uint64_t)fs[i].first * slot, 0, (uint64_t)fs[i].info.nframes * slot, nullptr), where = "memset";
-	if (e == hipSuccess && !descs.empty()) {
+	if (e == hipSuccess && !descs.empty())
 		e = hipMemcpyAsync(buf.p + rec_off, recs.data(), recs.size() * sizeof(Vp8gAnimFrame), hipMemcpyHostToDevice, nullptr), where = "upload";
-		if (e == hipSuccess)
-			e = hipMemcpyAsync(buf.p + desc_off, descs.data(), descs.size() * sizeof(Vp8gAnimDesc), hipMemcpyHostToDevice, nullptr);
-		if (e == hipSuccess && vp8g_anim_compose_batch_device(descs.data(), (const Vp8gAnimDesc*)(buf.p + desc_off), (uint32_t)descs.size(), t, channels,
-		                                                      buf.p, d_out, nullptr) != 0) {
-			if (errno != EIO) return fail_all(status, n, errno);
+	if (e == hipSuccess && ndirect) {
+		e = hipMemcpyAsync(d_descs, descs.data(), ndirect * sizeof(Vp8gAnimDesc), hipMemcpyHostToDevice, nullptr), where = "upload";
+		if (e == hipSuccess && vp8g_anim_compose_batch_device(descs.data(), d_descs, ndirect, t, channels, buf.p, d_out, nullptr) != 0) return launch_failed();
+	}
+
+	DevBuf stg;
+	if (e == hipSuccess && !groups.empty()) {
+		uint64_t most = 0;
+		for (const Group& g : groups) most = std::max(most, g.bytes);
+		if (hipError_t em = hipMalloc((void**)&stg.p, most); em != hipSuccess) {
+			(void)hipGetLastError();
 			(void)hipStreamSynchronize(nullptr);
-			return fail_all(status, n, EIO);
+			return fail_all(status, n, em == hipErrorOutOfMemory ? ENOMEM : EIO);
 		}
+	}
+	Vp8gTensorOpt st;  // the staging canvases: B, G, R, A bytes, the 0xAARRGGBB dword (width and height are not read)
+	memset(&st, 0, sizeof(st));
+	st.width = st.height = 1, st.dtype = VP8G_T_U8, st.layout = VP8G_T_NHWC, st.flags = VP8G_T_BGR;
+	for (size_t gi = 0; e == hipSuccess && gi < groups.size(); gi++) {
+		const Group& g = groups[gi];
+		std::vector<Vp8gScaleArgbTensorDesc> fd(g.nf);
+		std::vector<Vp8gScaleArgbDesc> pd(g.np);
+		std::vector<Vp8gTensorArgbDesc> td(g.np);
+		uint64_t work = g.np ? vp8g_scale_argb_head_size(g.np) : 0u;
+		uint32_t f_task = 0, nf = 0, np = 0, planes = 0, t_split = 0, t_scale = 0, t_merge = 0, t_tensor = 0;
+		for (uint32_t q = g.q0; q < g.q1; q++) {
+			const uint32_t i = by_route[q];
+			const File& f = fs[i];
+			const uint32_t cw = f.info.canvas_width, ch = f.info.canvas_height;
+			const uint64_t off = descs[q].dst;  // its canvases in the staging buffer
+			for (uint32_t k = 0; k < f.info.nframes; k++) {
+				const uint64_t src = off + k * canvas_bytes(i), dst = (uint64_t)(f.first + k) * slot;
+				if (f.route == kFused) {
+					if (vp8g_make_scale_argb_tensor_desc(cw, ch, src, &f.opt, dst, f_task, &fd[nf]) != 0) return fail_all(status, n, EINVAL);
+					f_task += fd[nf++].ntasks;
+					continue;
+				}
+				Vp8gScaleArgbDesc& p = pd[np];
+				if (vp8g_make_scale_argb_desc(cw, ch, src, &f.opt, work, np * scaled_px, planes, t_split, t_scale, t_merge, &p) != 0 ||
+				    vp8g_make_tensor_argb_desc(t, channels, np * scaled_px, dst, t_tensor, &td[np]) != 0)
+					return fail_all(status, n, EINVAL);
+				planes += p.nplanes, t_split += p.split_ntasks, t_scale += p.scale_ntasks, t_merge += p.merge_ntasks, t_tensor += td[np].ntasks;
+				work += p.work_bytes, np++;
+			}
+		}
+		const uint32_t cnt = g.q1 - g.q0;
+		e = hipMemcpyAsync(d_descs + g.q0, descs.data() + g.q0, cnt * sizeof(Vp8gAnimDesc), hipMemcpyHostToDevice, nullptr), where = "upload";
+		if (e == hipSuccess && vp8g_anim_compose_batch_device(descs.data() + g.q0, d_descs + g.q0, cnt, &st, 4, buf.p, stg.p, nullptr) != 0) return launch_failed();
+		if (e == hipSuccess && g.nf) {
+			e = hipMemcpyAsync(stg.p + g.o_fd, fd.data(), g.nf * sizeof(fd[0]), hipMemcpyHostToDevice, nullptr);
+			if (e == hipSuccess && vp8g_scale_argb_tensor_batch_device(fd.data(), (const Vp8gScaleArgbTensorDesc*)(stg.p + g.o_fd), g.nf, t, channels, stg.p,
+			                                                           d_out, nullptr) != 0)
+				return launch_failed();
+		}
+		if (e == hipSuccess && g.np) {
+			e = hipMemcpyAsync(stg.p + g.o_pd, pd.data(), g.np * sizeof(pd[0]), hipMemcpyHostToDevice, nullptr);
+			if (e == hipSuccess) e = hipMemcpyAsync(stg.p + g.o_td, td.data(), g.np * sizeof(td[0]), hipMemcpyHostToDevice, nullptr);
+			if (e == hipSuccess && (vp8g_scale_argb_batch_device(pd.data(), (const Vp8gScaleArgbDesc*)(stg.p + g.o_pd), g.np, stg.p, stg.p + g.o_work,
+			                                                     stg.p + g.o_sc, nullptr) != 0 ||
+			                        vp8g_tensor_batch_device_argb(td.data(), (const Vp8gTensorArgbDesc*)(stg.p + g.o_td), g.np, t, channels, stg.p + g.o_sc,
+			                                                      d_out, nullptr) != 0))
+				return launch_failed();
+		}
+		// (the next group reuses the staging buffer and this group's host descriptors end here)
+		if (e == hipSuccess) e = hipStreamSynchronize(nullptr), where = "sync";
 	}
 	if (e == hipSuccess) e = hipStreamSynchronize(nullptr), where = "sync";
 	if (e != hipSuccess) {
@@ -447,14 +589,21 @@ VP8G_API int vp8g_anim_info(const ByteSpan* files, uint32_t n, uint32_t* canvas_
 	return first ? vp8g::fail(first) : 0;
 }
 
-VP8G_API int vp8g_decode_webp_anim_tensor(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
-                                          const Vp8gTensorOpt* t, uint32_t channels, void* d_out, uint32_t* timestamps, int* status) {
+VP8G_API int vp8g_decode_webp_anim_tensor_scaled(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                                 const Vp8gScaleOpt* opts, uint32_t n_opts, uint64_t stage_bytes, const Vp8gTensorOpt* t,
+                                                 uint32_t channels, void* d_out, uint32_t* timestamps, int* status) {
 	if (!files || n == 0 || !d_out || (channels != 3 && channels != 4) || !vp8g_tensor_slot_size(t) ||
-	    (uintptr_t)d_out % (uint32_t)elem_bytes(t->dtype) || (flags & ~(VP8G_BATCH_DEVICE_M05 | VP8G_BATCH_MULTI_PARTITION)))
+	    (uintptr_t)d_out % (uint32_t)elem_bytes(t->dtype) || (flags & ~(VP8G_BATCH_DEVICE_M05 | VP8G_BATCH_MULTI_PARTITION)) ||
+	    (n_opts != 0 && n_opts != 1 && n_opts != n) || (n_opts && !opts))
 		return vp8g::fail(EINVAL);
 	try {
-		return anim_tensor(files, n, filtered, threads, flags, t, channels, (uint8_t*)d_out, timestamps, status);
+		return anim_tensor(files, n, filtered, threads, flags, opts, n_opts, stage_bytes, t, channels, (uint8_t*)d_out, timestamps, status);
 	} catch (const std::bad_alloc&) {
 		return fail_all(status, n, ENOMEM);
 	}
+}
+
+VP8G_API int vp8g_decode_webp_anim_tensor(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                          const Vp8gTensorOpt* t, uint32_t channels, void* d_out, uint32_t* timestamps, int* status) {
+	return vp8g_decode_webp_anim_tensor_scaled(files, n, filtered, threads, flags, nullptr, 0, 0, t, channels, d_out, timestamps, status);
 }

@@ -238,6 +238,13 @@ class Vp8gScaleArgbDesc(C.Structure):
         ("reserved", C.c_uint32 * 2), ("plane", Vp8gScaleDesc * 4)]
 
 
+class Vp8gScaleArgbTensorDesc(C.Structure):
+    """include/vp8g.h: per-picture descriptor of the fused ARGB crop / shrink into a tensor (vp8g_make_scale_argb_tensor_desc)."""
+    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64)] + [(n, C.c_uint32) for n in (
+        "width", "height", "src_width", "src_height", "crop_left", "crop_top", "win_w", "win_h", "fx", "fy", "fxy", "group", "tile_w",
+        "run_h", "tiles_x", "pitch", "block_rows", "task0", "ntasks", "reserved")]
+
+
 class WebPAnimInfo(C.Structure):
     """host/vp8_front.h: what webp_parse_anim found in an animated file as a whole."""
     _fields_ = [(n, C.c_uint32) for n in ("canvas_width", "canvas_height", "bgcolor", "loop_count", "nframes", "vp8x_flags")]
@@ -311,7 +318,7 @@ assert C.sizeof(Vp8gScalePlane) == 80
 assert C.sizeof(Vp8gScaleDesc) == 272
 assert C.sizeof(Vp8gTensorOpt) == 44
 assert C.sizeof(Vp8gTensorDesc) == 48
-assert C.sizeof(Vp8gScaleArgbDesc) == 1200
+assert C.sizeof(Vp8gScaleArgbDesc) == 1200 and C.sizeof(Vp8gScaleArgbTensorDesc) == 96
 assert C.sizeof(WebPAnimFrame) == 80 and C.sizeof(Vp8gAnimFrame) == 40 and C.sizeof(Vp8gAnimDesc) == 48
 
 VP8G_F_LOOPFILTER = 1
@@ -550,6 +557,16 @@ def gpu_lib():
             lib.vp8g_anim_info.argtypes = [P(ByteSpan), C.c_uint32, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), P(C.c_int)]
             lib.vp8g_decode_webp_anim_tensor.argtypes = [P(ByteSpan), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, P(Vp8gTensorOpt),
                                                          C.c_uint32, C.c_void_p, P(C.c_uint32), P(C.c_int)]
+        if hasattr(lib, "vp8g_scale_argb_tensor_batch_device"):  # (libraries built before the scaled animation path)
+            lib.vp8g_scale_argb_fused_geometry.argtypes = [P(C.c_uint32)]
+            lib.vp8g_scale_argb_fused_geometry.restype = None
+            lib.vp8g_make_scale_argb_tensor_desc.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, P(Vp8gScaleOpt), C.c_uint64, C.c_uint32,
+                                                             P(Vp8gScaleArgbTensorDesc)]
+            lib.vp8g_scale_argb_tensor_batch_device.argtypes = [P(Vp8gScaleArgbTensorDesc), C.c_void_p, C.c_uint32, P(Vp8gTensorOpt), C.c_uint32,
+                                                                C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.vp8g_decode_webp_anim_tensor_scaled.argtypes = [P(ByteSpan), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, P(Vp8gScaleOpt),
+                                                                C.c_uint32, C.c_uint64, P(Vp8gTensorOpt), C.c_uint32, C.c_void_p,
+                                                                P(C.c_uint32), P(C.c_int)]
         lib._typed = True
     return lib
 
@@ -1423,6 +1440,78 @@ def gpu_tensor_argb(argb_list, opt: Vp8gTensorOpt, channels: int = 4, slot_shift
     return out
 
 
+def scale_argb_fused_geometry():
+    """vp8g_scale_argb_fused_geometry: (pixels per 16-byte load, pixels of the longest row segment a task stages, source
+    rows per run) of the fused kernel as the library was built.  The boundary sizes of the tests come from it."""
+    g = (C.c_uint32 * 3)()
+    gpu_lib().vp8g_scale_argb_fused_geometry(g)
+    return int(g[0]), int(g[1]), int(g[2])
+
+
+def make_scale_argb_tensor_desc(w: int, h: int, opt: Vp8gScaleOpt, src: int = 0, dst: int = 0, task0: int = 0) -> Vp8gScaleArgbTensorDesc:
+    """vp8g_make_scale_argb_tensor_desc for a w x h picture; OSError with its errno (EINVAL, or ENOTSUP for valid options
+    that are not the fused kernel's) if refused."""
+    d = Vp8gScaleArgbTensorDesc()
+    if gpu_lib().vp8g_make_scale_argb_tensor_desc(w, h, src, C.byref(opt), dst, task0, C.byref(d)) != 0:
+        raise OSError(C.get_errno(), "vp8g_make_scale_argb_tensor_desc")
+    return d
+
+
+def gpu_scale_argb_tensor(argb_list, opts, topt: Vp8gTensorOpt, channels: int = 4, src_shift: int = 1, guard: int = 64, fill: int = 0xEE,
+                          mutate=None, ptr_shift=(0, 0, 0)):
+    """vp8g_make_scale_argb_tensor_desc + vp8g_scale_argb_tensor_batch_device over uint32 [h, w] 0xAARRGGBB pictures of mixed
+    sizes (opts: one Vp8gScaleOpt per picture) in one launch: the list of torch CPU tensors [C, h', w'] or [h', w', C] of
+    topt's dtype (topt's width and height are not read).  src_shift: every source picture starts this many DWORDS off a
+    16-byte boundary; guard (a multiple of 8): bytes kept in front of, between and behind the slots, which the call checks
+    still hold `fill`.  mutate(descs): called on the host descriptors after the device copies are made; ptr_shift: bytes
+    added to the source, output and descriptor pointers handed to the call (both for tests of the entry point's checks: a
+    refusal raises ValueError, once the output is seen untouched)."""
+    import torch
+    lib = gpu_lib()
+    dev = torch.device("cuda", 0)
+    n, eb = len(argb_list), T_ELEM[topt.dtype]
+    descs = (Vp8gScaleArgbTensorDesc * n)()
+    parts, so, do, task0 = [], 0, guard, 0
+    for i, (a, opt) in enumerate(zip(argb_list, opts)):
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        h, w = a.shape
+        pad = (-so) % 16 + 4 * src_shift
+        parts += [np.full(pad, 0x5A, np.uint8), a.reshape(-1).view(np.uint8)]
+        if lib.vp8g_make_scale_argb_tensor_desc(w, h, so + pad, C.byref(opt), do, task0, C.byref(descs[i])) != 0:
+            raise OSError(C.get_errno(), "vp8g_make_scale_argb_tensor_desc")
+        so += pad + a.size * 4
+        task0 += descs[i].ntasks
+        do += (channels * descs[i].width * descs[i].height * eb + 7) // 8 * 8 + guard
+    parts.append(np.full(16, 0x5A, np.uint8))
+    src = torch.from_numpy(np.concatenate(parts)).to(dev)
+    dst = torch.full((do,), fill, dtype=torch.uint8, device=dev)
+    d_descs = torch.frombuffer(bytearray(bytes(descs)) + bytearray(8), dtype=torch.uint8).to(dev)
+    if mutate:  # (after the device copies are made: the kernel never sees what a test breaks in the host copies)
+        mutate(descs)
+    stream = torch.cuda.current_stream(dev)
+    if lib.vp8g_scale_argb_tensor_batch_device(descs, C.c_void_p(d_descs.data_ptr() + ptr_shift[2]), n, C.byref(topt), channels,
+                                               C.c_void_p(src.data_ptr() + ptr_shift[0]), C.c_void_p(dst.data_ptr() + ptr_shift[1]),
+                                               C.c_void_p(stream.cuda_stream)) != 0:
+        en = C.get_errno()
+        if en == 22:
+            torch.cuda.synchronize(dev)
+            if not bool((dst == fill).all()):
+                raise AssertionError("gpu_scale_argb_tensor: a refused call wrote to the output")
+            raise ValueError("vp8g_scale_argb_tensor_batch_device: EINVAL")
+        raise RuntimeError(f"vp8g_scale_argb_tensor_batch_device failed: errno={en} {lib.vp8g_last_error()!r}")
+    stream.synchronize()
+    host = dst.cpu()
+    out, keep = [], np.ones(do, bool)
+    for d in descs:
+        nb = channels * d.width * d.height * eb
+        shape = (channels, d.height, d.width) if topt.layout == T_LAYOUTS["NCHW"] else (d.height, d.width, channels)
+        out.append(host[d.dst:d.dst + nb].clone().view(_torch_dtype(topt)).view(shape))
+        keep[d.dst:d.dst + nb] = False
+    if not (host.numpy()[keep] == fill).all():
+        raise AssertionError("gpu_scale_argb_tensor: bytes outside the slots were written")
+    return out
+
+
 # ---- animated files (DESIGN.md §18) ---------------------------------------------------------
 
 
@@ -1519,6 +1608,15 @@ def host_anim_compose(canvas_w: int, canvas_h: int, frames):
     return out, [int(f.key) for f in fr]
 
 
+def host_anim_scaled(data: bytes, opt: Vp8gScaleOpt):
+    """Every scaled canvas of an animated file on the host: host_anim_compose, then host_scale_argb of
+    each canvas with `opt` resolved against the canvas.  (uint32 [F, h', w'], timestamps); OSError with EINVAL if the
+    option does not fit the canvas."""
+    (cw, ch), frames, ts = host_anim_frames(data)
+    canvases, _ = host_anim_compose(cw, ch, frames)
+    return np.stack([host_scale_argb(c, opt) for c in canvases]), ts
+
+
 def anim_geometry():
     """vp8g_anim_geometry: (pixels per thread, pixels per task, frames per task or 0 for no limit) of the compositor
     kernel as the library was built.  The boundary sizes of the tests come from it."""
@@ -1613,12 +1711,15 @@ def anim_info(files: list[bytes]):
 
 
 def gpu_decode_webp_anim_tensor(files: list[bytes], opt: Vp8gTensorOpt, alpha: bool = True, filtered: bool = True, threads: int = 0,
-                                device_m05: bool = False, multi_partition: bool = False, prefill=None):
+                                device_m05: bool = False, multi_partition: bool = False, prefill=None, scale=None, stage_bytes: int = 0):
     """vp8g_decode_webp_anim_tensor: animated .webp files decoded and composited on the device into one dense tensor
     of canvases, [sum of frames, C, H, W] or [.., H, W, C] with C = 4 (alpha) or 3.  Returns (the torch.Tensor on the
     device, each file's first slot, the timestamps (cumulative end time in ms of every slot), list of errno); the
     slots of a failed file are zero, and a file that is no animation has none.  torch only allocates the tensor
-    (prefill: a value it is filled with before the call, for tests of the zero slots)."""
+    (prefill: a value it is filled with before the call, for tests of the zero slots).
+    scale: None (vp8g_decode_webp_anim_tensor: every canvas must have the tensor's size), or one Vp8gScaleOpt, or a list of
+    one per file -- vp8g_decode_webp_anim_tensor_scaled: each file's canvases cropped and rescaled to the tensor's size as
+    host_anim_scaled does; stage_bytes caps the canvas bytes of one staging group (0: the library's default)."""
     import time
     import torch
     lib = gpu_lib()
@@ -1637,12 +1738,18 @@ def gpu_decode_webp_anim_tensor(files: list[bytes], opt: Vp8gTensorOpt, alpha: b
     ts = (C.c_uint32 * max(total, 1))()
     st = (C.c_int * n)()
     t0 = time.perf_counter()
-    rc = lib.vp8g_decode_webp_anim_tensor(spans, n, int(filtered), threads,
-                                          (VP8G_BATCH_DEVICE_M05 if device_m05 else 0) | (VP8G_BATCH_MULTI_PARTITION if multi_partition else 0),
-                                          C.byref(opt), channels, C.c_void_p(out.data_ptr()), ts, st)
+    bflags = (VP8G_BATCH_DEVICE_M05 if device_m05 else 0) | (VP8G_BATCH_MULTI_PARTITION if multi_partition else 0)
+    if scale is None:
+        rc = lib.vp8g_decode_webp_anim_tensor(spans, n, int(filtered), threads, bflags, C.byref(opt), channels, C.c_void_p(out.data_ptr()),
+                                              ts, st)
+    else:
+        sl = list(scale) if isinstance(scale, (list, tuple)) else [scale]
+        opts = (Vp8gScaleOpt * len(sl))(*sl)
+        rc = lib.vp8g_decode_webp_anim_tensor_scaled(spans, n, int(filtered), threads, bflags, opts, len(sl), stage_bytes, C.byref(opt),
+                                                     channels, C.c_void_p(out.data_ptr()), ts, st)
     gpu_decode_webp_anim_tensor.seconds = time.perf_counter() - t0  # the C call alone
     en = C.get_errno()
-    if rc != 0 and (all(s == 5 for s in st) or not any(st)):  # EIO: device failure; or the call itself refused
+    if rc != 0 and (all(s == st[0] for s in st) and st[0] in (5, 12) or not any(st)):  # EIO / ENOMEM: every file; or the call itself refused
         raise RuntimeError(f"vp8g_decode_webp_anim_tensor failed: errno={en} {lib.vp8g_last_error()!r}")
     return out[:total], first, list(ts)[:total], list(st)
 
