@@ -21,7 +21,7 @@ HIP_SRC := $(PKG)/csrc/vp8g_kernels.hip $(PKG)/csrc/vp8g_plan.hip $(PKG)/csrc/vp
 	$(PKG)/csrc/vp8g_lossless.hip $(PKG)/csrc/vp8g_scale_argb.hip $(PKG)/csrc/vp8g_scale_argb_fused.hip \
 	$(PKG)/csrc/vp8g_anim.hip
 HIP_HDR := $(PKG)/csrc/vp8g_device.h include/vp8g.h $(PKG)/host/vp8_front.h $(PKG)/csrc/vp8g_quad.inc $(PKG)/csrc/vp8g_rgb_device.h \
-	$(PKG)/csrc/vp8g_tensor_device.h
+	$(PKG)/csrc/vp8g_tensor_device.h $(PKG)/csrc/vp8g_skew.h
 # libvp8g links the host front end (the end-to-end batch path runs m05 on worker threads)
 HIP_LINK := -L$(LIB) -lvp8host -Wl,-rpath,'$$ORIGIN' -lpthread
 
@@ -29,7 +29,7 @@ CFLAGS := -std=c11 -O3 -march=x86-64-v3 -Wall -Wextra -Wpedantic -fPIC -D_POSIX_
 HIPFLAGS := -std=c++17 -O3 --offload-arch=$(OFFLOAD_ARCH) -fPIC -Wall -Wno-unused-function \
 	-fvisibility=hidden -I include -munsafe-fp-atomics
 
-all: lib oracle $(LIB)/diag/libvp8g_stall.so
+all: lib oracle $(LIB)/diag/libvp8g_stall.so $(LIB)/diag/libvp8g_skew.so
 
 # (oracle/ re-links the reference CLI against libvp8g.so: build the library first)
 oracle: lib
@@ -55,7 +55,7 @@ oracle:
 # per-phase shader-clock stamps, and phase ablations (timing only, wrong output).
 DIAG := $(LIB)/diag
 DIAG_VARIANTS := stamps abl1 abl2 abl4 abl8 abl15 abl16 abl32 abl47
-diag: $(foreach v,$(DIAG_VARIANTS),$(DIAG)/libvp8g_$(v).so) $(DIAG)/libvp8g_stall.so
+diag: $(foreach v,$(DIAG_VARIANTS),$(DIAG)/libvp8g_$(v).so) $(DIAG)/libvp8g_stall.so $(DIAG)/libvp8g_skew.so
 $(DIAG):
 	mkdir -p $@
 $(DIAG)/libvp8g_stamps.so: $(HIP_SRC) $(HIP_HDR) | $(DIAG)
@@ -64,6 +64,11 @@ $(DIAG)/libvp8g_stamps.so: $(HIP_SRC) $(HIP_HDR) | $(DIAG)
 # (tests/test_gpu_batch.py: a stalled producer must end the launch promptly with EIO)
 $(DIAG)/libvp8g_stall.so: $(HIP_SRC) $(HIP_HDR) | $(DIAG)
 	$(HIPCC) $(HIPFLAGS) -DVP8G_WAIT_TICKS=2000000ull -DVP8G_TEST_STALL_WAVE=1 -shared -Wl,-Bsymbolic -o $@ $(HIP_SRC) -L$(LIB) -lvp8host -Wl,-rpath,'$$ORIGIN/..' -lpthread
+# test build: a delay after a quarter of the progress / flag publishes, the hand-off buffers poisoned
+# before every launch, a census of the wait sites, one wait's threshold lowered on request
+# (csrc/vp8g_skew.h, tests/test_gpu_skew.py: the hand-offs under a skewed schedule)
+$(DIAG)/libvp8g_skew.so: $(HIP_SRC) $(HIP_HDR) $(LIB)/libvp8host.so | $(DIAG)
+	$(HIPCC) $(HIPFLAGS) -DVP8G_TEST_SKEW -shared -Wl,-Bsymbolic -o $@ $(HIP_SRC) -L$(LIB) -lvp8host -Wl,-rpath,'$$ORIGIN/..' -lpthread
 $(DIAG)/libvp8g_abl%.so: $(HIP_SRC) $(HIP_HDR) | $(DIAG)
 	$(HIPCC) $(HIPFLAGS) -DVP8G_ABLATE=$* -shared -Wl,-Bsymbolic -o $@ $(HIP_SRC) -L$(LIB) -lvp8host -Wl,-rpath,'$$ORIGIN/..' -lpthread
 

@@ -35,6 +35,35 @@ def directed_frames(sizes, seed=11):
             for k, kind in enumerate(directed.KINDS) for r in range(4)]
 
 
+def compare(b, frames, pick, empty, exp):
+    """Every slot of the batch `b` after a launch against the oracle: slot i holds frames[pick[i]],
+    filtered when that index is odd; the slots of `empty` must still hold the 0xA5 fill.  `exp` caches
+    the oracle's output per (frame, filtered).  -> [] or ["first: <the first differing slot: its frame,
+    plane and byte>", differing slots ..., "empty slot i written" ...]"""
+    host, bad = b.out.cpu().numpy(), []
+    first = None
+    for i in range(len(pick)):
+        if i in empty:
+            continue
+        j = int(pick[i])
+        key = (j, bool(j % 2))
+        if key not in exp:
+            exp[key] = np.frombuffer(vp8g.oracle_reconstruct(frames[j], key[1]), np.uint8)
+        got = host[i * b.frame_bytes:i * b.frame_bytes + exp[key].size]
+        if not np.array_equal(got, exp[key]):
+            if first is None:
+                f, k = frames[j], int(np.flatnonzero(got != exp[key])[0])
+                ysz, csz = f.width * f.height, ((f.width + 1) // 2) * ((f.height + 1) // 2)
+                plane, o = ("Y", k) if k < ysz else (("U", k - ysz) if k < ysz + csz else ("V", k - ysz - csz))
+                first = (f"first: slot {i} frame {j} {f.width}x{f.height} filtered={key[1]} plane {plane} byte {o} "
+                         f"got {got[k]} expected {exp[key][k]}")
+            bad.append(i)
+    for i in sorted(empty):
+        if not (host[i * b.frame_bytes:i * b.frame_bytes + b.i420] == 0xA5).all():
+            bad.append(f"empty slot {i} written")
+    return ([first] if first else []) + bad
+
+
 def run(n=1800, seed=0x0A4D, launches=1, want_split=False, sizes=SIZES, frames=None, want_mode=vp8g.MODE_CHAIN | vp8g.MODE_QUAD):
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(seed)
@@ -65,31 +94,49 @@ def run(n=1800, seed=0x0A4D, launches=1, want_split=False, sizes=SIZES, frames=N
             return ["launch mode unknown: the loaded library has no vp8g_last_launch_mode"]
         if (mode if want_mode == 0 else mode & (vp8g.MODE_CHAIN | vp8g.MODE_QUAD)) != want_mode or (want_split and not mode & vp8g.MODE_MIRROR_SPLIT):
             return [f"launch mode {mode}: expected {want_mode}{' with the mirror split' if want_split else ''}"]
-    exp, bad = {}, []
-    for i in range(n):
-        if i in empty:
-            continue
-        j = int(pick[i])
-        key = (j, bool(j % 2))
-        if key not in exp:
-            exp[key] = vp8g.oracle_reconstruct(frames[j], bool(j % 2))
-        got = b.frame_output(i)[:len(exp[key])]
-        if got != exp[key]:
-            if not bad:  # the first differing slot: its frame, plane and byte
-                f, k = frames[j], int(np.flatnonzero(np.frombuffer(got, np.uint8) != np.frombuffer(exp[key], np.uint8))[0])
-                ysz, csz = f.width * f.height, ((f.width + 1) // 2) * ((f.height + 1) // 2)
-                plane, o = ("Y", k) if k < ysz else (("U", k - ysz) if k < ysz + csz else ("V", k - ysz - csz))
-                first = (f"first: slot {i} frame {j} {f.width}x{f.height} filtered={key[1]} plane {plane} byte {o} "
-                         f"got {got[k]} expected {exp[key][k]}")
-            bad.append(i)
-    for i in sorted(empty)[:16]:
-        if b.frame_output(i) != b"\xa5" * b.i420:
-            bad.append(f"empty slot {i} written")
+    bad = compare(b, frames, pick, empty, {})
     for f in frames:
         f.free()
-    if bad and isinstance(bad[0], int):
-        bad.insert(0, first)
     return bad
+
+
+def run_each(n, seed, launches, sizes, slot, want_mode, empties=True, before_launch=None):
+    """A batch of `n` slots of `slot` = (width, height) decoded `launches` times, with OTHER frames in the
+    same slots every time (launch k: slot i <- frame (pick[i] + k) mod 40 of 40 synthetic frames over
+    `sizes`, filtered when that index is odd -- so a slot's frame, size and filter setting change between
+    launches and whatever an earlier launch left in a hand-off buffer is the wrong context).  The output is
+    refilled with 0xA5 before and compared with the oracle after every launch; `want_mode`: the exact
+    launch-mode word.  before_launch(k) is called ahead of launch k.  -> per launch, run()'s list."""
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(seed)
+    frames = [vp8g.synth_frame(*sizes[i % len(sizes)], seed ^ (i * 0x9E37), profile=i % 3) for i in range(40)]
+    b = vp8g_batch.DeviceBatch(n, *slot, dev)
+    pick = rng.integers(0, len(frames), n)
+    empty = set(rng.choice(n, n // 8, replace=False).tolist()) if empties else set()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    exp, out = {}, []
+    for k in range(launches):
+        pk = (pick + k) % len(frames)
+        for i in range(n):
+            if i not in empty:
+                b.place(i, frames[pk[i]], bool(pk[i] % 2))
+        b.commit()
+        b.out.fill_(0xA5)
+        b.status.zero_()
+        if before_launch:
+            before_launch(k)
+        b.launch(stream)
+        torch.cuda.synchronize()
+        if b.status_word() != 0:
+            out.append([f"status {b.status_word()}"])
+            continue
+        if b.launch_mode() != want_mode:
+            out.append([f"launch mode {b.launch_mode()}: expected {want_mode}"])
+            continue
+        out.append(compare(b, frames, pk, empty, exp))
+    for f in frames:
+        f.free()
+    return out
 
 
 if __name__ == "__main__":

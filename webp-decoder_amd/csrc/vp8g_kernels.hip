@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "vp8g_device.h"
+#include "vp8g_skew.h"
 
 #define DEV __device__ __forceinline__
 
@@ -1097,10 +1098,19 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void frame_kerne
 			PRIO(1);
 			if (has_pred && !dead && !(VP8G_ABLATE & 8)) {
 				// (one column more lag across parts: the mailbox is read a step ahead of use)
-				const uint32_t lag = xin ? 5u : 4u;
+				// (skew build, early_site = kSkFPart / kSkFWg: one column less.  Memory-safe: what follows reads
+				// the context entries of columns t .. t + 2 -- addresses from t and the lane alone -- from the
+				// mailbox or the workgroup's context; the bytes are pixels for prediction and filter arithmetic)
+				const uint32_t lag = xin ? 5u - VP8G_SKEW_EARLY(kSkFPart) : 4u - VP8G_SKEW_EARLY(kSkFWg);
 				const uint32_t ahead = (t + lag < CP2) ? t + lag : CP2;
-				if (xin) wait_prog(0u, (k - 1) * CP2 + ahead, true);
-				else wait_prog((uint32_t)((wave + NW - 1) % NW), ((g - 1u) << kProgShift) + ahead, false);
+				if (xin) {
+					VP8G_SKEW_CENSUS(kSkFPart, __hip_atomic_load(gp_in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (k - 1) * CP2 + ahead);
+					wait_prog(0u, (k - 1) * CP2 + ahead, true);
+				} else {
+					VP8G_SKEW_CENSUS(kSkFWg, __hip_atomic_load(prog + (wave + NW - 1) % NW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >=
+					                             ((g - 1u) << kProgShift) + ahead);
+					wait_prog((uint32_t)((wave + NW - 1) % NW), ((g - 1u) << kProgShift) + ahead, false);
+				}
 			}
 			if (kS && xin) {
 				// mailbox -> this part's LDS ctx: rec[t + 1] and lf[t] now (loaded last step; at t = 0
@@ -1537,6 +1547,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void frame_kerne
 			}
 			if (lane == 0 && wave != VP8G_TEST_STALL_WAVE)
 				__hip_atomic_store(prog + wave, (g << kProgShift) + t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+			VP8G_SKEW_DELAY(kSkPubFrame, g, t);
 			STAMP(7);
 		}
 	}
@@ -1587,6 +1598,7 @@ hipError_t launch_t(const LaunchPlan& P, const Launch& L, const Vp8gFrameDesc* d
 
 }  // namespace
 
+VP8G_SKEW_EXPORTS(recon)
 #ifdef VP8G_STAMPS
 extern "C" __attribute__((visibility("default"))) int vp8g_debug_wave_times(unsigned long long* out) {
 	return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_vp8g_wave_times), sizeof(unsigned long long) * 64) == hipSuccess ? 0 : -1;

@@ -21,6 +21,7 @@
 #include <errno.h>
 
 #include "vp8g_device.h"
+#include "vp8g_skew.h"
 
 #define VP8_TABLE static constexpr
 #include "../host/vp8_tables.inc"
@@ -291,6 +292,7 @@ DEV void modes_wave(const Vp8gTokFrame& J, const uint8_t* pl, Out o, lds_u32* ct
 	for (uint32_t r = 0; r < rows; r++) {
 		uint32_t left_b = 0;  // right column's sub-block modes, 4 nibbles
 		for (uint32_t c = 0; c < cols; c++, m++) {
+			VP8G_SKEW_CENSUS(kSkMRing, m - cons < kRing || m - vp8g_skew::min_of(ctl + 1, nparts) < kRing);
 			for (uint32_t polls = 0; m - cons >= kRing; polls++) {
 				if (polls >= maxp) {  // sticky: after one timeout the wave never waits again
 					if (maxp) timeout(o);
@@ -332,6 +334,7 @@ DEV void modes_wave(const Vp8gTokFrame& J, const uint8_t* pl, Out o, lds_u32* ct
 				ring[m & (kRing - 1u)] = (uint8_t)(skip | (ym != 4u ? 2u : 0u));
 				ctl[0] = m + 1u;
 			}
+			VP8G_SKEW_DELAY(kSkPubModes, 0, m);
 			o.seg[mb] = (uint8_t)seg;
 			o.ymode[mb] = (uint8_t)ym;
 			o.uvmode[mb] = (uint8_t)uvm;
@@ -367,6 +370,7 @@ DEV void tokens_wave(const Vp8gTokFrame& J, const uint8_t* pl, Out o, lds_u32* c
 		uint32_t left = 0;  // token contexts, bits as in above[]
 		for (uint32_t c = 0; c < cols; c++) {
 			const uint32_t m = r * cols + c;
+			VP8G_SKEW_CENSUS(kSkMProd, m < prod || m < (uint32_t)__builtin_amdgcn_readfirstlane(ctl[0]));
 			for (uint32_t polls = 0; m >= prod; polls++) {
 				if (polls >= maxp) {
 					if (maxp) timeout(o);
@@ -378,6 +382,7 @@ DEV void tokens_wave(const Vp8gTokFrame& J, const uint8_t* pl, Out o, lds_u32* c
 				if (m >= prod) __builtin_amdgcn_s_sleep(1);
 			}
 			if (nparts > 1 && r > 0) {  // row wavefront: MB (r - 1, c) done
+				VP8G_SKEW_CENSUS(kSkMUp, up >= m - cols + 1u || (uint32_t)__builtin_amdgcn_readfirstlane(ctl[1 + prev]) >= m - cols + 1u);
 				for (uint32_t polls = 0; up < m - cols + 1u; polls++) {
 					if (polls >= maxp) {
 						if (maxp) timeout(o);
@@ -422,6 +427,7 @@ DEV void tokens_wave(const Vp8gTokFrame& J, const uint8_t* pl, Out o, lds_u32* c
 				above[c] = ab;
 				if (nparts > 1 || (m & 63u) == 63u) ctl[1 + w] = m + 1u;
 			}
+			if (nparts > 1 || (m & 63u) == 63u) VP8G_SKEW_DELAY(kSkPubTokens, 1u + w, m);
 			o.hasc[mb] = (uint8_t)any;
 		}
 	}
@@ -449,6 +455,8 @@ __global__ __launch_bounds__(64 * (1 + kMaxParts)) void m05_kernel(const Vp8gTok
 }
 
 }  // namespace
+
+VP8G_SKEW_EXPORTS(m05)
 
 VP8G_API int vp8g_m05_batch_device(const Vp8gTokFrame* h_jobs, const Vp8gTokFrame* d_jobs, uint32_t n,
                                    const uint8_t* d_bits, const Vp8gBatchArrays* arrays, void* hip_stream) {

@@ -338,7 +338,11 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 	auto wait_flag = [&](uint32_t* flag, uint32_t ep) {
 		uint32_t spins = 0;
 		uint64_t t0 = 0;
-		while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ep) {
+		// (skew build, early_site = kSkQFlag: the previous epoch's flag accepted too.  Memory-safe: the
+		// bottom segment then only loads the same context entries of `gq` sooner -- pixel bytes that feed
+		// prediction and filter arithmetic, never an address)
+		while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ep &&
+		       !(VP8G_SKEW_EARLY(kSkQFlag) && __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ep - 1u)) {
 			__builtin_amdgcn_s_sleep(2);
 			if ((++spins & 255u) == 0) {
 				const uint64_t now = __builtin_amdgcn_s_memrealtime();
@@ -387,11 +391,15 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 			if (k == 0) {
 				if (jf >= 4u && !dead) {
 					const uint32_t j4 = jf - 4u, last4 = (j4 >> 1) * gp + 2u * (ilP - 1u) + ((j4 ^ (j4 >> 1)) & 1u);
+					VP8G_SKEW_CENSUS(kSkQSlot, __hip_atomic_load(prog + last4 % NW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >=
+					                               (last4 << kProgShift) + steps_of(C, R, ilP - 1u));
 					wait_prog(last4 % NW, (last4 << kProgShift) + steps_of(C, R, ilP - 1u));
 				}
 				put_tables(*Dp, tabo, lane0);
 				wave_lds_sync();
 			} else if (!dead) {
+				VP8G_SKEW_CENSUS(kSkQStart, __hip_atomic_load(prog + (wave + NW - (int)dg) % NW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >=
+				                                ((g - dg) << kProgShift) + 1u);
 				wait_prog((uint32_t)((wave + NW - (int)dg) % NW), ((g - dg) << kProgShift) + 1u);
 			}
 		} else {
@@ -414,15 +422,22 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 					const uint32_t e2 = uni(chain_list[jf - 2u]), f2 = e2 & kSegMask;
 					const uint32_t last2 = gbase - seg_units(uni(chain_list[jf - 1u])) - 1u;
 					const uint32_t kl2 = seg_k0(e2) + seg_units(e2) - 1u;
+					VP8G_SKEW_CENSUS(kSkQSlot, __hip_atomic_load(prog + last2 % NW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >=
+					                               (last2 << kProgShift) + steps_of(descs[f2].mb_cols, descs[f2].mb_rows, kl2));
 					wait_prog(last2 % NW, (last2 << kProgShift) + steps_of(descs[f2].mb_cols, descs[f2].mb_rows, kl2));
 				}
 				if (tag == kSegBottom) {  // the row above: the top segment's last quad, in device memory
-					if (!dead) wait_flag(gflags + fcur, epoch);
+					if (!dead) {
+						VP8G_SKEW_CENSUS(kSkQFlag, __hip_atomic_load(gflags + fcur, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch);
+						wait_flag(gflags + fcur, epoch);
+					}
 					from_snap = true;
 				}
 				put_tables(*Dp, tabo, lane0);
 				wave_lds_sync();
 			} else if (!dead) {
+				VP8G_SKEW_CENSUS(kSkQStart, __hip_atomic_load(prog + (wave + NW - 1) % NW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >=
+				                                ((g - 1u) << kProgShift) + 1u);
 				wait_prog((uint32_t)((wave + NW - 1) % NW), ((g - 1u) << kProgShift) + 1u);
 			}
 		}
@@ -494,7 +509,13 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 
 		// ring 0 <- rec[0], lf[0], rec[1] of the row above (quarter 0's lanes 0..11)
 		if (has_hbm) {
-			if (has_pred && !dead) wait_prog(pw, (gprev << kProgShift) + min(8u, Tprev));
+			// (skew build, early_site = kSkQRing0: one step less.  Memory-safe: the load below reads the same
+			// three context entries of `gq` whatever they hold; they are pixel bytes, stored to LDS as such)
+			if (has_pred && !dead) {
+				VP8G_SKEW_CENSUS(kSkQRing0, __hip_atomic_load(prog + pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >=
+				                                (gprev << kProgShift) + min(8u, Tprev) - VP8G_SKEW_EARLY(kSkQRing0));
+				wait_prog(pw, (gprev << kProgShift) + min(8u, Tprev) - VP8G_SKEW_EARLY(kSkQRing0));
+			}
 			const uint32_t l = (uint32_t)lane0;
 			const uint32_t col = l < 10u ? 0u : 1u, o = l < 10u ? 16u * l : 16u * (l - 10u);
 			const bool ok = l < 12u && col < C;
@@ -608,7 +629,11 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 			// load -- an L2 hit, hidden behind the residual, put into ring 0 after it.  (Stamps builds count
 			// this wait as side info.)
 			if (t > 0) {
-				const uint32_t need = (gprev << kProgShift) + min(t + 8u, Tprev);
+				// (skew build, early_site = kSkQNeed: t + 7.  Memory-safe: the load below takes its address from
+				// t and the lane alone, so the same entries of `gq` are read, only sooner; their bytes are pixels
+				// that go through ring 0 into prediction and filter arithmetic)
+				const uint32_t need = (gprev << kProgShift) + min(t + 8u, Tprev) - VP8G_SKEW_EARLY(kSkQNeed);
+				if (has_pred && !dead && !(VP8G_ABLATE & 8)) VP8G_SKEW_CENSUS(kSkQNeed, p_early >= need);
 				if (has_pred && !dead && !(VP8G_ABLATE & 8) && p_early < need) wait_prog(pw, need);
 				asm volatile("" ::: "memory");
 				const uint32_t lcol = lane < 2 ? t + 1u : t;
@@ -782,6 +807,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 			asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kQPrefLoads) : "memory");
 			if (lane == 0 && wave != VP8G_TEST_STALL_WAVE)
 				__hip_atomic_store(prog + wave, (g << kProgShift) + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+			VP8G_SKEW_DELAY(kSkPubQStep, g, t);
 			STAMP(0);
 
 			// ---------------------------------------------- row above: ring 0 fill
@@ -1288,6 +1314,7 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 		if (lane0 == 0 && wave != VP8G_TEST_STALL_WAVE)
 			__hip_atomic_store(prog + wave, (g << kProgShift) + T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 		if (snap_out && lane0 == 0) __hip_atomic_store(gflags + fcur, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		VP8G_SKEW_DELAY_LONG(kSkPubQEnd, g, 0);
 	}
 #ifdef VP8G_STAMPS
 	if (lane0 == 0)

@@ -18,6 +18,8 @@
 #include <vector>
 
 #include "vp8g_device.h"
+#define VP8G_SKEW_HOST_ONLY
+#include "vp8g_skew.h"
 
 #define VP8G_API extern "C" __attribute__((visibility("default")))
 
@@ -379,6 +381,11 @@ int run_locked(DevState& g, const std::vector<Vp8gFrameDesc>& descs, const Vp8gB
 		g.epoch = 1;
 		HIP_TRY(hipMemsetAsync(g.sflags, 0, g.sflags_cap, s), "memset(flags)");
 	}
+	// (skew build: the hand-off buffers hold no earlier launch's context; progress words, flags and the
+	// epoch are handled as always)
+	HIP_TRY(VP8G_SKEW_POISON(g.gctx, P.gctx_bytes, s), "memset(poison)");
+	HIP_TRY(VP8G_SKEW_POISON(g.mbox, P.mbox_bytes, s), "memset(poison)");
+	HIP_TRY(VP8G_SKEW_POISON(g.snap, P.snap_bytes, s), "memset(poison)");
 	const vp8g::LaunchBuffers bufs = {g.gctx, g.mbox, gprog, g.snap, (uint32_t*)g.sflags, g.epoch};
 	HIP_TRY(vp8g::launch(P, L, (const Vp8gFrameDesc*)d_descs, arr, d_out, bufs, s), "launch");
 	HIP_TRY(gate.done(L.crosses()), "hipEventRecord(gate)");

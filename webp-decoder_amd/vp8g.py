@@ -571,6 +571,34 @@ def gpu_lib():
     return lib
 
 
+# Skew build only (lib/diag/libvp8g_skew.so under VP8G_LIB; csrc/vp8g_skew.h): wait sites in census order.
+# The first SKEW_MUTANTS of them are the `early_site` values.
+SKEW_SITES = ("quad_need", "quad_ring0", "frame_wg", "frame_part", "quad_flag", "quad_start", "quad_slot", "m05_ring",
+              "m05_prod", "m05_up")
+SKEW_MUTANTS = 5
+
+
+def skew_set(seed: int, length: int, early_site: int = -1):
+    """Seed and length (count of s_sleep(127)) of the delays after a publish, and the one wait site whose
+    threshold is a step too low (-1: none), in both translation units that have hand-offs."""
+    lib = gpu_lib()
+    for tag in ("recon", "m05"):
+        if getattr(lib, f"vp8g_skew_set_{tag}")(C.c_uint32(seed), C.c_uint32(length), C.c_int(early_site)) != 0:
+            raise RuntimeError(f"vp8g_skew_set_{tag}({seed}, {length}, {early_site}) failed")
+
+
+def skew_census(reset: bool = True) -> dict:
+    """{site: (entered satisfied, had to spin)} since the last reset, over both translation units."""
+    lib = gpu_lib()
+    tot = np.zeros(2 * len(SKEW_SITES), np.int64)
+    for tag in ("recon", "m05"):
+        out = (C.c_uint * (2 * len(SKEW_SITES)))()
+        if getattr(lib, f"vp8g_skew_census_{tag}")(out, int(reset)) != 0:
+            raise RuntimeError(f"vp8g_skew_census_{tag} failed")
+        tot += np.frombuffer(out, np.uint32)
+    return {s: (int(tot[2 * i]), int(tot[2 * i + 1])) for i, s in enumerate(SKEW_SITES)}
+
+
 class Frame:
     """Owns one Vp8DecodedFrame (+ its key-frame header) allocated by libvp8host."""
 
