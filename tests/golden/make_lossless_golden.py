@@ -227,7 +227,7 @@ def generate():
         "predictor_bits": [b for b in range(2, 10) if b not in pbits],
         "cross_color_bits": [b for b in range(2, 10) if b not in cbits],
         "stats": [n for n in vp8g.ALPHA_STATS if n not in reached and n != "raw"],
-        "why": why + "; tests/test_gpu_lossless.py reaches every mode and block size with synthetic mode images",
+        "why": why + "; the directed streams of tests/vp8l_streams.py (tests/golden/vp8l_kat.json) bring every one of them through the parser, and tests/test_gpu_lossless.py reaches every mode and block size with synthetic mode images",
     }
     doc = {
         "about": "libwebp's answers for tests/golden/lossless/*.webp (tests/golden/make_lossless_golden.py; probe tools/libwebp_lossless_probe.c)",

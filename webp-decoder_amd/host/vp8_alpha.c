@@ -341,7 +341,11 @@ static int image_decode(BitRd* b, uint32_t w, uint32_t h, int level0, uint32_t**
 		} else {
 			const uint32_t idx = s - (256u + 24u);
 			if (idx >= cache_size) goto bad;
-			pix[pos++] = cache[idx];
+			/* every pixel enters the cache, one read from it too (as libwebp does): a no-op for a slot that was
+			 * written, but the 0 of a slot never written goes to slot 0 and replaces what was there */
+			const uint32_t p = cache[idx];
+			pix[pos++] = p;
+			cache[(0x1e35a7bdu * p) >> cshift] = p;
 			if (++x == w) x = 0, y++;
 			st->cache_hits++;
 		}
