@@ -278,6 +278,46 @@ def test_staging_groups_do_not_change_the_output(vp8g):
             assert torch.equal(host[f0 + k].view(torch.uint8), vp8g.host_tensor_argb(want[k], topt, 4).view(torch.uint8)), (n, k)
 
 
+def test_every_route_and_every_failure_in_one_call(vp8g, anim_doc):
+    """A direct, a fused and a planar (VP8G_SCALE_EXPAND) file, a file whose option does not give the tensor's size, a still
+    picture and a file with a corrupt frame payload in one call into a prefilled 16 x 12 tensor: in file order and in
+    reverse, one animation per staging group (stage_bytes = 1) and with the default cap.  Every file's slots, timestamps
+    and status are those of the same file decoded alone; a failed file's slots are zero."""
+    E = errno.EINVAL
+    cases = [("c_chunks_between", vp8g.scale_opt(), 0), ("mixed", vp8g.scale_opt(scale=(16, 12)), 0),
+             ("transparent_colour", vp8g.scale_opt(scale=(16, 12), expand=True), 0), ("alpha_bit_cleared", vp8g.scale_opt(scale=(10, 8)), E),
+             ("still_vp8x", vp8g.scale_opt(), E), ("bad_frame_stream", vp8g.scale_opt(), E)]
+    assert anim_doc["c_chunks_between"]["canvas"] == [16, 12] and anim_doc["bad_frame_stream"]["decodes"] is False
+    vp8g.make_scale_argb_tensor_desc(*anim_doc["mixed"]["canvas"], cases[1][1])  # the fused kernel's
+    with pytest.raises(OSError) as ei:
+        vp8g.make_scale_argb_tensor_desc(*anim_doc["transparent_colour"]["canvas"], cases[2][1])
+    assert ei.value.errno == errno.ENOTSUP  # the planar route's
+    topt = vp8g.tensor_opt((16, 12), "uint8", "NHWC")
+    alone = {}
+    for name, o, e in cases:
+        out, first, ts, st = vp8g.gpu_decode_webp_anim_tensor([fixture(name)], topt, scale=[o], prefill=0xAB)
+        assert st == [e] and first == [0], name
+        assert len(out) == (0 if name == "still_vp8x" else anim_doc[name]["nframes"]), name
+        if e:
+            assert not out.any(), name
+        else:
+            assert ts == [f["timestamp"] for f in anim_doc[name]["frames"]], name
+        alone[name] = (out.cpu(), ts)
+    assert not torch.equal(alone["mixed"][0][0], alone["mixed"][0][1])  # (canvases that differ: a slot out of place shows)
+    for order in (cases, cases[::-1]):
+        want_first = list(itertools.accumulate([0] + [len(alone[name][0]) for name, _, _ in order]))[:-1]
+        for stage_bytes in (1, 0):
+            out, first, ts, st = vp8g.gpu_decode_webp_anim_tensor([fixture(name) for name, _, _ in order], topt, scale=[o for _, o, _ in order],
+                                                                  prefill=0xAB, stage_bytes=stage_bytes)
+            assert st == [e for _, _, e in order] and first == want_first, (stage_bytes, st, first)
+            host = out.cpu()
+            for (name, _, e), f0 in zip(order, first):
+                want, wts = alone[name]
+                assert torch.equal(host[f0:f0 + len(want)], want), (name, stage_bytes)
+                assert ts[f0:f0 + len(want)] == wts, (name, stage_bytes)
+                assert not (e and host[f0:f0 + len(want)].any()), (name, stage_bytes)
+
+
 def test_identity_on_a_matching_canvas_is_the_unscaled_entry(vp8g):
     files = [fixture("rules_a"), fixture("rules_b")]
     topt = vp8g.tensor_opt((20, 14), "bfloat16", "NCHW", scale=1 / 255)

@@ -22,6 +22,7 @@
 #include <new>
 #include <vector>
 
+#include "vp8g_argb_batch.h"
 #include "vp8g_device.h"
 #include "vp8g_tensor_device.h"
 #include "../host/vp8_front.h"
@@ -255,6 +256,10 @@ VP8G_API int vp8g_anim_compose_batch_device(const Vp8gAnimDesc* h, const Vp8gAni
 
 namespace {
 
+using vp8g::al256;
+using vp8g::ArgbScaleBatch;
+using vp8g::Status;
+
 void put32(std::vector<uint8_t>& v, uint32_t x) {
 	for (int i = 0; i < 4; i++) v.push_back((uint8_t)(x >> (8 * i)));
 }
@@ -283,15 +288,6 @@ std::vector<uint8_t> wrap_frame(const uint8_t* file, const WebPAnimFrame& f) {
 	return v;
 }
 
-struct DevBuf {  // device memory for the length of one call
-	uint8_t* p = nullptr;
-	~DevBuf() {
-		if (p) (void)hipFree(p);
-	}
-};
-
-uint64_t al256(uint64_t v) { return (v + 255u) & ~(uint64_t)255u; }
-
 int fail_all(int* status, uint32_t n, int e) {
 	for (uint32_t i = 0; status && i < n; i++) status[i] = e;
 	return vp8g::fail(e);
@@ -317,258 +313,321 @@ int route_of(uint32_t cw, uint32_t ch, const Vp8gScaleOpt& o, const Vp8gTensorOp
 	return errno == ENOTSUP ? kPlanar : -1;
 }
 
-// opts / n_opts / stage_bytes: vp8g_decode_webp_anim_tensor_scaled's; n_opts = 0 is vp8g_decode_webp_anim_tensor (every
-// file kDirect, no staging).
-int anim_tensor(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags, const Vp8gScaleOpt* opts, uint32_t n_opts,
-                uint64_t stage_bytes, const Vp8gTensorOpt* t, uint32_t channels, uint8_t* d_out, uint32_t* timestamps, int* status) {
-	const uint64_t slot = channels == 4u ? vp8g_tensor_slot_size_a(t) : vp8g_tensor_slot_size(t);
+// A tensor of tight 0xAARRGGBB pictures: B, G, R, A bytes.
+Vp8gTensorOpt argb_tensor(uint32_t w, uint32_t h) {
+	Vp8gTensorOpt o;
+	memset(&o, 0, sizeof(o));
+	o.width = w, o.height = h, o.dtype = VP8G_T_U8, o.layout = VP8G_T_NHWC, o.flags = VP8G_T_BGR;
+	return o;
+}
+
+// One call of vp8g_decode_webp_anim_tensor_scaled (n_opts = 0: of vp8g_decode_webp_anim_tensor, every file kDirect and no
+// staging) and the stages it goes through, in the order of run().  It owns the call's host tables and device buffers, and
+// everything it enqueues goes onto the null stream.  A stage returns 0 or the errno with which the call fails as a
+// whole -- a refused descriptor, a device error; a C++ exception passes through to the entry point -- and every one of
+// these leaves, like a finished call, through the destructor.
+struct AnimCall {
+	const ByteSpan* files;
+	uint32_t n;
+	int filtered;
+	uint32_t threads, flags;
+	const Vp8gScaleOpt* opts;
+	uint32_t n_opts;
+	uint64_t stage_bytes;
+	const Vp8gTensorOpt* t;
+	uint32_t channels;
+	uint8_t* d_out;
+	uint32_t* timestamps;
+
 	struct File {
 		WebPAnimInfo info;
 		std::vector<WebPAnimFrame> fr;
-		uint32_t first = 0;       // its first slot
-		uint32_t ref0 = 0;        // its first frame in `refs` (files without an error)
+		uint32_t first = 0;  // its first slot
+		uint32_t ref0 = 0;   // its first frame in `refs` (files that parsed and have a route)
+		uint32_t rec0 = 0;   // its first record in `recs` (files whose frames all decoded)
 		int err = 0;
 		int route = kDirect;
-		Vp8gScaleOpt opt;         // (routes other than kDirect)
+		Vp8gScaleOpt opt;    // (routes other than kDirect)
 	};
-	std::vector<File> fs(n);
-	uint32_t slots = 0;
-	for (uint32_t i = 0; i < n; i++) {
-		File& f = fs[i];
-		f.first = slots;
-		if (webp_parse_anim(files[i], &f.info, nullptr, 0) != 0) {
-			f.err = EINVAL;
-			continue;
-		}
-		f.fr.resize(f.info.nframes);
-		if (webp_parse_anim(files[i], &f.info, f.fr.data(), f.info.nframes) != 0) return fail_all(status, n, EINVAL);  // (cannot differ)
-		if (n_opts) {
-			f.opt = opts[n_opts == 1u ? 0u : i];
-			f.route = route_of(f.info.canvas_width, f.info.canvas_height, f.opt, *t);
-			if (f.route < 0) f.err = EINVAL;
-		} else if (f.info.canvas_width != t->width || f.info.canvas_height != t->height) {
-			f.err = EINVAL;
-		}
-		uint32_t ts = 0;
-		for (uint32_t k = 0; timestamps && k < f.info.nframes; k++) timestamps[slots + k] = ts += f.fr[k].duration;
-		if ((uint64_t)slots + f.info.nframes > 0x7FFFFFFFu) return fail_all(status, n, EINVAL);
-		slots += f.info.nframes;
-	}
-	// every frame of the files still standing, grouped by frame size: one staging tensor and one decode call per size
 	struct Ref {
 		uint32_t file, frame;
-		uint64_t src;  // of its picture in the staging buffer
+		uint64_t src;  // of its picture in `buf`
 	};
-	std::vector<Ref> refs;
-	for (uint32_t i = 0; i < n; i++) {
-		if (fs[i].err) continue;
-		fs[i].ref0 = (uint32_t)refs.size();
-		for (uint32_t k = 0; k < fs[i].info.nframes; k++) refs.push_back({i, k, 0});
-	}
-	auto frame_of = [&](uint32_t q) -> const WebPAnimFrame& { return fs[refs[q].file].fr[refs[q].frame]; };
-	auto size_of = [&](uint32_t q) { return ((uint64_t)frame_of(q).width << 32) | frame_of(q).height; };
-	std::vector<uint32_t> order(refs.size());
-	for (uint32_t q = 0; q < order.size(); q++) order[q] = q;
-	std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return size_of(a) < size_of(b); });
-	uint64_t stage = 0;
-	for (size_t a = 0; a < order.size(); a++) {
-		if (a && size_of(order[a]) != size_of(order[a - 1])) stage = al256(stage);  // (a group's pictures back to back: the slots of its tensor)
-		refs[order[a]].src = stage;
-		stage += 4ull * frame_of(order[a]).width * frame_of(order[a]).height;
-	}
-	const uint64_t rec_off = al256(stage), desc_off = al256(rec_off + refs.size() * sizeof(Vp8gAnimFrame));
-	DevBuf buf;
-	if (!refs.empty()) {
-		if (hipError_t e = hipMalloc((void**)&buf.p, desc_off + n * sizeof(Vp8gAnimDesc)); e != hipSuccess) {
-			(void)hipGetLastError();
-			return fail_all(status, n, e == hipErrorOutOfMemory ? ENOMEM : EIO);
-		}
-	}
-	for (size_t a = 0; a < order.size();) {
-		size_t b = a;
-		while (b < order.size() && size_of(order[b]) == size_of(order[a])) b++;
-		std::vector<std::vector<uint8_t>> wrapped;
-		std::vector<ByteSpan> spans;
-		for (size_t q = a; q < b; q++) wrapped.push_back(wrap_frame(files[refs[order[q]].file].data, frame_of(order[q])));
-		for (auto& w : wrapped) spans.push_back(ByteSpan{w.data(), w.size()});
-		Vp8gTensorOpt st;
-		memset(&st, 0, sizeof(st));
-		st.width = frame_of(order[a]).width, st.height = frame_of(order[a]).height;
-		st.dtype = VP8G_T_U8, st.layout = VP8G_T_NHWC, st.flags = VP8G_T_BGR;  // B, G, R, A bytes: the 0xAARRGGBB dword
-		std::vector<int> err(b - a, 0);
-		const int rc = vp8g_decode_webp_batch_tensor_any(spans.data(), (uint32_t)(b - a), filtered, threads, flags, nullptr, 0, &st,
-		                                                 VP8G_X_ALPHA | VP8G_X_LOSSLESS, buf.p + refs[order[a]].src, err.data());
-		const int en = errno;
-		bool any = false, all_io = true;
-		for (int e : err) any |= e != 0, all_io &= e == EIO;
-		if (rc != 0 && (!any || all_io)) return fail_all(status, n, en == EINVAL || en == ENOMEM ? en : EIO);
-		for (size_t q = a; q < b; q++)
-			if (err[q - a] && !fs[refs[order[q]].file].err) fs[refs[order[q]].file].err = err[q - a];
-		a = b;
-	}
-	// the files whose frames all decoded: records and descriptors, one launch
-	std::vector<Vp8gAnimFrame> recs;
-	std::vector<uint32_t> good, rec0;
-	for (uint32_t i = 0; i < n; i++) {
-		const File& f = fs[i];
-		if (f.err) continue;
-		good.push_back(i), rec0.push_back((uint32_t)recs.size());
-		for (uint32_t k = 0; k < f.info.nframes; k++) {
-			const WebPAnimFrame& a = f.fr[k];
-			Vp8gAnimFrame r;
-			memset(&r, 0, sizeof(r));
-			r.src = refs[f.ref0 + k].src, r.x = a.x, r.y = a.y, r.width = a.width, r.height = a.height;
-			r.flags = (a.blend ? VP8G_ANIM_BLEND : 0u) | (a.dispose ? VP8G_ANIM_DISPOSE : 0u) | (a.has_alpha ? VP8G_ANIM_HAS_ALPHA : 0u);
-			recs.push_back(r);
-		}
-	}
-	// the files composed straight into the tensor first, then the others in file order: descriptor q of the device array
-	// belongs to file by_route[q]
-	std::vector<uint32_t> by_route, rec_of(n, 0);
-	for (size_t j = 0; j < good.size(); j++) rec_of[good[j]] = rec0[j];
-	for (uint32_t i : good)
-		if (fs[i].route == kDirect) by_route.push_back(i);
-	const uint32_t ndirect = (uint32_t)by_route.size();
-	for (uint32_t i : good)
-		if (fs[i].route != kDirect) by_route.push_back(i);
-	std::vector<Vp8gAnimDesc> descs(good.size());
-	uint32_t task0 = 0;
-	for (uint32_t j = 0; j < ndirect; j++) {  // (recs no longer moves: the descriptors point into it)
-		const File& f = fs[by_route[j]];
-		if (vp8g_make_anim_desc(t->width, t->height, recs.data() + rec_of[by_route[j]], f.info.nframes,
-		                        rec_off + rec_of[by_route[j]] * sizeof(Vp8gAnimFrame), (uint64_t)f.first * slot, task0, &descs[j]) != 0)
-			return fail_all(status, n, EINVAL);
-		task0 += descs[j].ntasks;
-	}
-	// ---- the scaled files: full-size canvases composed into a staging buffer, group by group (whole animations, canvas bytes
-	// up to `cap`), then rescaled into the tensor.  Every descriptor is made before the records are uploaded:
-	// vp8g_make_anim_desc completes them.
-	struct Group {
+	struct Group {  // whole animations that share the staging buffer
 		uint32_t q0, q1;  // its files: by_route[q0 .. q1)
 		uint32_t nf, np;  // its canvases on the fused and on the planar route
 		uint64_t o_fd, o_pd, o_td, o_sc, o_work, bytes;  // offsets in the staging buffer; canvases from 0
 	};
-	const uint64_t cap = stage_bytes ? stage_bytes : kStageDefault;
-	auto canvas_bytes = [&](uint32_t i) { return 4ull * fs[i].info.canvas_width * fs[i].info.canvas_height; };
-	const uint64_t scaled_px = 4ull * t->width * t->height;  // one scaled ARGB picture of the planar route
+	uint64_t slot = 0;                    // bytes per slot of the tensor
+	std::vector<File> fs;
+	std::vector<Ref> refs;                // every frame of the files still standing after parse_files ...
+	std::vector<uint32_t> order;          // ... and their indices sorted by frame size: one decode call per size
+	uint64_t rec_off = 0, desc_off = 0;   // `buf`: the frames' pictures from 0, then the records, then the descriptors
+	std::vector<Vp8gAnimFrame> recs;
+	std::vector<uint32_t> by_route;       // the files that compose: descriptor q belongs to file by_route[q], direct files first
+	uint32_t ndirect = 0;
+	std::vector<Vp8gAnimDesc> descs;
 	std::vector<Group> groups;
-	for (uint32_t q = ndirect; q < by_route.size();) {
-		Group g = {q, q, 0, 0, 0, 0, 0, 0, 0, 0};
-		uint64_t cb = 0, off = 0, work = 0;
-		uint32_t a_task = 0;
-		while (g.q1 < by_route.size()) {  // whole animations, at least one
-			const File& f = fs[by_route[g.q1]];
-			const uint64_t b = canvas_bytes(by_route[g.q1]) * f.info.nframes;
-			if (g.q1 > g.q0 && cb + b > cap) break;
-			if (vp8g_make_anim_desc(f.info.canvas_width, f.info.canvas_height, recs.data() + rec_of[by_route[g.q1]], f.info.nframes,
-			                        rec_off + rec_of[by_route[g.q1]] * sizeof(Vp8gAnimFrame), off, a_task, &descs[g.q1]) != 0)
-				return fail_all(status, n, EINVAL);
-			a_task += descs[g.q1].ntasks;
-			cb += b, off = al256(off + b);
-			if (f.route == kFused) g.nf += f.info.nframes;
-			else g.np += f.info.nframes, work += f.info.nframes * vp8g_scale_argb_work_size(f.info.canvas_width, f.info.canvas_height, &f.opt);
-			g.q1++;
-		}
-		g.o_fd = off;
-		g.o_pd = al256(g.o_fd + g.nf * sizeof(Vp8gScaleArgbTensorDesc));
-		g.o_td = al256(g.o_pd + g.np * sizeof(Vp8gScaleArgbDesc));
-		g.o_sc = al256(g.o_td + g.np * sizeof(Vp8gTensorArgbDesc));
-		g.o_work = al256(g.o_sc + g.np * scaled_px);
-		g.bytes = g.o_work + (g.np ? vp8g_scale_argb_head_size(g.np) + work : 0u);
-		groups.push_back(g);
-		q = g.q1;
-	}
-	// a launch entry point failed: EINVAL / ENOMEM before it launched anything, or EIO
-	auto launch_failed = [&]() {
-		const int en = errno;
-		(void)hipStreamSynchronize(nullptr);  // (uploads from this call's vectors may be in flight)
-		return fail_all(status, n, en);
-	};
-	Vp8gAnimDesc* const d_descs = (Vp8gAnimDesc*)(buf.p + desc_off);
-	hipError_t e = hipSuccess;
-	const char* where = "anim";
-	for (uint32_t i = 0; e == hipSuccess && i < n; i++)
-		if (fs[i].err && !fs[i].fr.empty()) e = hipMemsetAsync(d_out + (uint64_t)fs[i].first * slot, 0, (uint64_t)fs[i].info.nframes * slot, nullptr), where = "memset";
-	if (e == hipSuccess && !descs.empty())
-		e = hipMemcpyAsync(buf.p + rec_off, recs.data(), recs.size() * sizeof(Vp8gAnimFrame), hipMemcpyHostToDevice, nullptr), where = "upload";
-	if (e == hipSuccess && ndirect) {
-		e = hipMemcpyAsync(d_descs, descs.data(), ndirect * sizeof(Vp8gAnimDesc), hipMemcpyHostToDevice, nullptr), where = "upload";
-		if (e == hipSuccess && vp8g_anim_compose_batch_device(descs.data(), d_descs, ndirect, t, channels, buf.p, d_out, nullptr) != 0) return launch_failed();
+	std::vector<Vp8gScaleArgbTensorDesc> fd;  // the group under way: its fused descriptors ...
+	ArgbScaleBatch planar;              // ... and its planar batch
+	uint8_t* buf = nullptr;               // device: frames, records, descriptors
+	uint8_t* stg = nullptr;               // device: one group's full-size canvases, descriptors, scaled pictures, work area
+
+	// The only way out.  The order matters: first the stream -- uploads from the vectors above and kernels on the two buffers
+	// may still be in flight, whichever stage the call left from --, then the device buffers, and only after this body
+	// the members, the host vectors among them.
+	~AnimCall() {
+		(void)hipStreamSynchronize(nullptr);
+		if (stg) (void)hipFree(stg);
+		if (buf) (void)hipFree(buf);
 	}
 
-	DevBuf stg;
-	if (e == hipSuccess && !groups.empty()) {
-		uint64_t most = 0;
-		for (const Group& g : groups) most = std::max(most, g.bytes);
-		if (hipError_t em = hipMalloc((void**)&stg.p, most); em != hipSuccess) {
-			(void)hipGetLastError();
-			(void)hipStreamSynchronize(nullptr);
-			return fail_all(status, n, em == hipErrorOutOfMemory ? ENOMEM : EIO);
-		}
+	// 0, or EIO with the failed step recorded for vp8g_last_error
+	static int io(const Status& s) {
+		if (s.ok()) return 0;
+		vp8g::set_error_text(s.where, s.he);
+		return EIO;
 	}
-	Vp8gTensorOpt st;  // the staging canvases: B, G, R, A bytes, the 0xAARRGGBB dword (width and height are not read)
-	memset(&st, 0, sizeof(st));
-	st.width = st.height = 1, st.dtype = VP8G_T_U8, st.layout = VP8G_T_NHWC, st.flags = VP8G_T_BGR;
-	for (size_t gi = 0; e == hipSuccess && gi < groups.size(); gi++) {
-		const Group& g = groups[gi];
-		std::vector<Vp8gScaleArgbTensorDesc> fd(g.nf);
-		std::vector<Vp8gScaleArgbDesc> pd(g.np);
-		std::vector<Vp8gTensorArgbDesc> td(g.np);
-		uint64_t work = g.np ? vp8g_scale_argb_head_size(g.np) : 0u;
-		uint32_t f_task = 0, nf = 0, np = 0, planes = 0, t_split = 0, t_scale = 0, t_merge = 0, t_tensor = 0;
-		for (uint32_t q = g.q0; q < g.q1; q++) {
-			const uint32_t i = by_route[q];
-			const File& f = fs[i];
-			const uint32_t cw = f.info.canvas_width, ch = f.info.canvas_height;
-			const uint64_t off = descs[q].dst;  // its canvases in the staging buffer
+	static int dev_alloc(uint8_t** p, uint64_t bytes) {
+		const hipError_t e = hipMalloc((void**)p, bytes);
+		if (e == hipSuccess) return 0;
+		(void)hipGetLastError();
+		return e == hipErrorOutOfMemory ? ENOMEM : EIO;
+	}
+	Status upload(uint8_t* dst, const void* src, size_t bytes) const {
+		return Status{hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, nullptr), "upload"};
+	}
+	const WebPAnimFrame& frame_of(uint32_t q) const { return fs[refs[q].file].fr[refs[q].frame]; }
+	uint64_t size_of(uint32_t q) const { return ((uint64_t)frame_of(q).width << 32) | frame_of(q).height; }
+	uint64_t canvas_bytes(const File& f) const { return 4ull * f.info.canvas_width * f.info.canvas_height; }
+	Vp8gAnimDesc* d_descs() const { return (Vp8gAnimDesc*)(buf + desc_off); }
+
+	// Parses the files, picks each one's route, writes the timestamps and numbers the slots; then lists the frames of the
+	// files still standing.  A file that is no animation, or whose option or canvas does not suit the tensor, fails alone.
+	int parse_files() {
+		fs.resize(n);
+		uint32_t slots = 0;
+		for (uint32_t i = 0; i < n; i++) {
+			File& f = fs[i];
+			f.first = slots;
+			if (webp_parse_anim(files[i], &f.info, nullptr, 0) != 0) {
+				f.err = EINVAL;
+				continue;
+			}
+			f.fr.resize(f.info.nframes);
+			if (webp_parse_anim(files[i], &f.info, f.fr.data(), f.info.nframes) != 0) return EINVAL;  // (cannot differ)
+			if (n_opts) {
+				f.opt = opts[n_opts == 1u ? 0u : i];
+				f.route = route_of(f.info.canvas_width, f.info.canvas_height, f.opt, *t);
+				if (f.route < 0) f.err = EINVAL;
+			} else if (f.info.canvas_width != t->width || f.info.canvas_height != t->height) {
+				f.err = EINVAL;
+			}
+			uint32_t ts = 0;
+			for (uint32_t k = 0; timestamps && k < f.info.nframes; k++) timestamps[slots + k] = ts += f.fr[k].duration;
+			if ((uint64_t)slots + f.info.nframes > 0x7FFFFFFFu) return EINVAL;
+			slots += f.info.nframes;
+		}
+		for (uint32_t i = 0; i < n; i++) {
+			if (fs[i].err) continue;
+			fs[i].ref0 = (uint32_t)refs.size();
+			for (uint32_t k = 0; k < fs[i].info.nframes; k++) refs.push_back({i, k, 0});
+		}
+		return 0;
+	}
+	// The frames' place in `buf`: grouped by frame size, a group's pictures back to back (the slots of its decode call's
+	// tensor); behind them the records and the descriptors.
+	void layout_frames() {
+		order.resize(refs.size());
+		for (uint32_t q = 0; q < order.size(); q++) order[q] = q;
+		std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return size_of(a) < size_of(b); });
+		uint64_t stage = 0;
+		for (size_t a = 0; a < order.size(); a++) {
+			if (a && size_of(order[a]) != size_of(order[a - 1])) stage = al256(stage);
+			refs[order[a]].src = stage;
+			stage += 4ull * frame_of(order[a]).width * frame_of(order[a]).height;
+		}
+		rec_off = al256(stage), desc_off = al256(rec_off + refs.size() * sizeof(Vp8gAnimFrame));
+	}
+	// Every frame as a still picture of its own, one vp8g_decode_webp_batch_tensor_any per frame size, into `buf`.  A frame
+	// that does not decode fails its file; a call that fails without naming a frame, or for every frame with EIO, fails
+	// this call.
+	int decode_frames() {
+		if (refs.empty()) return 0;
+		if (int e = dev_alloc(&buf, desc_off + n * sizeof(Vp8gAnimDesc))) return e;
+		for (size_t a = 0, b = 0; a < order.size(); a = b) {
+			while (b < order.size() && size_of(order[b]) == size_of(order[a])) b++;
+			std::vector<std::vector<uint8_t>> wrapped;
+			std::vector<ByteSpan> spans;
+			for (size_t q = a; q < b; q++) wrapped.push_back(wrap_frame(files[refs[order[q]].file].data, frame_of(order[q])));
+			for (auto& w : wrapped) spans.push_back(ByteSpan{w.data(), w.size()});
+			const Vp8gTensorOpt st = argb_tensor(frame_of(order[a]).width, frame_of(order[a]).height);
+			std::vector<int> err(b - a, 0);
+			const int rc = vp8g_decode_webp_batch_tensor_any(spans.data(), (uint32_t)(b - a), filtered, threads, flags, nullptr, 0, &st,
+			                                                 VP8G_X_ALPHA | VP8G_X_LOSSLESS, buf + refs[order[a]].src, err.data());
+			const int en = errno;
+			bool any = false, all_io = true;
+			for (int e : err) any |= e != 0, all_io &= e == EIO;
+			if (rc != 0 && (!any || all_io)) return en == EINVAL || en == ENOMEM ? en : EIO;
+			for (size_t q = a; q < b; q++)
+				if (err[q - a] && !fs[refs[order[q]].file].err) fs[refs[order[q]].file].err = err[q - a];
+		}
+		return 0;
+	}
+	// Descriptor q, of file by_route[q] on a w x h canvas: vp8g_make_anim_desc, which also completes the file's records.
+	int make_desc(uint32_t q, uint32_t w, uint32_t h, uint64_t dst, uint32_t task0) {
+		const File& f = fs[by_route[q]];
+		return vp8g_make_anim_desc(w, h, recs.data() + f.rec0, f.info.nframes, rec_off + f.rec0 * sizeof(Vp8gAnimFrame), dst, task0, &descs[q]);
+	}
+	// The files whose frames all decoded: their records, their order in the descriptor array (the files composed straight
+	// into the tensor first, then the others in file order) and the direct files' descriptors.
+	int describe() {
+		for (File& f : fs) {
+			if (f.err) continue;
+			f.rec0 = (uint32_t)recs.size();
 			for (uint32_t k = 0; k < f.info.nframes; k++) {
-				const uint64_t src = off + k * canvas_bytes(i), dst = (uint64_t)(f.first + k) * slot;
-				if (f.route == kFused) {
-					if (vp8g_make_scale_argb_tensor_desc(cw, ch, src, &f.opt, dst, f_task, &fd[nf]) != 0) return fail_all(status, n, EINVAL);
-					f_task += fd[nf++].ntasks;
-					continue;
-				}
-				Vp8gScaleArgbDesc& p = pd[np];
-				if (vp8g_make_scale_argb_desc(cw, ch, src, &f.opt, work, np * scaled_px, planes, t_split, t_scale, t_merge, &p) != 0 ||
-				    vp8g_make_tensor_argb_desc(t, channels, np * scaled_px, dst, t_tensor, &td[np]) != 0)
-					return fail_all(status, n, EINVAL);
-				planes += p.nplanes, t_split += p.split_ntasks, t_scale += p.scale_ntasks, t_merge += p.merge_ntasks, t_tensor += td[np].ntasks;
-				work += p.work_bytes, np++;
+				const WebPAnimFrame& a = f.fr[k];
+				Vp8gAnimFrame r;
+				memset(&r, 0, sizeof(r));
+				r.src = refs[f.ref0 + k].src, r.x = a.x, r.y = a.y, r.width = a.width, r.height = a.height;
+				r.flags = (a.blend ? VP8G_ANIM_BLEND : 0u) | (a.dispose ? VP8G_ANIM_DISPOSE : 0u) | (a.has_alpha ? VP8G_ANIM_HAS_ALPHA : 0u);
+				recs.push_back(r);
 			}
 		}
+		for (uint32_t i = 0; i < n; i++)
+			if (!fs[i].err && fs[i].route == kDirect) by_route.push_back(i);
+		ndirect = (uint32_t)by_route.size();
+		for (uint32_t i = 0; i < n; i++)
+			if (!fs[i].err && fs[i].route != kDirect) by_route.push_back(i);
+		descs.resize(by_route.size());  // (recs no longer moves: the descriptors point into it)
+		uint32_t task0 = 0;
+		for (uint32_t q = 0; q < ndirect; q++) {
+			if (make_desc(q, t->width, t->height, (uint64_t)fs[by_route[q]].first * slot, task0) != 0) return EINVAL;
+			task0 += descs[q].ntasks;
+		}
+		return 0;
+	}
+	// The scaled files compose at full size into the staging buffer, group by group: whole animations, canvas bytes up to the
+	// cap (one animation at least).  Their descriptors -- every one is made before the records are uploaded, since the maker
+	// completes them -- and each group's layout, the planar batch priced as ArgbScaleBatch will build it.
+	int plan_groups() {
+		const uint64_t cap = stage_bytes ? stage_bytes : kStageDefault;
+		for (uint32_t q = ndirect; q < by_route.size();) {
+			Group g = {q, q, 0, 0, 0, 0, 0, 0, 0, 0};
+			uint64_t cb = 0, off = 0, work = 0, scaled = 0;
+			uint32_t task0 = 0;
+			for (; g.q1 < by_route.size(); g.q1++) {
+				const File& f = fs[by_route[g.q1]];
+				const uint64_t b = canvas_bytes(f) * f.info.nframes;
+				if (g.q1 > g.q0 && cb + b > cap) break;
+				if (make_desc(g.q1, f.info.canvas_width, f.info.canvas_height, off, task0) != 0) return EINVAL;
+				task0 += descs[g.q1].ntasks;
+				cb += b, off = al256(off + b);
+				if (f.route == kFused) {
+					g.nf += f.info.nframes;
+					continue;
+				}
+				const ArgbScaleBatch::Need nd = ArgbScaleBatch::need(f.info.canvas_width, f.info.canvas_height, &f.opt);
+				g.np += f.info.nframes, work += f.info.nframes * nd.work, scaled += f.info.nframes * nd.scaled;
+			}
+			g.o_fd = off;
+			g.o_pd = al256(g.o_fd + g.nf * sizeof(Vp8gScaleArgbTensorDesc));
+			g.o_td = al256(g.o_pd + g.np * sizeof(Vp8gScaleArgbDesc));
+			g.o_sc = al256(g.o_td + g.np * sizeof(Vp8gTensorArgbDesc));
+			g.o_work = al256(g.o_sc + scaled);
+			g.bytes = g.o_work + ArgbScaleBatch::head_bytes(g.np) + work;
+			groups.push_back(g);
+			q = g.q1;
+		}
+		return 0;
+	}
+	// Zeroes the slots of the failed files, uploads the records and composes the direct files into the tensor.
+	int launch_direct() {
+		Status st;
+		for (uint32_t i = 0; st.ok() && i < n; i++)
+			if (fs[i].err && !fs[i].fr.empty())
+				st = Status{hipMemsetAsync(d_out + (uint64_t)fs[i].first * slot, 0, (uint64_t)fs[i].info.nframes * slot, nullptr), "memset"};
+		if (st.ok() && !descs.empty()) st = upload(buf + rec_off, recs.data(), recs.size() * sizeof(Vp8gAnimFrame));
+		if (st.ok() && ndirect) st = upload((uint8_t*)d_descs(), descs.data(), ndirect * sizeof(Vp8gAnimDesc));
+		if (!st.ok()) return io(st);
+		if (ndirect && vp8g_anim_compose_batch_device(descs.data(), d_descs(), ndirect, t, channels, buf, d_out, nullptr) != 0) return errno;
+		return 0;
+	}
+	int alloc_staging() {
+		uint64_t most = 0;
+		for (const Group& g : groups) most = std::max(most, g.bytes);
+		return groups.empty() ? 0 : dev_alloc(&stg, most);
+	}
+	// The rescale descriptors of a group's canvases, canvas k of a file from its k-th staged canvas into slot first + k.
+	int describe_group(const Group& g) {
+		fd.clear();
+		planar.begin(g.np, g.o_sc);
+		uint32_t f_task = 0;
+		for (uint32_t q = g.q0; q < g.q1; q++) {
+			const File& f = fs[by_route[q]];
+			const uint32_t cw = f.info.canvas_width, ch = f.info.canvas_height;
+			for (uint32_t k = 0; k < f.info.nframes; k++) {
+				const uint64_t src = descs[q].dst + k * canvas_bytes(f), dst = (uint64_t)(f.first + k) * slot;
+				if (f.route == kPlanar) {
+					if (planar.add(cw, ch, src, &f.opt, t, channels, dst) != 0) return EINVAL;
+					continue;
+				}
+				Vp8gScaleArgbTensorDesc d;
+				if (vp8g_make_scale_argb_tensor_desc(cw, ch, src, &f.opt, dst, f_task, &d) != 0) return EINVAL;
+				f_task += d.ntasks;
+				fd.push_back(d);
+			}
+		}
+		return 0;
+	}
+	// One group: composed into the staging buffer, then the fused launch, then the planar launches.  The synchronisation at
+	// the end is the group's own: the next group reuses the staging buffer, `fd` and `planar`.  A launch entry point that
+	// fails leaves the call's errno (EINVAL / ENOMEM before it launched anything, or EIO) and its own text.
+	int run_group(const Group& g) {
+		if (int e = describe_group(g)) return e;
 		const uint32_t cnt = g.q1 - g.q0;
-		e = hipMemcpyAsync(d_descs + g.q0, descs.data() + g.q0, cnt * sizeof(Vp8gAnimDesc), hipMemcpyHostToDevice, nullptr), where = "upload";
-		if (e == hipSuccess && vp8g_anim_compose_batch_device(descs.data() + g.q0, d_descs + g.q0, cnt, &st, 4, buf.p, stg.p, nullptr) != 0) return launch_failed();
-		if (e == hipSuccess && g.nf) {
-			e = hipMemcpyAsync(stg.p + g.o_fd, fd.data(), g.nf * sizeof(fd[0]), hipMemcpyHostToDevice, nullptr);
-			if (e == hipSuccess && vp8g_scale_argb_tensor_batch_device(fd.data(), (const Vp8gScaleArgbTensorDesc*)(stg.p + g.o_fd), g.nf, t, channels, stg.p,
-			                                                           d_out, nullptr) != 0)
-				return launch_failed();
+		const Vp8gTensorOpt st = argb_tensor(1, 1);  // the staging canvases (width and height are not read)
+		if (Status s = upload((uint8_t*)(d_descs() + g.q0), descs.data() + g.q0, cnt * sizeof(Vp8gAnimDesc)); !s.ok()) return io(s);
+		if (vp8g_anim_compose_batch_device(descs.data() + g.q0, d_descs() + g.q0, cnt, &st, 4, buf, stg, nullptr) != 0) return errno;
+		if (g.nf) {
+			if (Status s = upload(stg + g.o_fd, fd.data(), g.nf * sizeof(fd[0])); !s.ok()) return io(s);
+			if (vp8g_scale_argb_tensor_batch_device(fd.data(), (const Vp8gScaleArgbTensorDesc*)(stg + g.o_fd), g.nf, t, channels, stg, d_out, nullptr) != 0)
+				return errno;
 		}
-		if (e == hipSuccess && g.np) {
-			e = hipMemcpyAsync(stg.p + g.o_pd, pd.data(), g.np * sizeof(pd[0]), hipMemcpyHostToDevice, nullptr);
-			if (e == hipSuccess) e = hipMemcpyAsync(stg.p + g.o_td, td.data(), g.np * sizeof(td[0]), hipMemcpyHostToDevice, nullptr);
-			if (e == hipSuccess && (vp8g_scale_argb_batch_device(pd.data(), (const Vp8gScaleArgbDesc*)(stg.p + g.o_pd), g.np, stg.p, stg.p + g.o_work,
-			                                                     stg.p + g.o_sc, nullptr) != 0 ||
-			                        vp8g_tensor_batch_device_argb(td.data(), (const Vp8gTensorArgbDesc*)(stg.p + g.o_td), g.np, t, channels, stg.p + g.o_sc,
-			                                                      d_out, nullptr) != 0))
-				return launch_failed();
+		if (g.np) {
+			Status s = upload(stg + g.o_pd, planar.scale.data(), g.np * sizeof(Vp8gScaleArgbDesc));
+			if (s.ok()) s = upload(stg + g.o_td, planar.tensor.data(), g.np * sizeof(Vp8gTensorArgbDesc));
+			if (!s.ok()) return io(s);
+			if (!planar.launch((const Vp8gScaleArgbDesc*)(stg + g.o_pd), (const Vp8gTensorArgbDesc*)(stg + g.o_td), stg, stg + g.o_work, t, channels,
+			                   d_out, nullptr).ok())
+				return errno;
 		}
-		// (the next group reuses the staging buffer and this group's host descriptors end here)
-		if (e == hipSuccess) e = hipStreamSynchronize(nullptr), where = "sync";
+		return io(Status{hipStreamSynchronize(nullptr), "sync"});
 	}
-	if (e == hipSuccess) e = hipStreamSynchronize(nullptr), where = "sync";
-	if (e != hipSuccess) {
-		vp8g::set_error_text(where, e);
-		return fail_all(status, n, EIO);
+	// Every stage but the last; 0 when the tensor is complete.
+	int run() {
+		slot = channels == 4u ? vp8g_tensor_slot_size_a(t) : vp8g_tensor_slot_size(t);
+		if (int e = parse_files()) return e;
+		layout_frames();
+		if (int e = decode_frames()) return e;
+		if (int e = describe()) return e;
+		if (int e = plan_groups()) return e;
+		if (int e = launch_direct()) return e;
+		if (int e = alloc_staging()) return e;
+		for (const Group& g : groups)
+			if (int e = run_group(g)) return e;
+		return io(Status{hipStreamSynchronize(nullptr), "sync"});
 	}
-	int first = 0;
-	for (uint32_t i = 0; i < n; i++) {
-		if (status) status[i] = fs[i].err;
-		if (fs[i].err && !first) first = fs[i].err;
+	// The per-file status of a call that ran; the first error in index order, or 0.
+	int finish(int* status) const {
+		int first = 0;
+		for (uint32_t i = 0; i < n; i++) {
+			if (status) status[i] = fs[i].err;
+			if (fs[i].err && !first) first = fs[i].err;
+		}
+		return first;
 	}
-	return first ? vp8g::fail(first) : 0;
-}
+};
 
 }  // namespace
 
@@ -596,11 +655,17 @@ VP8G_API int vp8g_decode_webp_anim_tensor_scaled(const ByteSpan* files, uint32_t
 	    (uintptr_t)d_out % (uint32_t)elem_bytes(t->dtype) || (flags & ~(VP8G_BATCH_DEVICE_M05 | VP8G_BATCH_MULTI_PARTITION)) ||
 	    (n_opts != 0 && n_opts != 1 && n_opts != n) || (n_opts && !opts))
 		return vp8g::fail(EINVAL);
+	int whole = 0, first = 0;  // the errno of a call that fails as a whole; else of the first file that failed
 	try {
-		return anim_tensor(files, n, filtered, threads, flags, opts, n_opts, stage_bytes, t, channels, (uint8_t*)d_out, timestamps, status);
+		AnimCall c{files, n, filtered, threads, flags, opts, n_opts, stage_bytes, t, channels, (uint8_t*)d_out, timestamps};
+		whole = c.run();
+		if (!whole) first = c.finish(status);
 	} catch (const std::bad_alloc&) {
-		return fail_all(status, n, ENOMEM);
+		whole = ENOMEM;
 	}
+	// (~AnimCall has run: nothing of the call is in flight, and errno is set after it)
+	if (whole) return fail_all(status, n, whole);
+	return first ? vp8g::fail(first) : 0;
 }
 
 VP8G_API int vp8g_decode_webp_anim_tensor(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,

@@ -112,6 +112,25 @@ inline size_t chain_lds_bytes(uint32_t list_max) { return (size_t)kQList + 4 * (
 void set_error_text(const char* where, hipError_t e);
 inline int fail(int e) { return errno = e, -1; }
 
+// What a stage of an end-to-end call returns: hipSuccess, or the HIP error and the step that met it (vp8g_last_error's
+// text).  capi_status: of one of the library's C entry points, which leave HIP's error, if there was one, behind their
+// -1; errno stays what the entry point left, for a caller that passes it on.
+struct Status {
+	hipError_t he = hipSuccess;
+	const char* where = nullptr;
+	bool ok() const { return he == hipSuccess; }
+};
+inline Status capi_status(int rc, const char* where) {
+	if (rc == 0) return Status{};
+	const int en = errno;
+	const hipError_t e = hipGetLastError();
+	errno = en;
+	return Status{e == hipSuccess ? hipErrorInvalidValue : e, where};
+}
+
+// Offsets inside the device buffers of the end-to-end calls: every region starts on 256 bytes.
+inline uint64_t al256(uint64_t v) { return (v + 255u) & ~(uint64_t)255u; }
+
 int device_cus();  // the device's CU count; 0 = unknown
 // The grid of a launch whose workgroups loop over `tasks`: per_cu workgroups for every CU, no more than there are tasks.
 inline uint32_t grid_for(uint64_t tasks, uint32_t per_cu) {

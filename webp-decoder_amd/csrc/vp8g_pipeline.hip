@@ -36,11 +36,17 @@
 #include <vector>
 
 #include "../host/vp8_front.h"
+#include "vp8g_argb_batch.h"
 #include "vp8g_device.h"
 
 #define VP8G_API extern "C" __attribute__((visibility("default")))
 
 namespace {
+
+using vp8g::al256;
+using vp8g::ArgbScaleBatch;
+using vp8g::capi_status;
+using vp8g::Status;
 
 constexpr uint32_t kChunkFrames = 32;          // frames per host-m05 chunk (at most; tools/chunk_sweep.py: 32 shortens the tail)
 constexpr uint64_t kChunkMbs = 2u << 20;       // macroblocks per chunk (at most, unless one frame is bigger)
@@ -89,7 +95,6 @@ __global__ __launch_bounds__(256) void expand_kernel(const uint16_t* __restrict_
 	d4[1] = make_uint4(w[4], w[5], w[6], w[7]);
 }
 
-inline uint64_t al256(uint64_t x) { return (x + 255u) & ~(uint64_t)255u; }
 // bitstream slot of a payload: 16-B aligned start, >= 512 bytes of slack (the device bool
 // decoder loads its 256-byte windows one ahead, up to 512 bytes past a partition's end)
 inline uint64_t bits_slot(uint32_t psize) { return ((uint64_t)psize + 512u + 15u) & ~(uint64_t)15u; }
@@ -272,8 +277,7 @@ struct Slot {
 	std::vector<Vp8gScaleDesc> asdescs;  //   their alpha planes through the rescaler
 	std::vector<Vp8gTensorAlpha> talpha; //   one per tensor descriptor
 	std::vector<Vp8gLosslessDesc> ldescs;     // lossless sink: the chunk's lossless frames
-	std::vector<Vp8gTensorArgbDesc> ltdescs;  //   and their tensor descriptors
-	std::vector<Vp8gScaleArgbDesc> lsdescs;   //   those of them that are cropped / rescaled (VP8G_X_LOSSLESS_SCALE)
+	ArgbScaleBatch lbatch;                    //   their way into the tensor, cropped / rescaled (VP8G_X_LOSSLESS_SCALE) or as they are
 	std::vector<Vp8gTokFrame> jobs;  // device m05
 	uint32_t status = 0;
 	std::vector<D2H> d2h;          // the chunk's downloads (issued by a Copier)
@@ -426,19 +430,6 @@ void plan_frames(const ByteSpan* files, uint32_t n, bool tok, uint32_t threads, 
 		if (!dev[by_size[k]]) order[p++] = by_size[k];
 }
 
-// What a stage returns: hipSuccess, or the HIP error and the step that met it (vp8g_last_error's text).  capi_status:
-// of one of the library's C entry points, which leave HIP's error, if there was one, behind their -1.
-struct Status {
-	hipError_t he = hipSuccess;
-	const char* where = nullptr;
-	bool ok() const { return he == hipSuccess; }
-};
-inline Status capi_status(int rc, const char* where) {
-	if (rc == 0) return Status{};
-	const hipError_t e = hipGetLastError();
-	return Status{e == hipSuccess ? hipErrorInvalidValue : e, where};
-}
-
 // Where a call's pictures go, and what happens to them on the way (one per entry point).
 struct Sinks {
 	const Vp8gScaleOpt* opts = nullptr;   // crop / rescale on the device (vp8g_scale.hip): one for all frames or one each
@@ -529,7 +520,7 @@ ChunkLayout make_layout(const ChunkShape& sh, bool tok, const Sinks& sk, const v
 	L.lout = o, o = al256(o + sh.loutb);
 	L.ldesc = o, o = al256(o + sh.nl * sizeof(Vp8gLosslessDesc));
 	L.ltdesc = o, o = al256(o + sh.nl * sizeof(Vp8gTensorArgbDesc));
-	L.lswork = o, o = al256(o + (sh.nls ? vp8g_scale_argb_head_size(sh.nls) + sh.lsworkb : 0));
+	L.lswork = o, o = al256(o + ArgbScaleBatch::head_bytes(sh.nls) + sh.lsworkb);
 	L.lsout = o, o = al256(o + sh.lsoutb);
 	L.lsdesc = o, o = al256(o + sh.nls * sizeof(Vp8gScaleArgbDesc));
 	L.total = o;
@@ -748,14 +739,12 @@ struct Pipeline {
 				// a frame that is cropped / rescaled also holds its planes and its scaled picture
 				Vp8fScaleGeom g;
 				const bool scaled = !lossless_whole(fi, &g);
-				const uint64_t workb = scaled ? vp8g_scale_argb_work_size(feed.ll[fi].width, feed.ll[fi].height, sk.opt_of(fi)) : 0u;
-				const uint64_t soutb = scaled ? 4ull * g.out_w * g.out_h : 0u;
-				const uint64_t fx = extra_mbs(al256(srcb) + al256(outb) + al256(workb) + al256(soutb) +
-				                              (scaled ? 4u * sizeof(Vp8gScaleDesc) + sizeof(Vp8gScaleArgbDesc) : 0u));
+				const ArgbScaleBatch::Need nd = scaled ? ArgbScaleBatch::need(feed.ll[fi].width, feed.ll[fi].height, sk.opt_of(fi)) : ArgbScaleBatch::Need{0, 0, 0};
+				const uint64_t fx = extra_mbs(al256(srcb) + al256(outb) + nd.work + nd.scaled + nd.descs);
 				if (!(c.idx.empty() && c.lidx.empty()) && sh.mbs + xmbs + fx > caps.mbs[c.tok]) break;
 				xmbs += fx;
 				sh.lsrcb = al256(sh.lsrcb + srcb), sh.loutb = al256(sh.loutb + outb);
-				if (scaled) sh.nls++, sh.lsworkb = al256(sh.lsworkb + workb), sh.lsoutb = al256(sh.lsoutb + soutb);
+				if (scaled) sh.nls++, sh.lsworkb += nd.work, sh.lsoutb += nd.scaled;
 				c.lidx.push_back(fi);
 				continue;
 			}
@@ -1033,20 +1022,17 @@ struct Pipeline {
 	// Lossless sink: the residual images and transform data of the chunk's lossless frames are uploaded, the transforms
 	// inverted (vp8g_lossless.hip) and the ARGB pictures written to their slots of the tensor (same stream); with
 	// VP8G_X_LOSSLESS_SCALE the pictures whose option is not the identity pass through vp8g_scale_argb_batch_device between
-	// the two, and the tensor kernel reads their scaled copies.
+	// the two, and the tensor kernel reads their scaled copies (ArgbScaleBatch, vp8g_argb_batch.h, keeps the offsets and
+	// counters of those two launches).
 	Status launch_lossless(Chunk& c) {
 		Slot& s = c.s;
 		const ChunkLayout& L = c.L;
 		uint8_t* d = s.buf;
 		s.ldescs.clear();
-		s.ltdescs.clear();
-		s.lsdescs.clear();
+		s.lbatch.begin(c.sh.nls, L.lsout);
 		s.frames.insert(s.frames.end(), c.lidx.begin(), c.lidx.end());  // (their host data lives until the slot retires)
+		const uint32_t channels = sk.alpha ? 4u : 3u;
 		uint64_t so = 0, oo = 0;
-		// cropped / rescaled frames (VP8G_X_LOSSLESS_SCALE): offsets in the rescaler's work buffer (L.lswork, its head
-		// first) and in the scaled pictures (L.lsout); the running counters of vp8g_make_scale_argb_desc
-		uint64_t wo = vp8g_scale_argb_head_size(c.sh.nls), po = 0;
-		uint32_t planes = 0, t_split = 0, t_scale = 0, t_merge = 0;
 		for (uint32_t fi : c.lidx) {
 			const Vp8fLosslessImage& im = feed.ll[fi];
 			Vp8gLosslessTransform tr[4];
@@ -1061,43 +1047,26 @@ struct Pipeline {
 			}
 			so = al256(so);
 			Vp8gLosslessDesc ld;
-			Vp8gTensorArgbDesc td;
-			Vp8gScaleArgbDesc sd;
 			Vp8fScaleGeom g;
-			const bool scaled = !lossless_whole(fi, &g);
-			const uint64_t pic = scaled ? L.lsout + po : L.lout + oo;  // what the tensor kernel reads
-			if (vp8g_make_lossless_desc(im.width, im.height, src, L.lout + oo, im.ntransforms, tr, (uint32_t)s.ldescs.size(), &ld) != 0 ||
-			    (scaled && vp8g_make_scale_argb_desc(im.width, im.height, L.lout + oo, sk.opt_of(fi), wo, L.lsout + po, planes, t_split,
-			                                         t_scale, t_merge, &sd) != 0) ||
-			    vp8g_make_tensor_argb_desc(sk.topt, sk.alpha ? 4u : 3u, pic, (uint64_t)fi * sk.tslot, 0, &td) != 0) {
+			const uint64_t pic = L.lout + oo, dst = (uint64_t)fi * sk.tslot;  // the transform kernel's picture; the frame's slot
+			if (vp8g_make_lossless_desc(im.width, im.height, src, pic, im.ntransforms, tr, (uint32_t)s.ldescs.size(), &ld) != 0 ||
+			    (lossless_whole(fi, &g) ? s.lbatch.add_whole(sk.topt, channels, pic, dst)
+			                            : s.lbatch.add(im.width, im.height, pic, sk.opt_of(fi), sk.topt, channels, dst)) != 0) {
 				feed.err[fi] = EINVAL;  // (cannot happen for a stream the host decoder accepted and a size checked when gathered)
 				continue;
 			}
-			td.task0 = (uint32_t)s.ltdescs.size() * td.ntasks;
 			oo = al256(oo + 4u * (uint64_t)im.width * im.height);
 			s.ldescs.push_back(ld);
-			s.ltdescs.push_back(td);
-			if (scaled) {
-				s.lsdescs.push_back(sd);
-				planes += sd.nplanes, t_split += sd.split_ntasks, t_scale += sd.scale_ntasks, t_merge += sd.merge_ntasks;
-				wo = al256(wo + sd.work_bytes), po = al256(po + 4u * (uint64_t)sd.width * sd.height);
-			}
 			live[fi] = 1;
 		}
 		if (s.ldescs.empty()) return c.up_status();
-		if (!c.up(L.ldesc, s.ldescs) || !c.up(L.ltdesc, s.ltdescs) || !(s.lsdescs.empty() || c.up(L.lsdesc, s.lsdescs)))
+		if (!c.up(L.ldesc, s.ldescs) || !c.up(L.ltdesc, s.lbatch.tensor) || !(s.lbatch.scale.empty() || c.up(L.lsdesc, s.lbatch.scale)))
 			return c.up_status();
 		const uint32_t nl = (uint32_t)s.ldescs.size();
 		if (int rc = vp8g_lossless_batch_device(s.ldescs.data(), (const Vp8gLosslessDesc*)(d + L.ldesc), nl, d, d, c.stream); rc != 0)
 			return capi_status(rc, "lossless launch");
-		if (!s.lsdescs.empty())
-			if (int rc = vp8g_scale_argb_batch_device(s.lsdescs.data(), (const Vp8gScaleArgbDesc*)(d + L.lsdesc), (uint32_t)s.lsdescs.size(),
-			                                          d, d + L.lswork, d, c.stream);
-			    rc != 0)
-				return capi_status(rc, "lossless scale launch");
-		return capi_status(vp8g_tensor_batch_device_argb(s.ltdescs.data(), (const Vp8gTensorArgbDesc*)(d + L.ltdesc), nl, sk.topt,
-		                                                 sk.alpha ? 4u : 3u, d, sk.d_tensor, c.stream),
-		                   "tensor launch");
+		return s.lbatch.launch((const Vp8gScaleArgbDesc*)(d + L.lsdesc), (const Vp8gTensorArgbDesc*)(d + L.ltdesc), d, d + L.lswork, sk.topt, channels,
+		                       sk.d_tensor, c.stream);
 	}
 	// D2H into the callers' images (and of the status word, whatever the sink), by this kind's Copier once the
 	// kernels are done; then the workers may run a window ahead of this chunk.
