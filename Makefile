@@ -21,7 +21,7 @@ HIP_SRC := $(PKG)/csrc/vp8g_kernels.hip $(PKG)/csrc/vp8g_plan.hip $(PKG)/csrc/vp
 	$(PKG)/csrc/vp8g_lossless.hip $(PKG)/csrc/vp8g_scale_argb.hip $(PKG)/csrc/vp8g_scale_argb_fused.hip \
 	$(PKG)/csrc/vp8g_anim.hip
 HIP_HDR := $(PKG)/csrc/vp8g_device.h include/vp8g.h $(PKG)/host/vp8_front.h $(PKG)/csrc/vp8g_quad.inc $(PKG)/csrc/vp8g_rgb_device.h \
-	$(PKG)/csrc/vp8g_tensor_device.h $(PKG)/csrc/vp8g_skew.h $(PKG)/csrc/vp8g_argb_batch.h
+	$(PKG)/csrc/vp8g_tensor_device.h $(PKG)/csrc/vp8g_scale_device.h $(PKG)/csrc/vp8g_skew.h $(PKG)/csrc/vp8g_argb_batch.h
 # libvp8g links the host front end (the end-to-end batch path runs m05 on worker threads)
 HIP_LINK := -L$(LIB) -lvp8host -Wl,-rpath,'$$ORIGIN' -lpthread
 

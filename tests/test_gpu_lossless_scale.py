@@ -74,6 +74,25 @@ def test_kernels_vs_restatement(vp8g):
             assert np.array_equal(g, vp8g.host_scale_argb(p, o)), shift
 
 
+def test_every_alpha_and_colour_pair(vp8g):
+    """Every (alpha, colour byte) pair through the one premultiply / un-premultiply of vp8g_scale_device.h: row = alpha,
+    column = c, scaled to the picture's own size (still premultiply -> rescale -> un-premultiply), by the planar route at
+    every dword phase of the split's 16-byte loads and by the fused kernel.  Expected bytes are the host restatement's."""
+    a, c = np.arange(256, dtype=np.uint32)[:, None], np.arange(256, dtype=np.uint32)[None, :]
+    pic = a << 24 | ((7 * c + a) & 255) << 16 | (255 - c) << 8 | c
+    o = vp8g.scale_opt(scale=(256, 256))
+    want = vp8g.host_scale_argb(pic, o)
+    # not vacuous: the round trip alone, which changes most pixels and keeps every alpha
+    assert np.array_equal(want, vp8g.host_argb_mult(vp8g.host_argb_mult(pic), inverse=True))
+    assert (want != pic).mean() > 0.6 and np.array_equal(want >> 24, pic >> 24)
+    for shift in range(4):
+        (got,) = vp8g.gpu_scale_argb([pic], [o], src_shift=shift)
+        assert np.array_equal(got, want), shift
+    topt = vp8g.tensor_opt((256, 256), "uint8", "NHWC")
+    (t,) = vp8g.gpu_scale_argb_tensor([pic], [o], topt, 4)
+    assert torch.equal(t, vp8g.host_tensor_argb(want, topt, 4))
+
+
 def test_fixtures_equal_libwebps_rgba(vp8g, golden):
     names = sorted({c["file"] for c in golden["cases"]})
     images = []

@@ -15,9 +15,10 @@ the host's bytes first.
     vp8g_decode_webp_batch_tensor_any into a float16 NHWC RGBA tensor: 224x224 with VP8G_X_LOSSLESS_SCALE, beside the
     same files at their own size without it.
 
-Writes profiles/lossless_scale_bench.json and prints its rows.
+Writes profiles/lossless_scale_bench.json (or --out) and prints its rows.
 
   python tools/lossless_scale_bench.py [--images 256] [--runs 9] [--threads 16] [--e2e-frames 64] [--e2e-runs 9] [--trace]
+                                       [--out PATH]
 """
 import argparse
 import ctypes as C
@@ -203,6 +204,7 @@ def main():
     ap.add_argument("--e2e-frames", type=int, default=64)
     ap.add_argument("--e2e-runs", type=int, default=9)
     ap.add_argument("--trace", action="store_true", help="only the device calls of (a), for a kernel trace; writes nothing")
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "lossless_scale_bench.json"))
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream(dev)
@@ -216,7 +218,7 @@ def main():
            "build": f"sources sha256 {tree} (csrc/*, host/*, include/vp8g.h)",
            "timing": "HIP events (device), perf_counter (host, end to end); cold run discarded; median, min .. max",
            "rows": rows, "end_to_end": e2e}
-    out = ROOT / "profiles" / "lossless_scale_bench.json"
+    out = pathlib.Path(a.out)
     out.write_text(json.dumps(doc, indent=1) + "\n")
     print(f"wrote {out}")
 

@@ -2,24 +2,10 @@
 // (include/vp8g.h: vp8g_scale_batch_device, yuv420_rescale; host restatement host/vp8_scale.c;
 // DESIGN.md §14).
 //
-// libwebp's rescaler is a sequential import/export loop, but its result has a closed form: with
-// E(k) = ceil(k W / w) and F(j) = ceil(j H / h) (all values wrapping u32),
-//
-//   frow(y, k) = (carry + sum of s[y][x], x in [E(k), E(k+1))) * w - s[y][E(k+1)-1] * (E(k+1) w - (k+1) W)
-//                carry = k > 0 ? MULT(s[y][E(k)-1] * (E(k) w - k W), fx) : 0
-//   out(j, k)  = MULT(irow - FLOOR(frow(F(j+1)-1, k), ys), fxy)        ys = fy * (F(j+1) h - (j+1) H)
-//                irow = FLOOR(frow(F(j)-1, k), ys0) + sum of frow(y, k), y in [F(j), F(j+1))
-//
-// so every output sample depends only on its own source footprint plus one boundary row and column.
-//
-// One launch scales a batch of images of mixed sizes.  A workgroup task is one plane's tile of
-// tile_w output columns x run_h output rows.  It walks the source rows of its run top to bottom
-// (one extra row above when the run does not start the plane: the boundary row F(j0) - 1), staged
-// through LDS in blocks of block_rows row segments loaded with 16-byte loads (the next block is in
-// flight in registers while the current one is summed).  `group` lanes share an output column
-// (each sums every group-th sample of the footprint, combined by a butterfly of lane exchanges), so
-// a 17:1 and a 16383:1 reduction keep the lanes as busy as a 1:1 one; each lane keeps its column's
-// irow in a register and lane 0 of the group emits a sample at every F(j+1) boundary.
+// The closed form of libwebp's rescaler, the column footprint, the row walk of a run and the staging of a tile's rows
+// through LDS are stated once, in vp8g_scale_device.h; scale_kernel below is that walk for one byte plane.  One launch
+// scales a batch of images of mixed sizes; a workgroup task is one plane's tile of tile_w output columns x run_h
+// output rows.
 //
 // Planes that expand in x or in y (VP8G_SCALE_EXPAND; libwebp's bilinear path) belong to a second
 // kernel, expand_kernel below, launched on the same stream only when a batch has such a plane.  The
@@ -32,47 +18,36 @@
 
 #include "../host/vp8_front.h"
 #include "vp8g_device.h"
+#include "vp8g_scale_device.h"
 
 #define VP8G_API extern "C" __attribute__((visibility("default")))
 
 namespace {
 
-constexpr uint32_t kThreads = 256;
+using namespace vp8g_scale;
+
 constexpr uint32_t kBufBytes = 16448;  // LDS staging: one 16383-sample row segment at any alignment
-constexpr uint32_t kBufChunks = kBufBytes / 16u;
-constexpr uint32_t kMaxChunks = (kBufChunks + kThreads - 1u) / kThreads;  // 16-B loads per thread and block
-constexpr uint32_t kRunSrcRows = 64;   // source rows per task (about): 1 / 64 of the rows is read twice
-constexpr uint32_t kLanePerCol = 12;   // footprint samples per lane before another lane joins the column
 constexpr uint32_t kMaxDim = 16383;
 static_assert(kBufBytes % 16 == 0 && kBufBytes >= kMaxDim + 30, "staging buffer");
-
-__device__ __forceinline__ uint32_t mult_fix(uint32_t x, uint32_t y) { return __umulhi(x, y) + ((x * y) >> 31); }
-__device__ __forceinline__ uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1u) / b; }
 
 __global__ __launch_bounds__(kThreads) void scale_kernel(const Vp8gScaleDesc* __restrict__ descs, uint32_t n,
                                                          const uint8_t* __restrict__ src, uint8_t* __restrict__ dst) {
 	__shared__ __attribute__((aligned(16))) uint8_t lds[kBufBytes];
 	const uint32_t task = blockIdx.x, tid = threadIdx.x;
 	// the image that owns this task (tasks are numbered image by image), then its plane
-	uint32_t lo = 0, hi = n - 1u;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi + 1u) >> 1;
-		if (descs[mid].task0 <= task) lo = mid;
-		else hi = mid - 1u;
-	}
-	const Vp8gScaleDesc& D = descs[lo];
+	const Vp8gScaleDesc& D = descs[task_owner<Vp8gScaleDesc, &Vp8gScaleDesc::task0>(descs, n, task)];
 	uint32_t t = task - D.task0;
 	if (task < D.task0 || t >= D.ntasks) return;
 	uint32_t pi = 0;
 	while (pi < 2u && t >= D.p[pi].ntasks) t -= D.p[pi].ntasks, pi++;
 	const Vp8gScalePlane& P = D.p[pi];
 	const uint32_t W = P.src_w, H = P.src_h, w = P.dst_w, h = P.dst_h;
-	const uint32_t fx = P.fx, fy = P.fy, fxy = P.fxy;
-	const uint32_t G = P.group, pitch = P.pitch, R = P.block_rows, sstride = P.src_stride;
+	const uint32_t fx = P.fx, fxy = P.fxy;
+	const uint32_t G = P.group, pitch = P.pitch, R = P.block_rows;
 	if (t >= P.ntasks || G == 0 || (G & (G - 1u)) || G > 64u || P.tile_w * G != kThreads || P.tiles_x == 0) return;
 	const uint32_t tx = t % P.tiles_x, ry = t / P.tiles_x;
 
-	// -- columns: the tile's source segment [xs, xe) and this lane's footprint [e0, e1)
+	// -- columns: the tile's source segment [xs, xe) and this lane's footprint
 	const uint32_t k0 = tx * P.tile_w, kend = min(k0 + P.tile_w, w);
 	const uint32_t j0 = ry * P.run_h, j1 = min(j0 + P.run_h, h);
 	if (k0 >= w || j0 >= h) return;
@@ -81,101 +56,36 @@ __global__ __launch_bounds__(kThreads) void scale_kernel(const Vp8gScaleDesc* __
 	const uint32_t span = xe - xs;
 	if (span + 15u > pitch || (pitch & 15u) || R == 0 || (uint64_t)pitch * R > kBufBytes) return;  // (never: see make_plane)
 	const uint32_t gi = tid & (G - 1u), k = k0 + tid / G;
-	const bool active = k < kend;
-	uint32_t e0 = xs, e1 = xs, a0 = 0, a1 = 0;
-	if (active) {
-		e0 = ceil_div(k * W, w), e1 = ceil_div((k + 1u) * W, w);
-		a0 = e0 * w - k * W, a1 = e1 * w - (k + 1u) * W;
-	}
-	const bool carry_in = active && k > 0;
+	const ShrinkCol col(k, kend, xs, W, w);
+	ShrinkRows rows(j0, j1, H, h, P.fy);
+	StagedRows<1, kBufBytes> stage(src, (uintptr_t)src + P.src, P.src_stride, W, H, xs, span, pitch, tid);  // (+ P.src: the window's first sample)
 
-	// -- rows: source rows [y_first, y_last); with j0 > 0 the first one is the boundary row F(j0) - 1
-	const bool boundary = j0 > 0;
-	const uint32_t Fj0 = ceil_div(j0 * H, h);
-	const uint32_t y_first = boundary ? Fj0 - 1u : 0u, y_last = ceil_div(j1 * H, h);
-	const uint32_t ys0 = fy * (Fj0 * h - j0 * H);
-
-	// -- staging: row r of a block sits at r * pitch, its segment starting at byte (address & 15)
-	const uintptr_t base = (uintptr_t)src + P.src;  // the window's first sample
-	const uintptr_t ok_lo = base, ok_hi = base + (uintptr_t)(H - 1u) * sstride + W;  // the window's own bytes
-	const uint32_t cpr = pitch >> 4;
-	uint32_t ch_r[kMaxChunks], ch_c[kMaxChunks];
-#pragma unroll
-	for (uint32_t m = 0; m < kMaxChunks; m++) {
-		const uint32_t q = tid + m * kThreads;
-		ch_r[m] = q / cpr, ch_c[m] = q % cpr;
-	}
-	uint4 pre[kMaxChunks];
-	auto load_block = [&](uint32_t yb, uint32_t nr) {
-#pragma unroll
-		for (uint32_t m = 0; m < kMaxChunks; m++) {
-			pre[m] = make_uint4(0, 0, 0, 0);
-			if (ch_r[m] >= nr) continue;
-			const uintptr_t row = base + (uintptr_t)(yb + ch_r[m]) * sstride + xs;  // first wanted byte
-			const uintptr_t a = (row & ~(uintptr_t)15) + 16u * ch_c[m];
-			if (a >= row + span) continue;  // past the segment
-			if (a >= ok_lo && a + 16u <= ok_hi) {
-				pre[m] = *(const uint4*)a;
-			} else {  // a chunk that straddles the window's first or last byte: only the bytes inside
-				uint32_t v[4] = {0, 0, 0, 0};
-				for (uint32_t b = 0; b < 16u; b++)
-					if (a + b >= ok_lo && a + b < ok_hi) v[b >> 2] |= (uint32_t)(*(const uint8_t*)(a + b)) << (8u * (b & 3u));
-				pre[m] = make_uint4(v[0], v[1], v[2], v[3]);
-			}
-		}
-	};
-	auto store_block = [&](uint32_t nr) {
-#pragma unroll
-		for (uint32_t m = 0; m < kMaxChunks; m++)
-			if (ch_r[m] < nr) *(uint4*)(lds + ch_r[m] * pitch + 16u * ch_c[m]) = pre[m];
-	};
-
-	// F(j+1) and ya = F(j+1) h - (j+1) H step without a divide: H = qH h + rH, and from one output row to
-	// the next F grows by qH (+ 1 when rH exceeds what the last row left over)
-	const uint32_t qH = H / h, rH = H - qH * h;
-	uint32_t irow = 0, j = j0, nextF = ceil_div((j0 + 1u) * H, h);
-	uint32_t ya = nextF * h - (j0 + 1u) * H;
+	uint32_t irow = 0;
 	uint8_t* out = dst + P.dst + k;
-	load_block(y_first, min(R, y_last - y_first));
-	for (uint32_t yb = y_first; yb < y_last; yb += R) {
+	const uint32_t y_last = rows.y_last;
+	stage.load(rows.y_first, min(R, y_last - rows.y_first));
+	for (uint32_t yb = rows.y_first; yb < y_last; yb += R) {
 		const uint32_t nr = min(R, y_last - yb);
 		__syncthreads();  // the previous block has been summed
-		store_block(nr);
+		stage.store(lds, nr, [](uint32_t v) { return v; });
 		__syncthreads();
-		if (yb + R < y_last) load_block(yb + R, min(R, y_last - (yb + R)));  // in flight while this block is summed
+		if (yb + R < y_last) stage.load(yb + R, min(R, y_last - (yb + R)));  // in flight while this block is summed
 		for (uint32_t r = 0; r < nr; r++) {
 			const uint32_t y = yb + r;
-			const uint32_t mis = (uint32_t)((base + (uintptr_t)y * sstride + xs) & 15u);
-			const uint8_t* row = lds + r * pitch + mis - xs;  // row[x] = s[y][x] for x in [xs, xe)
+			const uint8_t* row = lds + stage.lds_offset(r, y) - xs;  // row[x] = s[y][x] for x in [xs, xe)
 			uint32_t part = 0;
-			for (uint32_t x = e0 + gi; x < e1; x += G) part += row[x];
+			for (uint32_t x = col.e0 + gi; x < col.e1; x += G) part += row[x];
 			for (uint32_t o = G >> 1; o; o >>= 1) part += __shfl_xor(part, (int)o);
-			uint32_t frow = 0;
-			if (active) {
-				// (24-bit multiplies: samples < 2^8, a0 / a1 / w < 2^14, a row sum < 2^22)
-				const uint32_t carry = carry_in ? mult_fix(__umul24(row[e0 - 1u], a0), fx) : 0u;
-				frow = __umul24(carry + part, w) - __umul24(row[e1 - 1u], a1);
-			}
-			if (boundary && y == y_first) {  // the row shared with the run above: only its lower part
-				irow = ys0 ? __umulhi(frow, ys0) : 0u;
+			const uint32_t frow = col.active ? col.frow(col.carry_in ? row[col.e0 - 1u] : 0u, part, row[col.e1 - 1u], w, fx) : 0u;
+			if (rows.shared_row(y)) {  // the row shared with the run above: only its lower part
+				irow = rows.lower_part(frow);
 				continue;
 			}
 			irow += frow;
-			if (y + 1u != nextF) continue;
-			const uint32_t ys = fy * ya;
-			const uint32_t frac = ys ? __umulhi(frow, ys) : 0u;
-			uint32_t v;
-			if (fxy) {
-				const int32_t sv = (int32_t)mult_fix(irow - frac, fxy);
-				v = sv > 255 ? 255u : (uint32_t)sv & 255u;
-			} else {
-				v = irow & 255u;  // (W == 1 and h == H: the sums are the samples)
-			}
-			if (active && gi == 0) out[(size_t)j * P.dst_stride] = (uint8_t)v;
-			irow = frac;
-			j++;
-			if (rH > ya) nextF += qH + 1u, ya = h - (rH - ya);
-			else nextF += qH, ya -= rH;
+			if (!rows.exports(y)) continue;
+			const uint32_t v = rows.sample(irow, frow, fxy);
+			if (col.active && gi == 0) out[(size_t)rows.j * P.dst_stride] = (uint8_t)v;
+			rows.next();
 		}
 	}
 }
@@ -203,29 +113,20 @@ __global__ __launch_bounds__(kThreads) void scale_kernel(const Vp8gScaleDesc* __
 // shrinks here, a lane sums its footprint with a plain loop (a 1000:1 shrink beside an expansion is
 // not a performance target).
 // xe and not ye: one lane per output column walks the run's source rows with its irow in a register,
-// exactly as scale_kernel does with group = 1; the four lanes of an aligned dword combine their
-// samples by lane exchange and one of them stores it.
+// the row walk of vp8g_scale_device.h as scale_kernel does it with group = 1 (and its run height); the
+// four lanes of an aligned dword combine their samples by lane exchange and one of them stores it.
 // Source samples are read straight from global memory (two taps per sum; the rows are re-read from
 // L1 / L2 by the neighbouring columns).
 constexpr uint32_t kXLdsBytes = 32768;                        // rows of horizontal sums
 constexpr uint32_t kXMinTile = 64, kXMaxTile = 256;           // output columns per task (ye)
 constexpr uint32_t kXMaxRows = kXLdsBytes / (4u * kXMinTile);  // 128 LDS rows at the narrowest tile
-constexpr uint32_t kXRunSrcRows = 64;                         // source rows per task (about), xe and not ye
-
-__device__ __forceinline__ uint32_t clamp_u8(uint32_t v) { return (int32_t)v > 255 ? 255u : v & 255u; }
 
 __global__ __launch_bounds__(kThreads) void expand_kernel(const Vp8gScaleDesc* __restrict__ descs, uint32_t n,
                                                           const uint8_t* __restrict__ src, uint8_t* __restrict__ dst) {
 	__shared__ __attribute__((aligned(16))) uint32_t sums[kXLdsBytes / 4u];
 	__shared__ uint32_t row_b[kXMaxRows], row_cur[kXMaxRows];
 	const uint32_t task = blockIdx.x, tid = threadIdx.x;
-	uint32_t lo = 0, hi = n - 1u;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi + 1u) >> 1;
-		if (descs[mid].task0 <= task) lo = mid;
-		else hi = mid - 1u;
-	}
-	const Vp8gScaleDesc& D = descs[lo];
+	const Vp8gScaleDesc& D = descs[task_owner<Vp8gScaleDesc, &Vp8gScaleDesc::task0>(descs, n, task)];
 	uint32_t t = task - D.task0;
 	if (task < D.task0 || t >= D.ntasks) return;
 	uint32_t pi = 0;
@@ -244,17 +145,13 @@ __global__ __launch_bounds__(kThreads) void expand_kernel(const Vp8gScaleDesc* _
 	// -- this lane's column of the horizontal pass: the two taps (xe) or the footprint [e0, e1)
 	const uint32_t c = tid & (tw - 1u), k = k0 + c;
 	const bool colok = k < kend;
-	uint32_t i0 = 0, acc = 0, e0 = 0, e1 = 0, a0 = 0, a1 = 0;
-	if (colok) {
-		if (xexp) {
-			const uint32_t up = ceil_div(k * (W - 1u), w - 1u);
-			i0 = up ? up - 1u : 0u;
-			acc = (i0 + 1u) * (w - 1u) - k * (W - 1u);
-		} else {
-			e0 = ceil_div(k * W, w), e1 = ceil_div((k + 1u) * W, w);
-			a0 = e0 * w - k * W, a1 = e1 * w - (k + 1u) * W;
-		}
+	uint32_t i0 = 0, acc = 0;
+	if (colok && xexp) {
+		const uint32_t up = ceil_div(k * (W - 1u), w - 1u);
+		i0 = up ? up - 1u : 0u;
+		acc = (i0 + 1u) * (w - 1u) - k * (W - 1u);
 	}
+	const ShrinkCol col(k, xexp ? 0u : kend, 0u, W, w);  // (xe: no footprint)
 	const uint8_t* sbase = src + P.src;  // the window's first sample; every load below is row y < H, column < W
 	// four source rows at a time, so that their loads are in flight together
 	auto hsum4 = [&](const uint32_t (&y)[4], uint32_t (&f)[4]) {
@@ -270,16 +167,16 @@ __global__ __launch_bounds__(kThreads) void expand_kernel(const Vp8gScaleDesc* _
 			return;
 		}
 		uint32_t sum[4] = {0, 0, 0, 0}, last[4] = {0, 0, 0, 0}, cs[4] = {0, 0, 0, 0};
-		if (k > 0) {
+		if (col.carry_in) {
 #pragma unroll
-			for (uint32_t q = 0; q < 4u; q++) cs[q] = row[q][e0 - 1u];
+			for (uint32_t q = 0; q < 4u; q++) cs[q] = row[q][col.e0 - 1u];
 		}
-		for (uint32_t x = e0; x < e1; x++) {  // (e1 > e0: W >= w)
+		for (uint32_t x = col.e0; x < col.e1; x++) {  // (e1 > e0: W >= w)
 #pragma unroll
 			for (uint32_t q = 0; q < 4u; q++) last[q] = row[q][x], sum[q] += last[q];
 		}
 #pragma unroll
-		for (uint32_t q = 0; q < 4u; q++) f[q] = (mult_fix(cs[q] * a0, fx) + sum[q]) * w - last[q] * a1;
+		for (uint32_t q = 0; q < 4u; q++) f[q] = col.frow(cs[q], sum[q], last[q], w, fx);
 	};
 
 	if (yexp) {
@@ -342,30 +239,23 @@ __global__ __launch_bounds__(kThreads) void expand_kernel(const Vp8gScaleDesc* _
 		const uint32_t L = row[i0], R = W > 1u ? row[i0 + 1u] : L;
 		return R * (w - 1u) + (L - R) * acc;
 	};
-	const bool boundary = j0 > 0;
-	const uint32_t Fj0 = ceil_div(j0 * H, h);
-	const uint32_t y_first = boundary ? Fj0 - 1u : 0u, y_last = ceil_div(j1 * H, h);
-	const uint32_t ys0 = fy * (Fj0 * h - j0 * H);
-	const uint32_t qH = H / h, rH = H - qH * h;
-	uint32_t irow = 0, j = j0, nextF = ceil_div((j0 + 1u) * H, h);
-	uint32_t ya = nextF * h - (j0 + 1u) * H;
+	ShrinkRows rows(j0, j1, H, h, fy);
+	uint32_t irow = 0;
 	uint8_t* out = dst + P.dst + k;
 	const uint32_t lane = tid & 63u;
-	for (uint32_t y = y_first; y < y_last; y++) {
+	for (uint32_t y = rows.y_first; y < rows.y_last; y++) {
 		const uint32_t frow = colok ? hsum(y) : 0u;
-		if (boundary && y == y_first) {
-			irow = ys0 ? __umulhi(frow, ys0) : 0u;
+		if (rows.shared_row(y)) {
+			irow = rows.lower_part(frow);
 			continue;
 		}
 		irow += frow;
-		if (y + 1u != nextF) continue;
-		const uint32_t ys = fy * ya;
-		const uint32_t frac = ys ? __umulhi(frow, ys) : 0u;
-		const uint32_t v = fxy ? clamp_u8(mult_fix(irow - frac, fxy)) : irow & 255u;  // (fxy == 0: w == 2 and h == H)
+		if (!rows.exports(y)) continue;
+		const uint32_t v = rows.sample(irow, frow, fxy);
 		// the lane whose byte starts an aligned dword stores it for the three lanes after it
 		const uint32_t pk = v | ((uint32_t)__shfl_down((int)v, 1) << 8) | ((uint32_t)__shfl_down((int)v, 2) << 16) |
 		                    ((uint32_t)__shfl_down((int)v, 3) << 24);
-		uint8_t* o = out + (size_t)j * P.dst_stride;
+		uint8_t* o = out + (size_t)rows.j * P.dst_stride;
 		const uint32_t a = (uint32_t)((uintptr_t)o & 3u);
 		if (colok) {
 			if (lane >= a && lane - a <= 60u && k - a + 3u < kend) {
@@ -374,10 +264,7 @@ __global__ __launch_bounds__(kThreads) void expand_kernel(const Vp8gScaleDesc* _
 				*o = (uint8_t)v;
 			}
 		}
-		irow = frac;
-		j++;
-		if (rH > ya) nextF += qH + 1u, ya = h - (rH - ya);
-		else nextF += qH, ya -= rH;
+		rows.next();
 	}
 }
 
@@ -397,26 +284,16 @@ void make_plane(Vp8gScalePlane* p, uint64_t src, uint32_t sstride, uint32_t W, u
 			p->run_h = p->block_rows - 1u;
 		} else {
 			p->tile_w = kThreads;
-			const uint32_t rh = (uint32_t)((uint64_t)kXRunSrcRows * h / H);
-			p->run_h = rh ? rh : 1u;
+			p->run_h = shrink_run_h(H, h);
 		}
 		p->tiles_x = (w + p->tile_w - 1u) / p->tile_w;
 		p->ntasks = p->tiles_x * ((h + p->run_h - 1u) / p->run_h);
 		return;
 	}
-	uint32_t g = 1;
-	while (g < 64u && (uint64_t)W > (uint64_t)kLanePerCol * g * w) g *= 2u;
-	p->group = g;
-	p->tile_w = kThreads / g;
-	p->tiles_x = (w + p->tile_w - 1u) / p->tile_w;
-	const uint32_t rh = (uint32_t)((uint64_t)kRunSrcRows * h / H);
-	p->run_h = rh ? rh : 1u;
-	p->ntasks = p->tiles_x * ((h + p->run_h - 1u) / p->run_h);
-	// a tile's source segment: E(k0 + tile_w) - E(k0) + 1 <= ceil(tile_w W / w) + 1 samples, at most W
-	const uint64_t sp = ((uint64_t)p->tile_w * W + w - 1u) / w + 2u;
-	const uint32_t span = sp < W ? (uint32_t)sp : W;
-	p->pitch = (span + 30u) & ~15u;  // + up to 15 bytes of misalignment, in whole 16-B chunks
-	p->block_rows = kBufBytes / p->pitch;
+	const ShrinkTiling t = shrink_tiling(W, H, w, h, 1u, kBufBytes);
+	p->group = t.group, p->tile_w = t.tile_w, p->tiles_x = t.tiles_x, p->run_h = t.run_h;
+	p->ntasks = (uint32_t)t.ntasks;  // (< 2^28: both sizes <= kMaxDim)
+	p->pitch = t.pitch, p->block_rows = t.block_rows;
 }
 
 bool expands(const Vp8gScalePlane& p) { return p.src_w < p.dst_w || p.src_h < p.dst_h; }
@@ -436,8 +313,7 @@ bool plane_ok(const Vp8gScalePlane& p) {
 			for (tw = kXMinTile; tw < kXMaxTile && tw < p.dst_w;) tw *= 2u;
 			if (p.pitch != 4u * tw || p.block_rows != kXLdsBytes / p.pitch || p.run_h != p.block_rows - 1u) return false;
 		} else {
-			const uint32_t rh = (uint32_t)((uint64_t)kXRunSrcRows * p.dst_h / p.src_h);
-			if (p.pitch != 0 || p.block_rows != 0 || p.run_h != (rh ? rh : 1u)) return false;
+			if (p.pitch != 0 || p.block_rows != 0 || p.run_h != shrink_run_h(p.src_h, p.dst_h)) return false;
 		}
 		return p.tile_w == tw && p.tiles_x == (p.dst_w + tw - 1u) / tw &&
 		       p.ntasks == p.tiles_x * ((p.dst_h + p.run_h - 1u) / p.run_h);

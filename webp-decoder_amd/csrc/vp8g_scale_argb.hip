@@ -29,13 +29,15 @@
 
 #include "../host/vp8_front.h"
 #include "vp8g_device.h"
+#include "vp8g_scale_device.h"
 
 #define VP8G_API extern "C" __attribute__((visibility("default")))
-#define DEV __device__ __forceinline__
 
 namespace {
 
-constexpr uint32_t kThreads = 256, kPerThread = 4;      // groups of four pixels per thread
+using namespace vp8g_scale;  // premultiply, unpremultiply, task_owner (vp8g_scale_device.h)
+
+constexpr uint32_t kPerThread = 4;                       // groups of four pixels per thread
 constexpr uint32_t kTaskGroups = kThreads * kPerThread;  // ... and per task
 constexpr uint32_t kPlaneDwords = 4u * sizeof(Vp8gScaleDesc) / 4u;
 // (no padding: desc_ok compares descriptors byte for byte)
@@ -43,48 +45,11 @@ static_assert(sizeof(Vp8gScaleArgbDesc) == 4 * 8 + 20 * 4 + 4 * sizeof(Vp8gScale
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4), aligned(4)));  // four pixels at a dword-aligned address
 
-// libwebp's WebPMultARGBRow, one pixel (vp8f_argb_mult_row)
-DEV uint32_t premultiply(uint32_t p) {
-	const uint32_t a = p >> 24;
-	if (a == 255u) return p;
-	if (a == 0u) return 0u;
-	const uint32_t scale = a * 65793u;  // (2^24 / 255; 255 * 254 * 65793 + 2^23 < 2^32)
-	uint32_t out = p & 0xFF000000u;
-#pragma unroll
-	for (uint32_t s = 0; s < 24u; s += 8u) out |= ((((p >> s) & 255u) * scale + (1u << 23)) >> 24) << s;
-	return out;
-}
-DEV uint32_t unpremultiply(uint32_t p) {
-	const uint32_t a = p >> 24;
-	if (a == 255u) return p;
-	if (a == 0u) return 0u;
-	const uint32_t scale = (255u << 24) / a;
-	uint32_t out = p & 0xFF000000u;
-#pragma unroll
-	for (uint32_t s = 0; s < 24u; s += 8u) {
-		const uint64_t v = ((uint64_t)((p >> s) & 255u) * scale + (1u << 23)) >> 24;  // (<= 255: colour <= alpha in a rescaled pixel)
-		out |= ((uint32_t)v & 255u) << s;
-	}
-	return out;
-}
-
-// the picture that owns task `task` of the launch whose first tasks are the member T0
-template <uint32_t Vp8gScaleArgbDesc::*T0>
-DEV uint32_t owner(const Vp8gScaleArgbDesc* descs, uint32_t n, uint32_t task) {
-	uint32_t lo = 0, hi = n - 1u;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi + 1u) >> 1;
-		if (descs[mid].*T0 <= task) lo = mid;
-		else hi = mid - 1u;
-	}
-	return lo;
-}
-
 __global__ __launch_bounds__(kThreads) void argb_split_kernel(const Vp8gScaleArgbDesc* __restrict__ descs, uint32_t n,
                                                               const uint8_t* __restrict__ src, uint8_t* __restrict__ work,
                                                               uint8_t* __restrict__ dst) {
 	const uint32_t task = blockIdx.x, tid = threadIdx.x;
-	const uint32_t im = owner<&Vp8gScaleArgbDesc::split_task0>(descs, n, task);
+	const uint32_t im = task_owner<Vp8gScaleArgbDesc, &Vp8gScaleArgbDesc::split_task0>(descs, n, task);
 	const Vp8gScaleArgbDesc& D = descs[im];
 	const uint32_t t = task - D.split_task0;
 	if (task < D.split_task0 || t >= D.split_ntasks) return;
@@ -146,7 +111,7 @@ __global__ __launch_bounds__(kThreads) void argb_split_kernel(const Vp8gScaleArg
 __global__ __launch_bounds__(kThreads) void argb_merge_kernel(const Vp8gScaleArgbDesc* __restrict__ descs, uint32_t n,
                                                               const uint8_t* __restrict__ work, uint8_t* __restrict__ dst) {
 	const uint32_t task = blockIdx.x, tid = threadIdx.x;
-	const uint32_t im = owner<&Vp8gScaleArgbDesc::merge_task0>(descs, n, task);
+	const uint32_t im = task_owner<Vp8gScaleArgbDesc, &Vp8gScaleArgbDesc::merge_task0>(descs, n, task);
 	const Vp8gScaleArgbDesc& D = descs[im];
 	const uint32_t t = task - D.merge_task0;
 	if (task < D.merge_task0 || t >= D.merge_ntasks) return;

@@ -10,7 +10,7 @@
 //            (the source is only dword-aligned and the window's origin may be odd: a segment starts 0, 4, 8 or 12 bytes
 //            into its first 16-byte chunk); every pixel is alpha-premultiplied on its way into LDS (§17.7 step 3), and
 //            the next block is in flight in registers while the current one is summed;
-//   sum      the closed form at the head of vp8g_scale.hip -- frow, irow, the boundary row of a run, `group` lanes per
+//   sum      the closed form at the head of vp8g_scale_device.h -- frow, irow, the boundary row of a run, `group` lanes per
 //            output column combined by the lane butterfly -- for the four byte channels of a column together: a lane
 //            reads a staged pixel once and adds its bytes to two registers of two 16-bit fields each (B | R and G | A;
 //            a lane sums at most kMaxSeg / 64 + 1 pixels of a row, so a field never carries), and keeps four irows;
@@ -32,6 +32,7 @@
 
 #include "../host/vp8_front.h"
 #include "vp8g_device.h"
+#include "vp8g_scale_device.h"
 #include "vp8g_tensor_device.h"
 
 #define VP8G_API extern "C" __attribute__((visibility("default")))
@@ -40,49 +41,18 @@
 namespace {
 
 using namespace vp8g_tensor;
+using namespace vp8g_scale;
 
-constexpr uint32_t kThreads = 256;
-constexpr uint32_t kBufBytes = 32768;  // LDS staging: five workgroups to a CU's 160 KB
-constexpr uint32_t kBufChunks = kBufBytes / 16u;
-constexpr uint32_t kMaxChunks = kBufChunks / kThreads;  // 16-B loads per thread and block
-constexpr uint32_t kMaxSeg = (kBufBytes - 16u) / 4u;    // pixels of the longest row segment that can be staged (8188)
-constexpr uint32_t kRunSrcRows = 64;  // source rows per task (about): 1 / 64 of the rows is read twice
-constexpr uint32_t kLanePerCol = 12;  // footprint pixels per lane before another lane joins the column
-constexpr uint32_t kQuad = 4;         // adjacent columns whose pixels one lane stores
-static_assert(kBufChunks % kThreads == 0, "whole chunks per thread");
+constexpr uint32_t kBufBytes = 32768;                 // LDS staging: five workgroups to a CU's 160 KB
+constexpr uint32_t kMaxSeg = (kBufBytes - 16u) / 4u;  // pixels of the longest row segment that can be staged (8188)
+constexpr uint32_t kQuad = 4;                         // adjacent columns whose pixels one lane stores
+static_assert(kBufBytes / 16u % kThreads == 0, "whole chunks per thread");
 static_assert((kMaxSeg / 64u + 1u) * 255u < 65536u, "a lane's sum of one byte channel over a row fits 16 bits");
 static_assert(sizeof(Vp8gScaleArgbTensorDesc) == 96, "descriptor layout (no padding: desc_ok compares byte for byte)");
 
 struct FusedParams {
 	float scale[3], bias[3];
 };
-
-DEV uint32_t mult_fix(uint32_t x, uint32_t y) { return __umulhi(x, y) + ((x * y) >> 31); }
-DEV uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1u) / b; }
-
-// libwebp's WebPMultARGBRow and its inverse, one pixel (vp8f_argb_mult_row).  The premultiply needs no special cases:
-// with a = 255 the scale is 2^24 - 1 and (x (2^24 - 1) + 2^23) >> 24 = x, with a = 0 it is 0 and so is the pixel.
-DEV uint32_t premultiply(uint32_t p) {
-	const uint32_t a = p >> 24;
-	const uint32_t scale = __umul24(a, 65793u);  // (2^24 / 255; 255 * 255 * 65793 + 2^23 < 2^32)
-	uint32_t out = p & 0xFF000000u;
-#pragma unroll
-	for (uint32_t s = 0; s < 24u; s += 8u) out |= ((__umul24((p >> s) & 255u, scale) + (1u << 23)) >> 24) << s;
-	return out;
-}
-DEV uint32_t unpremultiply(uint32_t p) {
-	const uint32_t a = p >> 24;
-	if (a == 255u) return p;
-	if (a == 0u) return 0u;
-	const uint32_t scale = (255u << 24) / a;
-	uint32_t out = p & 0xFF000000u;
-#pragma unroll
-	for (uint32_t s = 0; s < 24u; s += 8u) {
-		const uint64_t v = ((uint64_t)((p >> s) & 255u) * scale + (1u << 23)) >> 24;  // (<= 255: colour <= alpha in a rescaled pixel)
-		out |= ((uint32_t)v & 255u) << s;
-	}
-	return out;
-}
 
 // the four elements of pixel c (0xAARRGGBB) in the output's channel order
 template <uint32_t DT, bool BGR>
@@ -104,22 +74,16 @@ __global__ __launch_bounds__(kThreads) void scale_argb_fused_kernel(const Vp8gSc
 	const uint32_t* const ldsw = (const uint32_t*)lds;
 	const uint32_t task = blockIdx.x, tid = threadIdx.x;
 	// the picture that owns this task (tasks are numbered picture by picture)
-	uint32_t lo = 0, hi = n - 1u;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi + 1u) >> 1;
-		if (descs[mid].task0 <= task) lo = mid;
-		else hi = mid - 1u;
-	}
-	const Vp8gScaleArgbTensorDesc& D = descs[lo];
+	const Vp8gScaleArgbTensorDesc& D = descs[task_owner<Vp8gScaleArgbTensorDesc, &Vp8gScaleArgbTensorDesc::task0>(descs, n, task)];
 	const uint32_t t = task - D.task0;
 	if (task < D.task0 || t >= D.ntasks) return;
 	const uint32_t W = D.win_w, H = D.win_h, w = D.width, h = D.height;
-	const uint32_t fx = D.fx, fy = D.fy, fxy = D.fxy;
+	const uint32_t fx = D.fx, fxy = D.fxy;
 	const uint32_t G = D.group, pitch = D.pitch, R = D.block_rows, sw = D.src_width;
 	if (G == 0 || (G & (G - 1u)) || G > 64u || D.tile_w * G != kThreads || D.tiles_x == 0 || D.run_h == 0 || w > W || h > H) return;
 	const uint32_t tx = t % D.tiles_x, ry = t / D.tiles_x;
 
-	// -- columns: the tile's source segment [xs, xe) and this lane's footprint [e0, e1), in pixels of the window
+	// -- columns: the tile's source segment [xs, xe) and this lane's footprint, in pixels of the window
 	const uint32_t k0 = tx * D.tile_w, kend = min(k0 + D.tile_w, w);
 	const uint32_t j0 = ry * D.run_h, j1 = min(j0 + D.run_h, h);
 	if (k0 >= w || j0 >= h) return;
@@ -128,82 +92,32 @@ __global__ __launch_bounds__(kThreads) void scale_argb_fused_kernel(const Vp8gSc
 	const uint32_t span = xe - xs;
 	if (4u * span + 12u > pitch || (pitch & 15u) || R == 0 || (uint64_t)pitch * R > kBufBytes) return;  // (never: see make_desc)
 	const uint32_t gi = tid & (G - 1u), col = tid / G, k = k0 + col;
-	const bool active = k < kend;
-	uint32_t e0 = xs, e1 = xs, a0 = 0, a1 = 0;
-	if (active) {
-		e0 = ceil_div(k * W, w), e1 = ceil_div((k + 1u) * W, w);
-		a0 = e0 * w - k * W, a1 = e1 * w - (k + 1u) * W;
-	}
-	const bool carry_in = active && k > 0;
+	const ShrinkCol fp(k, kend, xs, W, w);
+	ShrinkRows rows(j0, j1, H, h, D.fy);
+	// (the window's first pixel; rows 4 src_width bytes apart)
+	StagedRows<4, kBufBytes> stage(src, (uintptr_t)src + D.src + 4u * ((uintptr_t)D.crop_top * sw + D.crop_left), 4u * sw, W, H, xs, span,
+	                               pitch, tid);
 
-	// -- rows: source rows [y_first, y_last); with j0 > 0 the first one is the boundary row F(j0) - 1
-	const bool boundary = j0 > 0;
-	const uint32_t Fj0 = ceil_div(j0 * H, h);
-	const uint32_t y_first = boundary ? Fj0 - 1u : 0u, y_last = ceil_div(j1 * H, h);
-	const uint32_t ys0 = fy * (Fj0 * h - j0 * H);
-
-	// -- staging: row r of a block sits at r * pitch, its segment starting at byte (address & 15)
-	const uintptr_t base = (uintptr_t)src + D.src + 4u * ((uintptr_t)D.crop_top * sw + D.crop_left);  // the window's first pixel
-	const uintptr_t ok_lo = base, ok_hi = base + 4u * ((uintptr_t)(H - 1u) * sw + W);  // from there to the window's last pixel
-	const uint32_t cpr = pitch >> 4;
-	uint32_t ch_r[kMaxChunks], ch_c[kMaxChunks];
-#pragma unroll
-	for (uint32_t m = 0; m < kMaxChunks; m++) {
-		const uint32_t q = tid + m * kThreads;
-		ch_r[m] = q / cpr, ch_c[m] = q % cpr;
-	}
-	uint4 pre[kMaxChunks];
-	auto load_block = [&](uint32_t yb, uint32_t nr) {
-#pragma unroll
-		for (uint32_t m = 0; m < kMaxChunks; m++) {
-			pre[m] = make_uint4(0, 0, 0, 0);
-			if (ch_r[m] >= nr) continue;
-			const uintptr_t row = base + 4u * ((uintptr_t)(yb + ch_r[m]) * sw + xs);  // first wanted byte
-			const uintptr_t a = (row & ~(uintptr_t)15) + 16u * ch_c[m];
-			if (a >= row + 4u * span) continue;  // past the segment
-			const uint8_t* const pa = src + (ptrdiff_t)(a - (uintptr_t)src);  // (an offset from the kernel's pointer: a global load)
-			if (a >= ok_lo && a + 16u <= ok_hi) {
-				pre[m] = *(const uint4*)pa;
-			} else {  // a chunk that straddles the window's first or last pixel: only the pixels inside
-				uint32_t v[4] = {0, 0, 0, 0};
-#pragma unroll
-				for (uint32_t b = 0; b < 4u; b++)
-					if (a + 4u * b >= ok_lo && a + 4u * b < ok_hi) v[b] = *(const uint32_t*)(pa + 4u * b);
-				pre[m] = make_uint4(v[0], v[1], v[2], v[3]);
-			}
-		}
-	};
-	auto store_block = [&](uint32_t nr) {
-#pragma unroll
-		for (uint32_t m = 0; m < kMaxChunks; m++)
-			if (ch_r[m] < nr)
-				*(uint4*)(lds + ch_r[m] * pitch + 16u * ch_c[m]) =
-				    make_uint4(premultiply(pre[m].x), premultiply(pre[m].y), premultiply(pre[m].z), premultiply(pre[m].w));
-	};
-
-	// F(j+1) and ya = F(j+1) h - (j+1) H step without a divide (vp8g_scale.hip)
-	const uint32_t qH = H / h, rH = H - qH * h;
-	uint32_t irow[4] = {0, 0, 0, 0}, j = j0, nextF = ceil_div((j0 + 1u) * H, h);
-	uint32_t ya = nextF * h - (j0 + 1u) * H;
+	uint32_t irow[4] = {0, 0, 0, 0};
 	// the lane that stores a quad: lane 0 of the first of four adjacent columns, all four in this wave and in the picture
 	const bool quads = kQuad * G <= 64u;
 	const bool quad_head = quads && gi == 0 && (col & (kQuad - 1u)) == 0 && k + kQuad <= kend;
 	const bool quad_tail = quads && k < kend && (k0 + (col & ~(kQuad - 1u))) + kQuad <= kend;  // its pixel goes out with a quad
 	uint8_t* const out = dst + D.dst;
 	const uint64_t plane = (uint64_t)w * h * EB;  // one NCHW plane of this picture
-	load_block(y_first, min(R, y_last - y_first));
-	for (uint32_t yb = y_first; yb < y_last; yb += R) {
+	const uint32_t y_last = rows.y_last;
+	stage.load(rows.y_first, min(R, y_last - rows.y_first));
+	for (uint32_t yb = rows.y_first; yb < y_last; yb += R) {
 		const uint32_t nr = min(R, y_last - yb);
 		__syncthreads();  // the previous block has been summed
-		store_block(nr);
+		stage.store(lds, nr, [](uint32_t p) { return premultiply(p); });  // (§17.7 step 3)
 		__syncthreads();
-		if (yb + R < y_last) load_block(yb + R, min(R, y_last - (yb + R)));  // in flight while this block is summed
+		if (yb + R < y_last) stage.load(yb + R, min(R, y_last - (yb + R)));  // in flight while this block is summed
 		for (uint32_t r = 0; r < nr; r++) {
 			const uint32_t y = yb + r;
-			const uint32_t mis = (uint32_t)((base + 4u * ((uintptr_t)y * sw + xs)) & 15u);
-			const uint32_t off = ((r * pitch + mis) >> 2) - xs;  // ldsw[off + x] = premultiplied s[y][x] for x in [xs, xe)
+			const uint32_t off = (stage.lds_offset(r, y) >> 2) - xs;  // ldsw[off + x] = premultiplied s[y][x] for x in [xs, xe)
 			uint32_t br = 0, ga = 0;  // B | R << 16 and G | A << 16
-			for (uint32_t x = e0 + gi; x < e1; x += G) {
+			for (uint32_t x = fp.e0 + gi; x < fp.e1; x += G) {
 				const uint32_t p = ldsw[off + x];
 				br += p & 0x00FF00FFu, ga += (p >> 8) & 0x00FF00FFu;
 			}
@@ -213,46 +127,30 @@ __global__ __launch_bounds__(kThreads) void scale_argb_fused_kernel(const Vp8gSc
 				for (int c = 0; c < 4; c++) part[c] += __shfl_xor(part[c], (int)o);
 			}
 			uint32_t frow[4] = {0, 0, 0, 0};
-			if (active) {
-				const uint32_t pc = carry_in ? ldsw[off + e0 - 1u] : 0u, pl = ldsw[off + e1 - 1u];
+			if (fp.active) {
+				const uint32_t pc = fp.carry_in ? ldsw[off + fp.e0 - 1u] : 0u, pl = ldsw[off + fp.e1 - 1u];
 #pragma unroll
-				for (int c = 0; c < 4; c++) {
-					// (24-bit multiplies: samples < 2^8, a0 / a1 / w < 2^14, a row sum < 2^22)
-					const uint32_t carry = carry_in ? mult_fix(__umul24((pc >> (8 * c)) & 255u, a0), fx) : 0u;
-					frow[c] = __umul24(carry + part[c], w) - __umul24((pl >> (8 * c)) & 255u, a1);
-				}
+				for (int c = 0; c < 4; c++) frow[c] = fp.frow((pc >> (8 * c)) & 255u, part[c], (pl >> (8 * c)) & 255u, w, fx);
 			}
-			if (boundary && y == y_first) {  // the row shared with the run above: only its lower part
+			if (rows.shared_row(y)) {  // the row shared with the run above: only its lower part
 #pragma unroll
-				for (int c = 0; c < 4; c++) irow[c] = ys0 ? __umulhi(frow[c], ys0) : 0u;
+				for (int c = 0; c < 4; c++) irow[c] = rows.lower_part(frow[c]);
 				continue;
 			}
 #pragma unroll
 			for (int c = 0; c < 4; c++) irow[c] += frow[c];
-			if (y + 1u != nextF) continue;
-			const uint32_t ys = fy * ya;
+			if (!rows.exports(y)) continue;
 			uint32_t px = 0;
 #pragma unroll
-			for (int c = 0; c < 4; c++) {
-				const uint32_t frac = ys ? __umulhi(frow[c], ys) : 0u;
-				uint32_t v;
-				if (fxy) {
-					const int32_t sv = (int32_t)mult_fix(irow[c] - frac, fxy);
-					v = sv > 255 ? 255u : (uint32_t)sv & 255u;
-				} else {
-					v = irow[c] & 255u;  // (W == 1 and h == H: the sums are the samples)
-				}
-				px |= v << (8 * c);
-				irow[c] = frac;
-			}
-			px = unpremultiply(px);
+			for (int c = 0; c < 4; c++) px |= rows.sample(irow[c], frow[c], fxy) << (8 * c);
+			px = unpremultiply(px);  // (§17.7 step 5)
 			// (every lane of the wave takes part in the exchange: the row test above is the same for all of them)
 			uint32_t q4[kQuad] = {px, 0u, 0u, 0u};
 			if (quads) {
 #pragma unroll
 				for (uint32_t q = 1; q < kQuad; q++) q4[q] = (uint32_t)__shfl_down((int)px, q * G);
 			}
-			const size_t pix = (size_t)j * w + k;
+			const size_t pix = (size_t)rows.j * w + k;
 			if (quad_head) {
 				uint32_t e[kQuad][4];
 #pragma unroll
@@ -271,7 +169,7 @@ __global__ __launch_bounds__(kThreads) void scale_argb_fused_kernel(const Vp8gSc
 						for (int c = 0; c < C; c++) run[C * q + c] = e[q][c];
 					store_run<DT, (int)kQuad * C>(out + pix * C * EB, run);
 				}
-			} else if (active && gi == 0 && !quad_tail) {  // a row's ragged end, or group > 16: element by element
+			} else if (fp.active && gi == 0 && !quad_tail) {  // a row's ragged end, or group > 16: element by element
 				uint32_t e[4];
 				elements<DT, BGR>(px, P, e);
 #pragma unroll
@@ -280,9 +178,7 @@ __global__ __launch_bounds__(kThreads) void scale_argb_fused_kernel(const Vp8gSc
 					store_elem<DT>(p, e[c]);
 				}
 			}
-			j++;
-			if (rH > ya) nextF += qH + 1u, ya = h - (rH - ya);
-			else nextF += qH, ya -= rH;
+			rows.next();
 		}
 	}
 }
@@ -309,22 +205,12 @@ int make_desc(uint32_t width, uint32_t height, uint64_t src, const Vp8gScaleOpt*
 	d.width = w, d.height = h, d.src_width = width, d.src_height = height;
 	d.crop_left = g.left, d.crop_top = g.top, d.win_w = W, d.win_h = H;
 	vp8f_scale_factors(W, H, w, h, &d.fx, &d.fy, &d.fxy);
-	uint32_t grp = 1;
-	while (grp < 64u && (uint64_t)W > (uint64_t)kLanePerCol * grp * w) grp *= 2u;
-	d.group = grp;
-	d.tile_w = kThreads / grp;
-	d.tiles_x = (w + d.tile_w - 1u) / d.tile_w;
-	const uint32_t rh = (uint32_t)((uint64_t)kRunSrcRows * h / H);
-	d.run_h = rh ? rh : 1u;
-	const uint64_t ntasks = (uint64_t)d.tiles_x * ((h + d.run_h - 1u) / d.run_h);
-	if (ntasks + task0 > 0x7FFFFFFFu) return vp8g::fail(EINVAL);
-	d.task0 = task0, d.ntasks = (uint32_t)ntasks;
-	// a tile's source segment: E(k0 + tile_w) - E(k0) + 1 <= ceil(tile_w W / w) + 1 pixels, at most W
-	const uint64_t sp = ((uint64_t)d.tile_w * W + w - 1u) / w + 2u;
-	const uint32_t span = sp < W ? (uint32_t)sp : W;
-	if (span > kMaxSeg) return vp8g::fail(ENOTSUP);  // (four columns of 64 lanes each: only where W / w exceeds 2046)
-	d.pitch = (4u * span + 12u + 15u) & ~15u;  // + up to 12 bytes of misalignment, in whole 16-B chunks
-	d.block_rows = kBufBytes / d.pitch;
+	const ShrinkTiling t = shrink_tiling(W, H, w, h, 4u, kBufBytes);
+	d.group = t.group, d.tile_w = t.tile_w, d.tiles_x = t.tiles_x, d.run_h = t.run_h;
+	if (t.ntasks + task0 > 0x7FFFFFFFu) return vp8g::fail(EINVAL);
+	d.task0 = task0, d.ntasks = (uint32_t)t.ntasks;
+	if (t.span > kMaxSeg) return vp8g::fail(ENOTSUP);  // (four columns of 64 lanes each: only where W / w exceeds 2046)
+	d.pitch = t.pitch, d.block_rows = t.block_rows;
 	*out = d;
 	return 0;
 }
