@@ -118,7 +118,9 @@ constexpr int kBS = 4 * kTP - 8;  // B_PRED: tile offset from sub-block (i, j) t
 // them (avg3 weights (1, 2, 1); TM_PRED = sat8(L + A - P) is the same dot with weights
 // (4, -4, 4) over the positions (L_r, P, A_c), which the avg3 modes' >> 2 divides out again); DC_PRED
 // is a direct sum.
-// Entry kBpModes-1 (all positions 128) serves out-of-range modes.
+// Entry kBpModes-1 serves out-of-range modes: like DC_PRED's (never used) it selects E[4] with
+// weights 0 and is its bias, 128.  So no entry weighs E[4..6], and the quad kernel loads E[4..7] as the
+// dword that ends at the corner instead of building it from the corner byte and three 128s.
 // Edge index notation of the builders: 0..3 = L3..L0, 4 = P, 5..12 = A0..A7.
 // ---------------------------------------------------------------------------------------------
 struct BpTab {
@@ -167,10 +169,12 @@ constexpr BpTab make_bptab() {
 			// weights (signed bytes) and bias of the one dot-product formula:
 			// value = (sdot4(E_xyz - 128, w) + bias) >> 2  (avg3: (1, 2, 1), 514; TM: (4, -4, 4), 512 -- four
 			// times L + A - P, so the shift every mode shares is exact for it; |dot| <= 4 * 3 * 128)
-			const bool tm = m == 1;
+			// The constant entries (DC_PRED's, unused; out-of-range modes) weigh nothing and are their bias, 514 >> 2
+			// = 128: no entry weighs E[4..6], so a kernel may leave whatever lies below the corner in them.
+			const bool tm = m == 1, flat = m == 0 || m >= 10;
 			t.v[(m * 16 + p) * 4] = sel;
 			t.v[(m * 16 + p) * 4 + 1] = mask;
-			t.v[(m * 16 + p) * 4 + 2] = tm ? 0x0004FC04u : 0x00010201u;
+			t.v[(m * 16 + p) * 4 + 2] = flat ? 0u : (tm ? 0x0004FC04u : 0x00010201u);
 			t.v[(m * 16 + p) * 4 + 3] = tm ? 512u : 514u;
 		}
 	return t;

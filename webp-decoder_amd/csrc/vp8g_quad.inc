@@ -1011,10 +1011,9 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 								uint8_t* const lb = lB + 36 * i0 - 16 * s;
 								const uint8_t* const pp = i0 == 0 ? (g ? lb - 1 : arow - 1) : lb - 1;
 								const uint32_t a03 = ld32(arow), a47 = ld32(a47p), lw = ld32(lb);
-								const uint32_t pv = *pp;
+								const uint32_t ey = ld32(pp - 3);  // E[4..7]: the corner on top of three bytes no tap weighs (make_bptab)
 								const u32x4 tb = tabp[16 * (kBpEntry / 16) * mode];
 								const int rv = rsp[16 * b0];
-								const uint32_t ey = (pv << 24) | 0x808080u;
 								const uint32_t lo = __builtin_amdgcn_perm(ey, lw, tb.x);
 								const uint32_t hi = __builtin_amdgcn_perm(a47, a03, tb.x);
 								const uint32_t x3 = (hi & tb.y) | (lo & ~tb.y);
@@ -1030,51 +1029,76 @@ __global__ __launch_bounds__(NW * 64, min_waves_per_simd<NW>()) void quad_kernel
 						}
 					}
 				} else if (bp_lane) {
-					// three or four: both groups in every lane of a B_PRED quarter (the loads of both groups
-					// first, as when the groups were lanes of one instruction)
+					// three or four: both groups in every B_PRED quarter.  Sub-steps 0, 1, 8, 9 hold one sub-block
+					// (group 0's): one pixel per lane, pixel (rr, cc) = l.  Sub-steps 2..7 hold two, and one
+					// instruction stream serves both: lanes 0..7 take group 0's sub-block, lanes 8..15 group 1's,
+					// each lane the pixel pair (r2, 2 c2), (r2, 2 c2 + 1) -- a sub-block's pixels depend on its
+					// edges alone, so its edge loads, corner word, DC value and mode are a lane's once, and only
+					// the table row, the perms and the dot product run per pixel.  The group-dependent offsets
+					// are per-lane bases, computed here.  (ey: the dword that ends at the corner, as above.)
+					static_assert(kBS % 8 == 0 && kBpEntry == 16, "the paired mapping's bases");
+					const uint32_t g8 = (uint32_t)l & 8u, r2 = __builtin_amdgcn_ubfe((uint32_t)l, 1u, 2u), c2 = (uint32_t)l & 1u;  // l = 8 g + 2 r2 + c2
+					const bool grp1 = g8 != 0u;
+					const u32x4* const tabp2 = (const u32x4*)(smem + kBpTable + (((uint32_t)l & 7u) << 5));  // pixel 4 r2 + 2 c2
+					const uint8_t* const tA2 = tY + slot * 16 + 3 * kTP + __umul24(g8, (uint32_t)(kBS / 8));
+					const uint8_t* const aE2 = grp1 ? tA2 : abY + 16;
+					uint8_t* const tpix2 = const_cast<uint8_t*>(tA2) + kTP + __umul24(r2, (uint32_t)kTP) + 2u * c2;
+					uint8_t* const lB2 = left + (grp1 ? 36 : 0);
+					uint8_t* const rc2 = lB2 + r2;               // right column -> the left column of sub-block column j + 1 ...
+					uint8_t* const rc2m = rc2 + (grp1 ? 0 : 64);  // ... and, from group 0's column 3, the next MB's
+					const int16_t* const rsp2 = (const int16_t*)(hv + kResid + (((uint32_t)l + g8) << 2));  // 16 (2 g) + 4 r2 + 2 c2
 					const int16_t* const rsp = (const int16_t*)(hv + kResid) + l;
 #pragma unroll
 					for (int s = 0; s < 10; s++) {
 						const int i0 = s <= 3 ? 0 : (s - 2) >> 1;
 						const int j0 = s - 2 * i0;
-						const bool vg0 = j0 <= 3, vg1 = i0 + 1 <= 3 && j0 >= 2;
+						const bool vg1 = i0 + 1 <= 3 && j0 >= 2;  // (group 0 is valid in every sub-step, in column 3 when j0 == 3)
 						const int b0 = 4 * i0 + j0;
-						uint32_t a03[2], a47[2], lwv[2], pvv[2];
-						u32x4 tb[2];
-						int rv[2], md[2];
-#pragma unroll
-						for (int gg = 0; gg < 2; gg++) {
-							if (!(gg ? vg1 : vg0)) continue;
-							const int bm = b0 + 2 * gg;
-							md[gg] = min((int)((bmw[bm >> 2] >> (8 * (bm & 3))) & 0xFFu), kBpModes - 1);
-							const uint8_t* const tA = tY + slot * 16 + 3 * kTP + kBS * gg;
-							const uint8_t* const aE = gg ? tA : abY + 16;
-							const uint8_t* const arow = i0 == 0 ? aE + 4 * s : tA + kBS * i0 + 4 * s;
-							const bool r3 = gg ? j0 == 5 : j0 == 3;
+						const bool r3 = j0 == 3;
+						if (vg1) {
+							const int b1 = b0 + 2;  // group 1's sub-block
+							const uint32_t mraw = grp1 ? (bmw[b1 >> 2] >> (8 * (b1 & 3))) & 0xFFu : (bmw[b0 >> 2] >> (8 * (b0 & 3))) & 0xFFu;
+							const int mode = min((int)mraw, kBpModes - 1);
+							const uint8_t* const arow = i0 == 0 ? aE2 + 4 * s : tA2 + kBS * i0 + 4 * s;
+							// (group 0 in column 3 takes the MB's above-right; in sub-block row 0 that is arow + 4 itself)
+							const uint8_t* const a47p = r3 && i0 > 0 && !grp1 ? abY + 32 : arow + 4;
+							const uint8_t* const lb = lB2 + 36 * i0 - 16 * s;
+							const uint8_t* const pp = i0 == 0 && !grp1 ? arow - 1 : lb - 1;
+							const uint32_t a03 = ld32(arow), a47 = ld32(a47p), lw = ld32(lb);
+							const uint32_t ey = ld32(pp - 3);
+							const u32x4* const tp = tabp2 + 16 * (kBpEntry / 16) * mode;
+							const u32x4 tb0 = tp[0], tb1 = tp[kBpEntry / 16];
+							const uint32_t rv2 = *(const uint32_t*)(rsp2 + 16 * b0);  // the pair's residuals: adjacent int16
+							const int vdc = (int)((__builtin_amdgcn_sad_u8(a03, 0u, __builtin_amdgcn_sad_u8(lw, 0u, 4u))) >> 3);
+							auto pixel = [&](const u32x4& tb, int rv) -> uint32_t {
+								const uint32_t lo = __builtin_amdgcn_perm(ey, lw, tb.x);
+								const uint32_t hi = __builtin_amdgcn_perm(a47, a03, tb.x);
+								const uint32_t x3 = (hi & tb.y) | (lo & ~tb.y);
+								const int vdir = sat8(__builtin_amdgcn_sdot4((int)(x3 ^ 0x00808080u), (int)tb.z, (int)tb.w, false) >> 2);
+								return (uint32_t)sat8((mode == 0 ? vdc : vdir) + rv);
+							};
+							const uint32_t px0 = pixel(tb0, (int)(int16_t)rv2), px1 = pixel(tb1, (int)rv2 >> 16);
+							*(uint16_t*)(tpix2 + kBS * i0 + 4 * s) = (uint16_t)(px0 | (px1 << 8));
+							if (c2) (r3 ? rc2m : rc2)[36 * i0 - 16 * s - 16] = (uint8_t)px1;
+						} else {
+							const int md = min((int)((bmw[b0 >> 2] >> (8 * (b0 & 3))) & 0xFFu), kBpModes - 1);
+							const uint8_t* const tA = tY + slot * 16 + 3 * kTP;
+							const uint8_t* const arow = i0 == 0 ? abY + 16 + 4 * s : tA + kBS * i0 + 4 * s;
 							const uint8_t* const a47p = r3 ? abY + 32 : arow + 4;
-							const uint8_t* const lb = left + 36 * gg + 36 * i0 - 16 * s;
-							const uint8_t* const pp = i0 == 0 ? (gg ? lb - 1 : arow - 1) : lb - 1;
-							a03[gg] = ld32(arow), a47[gg] = ld32(a47p), lwv[gg] = ld32(lb);
-							pvv[gg] = *pp;
-							tb[gg] = tabp[16 * (kBpEntry / 16) * md[gg]];
-							rv[gg] = rsp[16 * b0 + 32 * gg];
-						}
-#pragma unroll
-						for (int gg = 0; gg < 2; gg++) {
-							if (!(gg ? vg1 : vg0)) continue;
-							const uint32_t ey = (pvv[gg] << 24) | 0x808080u;
-							const uint32_t lo = __builtin_amdgcn_perm(ey, lwv[gg], tb[gg].x);
-							const uint32_t hi = __builtin_amdgcn_perm(a47[gg], a03[gg], tb[gg].x);
-							const uint32_t x3 = (hi & tb[gg].y) | (lo & ~tb[gg].y);
-							const int vdir = sat8(__builtin_amdgcn_sdot4((int)(x3 ^ 0x00808080u), (int)tb[gg].z, (int)tb[gg].w, false) >> 2);
-							const int vdc = (int)((__builtin_amdgcn_sad_u8(a03[gg], 0u, __builtin_amdgcn_sad_u8(lwv[gg], 0u, 4u))) >> 3);
-							const int pred = md[gg] == 0 ? vdc : vdir;
-							const int px = sat8(pred + rv[gg]);
-							uint8_t* const tpix = tY + slot * 16 + 4 * kTP + kBS * gg + kTP * rr + cc;
-							tpix[kBS * i0 + 4 * s] = (uint8_t)px;
-							const bool j3 = gg ? j0 == 5 : j0 == 3;
-							uint8_t* const lb = left + 36 * gg + 36 * i0 - 16 * s;
-							if (col3) (j3 ? left + 4 * (i0 + gg) + rr : lb - 16 + rr)[0] = (uint8_t)px;
+							uint8_t* const lb = left + 36 * i0 - 16 * s;
+							const uint8_t* const pp = i0 == 0 ? arow - 1 : lb - 1;
+							const uint32_t a03 = ld32(arow), a47 = ld32(a47p), lw = ld32(lb);
+							const uint32_t ey = ld32(pp - 3);
+							const u32x4 tb = tabp[16 * (kBpEntry / 16) * md];
+							const int rv = rsp[16 * b0];
+							const uint32_t lo = __builtin_amdgcn_perm(ey, lw, tb.x);
+							const uint32_t hi = __builtin_amdgcn_perm(a47, a03, tb.x);
+							const uint32_t x3 = (hi & tb.y) | (lo & ~tb.y);
+							const int vdir = sat8(__builtin_amdgcn_sdot4((int)(x3 ^ 0x00808080u), (int)tb.z, (int)tb.w, false) >> 2);
+							const int vdc = (int)((__builtin_amdgcn_sad_u8(a03, 0u, __builtin_amdgcn_sad_u8(lw, 0u, 4u))) >> 3);
+							const int px = sat8((md == 0 ? vdc : vdir) + rv);
+							(tY + slot * 16 + 4 * kTP + kTP * rr + cc)[kBS * i0 + 4 * s] = (uint8_t)px;
+							if (col3) (r3 ? left + 4 * i0 + rr : lb - 16 + rr)[0] = (uint8_t)px;
 						}
 						wave_lds_sync();
 					}
