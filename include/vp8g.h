@@ -567,6 +567,11 @@ typedef struct {
 int vp8g_make_alpha_desc(uint32_t width, uint32_t height, uint32_t filter, uint64_t src, uint32_t src_stride, uint64_t dst,
                          uint32_t dst_stride, uint32_t task0, Vp8gAlphaDesc* out);
 
+/* The hand-over between the gradient filter's bands, for the tests' model of its schedule (tests/bands.py): out[0] =
+ * skewed columns per tile step, out[1] = tile steps a band trails the band above, out[2] = bytes of a wave's ring of
+ * bottom-row results, out[3] = bytes of the full-width row between two rounds. */
+void vp8g_alpha_handover(uint32_t out[4]);
+
 /* Un-predict n planes of mixed sizes and filters in one launch on `hip_stream`.  h_descs / d_descs:
  * host and device copies of the descriptors (tasks numbered plane by plane).  Writes only each plane's
  * own width x height bytes.  Asynchronous; 0 or -1 + errno (EINVAL: NULL pointer, n = 0, an invalid or
@@ -666,6 +671,11 @@ int vp8g_make_lossless_desc(uint32_t width, uint32_t height, uint64_t src, uint6
 /* The kernel's geometry, for tests that aim at its boundaries: out[0] = columns per barrier group (the tile step),
  * out[1] = rows per wave (a band), out[2] = bands per workgroup round. */
 void vp8g_lossless_geometry(uint32_t out[3]);
+
+/* The hand-over between the predictor's bands, for the tests' model of its schedule (tests/bands.py): out[0] = columns a
+ * row trails the row above, out[1] = groups a band trails the band above, out[2] = a wave's ring of bottom-row pixels,
+ * out[3] = pixels of the full-width row between two rounds that a launch may ask for at most. */
+void vp8g_lossless_handover(uint32_t out[4]);
 
 /* Invert the transforms of n images of mixed sizes and transform lists in one launch on `hip_stream`.
  * One 16-wave workgroup per image; the predictor runs as a skewed wavefront (a row per lane, each row

@@ -25,6 +25,9 @@
 #include <string.h>
 
 #include "vp8g_device.h"
+#define VP8G_SKEW_HOST_ONLY  // (no wait sites here: the band hooks alone)
+#define VP8G_SKEW_BANDS
+#include "vp8g_skew.h"
 
 #define VP8G_API extern "C" __attribute__((visibility("default")))
 #define DEV __device__ __forceinline__
@@ -107,6 +110,7 @@ __global__ __launch_bounds__(kThreads) void alpha_kernel(const Vp8gAlphaDesc* __
 	uint32_t* const full32 = (uint32_t*)full8;
 	for (uint32_t pl = blockIdx.x; pl < n; pl += gridDim.x) {
 		const Vp8gAlphaDesc d = D[pl];
+		VP8G_BAND_POISON((uint32_t*)smem, (full_off + (uint32_t)kFull) / 4u);  // (the launch's whole dynamic LDS, either way)
 		const int w = (int)d.width, h = (int)d.height;
 		const uint8_t* __restrict__ s = src + d.src;
 		uint8_t* __restrict__ o = dst + d.dst;
@@ -149,22 +153,27 @@ __global__ __launch_bounds__(kThreads) void alpha_kernel(const Vp8gAlphaDesc* __
 			}
 		} else {
 			const int nbands = (h + 63) >> 6, ntiles = (w + 63 + kT - 1) / kT;
+			// (the skew build's mutants, csrc/vp8g_skew.h: in the shipped library mut is the constant 0)
+			const uint32_t mut = VP8G_BAND_MUTANT();
+			const int delay = kDelay - (mut == kBandMutDelay ? 1 : 0);
+			const uint32_t ringmask = (uint32_t)(mut == kBandMutRing ? kRing / 2 : kRing) - 1u;
 			// a round: every wave one band.  Wave j starts kDelay steps after wave j - 1; the next round starts
 			// when wave 0 trails wave 15 by kDelay steps at least (16 kDelay) and no earlier than kDelay steps
 			// after a band's last tile, so that a wave's ring is not rewritten while the wave below reads it
-			const int round_len = ntiles + kDelay > (int)kWaves * kDelay ? ntiles + kDelay : (int)kWaves * kDelay;
+			const int round_len =
+			    (ntiles + delay > (int)kWaves * delay && mut != kBandMutNoLong ? ntiles + delay : (int)kWaves * delay) - (mut == kBandMutRound ? 1 : 0);
 			const int rounds = (nbands + (int)kWaves - 1) / (int)kWaves;
-			const int steps = (rounds - 1) * round_len + ((int)kWaves - 1) * kDelay + ntiles;
+			const int steps = (rounds - 1) * round_len + ((int)kWaves - 1) * delay + ntiles;
 			uint32_t* const tile32 = (uint32_t*)(smem + wave * kTileBytes);
 			// bottom rows: written at the writer's t, read at the reader's t + 63
 			uint32_t* const hw32 = wave == (int)kWaves - 1 ? full32 : (uint32_t*)(smem + kOffRing + wave * kRing);
 			const uint32_t* const hr32 = wave == 0 ? full32 : (const uint32_t*)(smem + kOffRing + (wave - 1) * kRing);
-			const uint32_t wmask = wave == (int)kWaves - 1 ? 0x7FFFu : (uint32_t)kRing - 1u;
-			const uint32_t rmask = wave == 0 ? 0x7FFFu : (uint32_t)kRing - 1u;
+			const uint32_t wmask = wave == (int)kWaves - 1 ? 0x7FFFu : ringmask;
+			const uint32_t rmask = wave == 0 ? 0x7FFFu : ringmask;
 			const int trow = lane >> 4, tcol = lane & 15;  // load / store mapping: 16 lanes to a row, 4 rows per access
 			uint32_t cur = 0, ul = 0;
 			for (int st = 0; st < steps; st++) {
-				const int rel = st - kDelay * wave;
+				const int rel = st - delay * wave;
 				const int p = rel >= 0 ? rel / round_len : rounds;
 				const int k = rel - p * round_len;
 				const int b = p * (int)kWaves + wave;
@@ -223,6 +232,10 @@ bool desc_ok(const Vp8gAlphaDesc& d) {
 }
 
 }  // namespace
+
+// (tests/bands.py states the hand-over geometry once more; tests/test_gpu_bands.py holds the two together)
+VP8G_API void vp8g_alpha_handover(uint32_t out[4]) { out[0] = (uint32_t)kT, out[1] = (uint32_t)kDelay, out[2] = (uint32_t)kRing, out[3] = (uint32_t)kFull; }
+VP8G_BAND_EXPORTS(alpha)
 
 VP8G_API int vp8g_make_alpha_desc(uint32_t width, uint32_t height, uint32_t filter, uint64_t src, uint32_t src_stride, uint64_t dst,
                                   uint32_t dst_stride, uint32_t task0, Vp8gAlphaDesc* out) {

@@ -33,6 +33,9 @@
 #include <string.h>
 
 #include "vp8g_device.h"
+#define VP8G_SKEW_HOST_ONLY  // (no wait sites here: the band hooks alone)
+#define VP8G_SKEW_BANDS
+#include "vp8g_skew.h"
 
 #define VP8G_API extern "C" __attribute__((visibility("default")))
 #define DEV __device__ __forceinline__
@@ -46,6 +49,7 @@ constexpr int kG = 64;                   // steps (columns of lane 0) per group:
 constexpr int kDelay = 3;                // groups a band trails the band above
 constexpr int kRing = 256;               // bottom-row ring of a wave, in pixels, indexed by the column
 constexpr int kRingDwords = (int)kWaves * kRing;
+constexpr int kFullCap = 16384 + 64;      // the full-width row at most, in pixels (what the launch may ask for)
 // a reader's group reads columns up to kG (k + 1) of the row above; the writer's group k + kDelay - 1 has
 // written up to kG (k + kDelay) - 1 - kLag; and the writer's group k + kDelay must not reuse their slots
 static_assert(kDelay * kG >= kG + kLag + 1 && kRing >= kDelay * kG + kG - kLag && (kRing & (kRing - 1)) == 0 && kG % 4 == 0,
@@ -148,25 +152,30 @@ DEV void store_px4(uint32_t* row, int x, int w, bool rowok, const uint32_t (&o)[
 __device__ void predictor_pass(const uint8_t* in, uint32_t* out, int w, int h, const Vp8gLosslessTransform& pt,
                                const Vp8gLosslessTransform* cc, bool green, const uint8_t* src, uint32_t* smem, int lane, int wave) {
 	const int nbands = (h + 63) >> 6, ngroups = (w + kLag + kG - 1) / kG;
+	// (the skew build's mutants, csrc/vp8g_skew.h: in the shipped library mut is the constant 0)
+	const uint32_t mut = VP8G_BAND_MUTANT();
+	const int delay = kDelay - (mut == kBandMutDelay ? 1 : 0);
+	const uint32_t ringmask = (uint32_t)(mut == kBandMutRing ? kRing / 2 : kRing) - 1u;
 	// a round: every wave one band.  Wave j starts kDelay groups after wave j - 1; the next round starts
 	// when wave 0 trails wave 15 by kDelay groups at least (16 kDelay) and no earlier than kDelay groups
 	// after a band's last group, so that a wave's ring is not rewritten while the wave below reads it
-	const int round_len = ngroups + kDelay > (int)kWaves * kDelay ? ngroups + kDelay : (int)kWaves * kDelay;
+	const int round_len =
+	    (ngroups + delay > (int)kWaves * delay && mut != kBandMutNoLong ? ngroups + delay : (int)kWaves * delay) - (mut == kBandMutRound ? 1 : 0);
 	const int rounds = (nbands + (int)kWaves - 1) / (int)kWaves;
-	const int steps = (rounds - 1) * round_len + ((int)kWaves - 1) * kDelay + ngroups;
+	const int steps = (rounds - 1) * round_len + ((int)kWaves - 1) * delay + ngroups;
 	uint32_t* const full = smem + kRingDwords;
 	// bottom rows, indexed by the column (the full-width row holds every column: its mask changes nothing)
 	uint32_t* const hw = wave == (int)kWaves - 1 ? full : smem + wave * kRing;
 	const uint32_t* const hr = wave == 0 ? full : smem + (wave - 1) * kRing;
-	const uint32_t wmask = wave == (int)kWaves - 1 ? 0x7FFFu : (uint32_t)kRing - 1u;
-	const uint32_t rmask = wave == 0 ? 0x7FFFu : (uint32_t)kRing - 1u;
+	const uint32_t wmask = wave == (int)kWaves - 1 ? 0x7FFFu : ringmask;
+	const uint32_t rmask = wave == 0 ? 0x7FFFu : ringmask;
 	const uint8_t* const modes = src + pt.data;
 	const int pbits = (int)pt.bits, pbw = div_up(w, pbits), pmask = (1 << pbits) - 1;
 	const uint8_t* const ccdata = cc ? src + cc->data : src;
 	const int cbits = cc ? (int)cc->bits : 2, cbw = div_up(w, cbits), cmask = (1 << cbits) - 1;
 	uint32_t cur = 0, T = 0, TL = 0, first = 0, mode = 0, cce = 0;
 	for (int st = 0; st < steps; st++) {
-		const int rel = st - kDelay * wave;
+		const int rel = st - delay * wave;
 		const int p = rel >= 0 ? rel / round_len : rounds;
 		const int k = rel - p * round_len;
 		const int b = p * (int)kWaves + wave;
@@ -235,6 +244,7 @@ __global__ __launch_bounds__(kThreads) void lossless_kernel(const Vp8gLosslessDe
 	for (uint32_t im = blockIdx.x; im < n; im += gridDim.x) {
 		const Vp8gLosslessDesc& d = D[im];
 		const int h = (int)d.height, ntr = (int)d.ntransforms;
+		VP8G_BAND_POISON(smem, (uint32_t)kRingDwords + ((d.width + 64u) & ~63u));  // (no more than the launch's widest image asked for)
 		uint32_t* const out = (uint32_t*)(dst + d.dst);
 		const uint8_t* in = src + d.src;
 		int cw = (int)d.width;  // the width of the image at `in`
@@ -309,6 +319,10 @@ bool desc_ok(const Vp8gLosslessDesc& d) {
 // (tests/test_gpu_lossless.py takes its boundary sizes from here, through vp8g.lossless_geometry())
 VP8G_API void vp8g_lossless_geometry(uint32_t out[3]) { out[0] = (uint32_t)kG, out[1] = 64u, out[2] = kWaves; }
 
+// (tests/bands.py states the hand-over geometry once more; tests/test_gpu_bands.py holds the two together)
+VP8G_API void vp8g_lossless_handover(uint32_t out[4]) { out[0] = (uint32_t)kSkew, out[1] = (uint32_t)kDelay, out[2] = (uint32_t)kRing, out[3] = (uint32_t)kFullCap; }
+VP8G_BAND_EXPORTS(lossless)
+
 VP8G_API int vp8g_make_lossless_desc(uint32_t width, uint32_t height, uint64_t src, uint64_t dst, uint32_t ntransforms,
                                      const Vp8gLosslessTransform* tr, uint32_t task0, Vp8gLosslessDesc* out) {
 	if (!out || ntransforms > 4 || (ntransforms && !tr)) {
@@ -339,7 +353,7 @@ VP8G_API int vp8g_lossless_batch_device(const Vp8gLosslessDesc* h, const Vp8gLos
 		if (ok && h[i].width > maxw) maxw = h[i].width;
 	}
 	if (!ok) return vp8g::fail(EINVAL);
-	constexpr uint32_t kLdsMax = (uint32_t)(kRingDwords + 16384 + 64) * 4u;
+	constexpr uint32_t kLdsMax = (uint32_t)(kRingDwords + kFullCap) * 4u;
 	static const hipError_t attr =
 	    hipFuncSetAttribute((const void*)lossless_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
 	// the rings, and a full-width row as wide as the launch's widest image

@@ -118,4 +118,48 @@ __device__ __forceinline__ uint32_t early(int site) {
 #define VP8G_SKEW_POISON(ptr, bytes, stream) hipSuccess
 #endif
 
+// ---- The banded wavefront kernels (vp8g_lossless.hip, vp8g_alpha.hip) --------
+// A unit defines VP8G_SKEW_BANDS (and VP8G_SKEW_HOST_ONLY: it has no wait sites) before the include.
+// These kernels are paced by workgroup barriers alone, so there is nothing to delay and nothing to count;
+// the skew build
+//   * fills the LDS of a workgroup with 0xA5 before every image, so that a bottom row read too early is
+//     not the previous launch's (correct) row;
+//   * can alter one term of the schedule (`mutant`, below): the mutants tests/test_gpu_bands.py must catch.
+// A mutant changes only values that every thread of the workgroup computes alike (the band delay, the
+// round length, a ring's mask): every thread still reaches the same barriers, every LDS index stays
+// masked, and (band, group, lane) stay within the image -- wrong pixels, never another address.
+enum : unsigned {
+	kBandMutNone = 0,
+	kBandMutDelay = 1,     // a band trails the band above by kDelay - 1
+	kBandMutRound = 2,     // a round is one step shorter
+	kBandMutRing = 3,      // the ring's mask halved
+	kBandMutNoLong = 4,    // the long-round branch dropped: round_len = 16 kDelay whatever the width
+	kBandMutants = 5
+};
+#if defined(VP8G_TEST_SKEW) && defined(VP8G_SKEW_BANDS)
+namespace vp8g_skew {
+static __device__ uint32_t g_band_mutant;
+__device__ __forceinline__ uint32_t band_mutant() { return (uint32_t)__builtin_amdgcn_readfirstlane((int)g_band_mutant); }
+// (dwords < the workgroup's dynamic LDS; all threads of the workgroup)
+__device__ __forceinline__ void band_poison(uint32_t* lds, uint32_t dwords) {
+	for (uint32_t i = threadIdx.x; i < dwords; i += blockDim.x) lds[i] = 0xA5A5A5A5u;
+	__syncthreads();
+}
+}  // namespace vp8g_skew
+#define VP8G_BAND_MUTANT() vp8g_skew::band_mutant()
+#define VP8G_BAND_POISON(lds, dwords) vp8g_skew::band_poison(lds, dwords)
+// Diag-only export of the unit: the mutant of its kernel (0: none).  A synchronous copy: call between launches.
+#define VP8G_BAND_EXPORTS(tag)                                                                                \
+	extern "C" __attribute__((visibility("default"))) int vp8g_band_mutant_##tag(uint32_t mutant) {           \
+		if (mutant >= kBandMutants) return -1;                                                                \
+		return hipMemcpyToSymbol(HIP_SYMBOL(vp8g_skew::g_band_mutant), &mutant, sizeof(mutant)) == hipSuccess ? 0 : -1; \
+	}
+#else
+#define VP8G_BAND_MUTANT() 0u
+#define VP8G_BAND_POISON(lds, dwords) \
+	do {                              \
+	} while (0)
+#define VP8G_BAND_EXPORTS(tag)
+#endif
+
 #endif

@@ -285,6 +285,17 @@ def lossless_geometry():
     gpu_lib().vp8g_lossless_geometry(g)
     return int(g[0]), int(g[1]), int(g[2])
 
+
+def band_handover(kernel: str):
+    """vp8g_lossless_handover / vp8g_alpha_handover: the hand-over geometry of a banded wavefront kernel as the library
+    was built.  "lossless": (row skew, band delay in groups, ring in pixels, full-width row at most, in pixels);
+    "alpha": (tile step, band delay in tile steps, ring in bytes, full-width row in bytes).  tests/bands.py states
+    the same numbers for its model of the schedule."""
+    g = (C.c_uint32 * 4)()
+    getattr(gpu_lib(), f"vp8g_{kernel}_handover")(g)
+    return tuple(int(v) for v in g)
+
+
 T_OPAQUE = 0xFFFFFFFFFFFFFFFF
 VP8G_X_ALPHA = 1
 VP8G_X_LOSSLESS = 2
@@ -527,6 +538,10 @@ def gpu_lib():
         if hasattr(lib, "vp8g_lossless_batch_device"):  # (libraries built before the lossless path: A/B of old builds)
             lib.vp8g_lossless_geometry.argtypes = [P(C.c_uint32)]
             lib.vp8g_lossless_geometry.restype = None
+            for name in ("vp8g_lossless_handover", "vp8g_alpha_handover"):  # (libraries built before the tests' model of the bands)
+                if hasattr(lib, name):
+                    getattr(lib, name).argtypes = [P(C.c_uint32)]
+                    getattr(lib, name).restype = None
             lib.vp8g_make_lossless_desc.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32,
                                                     P(Vp8gLosslessTransform), C.c_uint32, P(Vp8gLosslessDesc)]
             lib.vp8g_lossless_batch_device.argtypes = [P(Vp8gLosslessDesc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
@@ -585,6 +600,17 @@ def skew_set(seed: int, length: int, early_site: int = -1):
     for tag in ("recon", "m05"):
         if getattr(lib, f"vp8g_skew_set_{tag}")(C.c_uint32(seed), C.c_uint32(length), C.c_int(early_site)) != 0:
             raise RuntimeError(f"vp8g_skew_set_{tag}({seed}, {length}, {early_site}) failed")
+
+
+BAND_MUTANTS = ("none", "delay", "round", "ring", "nolong")  # csrc/vp8g_skew.h: kBandMut*
+
+
+def band_mutant(kernel: str, mutant: str = "none"):
+    """Skew build only: the one term of the banded schedule of `kernel` ("lossless" / "alpha") that is altered from
+    the next launch on -- the band delay one step less, the round one step shorter, the ring's mask halved, the
+    long-round branch dropped ("none": the shipped schedule)."""
+    if getattr(gpu_lib(), f"vp8g_band_mutant_{kernel}")(C.c_uint32(BAND_MUTANTS.index(mutant))) != 0:
+        raise RuntimeError(f"vp8g_band_mutant_{kernel}({mutant}) failed")
 
 
 def skew_census(reset: bool = True) -> dict:
