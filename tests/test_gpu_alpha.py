@@ -93,7 +93,7 @@ def test_unfilter_refuses_bad_descriptors(vp8g):
     assert lib.vp8g_make_alpha_desc(4, 4, 3, 0, 4, 0, 4, 0, C.byref(d)) == 0
     dev = torch.device("cuda", 0)
     buf = torch.full((64,), 0xEE, dtype=torch.uint8, device=dev)
-    dd = torch.frombuffer(bytearray(bytes(d)), dtype=torch.uint8).to(dev)
+    dd = vp8g.device_copy(d)
     p = C.c_void_p(buf.data_ptr())
     for call in ((None, C.c_void_p(dd.data_ptr()), 1, p, p), (C.byref(d), None, 1, p, p), (C.byref(d), C.c_void_p(dd.data_ptr()), 0, p, p),
                  (C.byref(d), C.c_void_p(dd.data_ptr()), 1, None, p), (C.byref(d), C.c_void_p(dd.data_ptr()), 1, p, None)):
@@ -177,8 +177,8 @@ def test_tensor_alpha_offset_base_and_padded_planes(vp8g, w, h, dtype, layout):
         chunks.append(buf.reshape(-1))
         so += buf.size
     src = torch.from_numpy(np.concatenate(chunks)).to(dev)
-    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
-    d_al = torch.frombuffer(bytearray(bytes(al)), dtype=torch.uint8).to(dev)
+    d_descs = vp8g.device_copy(descs)
+    d_al = vp8g.device_copy(al)
     out = torch.full((eb + n * slot + 64,), 0xEE, dtype=torch.uint8, device=dev)
     assert out.data_ptr() % 16 == 0
     stream = torch.cuda.current_stream(dev)
@@ -200,8 +200,8 @@ def test_tensor_alpha_refuses_bad_arguments(vp8g):
     assert lib.vp8g_make_tensor_desc(C.byref(opt), 0, 64, 80, 16, 8, 0, 0, C.byref(d)) == 0
     src = torch.zeros(160, dtype=torch.uint8, device=dev)
     out = torch.full((2048,), 0xEE, dtype=torch.uint8, device=dev)
-    d_d = torch.frombuffer(bytearray(bytes(d)), dtype=torch.uint8).to(dev)
-    d_a = torch.frombuffer(bytearray(bytes(a)), dtype=torch.uint8).to(dev)
+    d_d = vp8g.device_copy(d)
+    d_a = vp8g.device_copy(a)
     pd, pa, ps, po = (C.c_void_p(t.data_ptr()) for t in (d_d, d_a, src, out))
     short = vp8g.Vp8gTensorAlpha(96, 15, 0)  # a stride below the width
     for call in ((C.byref(d), pd, None, pa, 1, C.byref(opt), ps, po), (C.byref(d), pd, C.byref(a), None, 1, C.byref(opt), ps, po),

@@ -106,7 +106,7 @@ def test_mixed_size_batch_one_launch(vp8g):
         do = (do + vp8g.i420_size(w, h) + 255) // 256 * 256
         task0 += descs[i].ntasks
     src = torch.from_numpy(np.concatenate([np.zeros(5, np.uint8)] + chunks)).to(dev)
-    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
+    d_descs = vp8g.device_copy(descs)
     out = torch.full((do + 64,), 0xEE, dtype=torch.uint8, device=dev)
     stream = torch.cuda.current_stream(dev)
     assert lib.vp8g_scale_batch_device(descs, C.c_void_p(d_descs.data_ptr()), n, C.c_void_p(src.data_ptr()),
@@ -226,8 +226,8 @@ def test_scaled_i420_chains_into_the_encoder_on_the_device(vp8g):
     small = torch.empty(do + 16, dtype=torch.uint8, device=dev)
     rgb = torch.empty(etotal + 16, dtype=torch.uint8, device=dev)
     work = torch.empty(lib.vp8g_encode_workspace_size(spans), dtype=torch.uint8, device=dev)
-    d_s = torch.frombuffer(bytearray(bytes(sdescs)), dtype=torch.uint8).to(dev)
-    d_e = torch.frombuffer(bytearray(bytes(edescs)), dtype=torch.uint8).to(dev)
+    d_s = vp8g.device_copy(sdescs)
+    d_e = vp8g.device_copy(edescs)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     assert lib.vp8g_scale_batch_device(sdescs, C.c_void_p(d_s.data_ptr()), n, C.c_void_p(src.data_ptr()),
                                        C.c_void_p(small.data_ptr()), stream) == 0

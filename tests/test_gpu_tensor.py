@@ -106,7 +106,7 @@ def test_mixed_launch_scattered_sources_offset_base(vp8g, w, h, dtype, layout, g
         assert lib.vp8g_make_tensor_desc(C.byref(opt), o[0], o[1], o[2], sy, suv, dsts[i], task0, C.byref(descs[i])) == 0
         task0 += descs[i].ntasks
     src = torch.from_numpy(np.concatenate(chunks)).to(dev)
-    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
+    d_descs = vp8g.device_copy(descs)
     total = dsts[-1] + slot
     out = torch.full((eb + total + 64,), 0xEE, dtype=torch.uint8, device=dev)
     assert out.data_ptr() % 16 == 0
@@ -132,7 +132,7 @@ def test_misaligned_base_is_refused_before_any_launch(vp8g):
         d = vp8g.Vp8gTensorDesc()
         assert lib.vp8g_make_tensor_desc(C.byref(opt), 0, 64, 80, 16, 8, 0, 0, C.byref(d)) == 0
         src = torch.zeros(96, dtype=torch.uint8, device=dev)
-        d_d = torch.frombuffer(bytearray(bytes(d)), dtype=torch.uint8).to(dev)
+        d_d = vp8g.device_copy(d)
         out = torch.full((1024,), 0xEE, dtype=torch.uint8, device=dev)
         C.set_errno(0)
         assert lib.vp8g_tensor_batch_device(C.byref(d), C.c_void_p(d_d.data_ptr()), 1, C.byref(opt), C.c_void_p(src.data_ptr()),
@@ -174,8 +174,8 @@ def test_scale_chains_into_the_tensor_kernel_on_the_device(vp8g):
     src = torch.from_numpy(np.frombuffer(b"".join(planes), dtype=np.uint8).copy()).to(dev)
     small = torch.empty(do + 16, dtype=torch.uint8, device=dev)
     out = torch.empty((n, 3, h, w), dtype=torch.float16, device=dev)
-    d_s = torch.frombuffer(bytearray(bytes(sdescs)), dtype=torch.uint8).to(dev)
-    d_t = torch.frombuffer(bytearray(bytes(tdescs)), dtype=torch.uint8).to(dev)
+    d_s = vp8g.device_copy(sdescs)
+    d_t = vp8g.device_copy(tdescs)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     assert lib.vp8g_scale_batch_device(sdescs, C.c_void_p(d_s.data_ptr()), n, C.c_void_p(src.data_ptr()),
                                        C.c_void_p(small.data_ptr()), stream) == 0

@@ -16,16 +16,16 @@ from __future__ import annotations
 import ctypes as C
 import os
 import pathlib
+from types import SimpleNamespace
 
 import numpy as np
+
+import vp8g_stage as S
+from vp8g_stage import ByteSpan, device_copy, image_bytes as _image_bytes  # noqa: F401  (names callers know from here)
 
 PKG_DIR = pathlib.Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
 LIB_DIR = PKG_DIR / "lib"
-
-
-class ByteSpan(C.Structure):
-    _fields_ = [("data", C.POINTER(C.c_uint8)), ("size", C.c_size_t)]
 
 
 class Vp8KeyFrameHeader(C.Structure):
@@ -309,8 +309,7 @@ T_LAYOUTS = {"NHWC": 0, "NCHW": 1}
 VP8G_T_BGR = 1
 
 PK_BLOCKS = 25  # per MB: Y 0..15, U 0..3, V 0..3, Y2
-VP8G_BATCH_DEVICE_M05 = 1
-VP8G_BATCH_MULTI_PARTITION = 2
+VP8G_BATCH_DEVICE_M05, VP8G_BATCH_MULTI_PARTITION = S.BATCH_DEVICE_M05, S.BATCH_MULTI_PARTITION
 VP8F_PACK_HASH = 1
 VP8F_MULTI_PARTITION = 2
 
@@ -769,7 +768,7 @@ def gpu_m05(files: list[bytes], multi_partition: bool = False) -> list[dict]:
         bits[b0:b0 + size] = np.frombuffer(data, np.uint8, size, off)
     dev = torch.device("cuda:0")
     d_bits = torch.from_numpy(bits).to(dev)
-    d_jobs = torch.from_numpy(np.frombuffer(bytes(jobs), np.uint8).copy()).to(dev)
+    d_jobs = device_copy(jobs)
     per = {n_: (dt, k) for n_, dt, k in FRAME_ARRAYS}
     names = ["coeff_y", "coeff_u", "coeff_v", "coeff_y2", "ymode", "uv_mode", "segment_id", "has_coeff", "bmode"]
     tdt = {np.dtype(np.int16): torch.int16, np.dtype(np.uint8): torch.uint8}
@@ -796,23 +795,17 @@ def gpu_decode_webp_batch(files: list[bytes], filtered: bool = True, threads: in
     device_m05: m05 on the device (VP8G_BATCH_DEVICE_M05) instead of the host threads."""
     lib = gpu_lib()
     n = len(files)
-    bufs = [(C.c_uint8 * max(1, len(b))).from_buffer_copy(b if b else b"\0") for b in files]
-    spans = (ByteSpan * n)(*[ByteSpan(C.cast(bufs[i], C.POINTER(C.c_uint8)), len(files[i])) for i in range(n)])
+    bufs, spans = S.file_spans(files)
+    flags = S.batch_flags(device_m05, multi_partition)
     imgs = (Yuv420Image * n)()
     st = (C.c_int * n)()
     import time
     t0 = time.perf_counter()
-    rc = lib.vp8g_decode_webp_batch_ex(spans, n, int(filtered), threads,
-                                       (VP8G_BATCH_DEVICE_M05 if device_m05 else 0)
-                                       | (VP8G_BATCH_MULTI_PARTITION if multi_partition else 0), imgs, st)
+    rc = lib.vp8g_decode_webp_batch_ex(spans, n, int(filtered), threads, flags, imgs, st)
     gpu_decode_webp_batch.seconds = time.perf_counter() - t0  # the C call alone (no Python copies)
     if rc != 0 and all(s == 5 for s in st):  # EIO: device failure, nothing returned
         raise RuntimeError(f"vp8g_decode_webp_batch failed: {lib.vp8g_last_error()!r}")
-    out = []
-    for i in range(n):
-        out.append(_image_bytes(imgs[i]) if st[i] == 0 else None)
-        lib.yuv420_free(C.byref(imgs[i]))
-    return out, list(st)
+    return S.take_images(lib, imgs, st, with_size=False), list(st)
 
 
 def scale_opt(crop=None, scale=None, dwebp_filter: bool = False, expand: bool = False) -> Vp8gScaleOpt:
@@ -869,32 +862,24 @@ def gpu_decode_webp_batch_scaled(files: list[bytes], scale, filtered: bool = Tru
     Returns (list of (I420 bytes, w, h) or None, list of errno)."""
     lib = gpu_lib()
     n = len(files)
-    bufs = [(C.c_uint8 * max(1, len(b))).from_buffer_copy(b if b else b"\0") for b in files]
-    spans = (ByteSpan * n)(*[ByteSpan(C.cast(bufs[i], C.POINTER(C.c_uint8)), len(files[i])) for i in range(n)])
-    opts = list(scale) if isinstance(scale, (list, tuple)) else [scale]
-    c_opts = (Vp8gScaleOpt * len(opts))(*opts)
+    bufs, spans = S.file_spans(files)
+    c_opts, nopts = S.scale_opts(scale)
+    flags = S.batch_flags(device_m05, multi_partition)
     imgs = (Yuv420Image * n)()
     st = (C.c_int * n)()
     import time
     t0 = time.perf_counter()
-    rc = lib.vp8g_decode_webp_batch_scaled(spans, n, int(filtered), threads,
-                                           (VP8G_BATCH_DEVICE_M05 if device_m05 else 0)
-                                           | (VP8G_BATCH_MULTI_PARTITION if multi_partition else 0), c_opts, len(opts),
-                                           imgs, st)
+    rc = lib.vp8g_decode_webp_batch_scaled(spans, n, int(filtered), threads, flags, c_opts, nopts, imgs, st)
     gpu_decode_webp_batch_scaled.seconds = time.perf_counter() - t0  # the C call alone
     en = C.get_errno()
     if rc != 0 and (all(s == 5 for s in st) or not any(st)):  # EIO: device failure; or the call itself refused
         raise RuntimeError(f"vp8g_decode_webp_batch_scaled failed: errno={en} {lib.vp8g_last_error()!r}")
-    out = []
-    for i in range(n):
-        out.append((_image_bytes(imgs[i]), int(imgs[i].width), int(imgs[i].height)) if st[i] == 0 else None)
-        lib.yuv420_free(C.byref(imgs[i]))
-    return out, list(st)
+    return S.take_images(lib, imgs, st, with_size=True), list(st)
 
 
 def _c_bytes(data: bytes):
-    buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(data if data else b"\0")
-    return buf, ByteSpan(C.cast(buf, C.POINTER(C.c_uint8)), len(data))
+    bufs, spans = S.file_spans([data])
+    return bufs[0], spans[0]
 
 
 def parse_simple(data: bytes):
@@ -952,44 +937,46 @@ def host_alpha_plane(data: bytes):
     return host_alpha_unfilter(res, flt)
 
 
+def stage_alpha_unfilter(planes, filters, src_pad: int = 0, guard: int = 0, fill: int = 0xEE):
+    """The host half of gpu_alpha_unfilter: descriptors, source bytes (rows padded by src_pad) and the guarded destination."""
+    lib = gpu_lib()
+    descs = (Vp8gAlphaDesc * len(planes))()
+    source, dst, task0 = S.Source(), S.Guarded(guard, fill), 0
+    for i, (p, f) in enumerate(zip(planes, filters)):
+        h, w = np.asarray(p).shape
+        padded = np.pad(np.asarray(p, dtype=np.uint8), ((0, 0), (0, src_pad)), constant_values=S.PAD)
+        if lib.vp8g_make_alpha_desc(w, h, f, source.put(padded), w + src_pad, dst.add(w * h), w, task0, C.byref(descs[i])) != 0:
+            raise ValueError(f"vp8g_make_alpha_desc failed: errno={C.get_errno()}")
+        task0 += descs[i].ntasks
+    return SimpleNamespace(descs=descs, source=source, src=source.finish(tail=0), dst=dst)
+
+
+def _run(name: str, st, what: str, *opt_args, mutate=None, desc_tail: int = 0, ptr_shift=(), einval=None):
+    """The device half of a staged call: upload, lib.<name>(descs, device descs, n, *opt_args, src, [work,] dst, stream),
+    and the destination back on the host (a torch CPU uint8 tensor) once the guards are seen to hold their fill --
+    AssertionError("<what> were written") otherwise.  ptr_shift: bytes added to the source, output and descriptor pointers."""
+    work = getattr(st, "work", None)
+    d_src, d_dst, d_descs = S.upload(st.src), st.dst.on_device(), device_copy(st.descs, desc_tail)
+    d_work = [work.on_device()] if work else []
+    if mutate:  # (after the device copies are made: the kernel never sees what a test breaks in the host copies)
+        mutate()
+    stream, shift = S.stream(), (*ptr_shift, 0, 0, 0)
+    S.call(gpu_lib(), name, st.descs, (d_descs, shift[2]), len(st.descs), *opt_args, (d_src, shift[0]), *d_work, (d_dst, shift[1]),
+           stream.cuda_stream, einval=einval, untouched=(d_dst, st.dst.fill))
+    stream.synchronize()
+    host = st.dst.fetch(d_dst, what)
+    if work:
+        work.fetch(d_work[0], what.split(":")[0] + ": bytes outside the work regions")
+    return host
+
+
 def gpu_alpha_unfilter(planes, filters, src_pad: int = 0, guard: int = 0, fill: int = 0xEE):
     """vp8g_alpha_unfilter_batch_device over residual planes (uint8 [h, w] each) of mixed sizes and filters in
     one launch: the list of un-predicted planes.  src_pad: extra bytes per source row (a padded stride);
     guard: bytes kept around every destination plane, which the call checks still hold `fill`."""
-    import torch
-    lib = gpu_lib()
-    dev = torch.device("cuda", 0)
-    n = len(planes)
-    descs = (Vp8gAlphaDesc * n)()
-    src_parts, so, do, task0 = [], 0, guard, 0
-    for i, (p, f) in enumerate(zip(planes, filters)):
-        p = np.ascontiguousarray(p, dtype=np.uint8)
-        h, w = p.shape
-        padded = np.full((h, w + src_pad), 0x5A, np.uint8)
-        padded[:, :w] = p
-        src_parts.append(padded.reshape(-1))
-        if lib.vp8g_make_alpha_desc(w, h, f, so, w + src_pad, do, w, task0, C.byref(descs[i])) != 0:
-            raise ValueError(f"vp8g_make_alpha_desc failed: errno={C.get_errno()}")
-        task0 += descs[i].ntasks
-        so += padded.size
-        do += w * h + guard
-    src = torch.from_numpy(np.concatenate(src_parts)).to(dev)
-    dst = torch.full((do,), fill, dtype=torch.uint8, device=dev)
-    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
-    stream = torch.cuda.current_stream(dev)
-    if lib.vp8g_alpha_unfilter_batch_device(descs, C.c_void_p(d_descs.data_ptr()), n, C.c_void_p(src.data_ptr()),
-                                            C.c_void_p(dst.data_ptr()), C.c_void_p(stream.cuda_stream)) != 0:
-        raise RuntimeError(f"vp8g_alpha_unfilter_batch_device failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
-    stream.synchronize()
-    host = dst.cpu().numpy()
-    out, keep = [], np.ones(do, bool)
-    for i, p in enumerate(planes):
-        h, w = np.asarray(p).shape
-        out.append(host[descs[i].dst:descs[i].dst + w * h].reshape(h, w).copy())
-        keep[descs[i].dst:descs[i].dst + w * h] = False
-    if not (host[keep] == fill).all():
-        raise AssertionError("gpu_alpha_unfilter: bytes outside the planes were written")
-    return out
+    st = stage_alpha_unfilter(planes, filters, src_pad, guard, fill)
+    host = _run("vp8g_alpha_unfilter_batch_device", st, "gpu_alpha_unfilter: bytes outside the planes").numpy()
+    return [host[o:o + n].reshape(np.asarray(p).shape).copy() for (o, n), p in zip(st.dst.regions, planes)]
 
 
 def host_scale_plane(plane, opt: Vp8gScaleOpt) -> np.ndarray:
@@ -1002,34 +989,28 @@ def host_scale_plane(plane, opt: Vp8gScaleOpt) -> np.ndarray:
     return np.frombuffer(out, np.uint8, ow * oh).reshape(oh, ow).copy()
 
 
+def stage_scale_planes(planes, opts):
+    """The host half of gpu_scale_planes: descriptors, the planes back to back, the destination with a 16-byte tail."""
+    lib = gpu_lib()
+    descs = (Vp8gScaleDesc * len(planes))()
+    source, dst, task0 = S.Source(), S.Guarded(0, 0xEE), 0
+    for i, (p, opt) in enumerate(zip(planes, opts)):
+        h, w = p.shape
+        if lib.vp8g_make_scale_desc_plane(w, h, source.put(np.asarray(p, dtype=np.uint8)), w, C.byref(opt), dst.size, task0,
+                                          C.byref(descs[i])) != 0:
+            raise ValueError(f"vp8g_make_scale_desc_plane failed: errno={C.get_errno()}")
+        task0 += descs[i].ntasks
+        dst.add(descs[i].width * descs[i].height)
+    dst.size += 16  # (no guards between the planes: a tail only)
+    return SimpleNamespace(descs=descs, source=source, src=source.finish(tail=0), dst=dst)
+
+
 def gpu_scale_planes(planes, opts):
     """vp8g_make_scale_desc_plane + vp8g_scale_batch_device over uint8 [h, w] planes (opts: one Vp8gScaleOpt per
     plane) in one launch: the list of scaled planes."""
-    import torch
-    lib = gpu_lib()
-    dev = torch.device("cuda", 0)
-    n = len(planes)
-    descs = (Vp8gScaleDesc * n)()
-    so = do = task0 = 0
-    for i, (p, opt) in enumerate(zip(planes, opts)):
-        h, w = p.shape
-        if lib.vp8g_make_scale_desc_plane(w, h, so, w, C.byref(opt), do, task0, C.byref(descs[i])) != 0:
-            raise ValueError(f"vp8g_make_scale_desc_plane failed: errno={C.get_errno()}")
-        task0 += descs[i].ntasks
-        so += w * h
-        do += descs[i].width * descs[i].height
-    src = torch.from_numpy(np.concatenate([np.ascontiguousarray(p, dtype=np.uint8).reshape(-1) for p in planes])).to(dev)
-    dst = torch.full((do + 16,), 0xEE, dtype=torch.uint8, device=dev)
-    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
-    stream = torch.cuda.current_stream(dev)
-    if lib.vp8g_scale_batch_device(descs, C.c_void_p(d_descs.data_ptr()), n, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
-                                   C.c_void_p(stream.cuda_stream)) != 0:
-        raise RuntimeError(f"vp8g_scale_batch_device failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
-    stream.synchronize()
-    host = dst.cpu().numpy()
-    if not (host[do:] == 0xEE).all():
-        raise AssertionError("gpu_scale_planes: bytes after the planes were written")
-    return [host[d.p[0].dst:d.p[0].dst + d.width * d.height].reshape(d.height, d.width).copy() for d in descs]
+    st = stage_scale_planes(planes, opts)
+    host = _run("vp8g_scale_batch_device", st, "gpu_scale_planes: bytes after the planes").numpy()
+    return [host[o:o + n].reshape(d.height, d.width).copy() for (o, n), d in zip(st.dst.regions, st.descs)]
 
 
 def _dtype_name(dtype) -> str:
@@ -1147,7 +1128,7 @@ def gpu_tensor(i420_list, w: int, h: int, opt: Vp8gTensorOpt, alpha=None):
                                      C.byref(descs[i])) != 0:
             raise ValueError("vp8g_make_tensor_desc failed")
         task0 += descs[i].ntasks
-    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
+    d_descs = device_copy(descs)
     stream = torch.cuda.current_stream(dev)
     if alpha is not None:
         if len(alpha) != n:
@@ -1163,20 +1144,14 @@ def gpu_tensor(i420_list, w: int, h: int, opt: Vp8gTensorOpt, alpha=None):
             al[i] = Vp8gTensorAlpha(ao, w, 0)
             parts.append(a.reshape(-1))
             ao += w * h
-        src = torch.from_numpy(np.concatenate([np.frombuffer(b"".join(i420_list), dtype=np.uint8)] + parts)).to(dev)
-        d_al = torch.frombuffer(bytearray(bytes(al)), dtype=torch.uint8).to(dev)
+        src = S.upload(np.concatenate([np.frombuffer(b"".join(i420_list), dtype=np.uint8)] + parts))
+        d_al = device_copy(al)
         out = torch.empty(_tensor_shape(n, opt, 4), dtype=_torch_dtype(opt), device=dev)
-        if lib.vp8g_tensor_batch_device_a(descs, C.c_void_p(d_descs.data_ptr()), al, C.c_void_p(d_al.data_ptr()), n, C.byref(opt),
-                                          C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()),
-                                          C.c_void_p(stream.cuda_stream)) != 0:
-            raise RuntimeError(f"vp8g_tensor_batch_device_a failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
-        stream.synchronize()
-        return out
-    src = torch.from_numpy(np.frombuffer(b"".join(i420_list), dtype=np.uint8).copy()).to(dev)
-    out = torch.empty(_tensor_shape(n, opt), dtype=_torch_dtype(opt), device=dev)
-    if lib.vp8g_tensor_batch_device(descs, C.c_void_p(d_descs.data_ptr()), n, C.byref(opt), C.c_void_p(src.data_ptr()),
-                                    C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)) != 0:
-        raise RuntimeError(f"vp8g_tensor_batch_device failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
+        S.call(lib, "vp8g_tensor_batch_device_a", descs, d_descs, al, d_al, n, C.byref(opt), src, out, stream.cuda_stream)
+    else:
+        src = S.upload(np.frombuffer(b"".join(i420_list), dtype=np.uint8).copy())
+        out = torch.empty(_tensor_shape(n, opt), dtype=_torch_dtype(opt), device=dev)
+        S.call(lib, "vp8g_tensor_batch_device", descs, d_descs, n, C.byref(opt), src, out, stream.cuda_stream)
     stream.synchronize()
     return out
 
@@ -1296,57 +1271,32 @@ def host_lossless_argb(data: bytes) -> np.ndarray:
     return host_lossless_apply(lossless_decode_host(data[c["vp8l_chunk_offset"]:c["vp8l_chunk_offset"] + c["vp8l_chunk_size"]]))
 
 
+def stage_lossless_argb(images, src_shift: int = 1, guard: int = 64, fill: int = 0xEE):
+    """The host half of gpu_lossless_argb: descriptors, the residual images, sub-images and colour tables src_shift bytes
+    off a dword boundary, the guarded destination."""
+    lib = gpu_lib()
+    descs = (Vp8gLosslessDesc * len(images))()
+    source, dst = S.Source(), S.Guarded(guard, fill)
+    for i, img in enumerate(images):
+        tr = (Vp8gLosslessTransform * 4)()
+        src = source.put(np.asarray(img["residual"], dtype=np.uint32), 4, src_shift)
+        for k, t in enumerate(img["transforms"]):
+            data = np.asarray(t["data"], dtype=np.uint32)
+            tr[k] = Vp8gLosslessTransform(source.put(data, 4, src_shift) if data.size else 0, t["type"], t["bits"], t["xsize"], t["ncolors"])
+        if lib.vp8g_make_lossless_desc(img["width"], img["height"], src, dst.add(4 * img["width"] * img["height"]), len(img["transforms"]),
+                                       tr, i, C.byref(descs[i])) != 0:
+            raise ValueError(f"vp8g_make_lossless_desc failed: errno={C.get_errno()}")
+    return SimpleNamespace(descs=descs, source=source, src=source.finish(), dst=dst)
+
+
 def gpu_lossless_argb(images, src_shift: int = 1, guard: int = 64, fill: int = 0xEE):
     """vp8g_lossless_batch_device over images in lossless_decode_host's form, of mixed sizes and transform lists, in
     one launch: the list of uint32 [h, w] pictures.  src_shift: every residual image, sub-image and colour table
     starts at an offset that is this much off a dword boundary; guard: bytes kept around every output, which the
     call checks still hold `fill`."""
-    import torch
-    lib = gpu_lib()
-    dev = torch.device("cuda", 0)
-    n = len(images)
-    descs = (Vp8gLosslessDesc * n)()
-    parts, so, do = [], 0, guard
-
-    def put(a):
-        nonlocal so
-        pad = (-so) % 4 + src_shift
-        parts.append(np.full(pad, 0x5A, np.uint8))
-        so += pad
-        off = so
-        b = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1).view(np.uint8)
-        parts.append(b)
-        so += b.size
-        return off
-
-    for i, img in enumerate(images):
-        tr = (Vp8gLosslessTransform * 4)()
-        src = put(img["residual"])
-        for k, t in enumerate(img["transforms"]):
-            tr[k] = Vp8gLosslessTransform(put(t["data"]) if np.asarray(t["data"]).size else 0, t["type"], t["bits"], t["xsize"],
-                                          t["ncolors"])
-        if lib.vp8g_make_lossless_desc(img["width"], img["height"], src, do, len(img["transforms"]), tr, i,
-                                       C.byref(descs[i])) != 0:
-            raise ValueError(f"vp8g_make_lossless_desc failed: errno={C.get_errno()}")
-        do += 4 * img["width"] * img["height"] + guard
-    parts.append(np.full(16, 0x5A, np.uint8))
-    src = torch.from_numpy(np.concatenate(parts)).to(dev)
-    dst = torch.full((do,), fill, dtype=torch.uint8, device=dev)
-    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
-    stream = torch.cuda.current_stream(dev)
-    if lib.vp8g_lossless_batch_device(descs, C.c_void_p(d_descs.data_ptr()), n, C.c_void_p(src.data_ptr()),
-                                      C.c_void_p(dst.data_ptr()), C.c_void_p(stream.cuda_stream)) != 0:
-        raise RuntimeError(f"vp8g_lossless_batch_device failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
-    stream.synchronize()
-    host = dst.cpu().numpy()
-    out, keep = [], np.ones(do, bool)
-    for i, img in enumerate(images):
-        nb = 4 * img["width"] * img["height"]
-        out.append(host[descs[i].dst:descs[i].dst + nb].view(np.uint32).reshape(img["height"], img["width"]).copy())
-        keep[descs[i].dst:descs[i].dst + nb] = False
-    if not (host[keep] == fill).all():
-        raise AssertionError("gpu_lossless_argb: bytes outside the images were written")
-    return out
+    st = stage_lossless_argb(images, src_shift, guard, fill)
+    host = _run("vp8g_lossless_batch_device", st, "gpu_lossless_argb: bytes outside the images").numpy()
+    return [host[o:o + n].view(np.uint32).reshape(img["height"], img["width"]).copy() for (o, n), img in zip(st.dst.regions, images)]
 
 
 def scaled_size_argb(w: int, h: int, opt: Vp8gScaleOpt):
@@ -1381,57 +1331,37 @@ def host_scale_argb(argb, opt: Vp8gScaleOpt) -> np.ndarray:
     return out
 
 
+def stage_scale_argb(argb_list, opts, src_shift: int = 1, guard: int = 64, fill: int = 0xEE):
+    """The host half of gpu_scale_argb: descriptors, the pictures src_shift dwords off a 16-byte boundary, the guarded work
+    area (its head exempt) and the guarded destination of 16-byte outputs."""
+    lib = gpu_lib()
+    n = len(argb_list)
+    descs = (Vp8gScaleArgbDesc * n)()
+    source, dst = S.Source(), S.Guarded(guard, fill, round_to=16)
+    work = S.Guarded(guard, fill, head=int(lib.vp8g_scale_argb_head_size(n)))
+    planes = t_split = t_scale = t_merge = 0
+    for i, (a, opt) in enumerate(zip(argb_list, opts)):
+        a = np.asarray(a, dtype=np.uint32)
+        h, w = a.shape
+        if lib.vp8g_make_scale_argb_desc(w, h, source.put(a, 16, 4 * src_shift), C.byref(opt), work.size, dst.size, planes, t_split, t_scale,
+                                         t_merge, C.byref(descs[i])) != 0:
+            raise ValueError(f"vp8g_make_scale_argb_desc failed: errno={C.get_errno()}")
+        d = descs[i]
+        assert d.work_bytes == lib.vp8g_scale_argb_work_size(w, h, C.byref(opt))
+        planes, t_split, t_scale, t_merge = planes + d.nplanes, t_split + d.split_ntasks, t_scale + d.scale_ntasks, t_merge + d.merge_ntasks
+        work.add(d.work_bytes)
+        dst.add(4 * d.width * d.height)
+    return SimpleNamespace(descs=descs, source=source, src=source.finish(), dst=dst, work=work)
+
+
 def gpu_scale_argb(argb_list, opts, src_shift: int = 1, guard: int = 64, fill: int = 0xEE):
     """vp8g_make_scale_argb_desc + vp8g_scale_argb_batch_device over uint32 [h, w] 0xAARRGGBB pictures of mixed sizes
     (opts: one Vp8gScaleOpt per picture) in one launch: the list of scaled uint32 [h', w'] pictures.  src_shift: every
     source picture starts this many DWORDS off a 16-byte boundary; guard (a multiple of 16): bytes kept around every
     picture's work region and every output, which the call checks still hold `fill`."""
-    import torch
-    lib = gpu_lib()
-    dev = torch.device("cuda", 0)
-    n = len(argb_list)
-    descs = (Vp8gScaleArgbDesc * n)()
-    parts, so = [], 0
-    wo, do = int(lib.vp8g_scale_argb_head_size(n)) + guard, guard
-    planes = t_split = t_scale = t_merge = 0
-    for i, (a, opt) in enumerate(zip(argb_list, opts)):
-        a = np.ascontiguousarray(a, dtype=np.uint32)
-        h, w = a.shape
-        pad = (-so) % 16 + 4 * src_shift
-        parts += [np.full(pad, 0x5A, np.uint8), a.reshape(-1).view(np.uint8)]
-        if lib.vp8g_make_scale_argb_desc(w, h, so + pad, C.byref(opt), wo, do, planes, t_split, t_scale, t_merge,
-                                         C.byref(descs[i])) != 0:
-            raise ValueError(f"vp8g_make_scale_argb_desc failed: errno={C.get_errno()}")
-        d = descs[i]
-        assert d.work_bytes == lib.vp8g_scale_argb_work_size(w, h, C.byref(opt))
-        so += pad + a.size * 4
-        planes, t_split, t_scale, t_merge = planes + d.nplanes, t_split + d.split_ntasks, t_scale + d.scale_ntasks, t_merge + d.merge_ntasks
-        wo += d.work_bytes + guard
-        do += (4 * d.width * d.height + 15) // 16 * 16 + guard
-    parts.append(np.full(16, 0x5A, np.uint8))
-    src = torch.from_numpy(np.concatenate(parts)).to(dev)
-    work = torch.full((wo,), fill, dtype=torch.uint8, device=dev)
-    dst = torch.full((do,), fill, dtype=torch.uint8, device=dev)
-    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
-    stream = torch.cuda.current_stream(dev)
-    if lib.vp8g_scale_argb_batch_device(descs, C.c_void_p(d_descs.data_ptr()), n, C.c_void_p(src.data_ptr()),
-                                        C.c_void_p(work.data_ptr()), C.c_void_p(dst.data_ptr()),
-                                        C.c_void_p(stream.cuda_stream)) != 0:
-        raise RuntimeError(f"vp8g_scale_argb_batch_device failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
-    stream.synchronize()
-    hw, hd = work.cpu().numpy(), dst.cpu().numpy()
-    out, keep_w, keep_d = [], np.ones(wo, bool), np.ones(do, bool)
-    keep_w[:int(lib.vp8g_scale_argb_head_size(n))] = False
-    for d in descs:
-        nb = 4 * d.width * d.height
-        out.append(hd[d.dst:d.dst + nb].view(np.uint32).reshape(d.height, d.width).copy())
-        keep_d[d.dst:d.dst + nb] = False
-        keep_w[d.work:d.work + d.work_bytes] = False
-    if not (hd[keep_d] == fill).all():
-        raise AssertionError("gpu_scale_argb: bytes outside the outputs were written")
-    if not (hw[keep_w] == fill).all():
-        raise AssertionError("gpu_scale_argb: bytes outside the work regions were written")
-    return out
+    st = stage_scale_argb(argb_list, opts, src_shift, guard, fill)
+    host = _run("vp8g_scale_argb_batch_device", st, "gpu_scale_argb: bytes outside the outputs").numpy()
+    return [host[o:o + n].view(np.uint32).reshape(d.height, d.width).copy() for (o, n), d in zip(st.dst.regions, st.descs)]
 
 
 def host_tensor_argb(argb, opt: Vp8gTensorOpt, channels: int = 4):
@@ -1479,17 +1409,13 @@ def gpu_tensor_argb(argb_list, opt: Vp8gTensorOpt, channels: int = 4, slot_shift
         if lib.vp8g_make_tensor_argb_desc(C.byref(opt), channels, i * 4 * w * h, i * slot, task0, C.byref(descs[i])) != 0:
             raise ValueError("vp8g_make_tensor_argb_desc failed")
         task0 += descs[i].ntasks
-    src = torch.from_numpy(np.concatenate([np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in argb_list])
-                           .view(np.uint8)).to(dev)
-    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
+    src = S.upload(np.concatenate([np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in argb_list]).view(np.uint8))
+    d_descs = device_copy(descs)
     shape = _tensor_shape(n, opt, channels)
     flat = torch.zeros(int(np.prod(shape)) + slot_shift, dtype=_torch_dtype(opt), device=dev)
     out = flat[slot_shift:].view(shape)
     stream = torch.cuda.current_stream(dev)
-    if lib.vp8g_tensor_batch_device_argb(descs, C.c_void_p(d_descs.data_ptr()), n, C.byref(opt), channels,
-                                         C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()),
-                                         C.c_void_p(stream.cuda_stream)) != 0:
-        raise RuntimeError(f"vp8g_tensor_batch_device_argb failed: errno={C.get_errno()} {lib.vp8g_last_error()!r}")
+    S.call(lib, "vp8g_tensor_batch_device_argb", descs, d_descs, n, C.byref(opt), channels, src, out, stream.cuda_stream)
     stream.synchronize()
     return out
 
@@ -1511,6 +1437,22 @@ def make_scale_argb_tensor_desc(w: int, h: int, opt: Vp8gScaleOpt, src: int = 0,
     return d
 
 
+def stage_scale_argb_tensor(argb_list, opts, topt: Vp8gTensorOpt, channels: int = 4, src_shift: int = 1, guard: int = 64, fill: int = 0xEE):
+    """The host half of gpu_scale_argb_tensor: descriptors, the pictures src_shift dwords off a 16-byte boundary, the guarded
+    destination of 8-byte slots.  OSError with the maker's errno if it refuses a picture."""
+    lib = gpu_lib()
+    descs = (Vp8gScaleArgbTensorDesc * len(argb_list))()
+    source, dst, task0 = S.Source(), S.Guarded(guard, fill, round_to=8), 0
+    for i, (a, opt) in enumerate(zip(argb_list, opts)):
+        a = np.asarray(a, dtype=np.uint32)
+        h, w = a.shape
+        if lib.vp8g_make_scale_argb_tensor_desc(w, h, source.put(a, 16, 4 * src_shift), C.byref(opt), dst.size, task0, C.byref(descs[i])) != 0:
+            raise OSError(C.get_errno(), "vp8g_make_scale_argb_tensor_desc")
+        task0 += descs[i].ntasks
+        dst.add(channels * descs[i].width * descs[i].height * T_ELEM[topt.dtype])
+    return SimpleNamespace(descs=descs, source=source, src=source.finish(), dst=dst)
+
+
 def gpu_scale_argb_tensor(argb_list, opts, topt: Vp8gTensorOpt, channels: int = 4, src_shift: int = 1, guard: int = 64, fill: int = 0xEE,
                           mutate=None, ptr_shift=(0, 0, 0)):
     """vp8g_make_scale_argb_tensor_desc + vp8g_scale_argb_tensor_batch_device over uint32 [h, w] 0xAARRGGBB pictures of mixed
@@ -1520,50 +1462,12 @@ def gpu_scale_argb_tensor(argb_list, opts, topt: Vp8gTensorOpt, channels: int = 
     still hold `fill`.  mutate(descs): called on the host descriptors after the device copies are made; ptr_shift: bytes
     added to the source, output and descriptor pointers handed to the call (both for tests of the entry point's checks: a
     refusal raises ValueError, once the output is seen untouched)."""
-    import torch
-    lib = gpu_lib()
-    dev = torch.device("cuda", 0)
-    n, eb = len(argb_list), T_ELEM[topt.dtype]
-    descs = (Vp8gScaleArgbTensorDesc * n)()
-    parts, so, do, task0 = [], 0, guard, 0
-    for i, (a, opt) in enumerate(zip(argb_list, opts)):
-        a = np.ascontiguousarray(a, dtype=np.uint32)
-        h, w = a.shape
-        pad = (-so) % 16 + 4 * src_shift
-        parts += [np.full(pad, 0x5A, np.uint8), a.reshape(-1).view(np.uint8)]
-        if lib.vp8g_make_scale_argb_tensor_desc(w, h, so + pad, C.byref(opt), do, task0, C.byref(descs[i])) != 0:
-            raise OSError(C.get_errno(), "vp8g_make_scale_argb_tensor_desc")
-        so += pad + a.size * 4
-        task0 += descs[i].ntasks
-        do += (channels * descs[i].width * descs[i].height * eb + 7) // 8 * 8 + guard
-    parts.append(np.full(16, 0x5A, np.uint8))
-    src = torch.from_numpy(np.concatenate(parts)).to(dev)
-    dst = torch.full((do,), fill, dtype=torch.uint8, device=dev)
-    d_descs = torch.frombuffer(bytearray(bytes(descs)) + bytearray(8), dtype=torch.uint8).to(dev)
-    if mutate:  # (after the device copies are made: the kernel never sees what a test breaks in the host copies)
-        mutate(descs)
-    stream = torch.cuda.current_stream(dev)
-    if lib.vp8g_scale_argb_tensor_batch_device(descs, C.c_void_p(d_descs.data_ptr() + ptr_shift[2]), n, C.byref(topt), channels,
-                                               C.c_void_p(src.data_ptr() + ptr_shift[0]), C.c_void_p(dst.data_ptr() + ptr_shift[1]),
-                                               C.c_void_p(stream.cuda_stream)) != 0:
-        en = C.get_errno()
-        if en == 22:
-            torch.cuda.synchronize(dev)
-            if not bool((dst == fill).all()):
-                raise AssertionError("gpu_scale_argb_tensor: a refused call wrote to the output")
-            raise ValueError("vp8g_scale_argb_tensor_batch_device: EINVAL")
-        raise RuntimeError(f"vp8g_scale_argb_tensor_batch_device failed: errno={en} {lib.vp8g_last_error()!r}")
-    stream.synchronize()
-    host = dst.cpu()
-    out, keep = [], np.ones(do, bool)
-    for d in descs:
-        nb = channels * d.width * d.height * eb
-        shape = (channels, d.height, d.width) if topt.layout == T_LAYOUTS["NCHW"] else (d.height, d.width, channels)
-        out.append(host[d.dst:d.dst + nb].clone().view(_torch_dtype(topt)).view(shape))
-        keep[d.dst:d.dst + nb] = False
-    if not (host.numpy()[keep] == fill).all():
-        raise AssertionError("gpu_scale_argb_tensor: bytes outside the slots were written")
-    return out
+    st = stage_scale_argb_tensor(argb_list, opts, topt, channels, src_shift, guard, fill)
+    host = _run("vp8g_scale_argb_tensor_batch_device", st, "gpu_scale_argb_tensor: bytes outside the slots", C.byref(topt), channels,
+                mutate=mutate and (lambda: mutate(st.descs)), desc_tail=8, ptr_shift=ptr_shift, einval=ValueError)
+    planar = topt.layout == T_LAYOUTS["NCHW"]
+    return [host[o:o + n].clone().view(_torch_dtype(topt)).view((channels, d.height, d.width) if planar else (d.height, d.width, channels))
+            for (o, n), d in zip(st.dst.regions, st.descs)]
 
 
 # ---- animated files (DESIGN.md §18) ---------------------------------------------------------
@@ -1689,6 +1593,24 @@ def anim_records(frames, srcs):
     return rec
 
 
+def stage_anim_compose(anims, opt: Vp8gTensorOpt, channels: int = 4, src_shift: int = 1, guard: int = 64, fill: int = 0xEE):
+    """The host half of gpu_anim_compose: descriptors, every frame picture src_shift dwords off a 16-byte boundary with each
+    animation's record array (`recs`, as vp8g_make_anim_desc completed them) behind its pictures, the guarded destination."""
+    lib = gpu_lib()
+    descs = (Vp8gAnimDesc * len(anims))()
+    source, dst, task0, recs = S.Source(), S.Guarded(guard, fill), 0, []
+    for i, (cw, ch, frames) in enumerate(anims):
+        rec = anim_records(frames, [source.put(np.asarray(f["argb"], dtype=np.uint32), 16, 4 * src_shift) for f in frames])
+        at = source.reserve(C.sizeof(rec), 8)  # (its offset goes into the descriptor, whose maker completes the records)
+        if lib.vp8g_make_anim_desc(cw, ch, rec, len(frames), at, dst.add(len(frames) * channels * cw * ch * T_ELEM[opt.dtype]), task0,
+                                   C.byref(descs[i])) != 0:
+            raise ValueError(f"vp8g_make_anim_desc failed: errno={C.get_errno()}")
+        source.fill(at, bytes(rec))
+        task0 += descs[i].ntasks
+        recs.append(rec)
+    return SimpleNamespace(descs=descs, source=source, src=source.finish(), dst=dst, recs=recs)
+
+
 def gpu_anim_compose(anims, opt: Vp8gTensorOpt, channels: int = 4, src_shift: int = 1, guard: int = 64, fill: int = 0xEE,
                      mutate=None, ptr_shift=(0, 0)):
     """vp8g_make_anim_desc + vp8g_anim_compose_batch_device over animations [(canvas_w, canvas_h, frames in
@@ -1697,67 +1619,22 @@ def gpu_anim_compose(anims, opt: Vp8gTensorOpt, channels: int = 4, src_shift: in
     starts this many DWORDS off a 16-byte boundary; guard (a multiple of 8): bytes kept in front of, between and behind
     the animations' canvases, which the call checks still hold `fill` (an animation's canvases are contiguous: a write
     into a neighbouring canvas shows in the comparison).  mutate(descs, records): called on the host descriptors and the
-    list of record arrays before the upload; ptr_shift: bytes added to the source and output pointers handed to the call
-    (both for tests of the entry point's checks: a refusal raises ValueError)."""
-    import torch
-    lib = gpu_lib()
-    dev = torch.device("cuda", 0)
-    n, eb = len(anims), T_ELEM[opt.dtype]
-    descs = (Vp8gAnimDesc * n)()
-    parts, so, do, task0, recs, rec_at = [], 0, guard, 0, [], []
-
-    def put(b, align, shift=0):
-        nonlocal so
-        pad = (-so) % align + shift
-        parts.append(np.full(pad, 0x5A, np.uint8))
-        so += pad + b.size
-        parts.append(b)
-        return so - b.size
-
-    for i, (cw, ch, frames) in enumerate(anims):
-        srcs = [put(np.ascontiguousarray(f["argb"], dtype=np.uint32).reshape(-1).view(np.uint8), 16, 4 * src_shift) for f in frames]
-        rec = anim_records(frames, srcs)
-        rec_at.append(put(np.zeros(C.sizeof(rec), np.uint8), 8))  # (filled in below, once vp8g_make_anim_desc has completed it)
-        recs.append((rec, len(parts) - 1))
-        if lib.vp8g_make_anim_desc(cw, ch, rec, len(frames), rec_at[i], do, task0, C.byref(descs[i])) != 0:
-            raise ValueError(f"vp8g_make_anim_desc failed: errno={C.get_errno()}")
-        task0 += descs[i].ntasks
-        do += len(frames) * channels * cw * ch * eb + guard
-    for rec, at in recs:
-        parts[at] = np.frombuffer(bytes(rec), np.uint8)
-    parts.append(np.full(16, 0x5A, np.uint8))
-    src = torch.from_numpy(np.concatenate(parts)).to(dev)
-    dst = torch.full((do,), fill, dtype=torch.uint8, device=dev)
-    d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
-    if mutate:  # (after the device copies are made: the kernel never sees what a test breaks in the host copies)
-        mutate(descs, [r for r, _ in recs])
-    stream = torch.cuda.current_stream(dev)
-    if lib.vp8g_anim_compose_batch_device(descs, C.c_void_p(d_descs.data_ptr()), n, C.byref(opt), channels,
-                                          C.c_void_p(src.data_ptr() + ptr_shift[0]), C.c_void_p(dst.data_ptr() + ptr_shift[1]),
-                                          C.c_void_p(stream.cuda_stream)) != 0:
-        en = C.get_errno()
-        if en == 22:
-            raise ValueError("vp8g_anim_compose_batch_device: EINVAL")
-        raise RuntimeError(f"vp8g_anim_compose_batch_device failed: errno={en} {lib.vp8g_last_error()!r}")
-    stream.synchronize()
-    host = dst.cpu()
-    out, keep = [], np.ones(do, bool)
-    for i, (cw, ch, frames) in enumerate(anims):
-        nb = len(frames) * channels * cw * ch * eb
-        shape = (len(frames), channels, ch, cw) if opt.layout == T_LAYOUTS["NCHW"] else (len(frames), ch, cw, channels)
-        out.append(host[descs[i].dst:descs[i].dst + nb].clone().view(_torch_dtype(opt)).view(shape))
-        keep[descs[i].dst:descs[i].dst + nb] = False
-    if not (host.numpy()[keep] == fill).all():
-        raise AssertionError("gpu_anim_compose: bytes outside the canvases were written")
-    return out
+    list of record arrays after the device copies are made; ptr_shift: bytes added to the source and output pointers handed
+    to the call (both for tests of the entry point's checks: a refusal raises ValueError, once the output is seen
+    untouched)."""
+    st = stage_anim_compose(anims, opt, channels, src_shift, guard, fill)
+    host = _run("vp8g_anim_compose_batch_device", st, "gpu_anim_compose: bytes outside the canvases", C.byref(opt), channels,
+                mutate=mutate and (lambda: mutate(st.descs, st.recs)), ptr_shift=ptr_shift, einval=ValueError)
+    planar = opt.layout == T_LAYOUTS["NCHW"]
+    return [host[o:o + n].clone().view(_torch_dtype(opt)).view((len(fr), channels, ch, cw) if planar else (len(fr), ch, cw, channels))
+            for (o, n), (cw, ch, fr) in zip(st.dst.regions, anims)]
 
 
 def anim_info(files: list[bytes]):
     """vp8g_anim_info: (list of {"canvas": [w, h], "nframes", "loop_count"}, list of errno) -- a refused file has no frames."""
     lib = gpu_lib()
     n = len(files)
-    bufs = [(C.c_uint8 * max(1, len(b))).from_buffer_copy(b if b else b"\0") for b in files]
-    spans = (ByteSpan * n)(*[ByteSpan(C.cast(bufs[i], C.POINTER(C.c_uint8)), len(files[i])) for i in range(n)])
+    bufs, spans = S.file_spans(files)
     cw, ch, nf, lc = ((C.c_uint32 * n)() for _ in range(4))
     st = (C.c_int * n)()
     lib.vp8g_anim_info(spans, n, cw, ch, nf, lc, st)
@@ -1781,8 +1658,7 @@ def gpu_decode_webp_anim_tensor(files: list[bytes], opt: Vp8gTensorOpt, alpha: b
     info, _ = anim_info(files)
     first = [sum(a["nframes"] for a in info[:i]) for i in range(n)]
     total = sum(a["nframes"] for a in info)
-    bufs = [(C.c_uint8 * max(1, len(b))).from_buffer_copy(b if b else b"\0") for b in files]
-    spans = (ByteSpan * n)(*[ByteSpan(C.cast(bufs[i], C.POINTER(C.c_uint8)), len(files[i])) for i in range(n)])
+    bufs, spans = S.file_spans(files)
     channels = 4 if alpha else 3
     dev = torch.device("cuda", 0)
     out = torch.empty(_tensor_shape(max(total, 1), opt, channels), dtype=_torch_dtype(opt), device=dev)
@@ -1791,15 +1667,14 @@ def gpu_decode_webp_anim_tensor(files: list[bytes], opt: Vp8gTensorOpt, alpha: b
     torch.cuda.synchronize(dev)
     ts = (C.c_uint32 * max(total, 1))()
     st = (C.c_int * n)()
+    c_opts, nopts = S.scale_opts(scale)
+    bflags = S.batch_flags(device_m05, multi_partition)
     t0 = time.perf_counter()
-    bflags = (VP8G_BATCH_DEVICE_M05 if device_m05 else 0) | (VP8G_BATCH_MULTI_PARTITION if multi_partition else 0)
     if scale is None:
         rc = lib.vp8g_decode_webp_anim_tensor(spans, n, int(filtered), threads, bflags, C.byref(opt), channels, C.c_void_p(out.data_ptr()),
                                               ts, st)
     else:
-        sl = list(scale) if isinstance(scale, (list, tuple)) else [scale]
-        opts = (Vp8gScaleOpt * len(sl))(*sl)
-        rc = lib.vp8g_decode_webp_anim_tensor_scaled(spans, n, int(filtered), threads, bflags, opts, len(sl), stage_bytes, C.byref(opt),
+        rc = lib.vp8g_decode_webp_anim_tensor_scaled(spans, n, int(filtered), threads, bflags, c_opts, nopts, stage_bytes, C.byref(opt),
                                                      channels, C.c_void_p(out.data_ptr()), ts, st)
     gpu_decode_webp_anim_tensor.seconds = time.perf_counter() - t0  # the C call alone
     en = C.get_errno()
@@ -1815,23 +1690,16 @@ def gpu_decode_webp_batch_x(files: list[bytes], scale=None, filtered: bool = Tru
     None, list of errno)."""
     lib = gpu_lib()
     n = len(files)
-    bufs = [(C.c_uint8 * max(1, len(b))).from_buffer_copy(b if b else b"\0") for b in files]
-    spans = (ByteSpan * n)(*[ByteSpan(C.cast(bufs[i], C.POINTER(C.c_uint8)), len(files[i])) for i in range(n)])
-    opts = [] if scale is None else (list(scale) if isinstance(scale, (list, tuple)) else [scale])
-    c_opts = (Vp8gScaleOpt * len(opts))(*opts) if opts else None
+    bufs, spans = S.file_spans(files)
+    c_opts, nopts = S.scale_opts(scale)
+    bflags = S.batch_flags(device_m05, multi_partition)
     imgs = (Yuv420Image * n)()
     st = (C.c_int * n)()
-    rc = lib.vp8g_decode_webp_batch_x(spans, n, int(filtered), threads,
-                                      (VP8G_BATCH_DEVICE_M05 if device_m05 else 0)
-                                      | (VP8G_BATCH_MULTI_PARTITION if multi_partition else 0), c_opts, len(opts), imgs, st)
+    rc = lib.vp8g_decode_webp_batch_x(spans, n, int(filtered), threads, bflags, c_opts, nopts, imgs, st)
     en = C.get_errno()
     if rc != 0 and (all(s == 5 for s in st) or not any(st)):  # EIO: device failure; or the call itself refused
         raise RuntimeError(f"vp8g_decode_webp_batch_x failed: errno={en} {lib.vp8g_last_error()!r}")
-    out = []
-    for i in range(n):
-        out.append((_image_bytes(imgs[i]), int(imgs[i].width), int(imgs[i].height)) if st[i] == 0 else None)
-        lib.yuv420_free(C.byref(imgs[i]))
-    return out, list(st)
+    return S.take_images(lib, imgs, st, with_size=True), list(st)
 
 
 def gpu_decode_webp_batch_tensor(files: list[bytes], opt: Vp8gTensorOpt, scale=None, filtered: bool = True, threads: int = 0,
@@ -1853,10 +1721,9 @@ def gpu_decode_webp_batch_tensor(files: list[bytes], opt: Vp8gTensorOpt, scale=N
     extended = extended or alpha  # (alpha arrives through the _x call only)
     lib = gpu_lib()
     n = len(files)
-    bufs = [(C.c_uint8 * max(1, len(b))).from_buffer_copy(b if b else b"\0") for b in files]
-    spans = (ByteSpan * n)(*[ByteSpan(C.cast(bufs[i], C.POINTER(C.c_uint8)), len(files[i])) for i in range(n)])
-    opts = [] if scale is None else (list(scale) if isinstance(scale, (list, tuple)) else [scale])
-    c_opts = (Vp8gScaleOpt * len(opts))(*opts) if opts else None
+    bufs, spans = S.file_spans(files)
+    c_opts, nopts = S.scale_opts(scale)
+    bflags = S.batch_flags(device_m05, multi_partition)
     if not lib.vp8g_tensor_slot_size(C.byref(opt)):
         raise ValueError("gpu_decode_webp_batch_tensor: invalid tensor options")
     dev = torch.device("cuda", 0)
@@ -1864,17 +1731,16 @@ def gpu_decode_webp_batch_tensor(files: list[bytes], opt: Vp8gTensorOpt, scale=N
     torch.cuda.synchronize(dev)
     st = (C.c_int * n)()
     t0 = time.perf_counter()
-    bflags = (VP8G_BATCH_DEVICE_M05 if device_m05 else 0) | (VP8G_BATCH_MULTI_PARTITION if multi_partition else 0)
     if lossless or lossless_scale:
-        rc = lib.vp8g_decode_webp_batch_tensor_any(spans, n, int(filtered), threads, bflags, c_opts, len(opts), C.byref(opt),
+        rc = lib.vp8g_decode_webp_batch_tensor_any(spans, n, int(filtered), threads, bflags, c_opts, nopts, C.byref(opt),
                                                    (VP8G_X_LOSSLESS if lossless else 0) | (VP8G_X_ALPHA if alpha else 0)
                                                    | (VP8G_X_LOSSLESS_SCALE if lossless_scale else 0),
                                                    C.c_void_p(out.data_ptr()), st)
     elif extended:  # (routed to the _x call only when asked)
-        rc = lib.vp8g_decode_webp_batch_tensor_x(spans, n, int(filtered), threads, bflags, c_opts, len(opts), C.byref(opt),
+        rc = lib.vp8g_decode_webp_batch_tensor_x(spans, n, int(filtered), threads, bflags, c_opts, nopts, C.byref(opt),
                                                  VP8G_X_ALPHA if alpha else 0, C.c_void_p(out.data_ptr()), st)
     else:
-        rc = lib.vp8g_decode_webp_batch_tensor(spans, n, int(filtered), threads, bflags, c_opts, len(opts), C.byref(opt),
+        rc = lib.vp8g_decode_webp_batch_tensor(spans, n, int(filtered), threads, bflags, c_opts, nopts, C.byref(opt),
                                                C.c_void_p(out.data_ptr()), st)
     gpu_decode_webp_batch_tensor.seconds = time.perf_counter() - t0  # the C call alone
     en = C.get_errno()
@@ -1886,12 +1752,6 @@ def gpu_decode_webp_batch_tensor(files: list[bytes], opt: Vp8gTensorOpt, scale=N
 def fnv1a64(buf: bytes | np.ndarray, h: int = 1469598103934665603) -> int:
     b = np.ascontiguousarray(np.frombuffer(buf, dtype=np.uint8) if isinstance(buf, (bytes, bytearray)) else buf)
     return int(host_lib().vp8f_fnv1a64(b.ctypes.data, b.nbytes, h))
-
-
-def _image_bytes(img: Yuv420Image) -> bytes:
-    ysz = img.stride_y * img.height
-    uvsz = img.stride_uv * ((img.height + 1) // 2)
-    return C.string_at(img.y, ysz) + C.string_at(img.u, uvsz) + C.string_at(img.v, uvsz)
 
 
 def gpu_reconstruct(f: Frame, filtered: bool) -> bytes:

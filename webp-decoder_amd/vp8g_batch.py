@@ -94,7 +94,7 @@ class DeviceBatch:
 
     def commit(self):
         """Descriptors to the device (after every slot is filled)."""
-        self.d_descs = torch.frombuffer(bytearray(bytes(self.h_descs)), dtype=torch.uint8).to(self.dev)
+        self.d_descs = vp8g.device_copy(self.h_descs, dev=self.dev)
         return self.d_descs
 
     def launch(self, stream: int, waves: int = 0):
