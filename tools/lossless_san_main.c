@@ -5,7 +5,7 @@
  *
  *   lossless_san <file.webp>...
  *
- * Each file is given to webp_parse_any whole, truncated (every length up to 2048 bytes, then 2048 evenly
+ * Each file is given to webp_parse_any, and to webp_locate_still in each of its modes, whole, truncated (every length up to 2048 bytes, then 2048 evenly
  * spaced lengths) and with 500 seeded single-byte corruptions; its VP8L payload (if any) goes to
  * vp8f_lossless_decode the same way (errno cleared before each call: a failure must set EINVAL or ENOMEM itself),
  * and what decodes goes through vp8f_lossless_apply.  Every buffer
@@ -35,6 +35,16 @@ static int parse(const uint8_t* data, size_t n, WebPContainerL* c) {
 	ByteSpan s = {copy, n};
 	const int rc = webp_parse_any(s, c);
 	if (rc == 0 && c->vp8l_chunk_offset && c->vp8l_chunk_offset + c->vp8l_chunk_size > n) abort();
+	/* the walk under the parsers, in each of its modes: what it locates lies inside the file, and with everything
+	 * accepted its verdict is webp_parse_any's */
+	for (unsigned accept = 0; accept <= (WEBP_ACCEPT_EXTENDED | WEBP_ACCEPT_LOSSLESS); accept++) {
+		WebPStill st;
+		const int got = webp_locate_still(s, accept, &st);
+		if (accept == (WEBP_ACCEPT_EXTENDED | WEBP_ACCEPT_LOSSLESS) && got != rc) abort();
+		if (got != 0) continue;
+		if (st.vp8_offset + st.vp8_size > n || st.alph_offset + st.alph_size > n || st.vp8l_offset + st.vp8l_size > n) abort();
+		if (!st.vp8_offset == !st.vp8l_offset) abort(); /* (one image chunk, of one kind) */
+	}
 	free(copy);
 	return rc;
 }

@@ -260,32 +260,18 @@ using vp8g::al256;
 using vp8g::ArgbScaleBatch;
 using vp8g::Status;
 
-void put32(std::vector<uint8_t>& v, uint32_t x) {
-	for (int i = 0; i < 4; i++) v.push_back((uint8_t)(x >> (8 * i)));
-}
-void put_chunk(std::vector<uint8_t>& v, const char* tag, const uint8_t* p, uint32_t n) {
-	v.insert(v.end(), tag, tag + 4);
-	put32(v, n);
-	v.insert(v.end(), p, p + n);
-	if (n & 1u) v.push_back(0);
-}
-// One frame's payload as a file of its own: 'VP8 ' alone, VP8X + ALPH + 'VP8 ', or 'VP8L'.
-std::vector<uint8_t> wrap_frame(const uint8_t* file, const WebPAnimFrame& f) {
-	std::vector<uint8_t> v = {'R', 'I', 'F', 'F', 0, 0, 0, 0, 'W', 'E', 'B', 'P'};
-	if (f.vp8l_offset) {
-		put_chunk(v, "VP8L", file + f.vp8l_offset, f.vp8l_size);
-	} else {
-		if (f.alph_offset) {
-			const uint32_t w = f.width - 1u, h = f.height - 1u;
-			const uint8_t x[10] = {0x10, 0, 0, 0, (uint8_t)w, (uint8_t)(w >> 8), (uint8_t)(w >> 16), (uint8_t)h, (uint8_t)(h >> 8), (uint8_t)(h >> 16)};
-			put_chunk(v, "VP8X", x, 10);
-			put_chunk(v, "ALPH", file + f.alph_offset, f.alph_size);
-		}
-		put_chunk(v, "VP8 ", file + f.vp8_offset, f.vp8_size);
-	}
-	const uint32_t riff = (uint32_t)v.size() - 8u;
-	for (int i = 0; i < 4; i++) v[4 + i] = (uint8_t)(riff >> (8 * i));
-	return v;
+// One frame as the still picture the pipeline decodes: its payloads where webp_parse_anim located them.
+WebPStill still_of(const uint8_t* file, const WebPAnimFrame& f) {
+	const auto chunk = [](uint32_t payload) { return 8u + (size_t)payload + (payload & 1u); };
+	WebPStill s;
+	memset(&s, 0, sizeof(s));
+	s.data = file;
+	s.vp8_offset = f.vp8_offset, s.vp8_size = f.vp8_size, s.alph_offset = f.alph_offset, s.alph_size = f.alph_size;
+	s.vp8l_offset = f.vp8l_offset, s.vp8l_size = f.vp8l_size;
+	s.width = f.width, s.height = f.height;
+	// the planner's price: the frame as a file of its own -- RIFF header, VP8X chunk in front of an ALPH, the frame's chunks
+	s.size = 12u + (f.alph_offset ? 18u + chunk(f.alph_size) : 0u) + chunk(f.vp8l_offset ? f.vp8l_size : f.vp8_size);
+	return s;
 }
 
 int fail_all(int* status, uint32_t n, int e) {
@@ -449,7 +435,8 @@ struct AnimCall {
 		}
 		rec_off = al256(stage), desc_off = al256(rec_off + refs.size() * sizeof(Vp8gAnimFrame));
 	}
-	// Every frame as a still picture of its own, one vp8g_decode_webp_batch_tensor_any per frame size, into `buf`.  A frame
+	// Every frame as a still picture of its own, one run of the still pipeline (vp8g::decode_located_tensor) per frame size,
+	// into `buf`.  A frame
 	// that does not decode fails its file; a call that fails without naming a frame, or for every frame with EIO, fails
 	// this call.
 	int decode_frames() {
@@ -457,14 +444,12 @@ struct AnimCall {
 		if (int e = dev_alloc(&buf, desc_off + n * sizeof(Vp8gAnimDesc))) return e;
 		for (size_t a = 0, b = 0; a < order.size(); a = b) {
 			while (b < order.size() && size_of(order[b]) == size_of(order[a])) b++;
-			std::vector<std::vector<uint8_t>> wrapped;
-			std::vector<ByteSpan> spans;
-			for (size_t q = a; q < b; q++) wrapped.push_back(wrap_frame(files[refs[order[q]].file].data, frame_of(order[q])));
-			for (auto& w : wrapped) spans.push_back(ByteSpan{w.data(), w.size()});
+			std::vector<WebPStill> pics;
+			for (size_t q = a; q < b; q++) pics.push_back(still_of(files[refs[order[q]].file].data, frame_of(order[q])));
 			const Vp8gTensorOpt st = argb_tensor(frame_of(order[a]).width, frame_of(order[a]).height);
 			std::vector<int> err(b - a, 0);
-			const int rc = vp8g_decode_webp_batch_tensor_any(spans.data(), (uint32_t)(b - a), filtered, threads, flags, nullptr, 0, &st,
-			                                                 VP8G_X_ALPHA | VP8G_X_LOSSLESS, buf + refs[order[a]].src, err.data());
+			const int rc = vp8g::decode_located_tensor(pics.data(), (uint32_t)(b - a), filtered, threads, flags, &st, VP8G_X_ALPHA | VP8G_X_LOSSLESS,
+			                                           buf + refs[order[a]].src, err.data());
 			const int en = errno;
 			bool any = false, all_io = true;
 			for (int e : err) any |= e != 0, all_io &= e == EIO;

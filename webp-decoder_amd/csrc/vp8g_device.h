@@ -7,6 +7,8 @@
 
 #include "vp8g.h"
 
+struct WebPStill;  // host/vp8_front.h
+
 namespace vp8g {
 
 // Per-half-wave LDS scratch (bytes).  A wave works on two macroblocks at once, one per 32-lane
@@ -280,5 +282,11 @@ int make_desc(const Vp8KeyFrameHeader* kf, const Vp8DecodedFrame* d, int filtere
 // Planes in the yuv420_alloc layout; init = false leaves them uninitialised (outputs a D2H
 // overwrites completely).
 int alloc_planes(Yuv420Image* img, uint32_t width, uint32_t height, bool init);
+
+// The end-to-end pipeline (vp8g_pipeline.hip) over pictures that are already located in their files (WebPStill,
+// host/vp8_front.h; every one a good record, its `size` what the batch planner prices it at): otherwise
+// vp8g_decode_webp_batch_tensor_any without options, xflags VP8G_X_ALPHA | VP8G_X_LOSSLESS.  Not exported.
+int decode_located_tensor(const WebPStill* pics, uint32_t n, int filtered, uint32_t threads, uint32_t flags, const Vp8gTensorOpt* t,
+                          uint32_t xflags, void* d_out, int* status);
 
 }  // namespace vp8g

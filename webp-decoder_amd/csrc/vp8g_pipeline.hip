@@ -1,7 +1,9 @@
 // vp8g_pipeline.hip -- end-to-end batch decode: .webp bytes in host memory -> I420 images in host memory, or
 // pictures in the caller's device tensor (vp8g_decode_webp_batch and its kin, include/vp8g.h).
 //
-//   worker threads   container + key-frame header + m05 (host/vp8_parse.c, reentrant) into the packed wire format (and
+//   decode_batch     locates every file's payloads once (webp_locate_still, host/vp8_front.h) in the mode the entry
+//                    point implies; every stage below reads that record, or the errno of the refusal
+//   worker threads   key-frame header + m05 (host/vp8_parse.c, reentrant) into the packed wire format (and
 //                    the ALPH chunk's entropy decode, if alpha is asked for), frames handed out in order from an
 //                    atomic counter and kept at most a window ahead of the device
 //   this thread      groups finished frames into chunks and takes each through the stages of Pipeline: H2D of the
@@ -10,8 +12,8 @@
 //                    tensor kernel -- and D2H of what the caller gets in host memory.  Chunk slots alternate (two per
 //                    chunk kind), so one chunk's device work and copies overlap the entropy decoding of the next ones.
 //
-// With VP8G_BATCH_DEVICE_M05 the workers only parse the container, the frame header and the first partition's
-// frame-level fields (vp8f_token_header_memory); the chunk uploads the compressed VP8 payloads themselves and m05 runs
+// With VP8G_BATCH_DEVICE_M05 the workers only parse the frame header and the first partition's
+// frame-level fields (vp8f_token_header); the chunk uploads the compressed VP8 payloads themselves and m05 runs
 // on the device (vp8g_m05.hip, one workgroup per frame) straight into the dense SoA -- except for the heaviest frames,
 // which plan_frames leaves to the host threads.
 // The reference decodes one file per process (src/main.c:591-705: m01..m05 then m06/m07); its
@@ -104,8 +106,6 @@ struct TokJob {
 	Vp8KeyFrameHeader kf;
 	Vp8DecodedFrame hdr;  // header fields only (no arrays)
 	Vp8gTokFrame tf;
-	uint64_t poff;  // VP8 payload in the file
-	uint32_t psize;
 };
 
 // The library's one background releaser of host frames (the last chunks' packed frames, freed
@@ -169,16 +169,16 @@ uint32_t default_threads() {
 // Frames handed from the workers to the device thread, in the order `order` (positions), each
 // either decoded on the host into the packed format or only header-parsed for device m05 (dev[i]).
 struct Feed {
-	const ByteSpan* files = nullptr;
+	const WebPStill* pics = nullptr;  // the located pictures ...
+	const int* refused = nullptr;     // ... or (not NULL, not 0) the errno with which a file's container was refused
 	uint32_t n = 0;
 	std::vector<uint8_t> dev;       // frame i: m05 on the device (workers fill tj[i], else pk[i])
 	std::vector<uint32_t> order;    // position -> frame index
 	unsigned fflags = 0;  // front-end flags (VP8F_MULTI_PARTITION)
-	bool alpha = false;             // also entropy-decode the ALPH chunk (VP8G_X_ALPHA): ares[i] = the residual plane
+	bool alpha = false;             // also entropy-decode the ALPH chunk, if there is one (VP8G_X_ALPHA): ares[i] = the residual plane
 	std::vector<uint8_t*> ares;     // (malloc; NULL = no alpha; freed with the frame's host data)
 	std::vector<uint32_t> afilter;
-	bool lossless = false;          // VP8G_X_LOSSLESS: a file whose image chunk is VP8L is entropy-decoded into ll[i]
-	std::vector<uint8_t> is_ll;     // frame i is lossless (it has no kf / pk / tj; it rides in the chunk its position falls in)
+	std::vector<uint8_t> is_ll;     // frame i is lossless (VP8G_X_LOSSLESS; it has no kf / pk / tj; it rides in the chunk its position falls in)
 	std::vector<Vp8fLosslessImage> ll;  // (freed with the frame's host data)
 	std::vector<Vp8gPackedFrame> pk;
 	std::vector<TokJob> tj;
@@ -200,35 +200,7 @@ struct Feed {
 				if (abort) return;
 			}
 			const uint32_t i = order[pos];
-			int stage = 0, e = 0;
-			WebPContainerL any;
-			if (!files[i].data) e = EINVAL;
-			else if (lossless && webp_parse_any(files[i], &any) != 0) e = errno ? errno : EINVAL;  // (a lossy file: webp_parse_extended's errno)
-			else if (lossless && any.vp8l_chunk_offset) {
-				is_ll[i] = 1;
-				if (vp8f_lossless_decode(files[i].data + any.vp8l_chunk_offset, any.vp8l_chunk_size, &ll[i], nullptr) != 0)
-					e = errno ? errno : EINVAL;
-			} else if (dev[i]) {
-				TokJob& j = tj[i];
-				if (vp8f_token_header_memory(files[i].data, files[i].size, &j.kf, &j.hdr, &j.tf, &j.poff, &j.psize, &stage,
-				                             fflags) != 0)
-					e = errno ? errno : EINVAL;
-			} else if (vp8f_decode_packed_memory(files[i].data, files[i].size, &pk[i], &stage, fflags) != 0)
-				e = errno ? errno : EINVAL;
-			if (alpha && e == 0 && !is_ll[i]) {  // a picture whose ALPH does not decode fails as a whole, as in libwebp
-				WebPContainerX x;
-				const Vp8KeyFrameHeader& kf = dev[i] ? tj[i].kf : pk[i].kf;
-				if (webp_parse_extended(files[i], &x) == 0 && x.alph_chunk_offset) {
-					ares[i] = (uint8_t*)malloc((size_t)kf.width * kf.height);
-					if (!ares[i]) e = ENOMEM;
-					else if (vp8f_alpha_decode(files[i].data + x.alph_chunk_offset, x.alph_chunk_size, kf.width, kf.height, ares[i],
-					                           &afilter[i], nullptr) != 0) {
-						e = errno ? errno : EINVAL;
-						free(ares[i]);
-						ares[i] = nullptr;
-					}
-				}
-			}
+			const int e = decode(i);
 			{
 				std::lock_guard<std::mutex> lk(mu);
 				err[i] = e;
@@ -236,6 +208,28 @@ struct Feed {
 			}
 			cv_ready.notify_all();
 		}
+	}
+	// The host's share of picture i, from its located payloads: 0, or the errno with which the picture fails.
+	int decode(uint32_t i) {
+		const WebPStill& p = pics[i];
+		if (refused && refused[i]) return refused[i];
+		if (p.vp8l_offset) {
+			is_ll[i] = 1;
+			return vp8f_lossless_decode(p.data + p.vp8l_offset, p.vp8l_size, &ll[i], nullptr) == 0 ? 0 : errno ? errno : EINVAL;
+		}
+		const ByteSpan payload = {p.data + p.vp8_offset, p.vp8_size};
+		if (dev[i] && p.vp8_size > 0xFFFFFFF0u) return EFBIG;  // (a payload's bitstream slot is sized in 32 bits)
+		if (dev[i] ? vp8f_token_header(payload, &tj[i].kf, &tj[i].hdr, &tj[i].tf, fflags) : vp8f_decode_packed(payload, &pk[i], fflags))
+			return errno ? errno : EINVAL;
+		if (!alpha || !p.alph_offset) return 0;
+		const Vp8KeyFrameHeader& kf = dev[i] ? tj[i].kf : pk[i].kf;
+		ares[i] = (uint8_t*)malloc((size_t)kf.width * kf.height);
+		if (!ares[i]) return ENOMEM;
+		if (vp8f_alpha_decode(p.data + p.alph_offset, p.alph_size, kf.width, kf.height, ares[i], &afilter[i], nullptr) == 0) return 0;
+		const int e = errno ? errno : EINVAL;  // a picture whose ALPH does not decode fails as a whole, as in libwebp
+		free(ares[i]);
+		ares[i] = nullptr;
+		return e;
 	}
 	void wait_ready(uint32_t i) {
 		std::unique_lock<std::mutex> lk(mu);
@@ -371,6 +365,17 @@ hipError_t grow(Slot& s, size_t need) {
 	return e;
 }
 
+// A batch's files located, each once, under `accept` (webp_locate_still): the records, and per file 0 or the errno with
+// which its container was refused.
+struct LocatedFiles {
+	std::vector<WebPStill> pics;
+	std::vector<int> refused;
+	LocatedFiles(const ByteSpan* files, uint32_t n, unsigned accept) : pics(n), refused(n, 0) {
+		for (uint32_t i = 0; i < n; i++)
+			if (webp_locate_still(files[i], accept, &pics[i]) != 0) refused[i] = errno ? errno : EINVAL;
+	}
+};
+
 // Which frames run m05 on the device and in which order the workers take them.  Without
 // VP8G_BATCH_DEVICE_M05 every frame is decoded on the host, in index order.  With it the device
 // runs m05 as one workgroup per frame, so the device part lasts as long as its heaviest frame
@@ -384,8 +389,9 @@ constexpr double kHostNsPerByte = 50.0;    // host m05 into the packed format, p
 constexpr double kD2HNsPerByte = 0.085;    // download into fresh pageable images (~12 GB/s)
 // (rates measured on the box: tools/e2e_probe.py chunk traces, tools/hybrid_sweep.py; profiles/r02_hybrid.json)
 // download = false (the tensor sink: the pictures stay on the device) prices no download.
-void plan_frames(const ByteSpan* files, uint32_t n, bool tok, uint32_t threads, std::vector<uint8_t>& dev,
-                 std::vector<uint32_t>& order, bool download, bool extended) {
+// A file is priced by its size (pics[i].size, whatever became of its container) and its picture's I420 bytes.
+void plan_frames(const WebPStill* pics, const int* refused, uint32_t n, bool tok, uint32_t threads, std::vector<uint8_t>& dev,
+                 std::vector<uint32_t>& order, bool download) {
 	dev.assign(n, tok ? 1 : 0);
 	order.resize(n);
 	for (uint32_t i = 0; i < n; i++) order[i] = i;
@@ -397,28 +403,22 @@ void plan_frames(const ByteSpan* files, uint32_t n, bool tok, uint32_t threads, 
 	if (const char* e = getenv("VP8G_D2H_NS_PER_BYTE")) d2h_per_b = atof(e);
 	if (!download) d2h_per_b = 0.0;
 	std::vector<double> outb(n, 0.0);  // I420 bytes (0 for a file whose header does not parse: it fails anyway)
-	for (uint32_t i = 0; i < n; i++) {
-		WebPContainer c;
-		WebPContainerX x;
-		Vp8KeyFrameHeader kf;
-		if (extended && files[i].data && webp_parse_extended(files[i], &x) == 0 && x.extended)  // (the canvas is the frame size)
-			outb[i] = (double)vp8g_i420_size(x.canvas_width, x.canvas_height);
-		else if (files[i].data && webp_parse_simple_lossy(files[i], &c) == 0 &&
-		    vp8_parse_keyframe_header(ByteSpan{files[i].data + c.vp8_chunk_offset, c.vp8_chunk_size}, &kf) == 0)
-			outb[i] = (double)vp8g_i420_size(kf.width, kf.height);
-	}
+	for (uint32_t i = 0; i < n; i++)
+		if (!(refused && refused[i]) && pics[i].vp8_offset && pics[i].width)  // (0 x 0: the simple layout with a bad frame header)
+			outb[i] = (double)vp8g_i420_size(pics[i].width, pics[i].height);
+	const auto size_of = [&](uint32_t i) { return (double)pics[i].size; };
 	std::vector<uint32_t> by_size(order);
-	std::stable_sort(by_size.begin(), by_size.end(), [&](uint32_t x, uint32_t y) { return files[x].size > files[y].size; });
+	std::stable_sort(by_size.begin(), by_size.end(), [&](uint32_t x, uint32_t y) { return pics[x].size > pics[y].size; });
 	double dev_out = 0;
 	for (uint32_t i = 0; i < n; i++) dev_out += outb[i];
 	const double thr = threads ? (double)threads : 1.0;
-	double host_ns = 0, best = dev_per_b * (double)files[by_size[0]].size + d2h_per_b * dev_out;
+	double host_ns = 0, best = dev_per_b * size_of(by_size[0]) + d2h_per_b * dev_out;
 	uint32_t best_k = 0;
 	for (uint32_t k = 1; k <= n; k++) {  // the k heaviest on the host
 		const uint32_t f = by_size[k - 1];
-		host_ns += host_per_b * (double)files[f].size / thr;
+		host_ns += host_per_b * size_of(f) / thr;
 		dev_out -= outb[f];
-		const double dev_ns = (k < n ? dev_per_b * (double)files[by_size[k]].size : 0.0) + d2h_per_b * dev_out;
+		const double dev_ns = (k < n ? dev_per_b * size_of(by_size[k]) : 0.0) + d2h_per_b * dev_out;
 		const double t = host_ns > dev_ns ? host_ns : dev_ns;
 		if (t < best) best = t, best_k = k;
 	}
@@ -557,7 +557,7 @@ struct Chunk {
 // chunk k's D2H overlaps chunk k+1's kernels.  Slots 0/1 alternate between device-m05 chunks, 2/3 between host-m05
 // chunks, so a hybrid batch's host chunks never wait for the (long) device-m05 chunk's slot.
 struct Pipeline {
-	const ByteSpan* files = nullptr;
+	const WebPStill* pics = nullptr;  // located by the caller (decode_batch); Feed has the refusals
 	uint32_t n = 0;
 	int filtered = 0;
 	Sinks sk;
@@ -635,8 +635,8 @@ struct Pipeline {
 	}
 	// Plans the batch, starts the workers, creates the device objects.  (No constructor: an exception on the way must
 	// leave a complete object, whose destructor joins the threads that did start.)
-	Status start(const ByteSpan* files_, uint32_t n_, int filtered_, uint32_t threads, uint32_t flags, const Sinks& sinks) {
-		files = files_, n = n_, filtered = filtered_, sk = sinks;
+	Status start(const WebPStill* pics_, const int* refused, uint32_t n_, int filtered_, uint32_t threads, uint32_t flags, const Sinks& sinks) {
+		pics = pics_, n = n_, filtered = filtered_, sk = sinks;
 		const bool tok = (flags & VP8G_BATCH_DEVICE_M05) != 0;
 		const long knob = getenv("VP8G_CHUNK_FRAMES") ? atol(getenv("VP8G_CHUNK_FRAMES")) : 0;  // test knob: smaller chunks
 		for (uint32_t& cf : chunk_frames)
@@ -646,19 +646,18 @@ struct Pipeline {
 		live.assign(n, 0);
 		if (!threads) threads = default_threads();
 		if (threads > n) threads = n;
-		feed.files = files, feed.n = n;
-		feed.fflags = ((flags & VP8G_BATCH_MULTI_PARTITION) ? VP8F_MULTI_PARTITION : 0u) | (sk.extended ? VP8F_EXTENDED : 0u);
+		feed.pics = pics, feed.refused = refused, feed.n = n;
+		feed.fflags = (flags & VP8G_BATCH_MULTI_PARTITION) ? VP8F_MULTI_PARTITION : 0u;
 		feed.pk.assign(n, Vp8gPackedFrame{});
 		if (tok) feed.tj.assign(n, TokJob{});
 		feed.err.assign(n, 0);
 		feed.alpha = sk.alpha;
 		feed.ares = std::vector<uint8_t*>(n, nullptr);
 		feed.afilter.resize(n);
-		feed.lossless = sk.lossless;
 		feed.is_ll.assign(n, 0);
 		feed.ll.assign(n, Vp8fLosslessImage{});
 		feed.ready.reset(new uint8_t[n]());
-		plan_frames(files, n, tok, threads, feed.dev, feed.order, sk.topt == nullptr, sk.extended);
+		plan_frames(pics, refused, n, tok, threads, feed.dev, feed.order, sk.topt == nullptr);
 		trace = getenv("VP8G_PIPE_TRACE") && atoi(getenv("VP8G_PIPE_TRACE")) != 0;
 		if (trace) {
 			uint32_t nd = 0;
@@ -766,7 +765,7 @@ struct Pipeline {
 			if (apl) sh.ab = al256(sh.ab + apl), sh.asb = al256(sh.asb + aspl);
 			c.idx.push_back(fi);
 			sh.mbs += f.mb_total;
-			if (c.tok) sh.bitsb += bits_slot(feed.tj[fi].psize);
+			if (c.tok) sh.bitsb += bits_slot(pics[fi].vp8_size);
 			else sh.vals += feed.pk[fi].n_values;
 			sh.outb = al256(sh.outb + ownb);
 			if (f.mb_cols > sh.max_cols) sh.max_cols = f.mb_cols;
@@ -850,12 +849,12 @@ struct Pipeline {
 			const uint32_t fi = c.idx[j];
 			const uint64_t mt = f_of(fi).mb_total;
 			if (c.tok) {
-				const TokJob& t = feed.tj[fi];
-				s.jobs[j] = t.tf;
+				const WebPStill& pic = pics[fi];
+				s.jobs[j] = feed.tj[fi].tf;
 				s.jobs[j].data = po;
 				s.jobs[j].mb_offset = mo;
-				c.up(L.bits + po, files[fi].data + t.poff, t.psize);
-				po += bits_slot(t.psize);
+				c.up(L.bits + po, pic.data + pic.vp8_offset, pic.vp8_size);
+				po += bits_slot(pic.vp8_size);
 			} else {
 				Vp8gPackedFrame& p = feed.pk[fi];
 				for (uint32_t m = 0; po && m < mt; m++) p.mb_off[m] += (uint32_t)po;  // chunk-relative value offsets
@@ -1160,20 +1159,25 @@ int fail_all(Yuv420Image* outs, uint32_t n, int* status, int e) {
 	return fail(e);
 }
 
-// The body of every end-to-end entry point.  0, or -1 with errno = the first failed frame's error in index order and
+// The body of every end-to-end entry point: the files, each located here, once, in the mode the sinks imply
+// (webp_locate_still: a refused file keeps the errno as its status), or (files = NULL) pictures already located, all of
+// them good.  0, or -1 with errno = the first failed frame's error in index order and
 // status[i] per frame (a failed frame's image is freed, its tensor slot zero).  After a device failure every status is EIO
 // and every output freed; a C++ exception (no memory, no thread) unwinds through ~Pipeline and ends the call alike.
-int decode_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags, Sinks sk, int* status) {
+int decode_batch(const ByteSpan* files, const WebPStill* located, uint32_t n, int filtered, uint32_t threads, uint32_t flags, Sinks sk,
+                 int* status) {
 	sk.tslot = sk.topt ? (sk.alpha ? vp8g_tensor_slot_size_a(sk.topt) : vp8g_tensor_slot_size(sk.topt)) : 0;
-	if (!files || (sk.topt ? !sk.d_tensor || !sk.tslot || sk.outs : !sk.outs) || n == 0 || (sk.alpha && !(sk.topt && sk.extended)) ||
+	if ((!files && !located) || (sk.topt ? !sk.d_tensor || !sk.tslot || sk.outs : !sk.outs) || n == 0 || (sk.alpha && !(sk.topt && sk.extended)) ||
 	    (sk.lossless && !(sk.topt && sk.extended)) ||
 	    (flags & ~(VP8G_BATCH_DEVICE_M05 | VP8G_BATCH_MULTI_PARTITION)))
 		return fail(EINVAL);
 	for (uint32_t i = 0; sk.outs && i < n; i++) memset(&sk.outs[i], 0, sizeof(sk.outs[i]));
 	std::vector<int> err;  // per frame, once every chunk has retired
 	try {
+		const unsigned accept = !sk.extended ? 0u : sk.lossless ? WEBP_ACCEPT_EXTENDED | WEBP_ACCEPT_LOSSLESS : WEBP_ACCEPT_EXTENDED;
+		const LocatedFiles lf(files, files ? n : 0, accept);  // (outlives the Pipeline, whose workers read the records)
 		Pipeline p;
-		p.failure = p.start(files, n, filtered, threads, flags, sk);
+		p.failure = p.start(files ? lf.pics.data() : located, files ? lf.refused.data() : nullptr, n, filtered, threads, flags, sk);
 		if (p.failure.ok()) p.failure = p.run();
 		p.finished = p.failure.ok();
 		if (p.finished && p.trace) fprintf(stderr, "[pipe] all chunks retired at %.1f ms\n", p.ms_now());
@@ -1203,7 +1207,8 @@ VP8G_API int vp8g_plan_batch(const ByteSpan* files, uint32_t n, uint32_t threads
 	std::vector<uint8_t> d;
 	std::vector<uint32_t> o;
 	try {
-		plan_frames(files, n, (flags & VP8G_BATCH_DEVICE_M05) != 0, thr, d, o, true, false);
+		const LocatedFiles lf(files, n, 0);  // (as vp8g_decode_webp_batch_ex locates them)
+		plan_frames(lf.pics.data(), lf.refused.data(), n, (flags & VP8G_BATCH_DEVICE_M05) != 0, thr, d, o, true);
 	} catch (const std::bad_alloc&) {
 		return fail(ENOMEM);
 	}
@@ -1214,7 +1219,7 @@ VP8G_API int vp8g_plan_batch(const ByteSpan* files, uint32_t n, uint32_t threads
 
 VP8G_API int vp8g_decode_webp_batch_ex(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
                                        Yuv420Image* outs, int* status) {
-	return decode_batch(files, n, filtered, threads, flags, Sinks{nullptr, 0, outs}, status);
+	return decode_batch(files, nullptr, n, filtered, threads, flags, Sinks{nullptr, 0, outs}, status);
 }
 
 // With `opts` (n_opts = 1 or n) each chunk's frames are cropped / rescaled on the device (vp8g_scale.hip) into a second
@@ -1222,7 +1227,7 @@ VP8G_API int vp8g_decode_webp_batch_ex(const ByteSpan* files, uint32_t n, int fi
 VP8G_API int vp8g_decode_webp_batch_scaled(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
                                            const Vp8gScaleOpt* opts, uint32_t n_opts, Yuv420Image* outs, int* status) {
 	if (!opts || !opts_ok(opts, n_opts, n)) return fail(EINVAL);
-	return decode_batch(files, n, filtered, threads, flags, Sinks{opts, n_opts, outs}, status);
+	return decode_batch(files, nullptr, n, filtered, threads, flags, Sinks{opts, n_opts, outs}, status);
 }
 
 // The sink is the caller's device tensor: each chunk's frames, scaled or not, are written to their slots of d_out
@@ -1231,15 +1236,15 @@ VP8G_API int vp8g_decode_webp_batch_tensor(const ByteSpan* files, uint32_t n, in
                                            const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, void* d_out,
                                            int* status) {
 	if (!tensor_ok(t, d_out) || !opts_ok(opts, n_opts, n)) return fail(EINVAL);
-	return decode_batch(files, n, filtered, threads, flags, Sinks{opts, n_opts, nullptr, t, (uint8_t*)d_out}, status);
+	return decode_batch(files, nullptr, n, filtered, threads, flags, Sinks{opts, n_opts, nullptr, t, (uint8_t*)d_out}, status);
 }
 
-// The extended container (webp_parse_extended) in front of the same pipeline: VP8X files decode, alpha
+// The extended container (WEBP_ACCEPT_EXTENDED) in front of the same pipeline: VP8X files decode, alpha
 // is ignored.
 VP8G_API int vp8g_decode_webp_batch_x(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
                                       const Vp8gScaleOpt* opts, uint32_t n_opts, Yuv420Image* outs, int* status) {
 	if (!opts_ok(opts, n_opts, n)) return fail(EINVAL);
-	return decode_batch(files, n, filtered, threads, flags, Sinks{opts, n_opts, outs, nullptr, nullptr, /*extended=*/true}, status);
+	return decode_batch(files, nullptr, n, filtered, threads, flags, Sinks{opts, n_opts, outs, nullptr, nullptr, /*extended=*/true}, status);
 }
 
 // ... and with VP8G_X_ALPHA the ALPH planes as the tensor's fourth channel.
@@ -1248,7 +1253,7 @@ VP8G_API int vp8g_decode_webp_batch_tensor_x(const ByteSpan* files, uint32_t n, 
                                              void* d_out, int* status) {
 	if ((xflags & ~VP8G_X_ALPHA) || !tensor_ok(t, d_out) || !opts_ok(opts, n_opts, n)) return fail(EINVAL);
 	const Sinks sk{opts, n_opts, nullptr, t, (uint8_t*)d_out, /*extended=*/true, /*alpha=*/(xflags & VP8G_X_ALPHA) != 0};
-	return decode_batch(files, n, filtered, threads, flags, sk, status);
+	return decode_batch(files, nullptr, n, filtered, threads, flags, sk, status);
 }
 
 // ... and with VP8G_X_LOSSLESS lossless files beside the lossy ones.
@@ -1260,7 +1265,17 @@ VP8G_API int vp8g_decode_webp_batch_tensor_any(const ByteSpan* files, uint32_t n
 		return fail(EINVAL);
 	const Sinks sk{opts,  n_opts, nullptr, t, (uint8_t*)d_out, /*extended=*/true, /*alpha=*/(xflags & VP8G_X_ALPHA) != 0,
 	               /*lossless=*/(xflags & VP8G_X_LOSSLESS) != 0, /*lossless_scale=*/(xflags & VP8G_X_LOSSLESS_SCALE) != 0};
-	return decode_batch(files, n, filtered, threads, flags, sk, status);
+	return decode_batch(files, nullptr, n, filtered, threads, flags, sk, status);
+}
+
+// vp8g_decode_webp_batch_tensor_any without options, over pictures located by the caller (vp8g_device.h): the animation
+// path's frames, which its parser has located already.
+int vp8g::decode_located_tensor(const WebPStill* pics, uint32_t n, int filtered, uint32_t threads, uint32_t flags, const Vp8gTensorOpt* t,
+                                uint32_t xflags, void* d_out, int* status) {
+	if ((xflags & ~(VP8G_X_ALPHA | VP8G_X_LOSSLESS)) || !tensor_ok(t, d_out)) return fail(EINVAL);
+	const Sinks sk{nullptr, 0, nullptr, t, (uint8_t*)d_out, /*extended=*/true, /*alpha=*/(xflags & VP8G_X_ALPHA) != 0,
+	               /*lossless=*/(xflags & VP8G_X_LOSSLESS) != 0};
+	return decode_batch(nullptr, pics, n, filtered, threads, flags, sk, status);
 }
 
 VP8G_API int vp8g_decode_webp_batch(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, Yuv420Image* outs,

@@ -5,7 +5,7 @@
  * (serial entropy decode), but the CLI and the GPU-box tests need it,
  * so it is written here from RFC 6386 with the reference's exact output semantics and the same
  * public names as the reference modules it stands in for:
- *   webp_parse_simple_lossy    <- src/m01_container/webp_container.c:19
+ *   webp_parse_simple_lossy    <- src/m01_container/webp_container.c:19  (a view of webp_locate_still, below)
  *   vp8_parse_keyframe_header  <- src/m02_vp8_header/vp8_header.c:13
  *   vp8_decode_decoded_frame   <- src/m05_tokens/vp8_tokens.c:673
  *   vp8_decoded_frame_free     <- src/m05_tokens/vp8_tokens.c:658
@@ -50,8 +50,8 @@ int vp8f_decode_memory(const uint8_t* data, size_t size, Vp8KeyFrameHeader* kf, 
 /* also accept 2/4/8 token partitions (RFC 6386 9.5), which the reference rejects with ENOTSUP
  * (vp8_tokens.c:357-360); SURVEY §8(f4) */
 #define VP8F_MULTI_PARTITION 2u
-/* (the _memory forms only) read the container with webp_parse_extended instead of
- * webp_parse_simple_lossy: VP8X files decode, their ALPH chunk is not looked at */
+/* (the _memory forms only) read the container by webp_parse_extended's rules instead of
+ * webp_parse_simple_lossy's: VP8X files decode, their ALPH chunk is not looked at */
 #define VP8F_EXTENDED 4u
 int vp8f_decode_packed(ByteSpan vp8_payload, Vp8gPackedFrame* out, unsigned flags);
 /* container + key-frame header + vp8f_decode_packed; stage codes as vp8f_decode_file */
@@ -134,6 +134,33 @@ void vp8f_argb_mult_row(uint32_t* px, uint32_t n, int inverse);
  * (EINVAL as vp8f_scale_resolve_argb, ENOMEM). */
 int vp8f_argb_scale(const uint32_t* argb, uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, uint32_t* out);
 
+/* ---- a still picture located in its file -------------------------------- */
+
+/* Where a file's payloads are: the one record of a still picture's container, read in one walk of its chunks.
+ * Offsets are payload offsets from `data`, 0 = no such chunk; the image is 'VP8 ' (with or without an ALPH)
+ * or 'VP8L', never both. */
+typedef struct WebPStill {
+	const uint8_t* data;
+	size_t size;                                 /* of the file: what the batch planner prices it at */
+	size_t vp8_offset, alph_offset, vp8l_offset;
+	uint32_t vp8_size, alph_size, vp8l_size;
+	uint32_t width, height;                      /* the canvas of a VP8X file, else the bitstream's size (0 x 0: a
+	                                                simple lossy file whose frame header does not parse) */
+	uint32_t riff_size;
+	uint32_t extended;                           /* the file starts with a VP8X chunk */
+	uint32_t vp8x_flags;                         /* its flag byte (ICC 0x20, alpha 0x10, EXIF 0x08, XMP 0x04, animation 0x02) */
+} WebPStill;
+
+/* What webp_locate_still accepts beyond the simple lossy layout, which is strict (RIFF size + 8 == file size, one
+ * 'VP8 ' chunk with its pad byte, nothing behind it; the frame header is not looked at): */
+#define WEBP_ACCEPT_EXTENDED 1u /* VP8X files, by the rules stated at webp_parse_extended */
+#define WEBP_ACCEPT_LOSSLESS 2u /* (with WEBP_ACCEPT_EXTENDED) a 'VP8L' image too, by those at webp_parse_any */
+
+/* The one walk.  `accept` picks whose verdict it gives: 0 webp_parse_simple_lossy's, WEBP_ACCEPT_EXTENDED
+ * webp_parse_extended's, with WEBP_ACCEPT_LOSSLESS webp_parse_any's -- those three fill their structs from this
+ * record.  0, or -1 + errno (EINVAL, ENOTSUP) with out->data / out->size set and the rest unspecified. */
+int webp_locate_still(ByteSpan file, unsigned accept, WebPStill* out);
+
 /* ---- extended container (VP8X) and the ALPH chunk (RFC 9649 2.7) ----------- */
 
 /* What webp_parse_extended found.  alph_chunk_offset = 0: no alpha. */
@@ -149,7 +176,8 @@ typedef struct {
 	uint32_t canvas_width, canvas_height;
 } WebPContainerX;
 
-/* The simple layout as webp_parse_simple_lossy reads it, or a VP8X file: the 10-byte VP8X chunk
+/* webp_locate_still(WEBP_ACCEPT_EXTENDED) as a WebPContainerX (canvas 0 x 0 without VP8X).
+ * The simple layout as webp_parse_simple_lossy reads it, or a VP8X file: the 10-byte VP8X chunk
  * first, then chunks up to the first 'VP8 ' chunk, which ends the parse as it does in libwebp (what
  * follows the image -- EXIF, XMP, a late ALPH -- is not looked at).  ICCP, EXIF, 'XMP ' and unknown
  * chunks are skipped (odd sizes padded); of several ALPH chunks before the image the last counts
@@ -205,7 +233,8 @@ typedef struct {
 	uint32_t vp8l_chunk_size;
 } WebPContainerL;
 
-/* webp_parse_extended, which also accepts a simple RIFF/WEBP/VP8L file (the chunk must lie inside
+/* webp_locate_still(WEBP_ACCEPT_EXTENDED | WEBP_ACCEPT_LOSSLESS) as a WebPContainerL:
+ * webp_parse_extended, which also accepts a simple RIFF/WEBP/VP8L file (the chunk must lie inside
  * the file and the RIFF payload; what follows it is ignored) and a VP8X file whose image chunk is
  * 'VP8L'.  Animation stays -1 + ENOTSUP; a VP8X canvas that differs from the VP8L header's size, or
  * a VP8L header that does not parse, is -1 + EINVAL. */

@@ -1,8 +1,10 @@
 /*
- * webp_riff.c -- RIFF/WEBP container (RFC 9649 simple lossy layout) and the VP8 frame tag /
- * key-frame header (RFC 6386 9.1), with the reference's acceptance rules:
- *   container: 'RIFF' <size> 'WEBP' then exactly one 'VP8 ' chunk, RIFF size + 8 == file size,
- *              nothing after the (even-padded) chunk  (reference src/m01_container/webp_container.c:19-89)
+ * webp_riff.c -- the RIFF/WEBP container (RFC 9649) and the VP8 frame tag / key-frame header (RFC 6386 9.1).
+ *   container: one chunk iterator (riff_chunk) under two walks: a still picture's (webp_locate_still, of which
+ *              webp_parse_simple_lossy, webp_parse_extended and webp_parse_any are views) and an animation's
+ *              (webp_parse_anim).  The simple lossy layout keeps the reference's acceptance rules: 'RIFF' <size>
+ *              'WEBP' then exactly one 'VP8 ' chunk, RIFF size + 8 == file size, nothing after the (even-padded)
+ *              chunk  (reference src/m01_container/webp_container.c:19-89); the others libwebp's.
  *   header:    key frame, start code 9d 01 2a, 14-bit non-zero width/height, first partition
  *              fits in the payload  (reference src/m02_vp8_header/vp8_header.c:13-66)
  */
@@ -16,211 +18,150 @@
 static uint32_t rd_le32(const uint8_t* p) {
 	return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
+static uint32_t rd_le24(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16); }
+
+typedef struct {
+	const uint8_t* tag; /* four bytes */
+	uint32_t size;      /* of the payload, which starts 8 bytes behind the tag */
+	size_t padded;      /* ... rounded up to even: the next chunk is 8 + padded on */
+} RiffChunk;
+
+static int tagged(const RiffChunk* c, const char* tag) { return memcmp(c->tag, tag, 4) == 0; }
+
+/* The chunk at pos of a RIFF payload that ends at `end` (pos <= end): the one statement of a chunk header's bounds.
+ * 0 = refused: no room for a header, or a size beyond 0xFFFFFFF6 or beyond the payload.  1 = the chunk and its pad
+ * byte lie inside.  2 = the chunk does, its pad byte is missing: a still picture's image chunk may end so, no other. */
+static int riff_chunk(const uint8_t* data, size_t pos, size_t end, RiffChunk* c) {
+	if (end - pos < 8u) return 0;
+	c->tag = data + pos;
+	c->size = rd_le32(data + pos + 4);
+	c->padded = (size_t)c->size + (c->size & 1u);
+	if (c->size > 0xFFFFFFF6u || (size_t)c->size > end - pos - 8u) return 0;
+	return c->padded > end - pos - 8u ? 2 : 1;
+}
+
+/* The end of a RIFF payload of at least `least` bytes that must lie inside the file (bytes after it are ignored), or 0. */
+static size_t riff_end(ByteSpan file, uint32_t least) {
+	const uint32_t riff_size = rd_le32(file.data + 4);
+	if (riff_size < least || riff_size > 0xFFFFFFF6u || (size_t)riff_size > file.size - 8u) return 0;
+	return 8u + (size_t)riff_size;
+}
+
+static int refuse(int e) {
+	errno = e;
+	return -1;
+}
+
+/* RFC 9649 2.5 - 2.7, with libwebp's reading where the RFC leaves a choice (tests/golden/alpha.json and lossless.json
+ * record its verdict on the directed containers). */
+int webp_locate_still(ByteSpan file, unsigned accept, WebPStill* out) {
+	if (!out) return -1;
+	memset(out, 0, sizeof(*out));
+	out->data = file.data, out->size = file.size;
+	const uint8_t* d = file.data;
+	const int ext = (accept & WEBP_ACCEPT_EXTENDED) != 0, lossless = ext && (accept & WEBP_ACCEPT_LOSSLESS);
+	if (!d || file.size < 12 || memcmp(d, "RIFF", 4) != 0) return refuse(EINVAL);
+	out->riff_size = rd_le32(d + 4);
+	if (file.size < 20 || memcmp(d + 8, "WEBP", 4) != 0) return refuse(EINVAL);
+	const int vp8x = ext && memcmp(d + 12, "VP8X", 4) == 0;
+	const int simple_vp8l = ext && memcmp(d + 12, "VP8L", 4) == 0;
+	if (simple_vp8l && !lossless) return refuse(ENOTSUP);
+	size_t pos = 12, end = file.size;
+	if (vp8x || simple_vp8l) {
+		if ((end = riff_end(file, 12)) == 0) return refuse(EINVAL);
+	} else if ((size_t)out->riff_size + 8u != file.size) { /* the simple lossy layout is strict */
+		return refuse(EINVAL);
+	}
+	if (vp8x) {
+		if (end < 30u || rd_le32(d + 16) != 10u) return refuse(EINVAL);
+		out->extended = 1;
+		out->vp8x_flags = d[20];
+		out->width = 1u + rd_le24(d + 24), out->height = 1u + rd_le24(d + 27);
+		if (out->vp8x_flags & 0x02u) return refuse(ENOTSUP);
+		pos = 30;
+	}
+	RiffChunk c;
+	for (;;) { /* up to the image chunk */
+		const int got = riff_chunk(d, pos, end, &c);
+		if (!got) return refuse(EINVAL); /* (also: no image chunk) */
+		const int is_vp8 = tagged(&c, "VP8 "), is_vp8l = tagged(&c, "VP8L");
+		if (!vp8x) { /* a simple layout: the image chunk and, for the lossy one, nothing behind it */
+			if (simple_vp8l ? !is_vp8l : (!is_vp8 || pos + 8u + c.padded != end)) return refuse(EINVAL);
+		} else if ((is_vp8l && !lossless) || tagged(&c, "ANIM") || tagged(&c, "ANMF")) {
+			return refuse(ENOTSUP);
+		}
+		if (is_vp8) out->vp8_offset = pos + 8u, out->vp8_size = c.size;
+		if (is_vp8l) { /* (an ALPH chunk beside a VP8L image is ignored, as libwebp ignores it) */
+			out->vp8l_offset = pos + 8u, out->vp8l_size = c.size;
+			out->alph_offset = 0, out->alph_size = 0;
+		}
+		if (is_vp8 || is_vp8l) break;
+		if (tagged(&c, "ALPH")) out->alph_offset = pos + 8u, out->alph_size = c.size;
+		if (got != 1) return refuse(EINVAL);
+		pos += 8u + c.padded;
+	}
+	/* the bitstream's size: in a VP8X file it must be the canvas; in the simple lossy layout a frame header that does
+	 * not parse is not the container's business (0 x 0) */
+	uint32_t w = 0, h = 0, hint;
+	Vp8KeyFrameHeader kf;
+	if (out->vp8l_offset) {
+		if (vp8f_lossless_header(d + out->vp8l_offset, out->vp8l_size, &w, &h, &hint) != 0) return -1;
+	} else {
+		const ByteSpan payload = {d + out->vp8_offset, out->vp8_size};
+		if (vp8_parse_keyframe_header(payload, &kf) == 0) w = kf.width, h = kf.height;
+		else if (vp8x) return -1;
+	}
+	if (vp8x && (w != out->width || h != out->height)) return refuse(EINVAL);
+	out->width = w, out->height = h;
+	return 0;
+}
+
+/* ---- the three parsers: views of a WebPStill ----------------------------------------------- */
 
 int webp_parse_simple_lossy(ByteSpan file, WebPContainer* out) {
 	if (!out) return -1;
+	WebPStill s;
+	const int rc = webp_locate_still(file, 0, &s);
 	memset(out, 0, sizeof(*out));
-	out->actual_size = file.size;
-	if (!file.data || file.size < 12 || memcmp(file.data, "RIFF", 4) != 0) {
-		errno = EINVAL;
-		return -1;
-	}
-	out->riff_size = rd_le32(file.data + 4);
-	if (memcmp(file.data + 8, "WEBP", 4) != 0 || (size_t)out->riff_size + 8u != file.size || file.size < 20) {
-		errno = EINVAL;
-		return -1;
-	}
-	const uint8_t* chunk = file.data + 12;
-	const uint32_t csize = rd_le32(chunk + 4);
-	if (memcmp(chunk, "VP8 ", 4) != 0 || csize > file.size - 20) {
-		errno = EINVAL;
-		return -1;
-	}
-	size_t end = 20u + (size_t)csize;
-	end += end & 1u; /* chunks are padded to even length */
-	if (end != file.size) {
-		errno = EINVAL;
-		return -1;
-	}
-	out->vp8_chunk_offset = 20;
-	out->vp8_chunk_size = csize;
-	return 0;
+	out->riff_size = s.riff_size, out->actual_size = file.size;
+	out->vp8_chunk_offset = s.vp8_offset, out->vp8_chunk_size = s.vp8_size;
+	return rc;
 }
 
-/* RFC 9649 2.7 (extended file format), with libwebp's reading where the RFC leaves a choice
- * (tests/golden/alpha.json records its verdict on the directed containers). */
+int webp_parse_any(ByteSpan file, WebPContainerL* out) {
+	if (!out) return -1;
+	WebPStill s;
+	const int rc = webp_locate_still(file, WEBP_ACCEPT_EXTENDED | WEBP_ACCEPT_LOSSLESS, &s);
+	memset(out, 0, sizeof(*out));
+	out->riff_size = s.riff_size, out->actual_size = file.size;
+	out->vp8_chunk_offset = s.vp8_offset, out->vp8_chunk_size = s.vp8_size;
+	out->alph_chunk_offset = s.alph_offset, out->alph_chunk_size = s.alph_size;
+	out->vp8l_chunk_offset = s.vp8l_offset, out->vp8l_chunk_size = s.vp8l_size;
+	out->extended = s.extended, out->vp8x_flags = s.vp8x_flags;
+	if (s.extended || s.vp8l_offset) out->canvas_width = s.width, out->canvas_height = s.height; /* (a simple lossy file names none) */
+	return rc;
+}
+
 int webp_parse_extended(ByteSpan file, WebPContainerX* out) {
 	if (!out) return -1;
+	WebPStill s;
+	const int rc = webp_locate_still(file, WEBP_ACCEPT_EXTENDED, &s);
 	memset(out, 0, sizeof(*out));
-	out->actual_size = file.size;
-	if (!file.data || file.size < 20 || memcmp(file.data, "RIFF", 4) != 0 || memcmp(file.data + 8, "WEBP", 4) != 0) {
-		errno = EINVAL;
-		return -1;
-	}
-	if (memcmp(file.data + 12, "VP8X", 4) != 0) {
-		WebPContainer c;
-		if (memcmp(file.data + 12, "VP8L", 4) == 0) {
-			errno = ENOTSUP;
-			return -1;
-		}
-		if (webp_parse_simple_lossy(file, &c) != 0) return -1;
-		out->riff_size = c.riff_size;
-		out->vp8_chunk_offset = c.vp8_chunk_offset, out->vp8_chunk_size = c.vp8_chunk_size;
-		return 0;
-	}
-	out->riff_size = rd_le32(file.data + 4);
-	/* the RIFF payload must lie inside the file; bytes after it are ignored */
-	if (out->riff_size > 0xFFFFFFF6u || (size_t)out->riff_size > file.size - 8u || out->riff_size < 12u) {
-		errno = EINVAL;
-		return -1;
-	}
-	const size_t end = 8u + (size_t)out->riff_size;
-	if (end < 30u || rd_le32(file.data + 16) != 10u) {
-		errno = EINVAL;
-		return -1;
-	}
-	out->extended = 1;
-	out->vp8x_flags = file.data[20];
-	out->canvas_width = 1u + ((uint32_t)file.data[24] | (uint32_t)file.data[25] << 8 | (uint32_t)file.data[26] << 16);
-	out->canvas_height = 1u + ((uint32_t)file.data[27] | (uint32_t)file.data[28] << 8 | (uint32_t)file.data[29] << 16);
-	if (out->vp8x_flags & 0x02u) {
-		errno = ENOTSUP;
-		return -1;
-	}
-	size_t pos = 30;
-	for (;;) {
-		if (end - pos < 8u) { /* no image chunk */
-			errno = EINVAL;
-			return -1;
-		}
-		const uint8_t* chunk = file.data + pos;
-		const uint32_t csize = rd_le32(chunk + 4);
-		if (csize > 0xFFFFFFF6u || (size_t)csize > end - pos - 8u) {
-			errno = EINVAL;
-			return -1;
-		}
-		if (memcmp(chunk, "VP8L", 4) == 0 || memcmp(chunk, "ANIM", 4) == 0 || memcmp(chunk, "ANMF", 4) == 0) {
-			errno = ENOTSUP;
-			return -1;
-		}
-		if (memcmp(chunk, "VP8 ", 4) == 0) {
-			out->vp8_chunk_offset = pos + 8u, out->vp8_chunk_size = csize;
-			break;
-		}
-		if (memcmp(chunk, "ALPH", 4) == 0) out->alph_chunk_offset = pos + 8u, out->alph_chunk_size = csize;
-		const size_t padded = (size_t)csize + (csize & 1u);
-		if (padded > end - pos - 8u) { /* (the pad byte of the last chunk may be missing only for the image) */
-			errno = EINVAL;
-			return -1;
-		}
-		pos += 8u + padded;
-	}
-	Vp8KeyFrameHeader kf;
-	ByteSpan payload = {file.data + out->vp8_chunk_offset, out->vp8_chunk_size};
-	if (vp8_parse_keyframe_header(payload, &kf) != 0) return -1;
-	if (kf.width != out->canvas_width || kf.height != out->canvas_height) {
-		errno = EINVAL;
-		return -1;
-	}
-	return 0;
+	out->riff_size = s.riff_size, out->actual_size = file.size;
+	out->vp8_chunk_offset = s.vp8_offset, out->vp8_chunk_size = s.vp8_size;
+	out->alph_chunk_offset = s.alph_offset, out->alph_chunk_size = s.alph_size;
+	out->extended = s.extended, out->vp8x_flags = s.vp8x_flags;
+	if (s.extended) out->canvas_width = s.width, out->canvas_height = s.height;
+	return rc;
 }
 
-/* (here, not beside the stream decoder in vp8_alpha.c: webp_parse_any needs it, and this file links on its own) */
 int vp8f_lossless_header(const uint8_t* data, size_t size, uint32_t* width, uint32_t* height, uint32_t* alpha_hint) {
-	if (!data || !width || !height || !alpha_hint || size < 5 || data[0] != 0x2f) {
-		errno = EINVAL;
-		return -1;
-	}
-	const uint32_t v = (uint32_t)data[1] | (uint32_t)data[2] << 8 | (uint32_t)data[3] << 16 | (uint32_t)data[4] << 24;
-	if (v >> 29) { /* version */
-		errno = EINVAL;
-		return -1;
-	}
+	if (!data || !width || !height || !alpha_hint || size < 5 || data[0] != 0x2f) return refuse(EINVAL);
+	const uint32_t v = rd_le32(data + 1);
+	if (v >> 29) return refuse(EINVAL); /* version */
 	*width = (v & 0x3FFFu) + 1u, *height = ((v >> 14) & 0x3FFFu) + 1u, *alpha_hint = (v >> 28) & 1u;
 	return 0;
 }
-
-static void copy_container(WebPContainerL* out, const WebPContainerX* x) {
-	out->riff_size = x->riff_size, out->actual_size = x->actual_size;
-	out->vp8_chunk_offset = x->vp8_chunk_offset, out->vp8_chunk_size = x->vp8_chunk_size;
-	out->alph_chunk_offset = x->alph_chunk_offset, out->alph_chunk_size = x->alph_chunk_size;
-	out->extended = x->extended, out->vp8x_flags = x->vp8x_flags;
-	out->canvas_width = x->canvas_width, out->canvas_height = x->canvas_height;
-}
-
-/* webp_parse_extended's walk, with a 'VP8L' image chunk accepted (simple layout: as libwebp reads it, the
- * chunk inside the RIFF payload and the file, the rest ignored). */
-int webp_parse_any(ByteSpan file, WebPContainerL* out) {
-	if (!out) return -1;
-	memset(out, 0, sizeof(*out));
-	WebPContainerX x;
-	if (webp_parse_extended(file, &x) == 0) {
-		copy_container(out, &x);
-		return 0;
-	}
-	if (errno != ENOTSUP) {
-		out->actual_size = file.size;
-		return -1;
-	}
-	/* animation, or a lossless image: the file has passed the checks in front of the chunk walk */
-	copy_container(out, &x);
-	out->vp8_chunk_offset = 0, out->vp8_chunk_size = 0, out->alph_chunk_offset = 0, out->alph_chunk_size = 0;
-	size_t pos, end;
-	if (!x.extended) {
-		out->riff_size = rd_le32(file.data + 4);
-		if (out->riff_size > 0xFFFFFFF6u || (size_t)out->riff_size > file.size - 8u || out->riff_size < 12u) {
-			errno = EINVAL;
-			return -1;
-		}
-		pos = 12, end = 8u + (size_t)out->riff_size;
-	} else {
-		if (x.vp8x_flags & 0x02u) {
-			errno = ENOTSUP;
-			return -1;
-		}
-		pos = 30, end = 8u + (size_t)x.riff_size;
-	}
-	for (;;) {
-		if (end - pos < 8u) {
-			errno = EINVAL;
-			return -1;
-		}
-		const uint8_t* chunk = file.data + pos;
-		const uint32_t csize = rd_le32(chunk + 4);
-		if (csize > 0xFFFFFFF6u || (size_t)csize > end - pos - 8u) {
-			errno = EINVAL;
-			return -1;
-		}
-		if (memcmp(chunk, "ANIM", 4) == 0 || memcmp(chunk, "ANMF", 4) == 0) {
-			errno = ENOTSUP;
-			return -1;
-		}
-		if (memcmp(chunk, "VP8L", 4) == 0) {
-			out->vp8l_chunk_offset = pos + 8u, out->vp8l_chunk_size = csize;
-			break;
-		}
-		if (!x.extended || memcmp(chunk, "VP8 ", 4) == 0) { /* (unreachable after webp_parse_extended's verdict) */
-			errno = EINVAL;
-			return -1;
-		}
-		const size_t padded = (size_t)csize + (csize & 1u);
-		if (padded > end - pos - 8u) {
-			errno = EINVAL;
-			return -1;
-		}
-		pos += 8u + padded;
-	}
-	uint32_t w, h, hint;
-	if (vp8f_lossless_header(file.data + out->vp8l_chunk_offset, out->vp8l_chunk_size, &w, &h, &hint) != 0) return -1;
-	if (x.extended && (w != out->canvas_width || h != out->canvas_height)) {
-		errno = EINVAL;
-		return -1;
-	}
-	if (!x.extended) out->canvas_width = w, out->canvas_height = h;
-	return 0;
-}
-
-static uint32_t rd_le24(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16); }
 
 /* The sub-chunks of one frame from *pos on, in a RIFF payload that ends at `end`, as libwebp's demuxer walks them: an
  * optional ALPH, then 'VP8 ' or 'VP8L'; the walk stops in front of the first chunk that is neither (or a second of
@@ -230,34 +171,30 @@ static int anim_frame_chunks(const uint8_t* data, size_t* at, size_t end, WebPAn
 	uint32_t bw = 0, bh = 0, hint = 0;
 	size_t pos = *at;
 	for (;;) {
-		if (end - pos < 8u) return -1; /* (a frame's walk needs a chunk header to look at, and one after each chunk it took) */
-		const uint8_t* chunk = data + pos;
-		const uint32_t csize = rd_le32(chunk + 4);
-		if (csize > 0xFFFFFFF6u) return -1;
-		const size_t padded = (size_t)csize + (csize & 1u);
-		if (padded > end - pos - 8u) return -1;
-		const int is_vp8 = memcmp(chunk, "VP8 ", 4) == 0, is_vp8l = memcmp(chunk, "VP8L", 4) == 0;
-		if (memcmp(chunk, "ALPH", 4) == 0) {
+		RiffChunk c; /* (a frame's walk needs a chunk header to look at, and one after each chunk it took) */
+		if (riff_chunk(data, pos, end, &c) != 1) return -1;
+		const int is_vp8 = tagged(&c, "VP8 "), is_vp8l = tagged(&c, "VP8L");
+		if (tagged(&c, "ALPH")) {
 			if (f->alph_offset) break;
-			f->alph_offset = pos + 8u, f->alph_size = csize;
+			f->alph_offset = pos + 8u, f->alph_size = c.size;
 		} else if (is_vp8 || is_vp8l) {
 			if (is_vp8l && f->alph_offset) return -1;
 			if (f->vp8_offset || f->vp8l_offset) break;
 			if (is_vp8) {
 				Vp8KeyFrameHeader kf;
-				ByteSpan payload = {chunk + 8, csize};
+				ByteSpan payload = {c.tag + 8, c.size};
 				if (vp8_parse_keyframe_header(payload, &kf) != 0) return -1;
 				bw = kf.width, bh = kf.height;
-				f->vp8_offset = pos + 8u, f->vp8_size = csize;
+				f->vp8_offset = pos + 8u, f->vp8_size = c.size;
 			} else {
-				if (vp8f_lossless_header(chunk + 8, csize, &bw, &bh, &hint) != 0) return -1;
-				f->vp8l_offset = pos + 8u, f->vp8l_size = csize;
+				if (vp8f_lossless_header(c.tag + 8, c.size, &bw, &bh, &hint) != 0) return -1;
+				f->vp8l_offset = pos + 8u, f->vp8l_size = c.size;
 			}
 			f->width = bw, f->height = bh; /* (the bitstream's size counts, whatever the ANMF header names: as in libwebp) */
 		} else {
 			break;
 		}
-		pos += 8u + padded;
+		pos += 8u + c.padded;
 		if (pos == end) break;
 	}
 	*at = pos;
@@ -271,45 +208,34 @@ static int anim_frame_chunks(const uint8_t* data, size_t* at, size_t end, WebPAn
 
 static int parse_anim(ByteSpan file, WebPAnimInfo* info, WebPAnimFrame* frames, uint32_t max_frames) {
 	if (!file.data || file.size < 20 || memcmp(file.data, "RIFF", 4) != 0 || memcmp(file.data + 8, "WEBP", 4) != 0) return -1;
-	const uint32_t riff_size = rd_le32(file.data + 4);
-	/* the RIFF payload must lie inside the file; bytes after it are ignored */
-	if (riff_size < 22u || riff_size > 0xFFFFFFF6u || (size_t)riff_size > file.size - 8u) return -1; /* (a VP8X chunk at the least) */
-	const size_t end = 8u + (size_t)riff_size;
-	if (memcmp(file.data + 12, "VP8X", 4) != 0) return -1; /* a still picture */
-	const uint32_t xsize = rd_le32(file.data + 16);
-	if (xsize < 10u || xsize > 0xFFFFFFF6u || (size_t)xsize + (xsize & 1u) > end - 20u) return -1;
+	const size_t end = riff_end(file, 22); /* (a VP8X chunk at the least) */
+	RiffChunk c;
+	if (!end || riff_chunk(file.data, 12, end, &c) != 1 || !tagged(&c, "VP8X") || c.size < 10u) return -1; /* (not VP8X: a still picture) */
 	info->vp8x_flags = file.data[20];
 	info->canvas_width = 1u + rd_le24(file.data + 24), info->canvas_height = 1u + rd_le24(file.data + 27);
 	/* (libwebp's limit is the canvas area; this decoder's is the size of a tensor's picture) */
 	if (info->canvas_width > 16383u || info->canvas_height > 16383u) return -1;
 	if (!(info->vp8x_flags & 0x02u) || (info->vp8x_flags & ~0x3Eu)) return -1;
-	size_t pos = 20u + (size_t)xsize + (xsize & 1u);
+	size_t pos = 20u + c.padded;
 	uint32_t anims = 0, n = 0;
 	while (pos != end) {
-		if (end - pos < 8u) return -1;
-		const uint8_t* chunk = file.data + pos;
-		const uint32_t csize = rd_le32(chunk + 4);
-		if (csize > 0xFFFFFFF6u) return -1;
-		const size_t padded = (size_t)csize + (csize & 1u);
-		if (padded > end - pos - 8u) return -1;
-		if (memcmp(chunk, "VP8X", 4) == 0 || memcmp(chunk, "VP8 ", 4) == 0 || memcmp(chunk, "VP8L", 4) == 0 ||
-		    memcmp(chunk, "ALPH", 4) == 0)
-			return -1;
-		if (memcmp(chunk, "ANIM", 4) == 0) {
-			if (padded < 6u) return -1;
-			if (anims++ == 0) info->bgcolor = rd_le32(chunk + 8), info->loop_count = (uint32_t)chunk[12] | (uint32_t)chunk[13] << 8;
-		} else if (memcmp(chunk, "ANMF", 4) == 0) {
-			if (anims == 0 || padded < 16u) return -1;
+		if (riff_chunk(file.data, pos, end, &c) != 1) return -1;
+		if (tagged(&c, "VP8X") || tagged(&c, "VP8 ") || tagged(&c, "VP8L") || tagged(&c, "ALPH")) return -1;
+		const uint8_t* p = c.tag + 8;
+		if (tagged(&c, "ANIM")) {
+			if (c.padded < 6u) return -1;
+			if (anims++ == 0) info->bgcolor = rd_le32(p), info->loop_count = (uint32_t)p[4] | (uint32_t)p[5] << 8;
+		} else if (tagged(&c, "ANMF")) {
+			if (anims == 0 || c.padded < 16u) return -1;
 			WebPAnimFrame f;
 			memset(&f, 0, sizeof(f));
-			const uint8_t* p = chunk + 8;
-			f.offset = pos + 8u, f.size = csize;
+			f.offset = pos + 8u, f.size = c.size;
 			f.x = 2u * rd_le24(p), f.y = 2u * rd_le24(p + 3), f.width = 1u + rd_le24(p + 6), f.height = 1u + rd_le24(p + 9);
 			f.duration = rd_le24(p + 12);
 			f.dispose = p[15] & 1u, f.blend = (p[15] & 2u) ? 0u : 1u;
 			size_t at = pos + 24u;
 			const int got = anim_frame_chunks(file.data, &at, end, &f);
-			if (got < 0 || at > pos + 8u + padded) return -1; /* (a sub-chunk that runs past the ANMF's own end) */
+			if (got < 0 || at > pos + 8u + c.padded) return -1; /* (a sub-chunk that runs past the ANMF's own end) */
 			if (got > 0) {
 				if ((uint64_t)f.x + f.width > info->canvas_width || (uint64_t)f.y + f.height > info->canvas_height) return -1;
 				if (n < max_frames) frames[n] = f;
@@ -320,7 +246,7 @@ static int parse_anim(ByteSpan file, WebPAnimInfo* info, WebPAnimFrame* frames, 
 			pos = at;
 			continue;
 		}
-		pos += 8u + padded;
+		pos += 8u + c.padded;
 	}
 	if (n == 0) return -1;
 	info->nframes = n;
@@ -371,53 +297,37 @@ int vp8_parse_keyframe_header(ByteSpan p, Vp8KeyFrameHeader* out) {
 	return 0;
 }
 
+/* the VP8 payload of a file: the simple layout, or with VP8F_EXTENDED the extended one as well */
+static int locate_vp8(const uint8_t* data, size_t size, unsigned flags, ByteSpan* payload, size_t* offset) {
+	WebPStill s;
+	const ByteSpan file = {data, size};
+	if (webp_locate_still(file, (flags & VP8F_EXTENDED) ? WEBP_ACCEPT_EXTENDED : 0u, &s) != 0) return -1;
+	payload->data = data + s.vp8_offset, payload->size = s.vp8_size;
+	if (offset) *offset = s.vp8_offset;
+	return 0;
+}
+
 int vp8f_decode_memory(const uint8_t* data, size_t size, Vp8KeyFrameHeader* kf, Vp8DecodedFrame* out, int* stage) {
-	int st = 0;
-	WebPContainer c;
-	ByteSpan file = {data, size};
-	int rc = -1;
-	if (webp_parse_simple_lossy(file, &c) != 0) {
-		st = 2;
-		goto out;
-	}
-	ByteSpan payload = {data + c.vp8_chunk_offset, c.vp8_chunk_size};
-	if (vp8_parse_keyframe_header(payload, kf) != 0 || !kf->is_key_frame) {
-		st = 3;
-		goto out;
-	}
-	if (vp8_decode_decoded_frame(payload, out) != 0) {
-		st = 4;
-		goto out;
-	}
-	rc = 0;
-out:
+	int st = 0, rc = -1;
+	ByteSpan payload;
+	if (locate_vp8(data, size, 0, &payload, NULL) != 0) st = 2;
+	else if (vp8_parse_keyframe_header(payload, kf) != 0 || !kf->is_key_frame) st = 3;
+	else if (vp8_decode_decoded_frame(payload, out) != 0) st = 4;
+	else rc = 0;
 	if (stage) *stage = st;
 	return rc;
 }
 
-/* the VP8 payload of a file: the simple layout, or with VP8F_EXTENDED the extended one as well */
-static int locate_payload(ByteSpan file, unsigned flags, WebPContainer* c) {
-	if (!(flags & VP8F_EXTENDED)) return webp_parse_simple_lossy(file, c);
-	WebPContainerX x;
-	if (webp_parse_extended(file, &x) != 0) return -1;
-	memset(c, 0, sizeof(*c));
-	c->riff_size = x.riff_size, c->actual_size = x.actual_size;
-	c->vp8_chunk_offset = x.vp8_chunk_offset, c->vp8_chunk_size = x.vp8_chunk_size;
-	return 0;
-}
-
 int vp8f_decode_packed_memory(const uint8_t* data, size_t size, Vp8gPackedFrame* out, int* stage, unsigned flags) {
 	int st = 0, rc = -1;
-	WebPContainer c;
-	ByteSpan file = {data, size};
+	ByteSpan payload;
 	if (out) memset(out, 0, sizeof(*out));
 	if (!out) {
 		errno = EINVAL;
 		st = 4;
-	} else if (locate_payload(file, flags, &c) != 0) {
+	} else if (locate_vp8(data, size, flags, &payload, NULL) != 0) {
 		st = 2;
 	} else {
-		ByteSpan payload = {data + c.vp8_chunk_offset, c.vp8_chunk_size};
 		if (vp8_parse_keyframe_header(payload, &out->kf) != 0 || !out->kf.is_key_frame) st = 3;
 		else if (vp8f_decode_packed(payload, out, flags & ~VP8F_EXTENDED) != 0) st = 4;
 		else rc = 0;
@@ -430,26 +340,25 @@ int vp8f_token_header_memory(const uint8_t* data, size_t size, Vp8KeyFrameHeader
                              Vp8gTokFrame* tf, uint64_t* payload_off, uint32_t* payload_size, int* stage,
                              unsigned flags) {
 	int st = 0, rc = -1;
-	WebPContainer c;
-	ByteSpan file = {data, size};
+	ByteSpan payload;
+	size_t off;
 	if (!kf || !hdr || !tf || !payload_off || !payload_size) {
 		errno = EINVAL;
 		st = 4;
-	} else if (locate_payload(file, flags, &c) != 0) {
+	} else if (locate_vp8(data, size, flags, &payload, &off) != 0) {
 		st = 2;
-	} else if (c.vp8_chunk_size > 0xFFFFFFF0u) {
+	} else if (payload.size > 0xFFFFFFF0u) {
 		errno = EFBIG;
 		st = 4;
 	} else {
-		ByteSpan payload = {data + c.vp8_chunk_offset, c.vp8_chunk_size};
 		if (vp8_parse_keyframe_header(payload, kf) != 0 || !kf->is_key_frame) {
 			errno = EINVAL;
 			st = 3;
 		} else if (vp8f_token_header(payload, kf, hdr, tf, flags & ~VP8F_EXTENDED) != 0) {
 			st = 4;
 		} else {
-			*payload_off = c.vp8_chunk_offset;
-			*payload_size = (uint32_t)c.vp8_chunk_size;
+			*payload_off = off;
+			*payload_size = (uint32_t)payload.size;
 			rc = 0;
 		}
 	}

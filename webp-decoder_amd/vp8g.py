@@ -169,6 +169,16 @@ class Vp8gTensorDesc(C.Structure):
         "stride_y", "stride_uv", "task0", "ntasks")]
 
 
+class WebPStill(C.Structure):
+    """host/vp8_front.h: a still picture located in its file by webp_locate_still (an offset of 0 = no such chunk)."""
+    _fields_ = [("data", C.c_void_p), ("size", C.c_size_t), ("vp8_offset", C.c_size_t), ("alph_offset", C.c_size_t),
+                ("vp8l_offset", C.c_size_t)] + [(n, C.c_uint32) for n in (
+        "vp8_size", "alph_size", "vp8l_size", "width", "height", "riff_size", "extended", "vp8x_flags")]
+
+
+WEBP_ACCEPT_EXTENDED, WEBP_ACCEPT_LOSSLESS = 1, 2
+
+
 class WebPContainerX(C.Structure):
     """host/vp8_front.h: what webp_parse_extended found (alph_chunk_offset 0 = no alpha)."""
     _fields_ = [("riff_size", C.c_uint32), ("actual_size", C.c_size_t), ("vp8_chunk_offset", C.c_size_t),
@@ -409,29 +419,27 @@ def host_lib():
                                         C.POINTER(Vp8gScaleOpt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         lib.webp_parse_simple_lossy.argtypes = [ByteSpan, C.c_void_p]
         lib.vp8_parse_keyframe_header.argtypes = [ByteSpan, C.POINTER(Vp8KeyFrameHeader)]
-        if hasattr(lib, "webp_parse_extended"):  # (libraries built before the alpha path: A/B of old builds)
-            lib.webp_parse_extended.argtypes = [ByteSpan, C.POINTER(WebPContainerX)]
-            lib.vp8f_alpha_decode.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
-                                              C.POINTER(C.c_uint32), C.POINTER(Vp8fAlphaStats)]
-            lib.vp8f_alpha_unfilter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-        if hasattr(lib, "webp_parse_any"):  # (libraries built before the lossless path: A/B of old builds)
-            lib.webp_parse_any.argtypes = [ByteSpan, C.POINTER(WebPContainerL)]
-            lib.vp8f_lossless_header.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
-                                                 C.POINTER(C.c_uint32)]
-            lib.vp8f_lossless_decode.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(Vp8fLosslessImage),
-                                                 C.POINTER(Vp8fAlphaStats)]
-            lib.vp8f_lossless_free.argtypes = [C.POINTER(Vp8fLosslessImage)]
-            lib.vp8f_lossless_free.restype = None
-            lib.vp8f_lossless_apply.argtypes = [C.POINTER(Vp8fLosslessImage), C.c_void_p]
+        lib.webp_locate_still.argtypes = [ByteSpan, C.c_uint, C.POINTER(WebPStill)]
+        lib.webp_parse_extended.argtypes = [ByteSpan, C.POINTER(WebPContainerX)]
+        lib.vp8f_alpha_decode.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
+                                          C.POINTER(C.c_uint32), C.POINTER(Vp8fAlphaStats)]
+        lib.vp8f_alpha_unfilter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.webp_parse_any.argtypes = [ByteSpan, C.POINTER(WebPContainerL)]
+        lib.vp8f_lossless_header.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                             C.POINTER(C.c_uint32)]
+        lib.vp8f_lossless_decode.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(Vp8fLosslessImage),
+                                             C.POINTER(Vp8fAlphaStats)]
+        lib.vp8f_lossless_free.argtypes = [C.POINTER(Vp8fLosslessImage)]
+        lib.vp8f_lossless_free.restype = None
+        lib.vp8f_lossless_apply.argtypes = [C.POINTER(Vp8fLosslessImage), C.c_void_p]
         if hasattr(lib, "vp8f_argb_scale"):  # (libraries built before the scaled lossless path: A/B of old builds)
             lib.vp8f_scale_resolve_argb.argtypes = lib.vp8f_scale_resolve.argtypes
             lib.vp8f_argb_mult_row.argtypes = [C.c_void_p, C.c_uint32, C.c_int]
             lib.vp8f_argb_mult_row.restype = None
             lib.vp8f_argb_scale.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Vp8gScaleOpt), C.c_void_p]
-        if hasattr(lib, "webp_parse_anim"):  # (libraries built before the animation path: A/B of old builds)
-            lib.webp_parse_anim.argtypes = [ByteSpan, C.POINTER(WebPAnimInfo), C.POINTER(WebPAnimFrame), C.c_uint32]
-            lib.vp8f_anim_keyframes.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(Vp8fAnimFrame), C.c_uint32]
-            lib.vp8f_anim_compose.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(Vp8fAnimFrame), C.c_uint32, C.c_void_p]
+        lib.webp_parse_anim.argtypes = [ByteSpan, C.POINTER(WebPAnimInfo), C.POINTER(WebPAnimFrame), C.c_uint32]
+        lib.vp8f_anim_keyframes.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(Vp8fAnimFrame), C.c_uint32]
+        lib.vp8f_anim_compose.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(Vp8fAnimFrame), C.c_uint32, C.c_void_p]
         lib._typed = True
     return lib
 
@@ -889,6 +897,16 @@ def parse_simple(data: bytes):
     if host_lib().webp_parse_simple_lossy(span, out) != 0:
         raise OSError(C.get_errno(), "webp_parse_simple_lossy")
     return int.from_bytes(bytes(out[16:24]), "little"), int.from_bytes(bytes(out[24:28]), "little")
+
+
+def locate_still(data: bytes, accept: int = 0) -> dict:
+    """webp_locate_still (accept: WEBP_ACCEPT_*): the fields of WebPStill but the base pointer, as a dict; OSError with
+    its errno (EINVAL, ENOTSUP) if refused.  The three parsers below are views of this record."""
+    s = WebPStill()
+    buf, span = _c_bytes(data)
+    if host_lib().webp_locate_still(span, accept, C.byref(s)) != 0:
+        raise OSError(C.get_errno(), "webp_locate_still")
+    return {n: int(getattr(s, n)) for n, _ in WebPStill._fields_ if n != "data"}
 
 
 def parse_extended(data: bytes) -> dict:
