@@ -392,11 +392,14 @@ int vp8g_encode_batch_device(const Vp8gEncDesc* h_descs, const Vp8gEncDesc* d_de
  * axis: 500 x 200 -> 224 x 224 shrinks x and expands y; 5 -> 6 expands luma while chroma 3 -> 3 is a
  * copy), bit-exact as well.
  * The output is I420: luma scaled to the target, each chroma plane independently from
- * ceil(window / 2) to ceil(target / 2).  RGB of a scaled picture is DEFINED as the encoder
- * (vp8g_encode_batch_device, fancy upsampling) run on that scaled I420 -- deliberately not
- * `dwebp -ppm -scale`, which rescales chroma straight to luma resolution and skips the fancy
- * upsampler.  vp8g_decode_webp_batch_tensor (below) is the on-device route to it: scaled I420 ->
- * RGB tensor with no host copy. */
+ * ceil(window / 2) to ceil(target / 2).  RGB of a scaled picture has two definitions:
+ *   this library's   the encoder (vp8g_encode_batch_device, fancy upsampling) run on that scaled I420;
+ *                    vp8g_decode_webp_batch_tensor (below) is the on-device route to it, scaled I420 ->
+ *                    RGB tensor with no host copy;
+ *   libwebp's        `dwebp -ppm -scale`, WebPDecode with use_scaling into MODE_RGB / MODE_RGBA: chroma is
+ *                    rescaled straight to luma resolution and the fancy upsampler is skipped.  That is
+ *                    vp8g_make_scale_desc_444, vp8g_tensor_batch_device_444 and
+ *                    vp8g_decode_webp_batch_tensor_rgb (below), bit-exact to libwebp. */
 typedef struct {
 	uint32_t crop_left, crop_top, crop_w, crop_h;
 	uint32_t scaled_w, scaled_h;
@@ -777,6 +780,53 @@ int vp8g_scale_argb_batch_device(const Vp8gScaleArgbDesc* h_descs, const Vp8gSca
 #define VP8G_X_LOSSLESS 2u
 #define VP8G_X_LOSSLESS_SCALE 16u
 int vp8g_decode_webp_batch_tensor_any(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                      const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, uint32_t xflags,
+                                      void* d_out, int* status);
+
+/* ---- Scaled RGB exact to libwebp's (dwebp -ppm -scale) -------------------- */
+
+/* libwebp asked for a scaled RGB picture of a lossy file rescales Y, U and V EACH straight to the target size and
+ * converts pixel by pixel (VP8YuvToRgb); no upsampler runs.  An option with a target size (scaled_w or scaled_h not 0,
+ * a target equal to the window included) resolves as for I420 (window origin snapped down to even, a derived dimension
+ * by the ceiling, VP8G_SCALE_EXPAND deciding only whether the target may exceed the LUMA window), and then
+ *   Y     window win_w x win_h -> w x h;
+ *   U, V  origin (left / 2, top / 2), ceil(win_w / 2) x ceil(win_h / 2) -> the same w x h; each axis shrinks or expands
+ *         as its own sizes say (128 -> 100 shrinks luma and expands chroma 64 -> 100);
+ *   A     as luma (vp8g_make_scale_desc_plane); the A byte is not premultiplied (MODE_RGBA, not MODE_rgbA).
+ * With VP8G_SCALE_DWEBP_FILTER and a filtered request the result is libwebp's.
+ *
+ * vp8g_make_scale_desc for that: the three planes w x h each, back to back at dst_offset, stride w.  0, or -1 + EINVAL
+ * as vp8g_make_scale_desc, and for an option WITHOUT a target size (libwebp then runs the fancy upsampler on the window:
+ * the I420 route).  vp8g_scale_batch_device takes such descriptors beside the others. */
+int vp8g_make_scale_desc_444(uint32_t width, uint32_t height, uint64_t src_y, uint64_t src_u, uint64_t src_v,
+                             uint32_t stride_y, uint32_t stride_uv, const Vp8gScaleOpt* opt, uint64_t dst_offset,
+                             uint32_t task0, Vp8gScaleDesc* out);
+
+/* vp8g_make_tensor_desc for three planes of opt->width x opt->height each: stride_uv is the stride of the (full-width)
+ * U and V planes, >= opt->width.  The planes may start at any byte. */
+int vp8g_make_tensor_desc_444(const Vp8gTensorOpt* opt, uint64_t src_y, uint64_t src_u, uint64_t src_v, uint32_t stride_y,
+                              uint32_t stride_uv, uint64_t dst_offset, uint32_t task0, Vp8gTensorDesc* out);
+
+/* vp8g_tensor_batch_device / _a for such planes: pixel = VP8YuvToRgb(Y, U, V) of its own three samples; the element
+ * for a colour byte, the layouts, VP8G_T_BGR and alpha are exactly those of the 4:2:0 kernel.  channels = 3: h_alpha and
+ * d_alpha NULL, slots of vp8g_tensor_slot_size; channels = 4: both given, slots of vp8g_tensor_slot_size_a.  Anything
+ * else, a stride below the width, tasks out of order or a slot off the element size: -1 + EINVAL.  Writes only the
+ * images' own slot bytes; no LDS, no barrier, no wait on another workgroup.  Asynchronous. */
+int vp8g_tensor_batch_device_444(const Vp8gTensorDesc* h_descs, const Vp8gTensorDesc* d_descs, const Vp8gTensorAlpha* h_alpha,
+                                 const Vp8gTensorAlpha* d_alpha, uint32_t n, const Vp8gTensorOpt* opt, uint32_t channels,
+                                 const uint8_t* d_src, void* d_dst, void* hip_stream);
+
+/* Single image: upload src, the three planes to the target size, the 4:4:4 tensor kernel, download: *rgb = out_w * out_h
+ * tight R, G, B triples (malloc; the caller frees it) -- libwebp's MODE_RGB bytes, the payload of `dwebp -ppm -scale`.
+ * 0, or -1 + errno (EINVAL, also for an option without a target size; ENOMEM; EIO). */
+int yuv420_rescale_rgb(const Yuv420Image* src, const Vp8gScaleOpt* opt, uint8_t** rgb, uint32_t* out_w, uint32_t* out_h);
+
+/* vp8g_decode_webp_batch_tensor_any (same arguments, same xflags) with one difference: a lossy frame whose option has a
+ * target size gets libwebp's RGB as above (vp8g_make_scale_desc_444, then vp8g_tensor_batch_device_444 on the chunk's
+ * stream; the intermediate is 3 * w * h bytes of the chunk buffer).  Frames without a target size (no option, crop only)
+ * take the 4:2:0 route, which is what libwebp computes for them; lossless frames take their ARGB route; statuses, zero
+ * slots of failed frames and the size check against the tensor are those of _any. */
+int vp8g_decode_webp_batch_tensor_rgb(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
                                       const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, uint32_t xflags,
                                       void* d_out, int* status);
 

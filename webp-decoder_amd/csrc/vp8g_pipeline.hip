@@ -270,6 +270,8 @@ struct Slot {
 	std::vector<Vp8gAlphaDesc> adescs;   // alpha sink: the chunk's frames that have an ALPH plane
 	std::vector<Vp8gScaleDesc> asdescs;  //   their alpha planes through the rescaler
 	std::vector<Vp8gTensorAlpha> talpha; //   one per tensor descriptor
+	std::vector<Vp8gTensorDesc> tdescs444;   // libwebp's scaled RGB (Sinks::rgb_scale): the frames whose planes are 4:4:4,
+	std::vector<Vp8gTensorAlpha> talpha444;  //   a launch of their own
 	std::vector<Vp8gLosslessDesc> ldescs;     // lossless sink: the chunk's lossless frames
 	ArgbScaleBatch lbatch;                    //   their way into the tensor, cropped / rescaled (VP8G_X_LOSSLESS_SCALE) or as they are
 	std::vector<Vp8gTokFrame> jobs;  // device m05
@@ -441,8 +443,13 @@ struct Sinks {
 	bool alpha = false;                   // VP8G_X_ALPHA: ALPH planes become the tensor's fourth channel
 	bool lossless = false;                // VP8G_X_LOSSLESS: lossless files decode as well (vp8g_lossless.hip)
 	bool lossless_scale = false;          // VP8G_X_LOSSLESS_SCALE: ... and are cropped / rescaled (vp8g_scale_argb.hip)
+	bool rgb_scale = false;               // vp8g_decode_webp_batch_tensor_rgb: a lossy frame with a target size gets libwebp's RGB
 	uint64_t tslot = 0;                   // bytes per tensor slot (decode_batch fills it in)
 	const Vp8gScaleOpt* opt_of(uint32_t i) const { return opts ? &opts[n_opts == 1 ? 0 : i] : nullptr; }
+	// Whether lossy frame i is rescaled as libwebp rescales for RGB output: Y, U and V each to the target
+	// size (vp8g_make_scale_desc_444), for the tensor kernel's 4:4:4 mode.  Only with a target size: a crop alone is the
+	// fancy upsampler on the window in libwebp too, the 4:2:0 route.
+	bool yuv444(uint32_t i) const { return rgb_scale && opts && (opt_of(i)->scaled_w | opt_of(i)->scaled_h) != 0; }
 };
 
 // Device bytes per macroblock at which the memory budget prices a chunk.  Either kind holds per MB (ChunkLayout) ymode,
@@ -474,7 +481,7 @@ MbCaps chunk_budget(size_t free_bytes) {
 struct ChunkShape {
 	uint32_t nf = 0, max_cols = 0, max_rows = 0;
 	uint64_t mbs = 0, vals = 0, bitsb = 0;          // macroblocks; packed values (host m05); bitstream slots (device m05)
-	uint64_t outb = 0, soutb = 0, ab = 0, asb = 0;  // bytes of I420, scaled I420, alpha planes, scaled alpha planes
+	uint64_t outb = 0, soutb = 0, ab = 0, asb = 0;  // bytes of I420, scaled I420 (or 4:4:4 planes: 3 w h), alpha planes, scaled alpha planes
 	uint32_t nl = 0;                                // lossless frames
 	uint64_t lsrcb = 0, loutb = 0;                  // bytes of their residual images + transform data, of their ARGB pictures
 	uint32_t nls = 0;                               // those of them that are cropped / rescaled
@@ -540,6 +547,7 @@ struct Chunk {
 	vp8g::LaunchPlan plan = {};  // the recon launch, for either outcome of the launch gate
 	ChunkLayout L;
 	std::vector<uint32_t> sj;             // chunk position of each scale descriptor
+	std::vector<uint8_t> s444;            //   ... and whether it is a 4:4:4 one (Sinks::yuv444)
 	std::vector<Vp8gTensorAlpha> aplane;  // per chunk position: where the tensor kernel finds the frame's alpha
 	hipError_t up_err = hipSuccess;
 	// H2D onto the chunk's stream, to an offset of its buffer; after a failure the rest are skipped.  false: up_status
@@ -753,8 +761,8 @@ struct Pipeline {
 			else if (sk.topt && (sw != sk.topt->width || sh_ != sk.topt->height)) feed.err[fi] = EINVAL;  // not the tensor's size
 			if (feed.err[fi]) continue;
 			const Vp8DecodedFrame& f = f_of(fi);
-			const uint64_t ownb = vp8g_i420_size(w, h), sclb = sk.opts ? vp8g_i420_size(sw, sh_) : 0;
-			uint64_t fx = sclb > ownb ? extra_mbs(sclb - ownb) : 0u;  // (0 unless VP8G_SCALE_EXPAND grows it)
+			const uint64_t ownb = vp8g_i420_size(w, h), sclb = scaled_bytes(fi, sw, sh_);
+			uint64_t fx = sclb > ownb ? extra_mbs(sclb - ownb) : 0u;  // (0 unless VP8G_SCALE_EXPAND grows it, or 4:4:4 planes of a mild shrink)
 			// alpha planes count against the chunk's memory budget: residual + un-predicted (+ scaled)
 			const uint64_t apl = feed.ares[fi] ? (uint64_t)w * h : 0u;
 			const uint64_t aspl = apl && sk.opts ? (uint64_t)sw * sh_ : 0u;
@@ -773,6 +781,10 @@ struct Pipeline {
 		}
 		sh.nf = (uint32_t)c.idx.size();
 		sh.nl = (uint32_t)c.lidx.size();
+	}
+	// bytes of lossy frame fi's scaled planes in the chunk's small buffer
+	uint64_t scaled_bytes(uint32_t fi, uint32_t sw, uint32_t sh_) const {
+		return !sk.opts ? 0u : sk.yuv444(fi) ? 3ull * sw * sh_ : vp8g_i420_size(sw, sh_);
 	}
 	// a lossless frame's upload: the residual image and every transform's data, each padded to a dword count
 	static uint64_t lossless_tr_dwords(const Vp8fLosslessImage& im, uint32_t k) {
@@ -927,15 +939,18 @@ struct Pipeline {
 			const Vp8gFrameDesc& fd = s.descs[j];
 			if (!live[c.idx[j]]) continue;  // (a frame that failed above)
 			Vp8gScaleDesc sd;
-			if (vp8g_make_scale_desc(fd.width, fd.height, c.L.out + fd.out_y, c.L.out + fd.out_u, c.L.out + fd.out_v, fd.stride_y,
-			                         fd.stride_uv, sk.opt_of(c.idx[j]), c.L.sout + so, task0, &sd) != 0) {
+			const bool y444 = sk.yuv444(c.idx[j]);
+			if ((y444 ? vp8g_make_scale_desc_444 : vp8g_make_scale_desc)(fd.width, fd.height, c.L.out + fd.out_y, c.L.out + fd.out_u,
+			                                                             c.L.out + fd.out_v, fd.stride_y, fd.stride_uv, sk.opt_of(c.idx[j]),
+			                                                             c.L.sout + so, task0, &sd) != 0) {
 				feed.err[c.idx[j]] = EINVAL;  // (cannot happen: the options were resolved when the chunk was gathered)
 				continue;
 			}
 			s.sdescs.push_back(sd);
 			c.sj.push_back(j);
+			c.s444.push_back(y444);
 			task0 += sd.ntasks;
-			so = al256(so + vp8g_i420_size(sd.width, sd.height));
+			so = al256(so + scaled_bytes(c.idx[j], sd.width, sd.height));
 		}
 		return scale_batch(c, s.sdescs, c.L.sdesc, "scale launch");
 	}
@@ -982,41 +997,56 @@ struct Pipeline {
 		return scale_batch(c, s.asdescs, L.asdesc, "alpha scale launch");
 	}
 	// One frame of the chunk (position j, its planes at offsets of the chunk's buffer) into its slot of the tensor.
-	void add_tensor_desc(Chunk& c, uint32_t j, uint64_t y, uint64_t u, uint64_t v, uint32_t sy, uint32_t suv) {
+	// y444: the planes are 4:4:4 (launch_scale made them with vp8g_make_scale_desc_444); those frames have a launch of their own.
+	void add_tensor_desc(Chunk& c, uint32_t j, uint64_t y, uint64_t u, uint64_t v, uint32_t sy, uint32_t suv, bool y444 = false) {
 		const uint32_t fi = c.idx[j];
 		if (feed.err[fi]) return;  // (a frame whose alpha stage failed above)
 		Vp8gTensorDesc td;
-		if (vp8g_make_tensor_desc(sk.topt, y, u, v, sy, suv, (uint64_t)fi * sk.tslot, 0, &td) != 0) {
+		if ((y444 ? vp8g_make_tensor_desc_444 : vp8g_make_tensor_desc)(sk.topt, y, u, v, sy, suv, (uint64_t)fi * sk.tslot, 0, &td) != 0) {
 			feed.err[fi] = EINVAL;  // (cannot happen: the size was checked when the chunk was gathered)
 			return;
 		}
-		td.task0 = (uint32_t)c.s.tdescs.size() * td.ntasks;  // (every image of a tensor has the same task count)
-		c.s.tdescs.push_back(td);
-		c.s.talpha.push_back(c.aplane[j]);
+		std::vector<Vp8gTensorDesc>& descs = y444 ? c.s.tdescs444 : c.s.tdescs;
+		td.task0 = (uint32_t)descs.size() * td.ntasks;  // (every image of a tensor has the same task count)
+		descs.push_back(td);
+		(y444 ? c.s.talpha444 : c.s.talpha).push_back(c.aplane[j]);
 	}
 	// Tensor sink: the chunk's frames (scaled or as reconstructed) into their slots of the caller's tensor (same stream).
+	// A chunk may hold 4:2:0 frames and 4:4:4 ones (Sinks::yuv444): one launch each, the second's descriptors behind the
+	// first's in the chunk's buffer; each launch writes only its own frames' slots.
 	Status launch_tensor(Chunk& c) {
 		Slot& s = c.s;
 		const ChunkLayout& L = c.L;
 		uint8_t* d = s.buf;
 		s.tdescs.clear();
 		s.talpha.clear();
+		s.tdescs444.clear();
+		s.talpha444.clear();
 		for (size_t q = 0; sk.topt && sk.opts && q < s.sdescs.size(); q++) {
 			const Vp8gScaleDesc& sd = s.sdescs[q];
-			add_tensor_desc(c, c.sj[q], sd.p[0].dst, sd.p[1].dst, sd.p[2].dst, sd.p[0].dst_stride, sd.p[1].dst_stride);
+			add_tensor_desc(c, c.sj[q], sd.p[0].dst, sd.p[1].dst, sd.p[2].dst, sd.p[0].dst_stride, sd.p[1].dst_stride, c.s444[q] != 0);
 		}
 		for (uint32_t j = 0; sk.topt && !sk.opts && j < c.sh.nf; j++) {
 			const Vp8gFrameDesc& fd = s.descs[j];
 			if (live[c.idx[j]]) add_tensor_desc(c, j, L.out + fd.out_y, L.out + fd.out_u, L.out + fd.out_v, fd.stride_y, fd.stride_uv);
 		}
-		if (s.tdescs.empty()) return Status{};
-		const uint32_t nt = (uint32_t)s.tdescs.size();
-		if (!c.up(L.tdesc, s.tdescs) || (sk.alpha && !c.up(L.talpha, s.talpha))) return c.up_status();
-		return capi_status(sk.alpha ? vp8g_tensor_batch_device_a(s.tdescs.data(), (const Vp8gTensorDesc*)(d + L.tdesc), s.talpha.data(),
-		                                                         (const Vp8gTensorAlpha*)(d + L.talpha), nt, sk.topt, d, sk.d_tensor, c.stream)
-		                            : vp8g_tensor_batch_device(s.tdescs.data(), (const Vp8gTensorDesc*)(d + L.tdesc), nt, sk.topt, d,
-		                                                       sk.d_tensor, c.stream),
-		                   "tensor launch");
+		const uint32_t nt = (uint32_t)s.tdescs.size(), nt444 = (uint32_t)s.tdescs444.size();
+		if (nt) {
+			if (!c.up(L.tdesc, s.tdescs) || (sk.alpha && !c.up(L.talpha, s.talpha))) return c.up_status();
+			const Status st = capi_status(
+			    sk.alpha ? vp8g_tensor_batch_device_a(s.tdescs.data(), (const Vp8gTensorDesc*)(d + L.tdesc), s.talpha.data(),
+			                                          (const Vp8gTensorAlpha*)(d + L.talpha), nt, sk.topt, d, sk.d_tensor, c.stream)
+			             : vp8g_tensor_batch_device(s.tdescs.data(), (const Vp8gTensorDesc*)(d + L.tdesc), nt, sk.topt, d, sk.d_tensor, c.stream),
+			    "tensor launch");
+			if (!st.ok()) return st;
+		}
+		if (!nt444) return Status{};
+		const uint64_t o_desc = L.tdesc + nt * sizeof(Vp8gTensorDesc), o_alpha = L.talpha + nt * sizeof(Vp8gTensorAlpha);  // (both regions hold nf entries)
+		if (!c.up(o_desc, s.tdescs444) || (sk.alpha && !c.up(o_alpha, s.talpha444))) return c.up_status();
+		return capi_status(vp8g_tensor_batch_device_444(s.tdescs444.data(), (const Vp8gTensorDesc*)(d + o_desc), sk.alpha ? s.talpha444.data() : nullptr,
+		                                                sk.alpha ? (const Vp8gTensorAlpha*)(d + o_alpha) : nullptr, nt444, sk.topt,
+		                                                sk.alpha ? 4u : 3u, d, sk.d_tensor, c.stream),
+		                   "tensor launch (4:4:4)");
 	}
 	// Lossless sink: the residual images and transform data of the chunk's lossless frames are uploaded, the transforms
 	// inverted (vp8g_lossless.hip) and the ARGB pictures written to their slots of the tensor (same stream); with
@@ -1265,6 +1295,19 @@ VP8G_API int vp8g_decode_webp_batch_tensor_any(const ByteSpan* files, uint32_t n
 		return fail(EINVAL);
 	const Sinks sk{opts,  n_opts, nullptr, t, (uint8_t*)d_out, /*extended=*/true, /*alpha=*/(xflags & VP8G_X_ALPHA) != 0,
 	               /*lossless=*/(xflags & VP8G_X_LOSSLESS) != 0, /*lossless_scale=*/(xflags & VP8G_X_LOSSLESS_SCALE) != 0};
+	return decode_batch(files, nullptr, n, filtered, threads, flags, sk, status);
+}
+
+// ... and with libwebp's own RGB for a lossy frame that is rescaled: chroma straight to the target size,
+// VP8YuvToRgb per pixel, no upsampler.
+VP8G_API int vp8g_decode_webp_batch_tensor_rgb(const ByteSpan* files, uint32_t n, int filtered, uint32_t threads, uint32_t flags,
+                                               const Vp8gScaleOpt* opts, uint32_t n_opts, const Vp8gTensorOpt* t, uint32_t xflags,
+                                               void* d_out, int* status) {
+	if ((xflags & ~(VP8G_X_ALPHA | VP8G_X_LOSSLESS | VP8G_X_LOSSLESS_SCALE)) ||
+	    ((xflags & VP8G_X_LOSSLESS_SCALE) && !(xflags & VP8G_X_LOSSLESS)) || !tensor_ok(t, d_out) || !opts_ok(opts, n_opts, n))
+		return fail(EINVAL);
+	const Sinks sk{opts,  n_opts, nullptr, t, (uint8_t*)d_out, /*extended=*/true, /*alpha=*/(xflags & VP8G_X_ALPHA) != 0,
+	               /*lossless=*/(xflags & VP8G_X_LOSSLESS) != 0, /*lossless_scale=*/(xflags & VP8G_X_LOSSLESS_SCALE) != 0, /*rgb_scale=*/true};
 	return decode_batch(files, nullptr, n, filtered, threads, flags, sk, status);
 }
 

@@ -78,6 +78,17 @@ VP8G_RGB_DEV void chunk_rgb(const uint8_t* yrow, const uint8_t* ua_row, const ui
 	}
 }
 
+// The kChunk colours of the whole chunk [x0, x0 + kChunk) of a row of 4:4:4 planes (x0 + kChunk <= the width; the
+// planes of libwebp's scaled RGB, which has no upsampler: DESIGN.md §14.2): one 12-byte load per plane, at whatever
+// address the row and x0 give (u32x3u says so to the compiler; gfx950 runs global loads in unaligned mode,
+// tools/ubench/unaligned.hip), then VP8YuvToRgb per pixel.
+typedef uint32_t u32x3u __attribute__((ext_vector_type(3), aligned(1)));
+VP8G_RGB_DEV void chunk_yuv444(const uint8_t* yrow, const uint8_t* urow, const uint8_t* vrow, uint32_t x0, uint32_t (&c)[kChunk]) {
+	const u32x3 yl = *(const u32x3u*)(yrow + x0), ul = *(const u32x3u*)(urow + x0), vl = *(const u32x3u*)(vrow + x0);
+#pragma unroll
+	for (int i = 0; i < (int)kChunk; i++) c[i] = yuv_rgb((int)byte_of3(yl, i), (int)byte_of3(ul, i), (int)byte_of3(vl, i));
+}
+
 // The colour of pixel x of a row (the generic path: a row's last, partial chunk; images narrower
 // than 15 pixels, whose chroma rows are shorter than the 8-byte load).
 VP8G_RGB_DEV uint32_t pixel_rgb(const uint8_t* yrow, const uint8_t* ua_row, const uint8_t* ub_row, const uint8_t* va_row,

@@ -361,6 +361,31 @@ VP8G_API int vp8g_make_scale_desc(uint32_t width, uint32_t height, uint64_t src_
 	return 0;
 }
 
+// libwebp's scaled RGB: chroma goes from its own window straight to the luma target, so the three planes
+// are w x h each, back to back; a chroma plane that grows in an axis is the expand kernel's, whatever the option says
+// of luma.  The tensor kernel's 4:4:4 mode reads them (vp8g_tensor_batch_device_444).
+VP8G_API int vp8g_make_scale_desc_444(uint32_t width, uint32_t height, uint64_t src_y, uint64_t src_u, uint64_t src_v,
+                                      uint32_t stride_y, uint32_t stride_uv, const Vp8gScaleOpt* opt, uint64_t dst_offset,
+                                      uint32_t task0, Vp8gScaleDesc* d) {
+	Vp8fScaleGeom g;
+	if (!d || vp8f_scale_resolve(width, height, opt, &g) != 0 || !g.scaling || stride_y < width || stride_uv < (width + 1u) / 2u) {
+		errno = EINVAL;
+		return -1;
+	}
+	memset(d, 0, sizeof(*d));
+	d->width = g.out_w, d->height = g.out_h;
+	d->src_width = width, d->src_height = height, d->crop_left = g.left, d->crop_top = g.top;
+	const uint32_t cw = (g.win_w + 1u) / 2u, ch = (g.win_h + 1u) / 2u;
+	const uint64_t co = (uint64_t)(g.top / 2u) * stride_uv + g.left / 2u;
+	const uint64_t sz = (uint64_t)g.out_w * g.out_h;
+	make_plane(&d->p[0], src_y + (uint64_t)g.top * stride_y + g.left, stride_y, g.win_w, g.win_h, dst_offset, g.out_w, g.out_h);
+	make_plane(&d->p[1], src_u + co, stride_uv, cw, ch, dst_offset + sz, g.out_w, g.out_h);
+	make_plane(&d->p[2], src_v + co, stride_uv, cw, ch, dst_offset + 2u * sz, g.out_w, g.out_h);
+	d->task0 = task0;
+	d->ntasks = d->p[0].ntasks + d->p[1].ntasks + d->p[2].ntasks;
+	return 0;
+}
+
 // One plane scaled as luma (the A plane of an extended picture: libwebp rescales it with the luma
 // arithmetic, window and target); p[1] and p[2] stay empty (no tasks).
 VP8G_API int vp8g_make_scale_desc_plane(uint32_t width, uint32_t height, uint64_t src, uint32_t stride, const Vp8gScaleOpt* opt,
@@ -455,5 +480,67 @@ VP8G_API int yuv420_rescale(const Yuv420Image* img, const Vp8gScaleOpt* opt, Yuv
 		errno = en;
 		return -1;
 	}
+	return 0;
+}
+
+// libwebp's scaled RGB of one picture: upload, the three planes to the target size
+// (vp8g_make_scale_desc_444), the tensor kernel's 4:4:4 mode into uint8 RGB triples, download.
+VP8G_API int yuv420_rescale_rgb(const Yuv420Image* img, const Vp8gScaleOpt* opt, uint8_t** rgb, uint32_t* out_w, uint32_t* out_h) {
+	if (!img || !opt || !rgb || !out_w || !out_h || !img->y || !img->u || !img->v || img->width == 0 || img->height == 0 ||
+	    img->stride_y < img->width || img->stride_uv < (img->width + 1u) / 2u) {
+		errno = EINVAL;
+		return -1;
+	}
+	const uint32_t w = img->width, h = img->height, cw = (w + 1u) / 2u, ch = (h + 1u) / 2u;
+	const uint64_t ysz = (uint64_t)w * h, csz = (uint64_t)cw * ch;
+	const uint64_t o_desc = (ysz + 2 * csz + 255u) & ~255ull, o_planes = o_desc + 512u;
+	Vp8gScaleDesc desc;
+	if (vp8g_make_scale_desc_444(w, h, 0, ysz, ysz + csz, w, cw, opt, o_planes, 0, &desc) != 0) return -1;
+	const uint32_t ow = desc.width, oh = desc.height;
+	const uint64_t osz = (uint64_t)ow * oh, o_rgb = (o_planes + 3u * osz + 255u) & ~255ull;
+	Vp8gTensorOpt topt;
+	memset(&topt, 0, sizeof(topt));
+	topt.width = ow, topt.height = oh, topt.dtype = VP8G_T_U8, topt.layout = VP8G_T_NHWC;
+	Vp8gTensorDesc tdesc;
+	if (vp8g_make_tensor_desc_444(&topt, o_planes, o_planes + osz, o_planes + 2u * osz, ow, ow, 0, 0, &tdesc) != 0) return -1;
+	static_assert(sizeof(Vp8gScaleDesc) + sizeof(Vp8gTensorDesc) <= 512u, "the two descriptors' room");
+	uint8_t* host = (uint8_t*)malloc(3u * osz);
+	if (!host) {
+		errno = ENOMEM;
+		return -1;
+	}
+	hipStream_t s = nullptr;
+	uint8_t* b = nullptr;
+	const char* where = "stream";
+	hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+	if (e == hipSuccess) where = "hipMalloc", e = hipMalloc((void**)&b, o_rgb + 3u * osz + 16u);
+	if (e == hipSuccess) {
+		where = "H2D";
+		if ((e = hipMemcpy2DAsync(b, w, img->y, img->stride_y, w, h, hipMemcpyHostToDevice, s)) == hipSuccess &&
+		    (e = hipMemcpy2DAsync(b + ysz, cw, img->u, img->stride_uv, cw, ch, hipMemcpyHostToDevice, s)) == hipSuccess &&
+		    (e = hipMemcpy2DAsync(b + ysz + csz, cw, img->v, img->stride_uv, cw, ch, hipMemcpyHostToDevice, s)) == hipSuccess &&
+		    (e = hipMemcpyAsync(b + o_desc, &desc, sizeof(desc), hipMemcpyHostToDevice, s)) == hipSuccess)
+			e = hipMemcpyAsync(b + o_desc + sizeof(desc), &tdesc, sizeof(tdesc), hipMemcpyHostToDevice, s);
+	}
+	int rc = 0;
+	if (e == hipSuccess) rc = vp8g_scale_batch_device(&desc, (const Vp8gScaleDesc*)(b + o_desc), 1, b, b, s);
+	if (e == hipSuccess && rc == 0)
+		rc = vp8g_tensor_batch_device_444(&tdesc, (const Vp8gTensorDesc*)(b + o_desc + sizeof(desc)), nullptr, nullptr, 1, &topt, 3, b,
+		                                  b + o_rgb, s);
+	if (e == hipSuccess && rc == 0) {
+		where = "D2H";
+		if ((e = hipMemcpyAsync(host, b + o_rgb, 3u * osz, hipMemcpyDeviceToHost, s)) == hipSuccess) where = "sync", e = hipStreamSynchronize(s);
+	}
+	if (s && e != hipSuccess) (void)hipStreamSynchronize(s);
+	if (b) (void)hipFree(b);
+	if (s) (void)hipStreamDestroy(s);
+	if (e != hipSuccess || rc != 0) {
+		const int en = e != hipSuccess ? EIO : errno;
+		if (e != hipSuccess) vp8g::set_error_text(where, e);
+		free(host);
+		errno = en;
+		return -1;
+	}
+	*rgb = host, *out_w = ow, *out_h = oh;
 	return 0;
 }

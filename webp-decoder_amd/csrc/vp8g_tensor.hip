@@ -18,7 +18,10 @@
 // shorter than the 8-byte load).  Every store lies inside the image's own C * w * h elements.
 // No LDS and no barriers.  A workgroup task is 256 consecutive chunks of one image; the dtype,
 // layout, channel order and channel count are template parameters picked on the host.
-// ARGB sources (lossless images) have a kernel of their own further down; the three entry points share
+// Three planes of the picture's own size (vp8g_tensor_batch_device_444: libwebp's scaled RGB, whose chroma the rescaler
+// has already taken to the luma target) are a source mode of the same kernel, tensor_kernel_444: a whole
+// chunk is one unaligned 12-byte load per plane and VP8YuvToRgb per pixel, and everything from the colour on is shared.
+// ARGB sources (lossless images) have a kernel of their own further down; the entry points share
 // one host path, launch_tensor.
 #include <errno.h>
 #include <string.h>
@@ -52,10 +55,12 @@ struct TensorParams {
 	float scale[3], bias[3];
 };
 
-template <uint32_t DT, bool PLANAR, bool BGR, int C>
-__global__ __launch_bounds__(kThreads) void tensor_kernel(const Vp8gTensorDesc* __restrict__ D, const Vp8gTensorAlpha* __restrict__ A,
-                                                          uint32_t total, TensorParams P, const uint8_t* __restrict__ src,
-                                                          uint8_t* __restrict__ dst) {
+// S444: the source is three planes of the picture's own size (libwebp's scaled RGB; stride_uv is then the
+// stride of full-width U and V planes): the pixel is VP8YuvToRgb of its own three samples, no upsampler.  Everything
+// after the colours -- alpha, elements, stores -- is the one code below.
+template <uint32_t DT, bool PLANAR, bool BGR, int C, bool S444>
+DEV void tensor_body(const Vp8gTensorDesc* __restrict__ D, const Vp8gTensorAlpha* __restrict__ A, uint32_t total, const TensorParams& P,
+                     const uint8_t* __restrict__ src, uint8_t* __restrict__ dst) {
 	static_assert(C == 3 || C == 4, "RGB, or RGB and alpha");
 	constexpr uint32_t EB = (uint32_t)elem_bytes(DT);
 	const uint32_t tid = threadIdx.x, W = P.w;
@@ -67,7 +72,8 @@ __global__ __launch_bounds__(kThreads) void tensor_kernel(const Vp8gTensorDesc* 
 		const uint32_t y = gc / P.cpr, x0 = (gc - y * P.cpr) * kChunk;
 		// chroma rows (as vp8g_rgb.hip): row 0 uses row 0 twice; row y sits between a = (y-1)/2 and
 		// b = min(a+1, ch-1), nearer a when y is odd
-		const uint32_t a = y ? (y - 1u) >> 1 : 0u, b = y ? min(a + 1u, P.ch - 1u) : 0u;
+		// (S444: both "chroma rows" are the pixel row's own)
+		const uint32_t a = S444 ? y : y ? (y - 1u) >> 1 : 0u, b = S444 ? y : y ? min(a + 1u, P.ch - 1u) : 0u;
 		const bool near_a = y == 0 || (y & 1u);
 		const uint8_t* yrow = src + d.src_y + (size_t)y * d.stride_y;
 		const uint8_t* ua = src + d.src_u + (size_t)a * d.stride_uv;
@@ -86,9 +92,10 @@ __global__ __launch_bounds__(kThreads) void tensor_kernel(const Vp8gTensorDesc* 
 		[[maybe_unused]] auto alpha = [&](uint32_t x) { return conv_a<DT>(opaque ? 255u : (uint32_t)arow[x]); };
 		uint8_t* out = dst + d.dst;
 		const size_t pix = (size_t)y * W + x0;  // the chunk's first pixel in the image
-		if (x0 + kChunk <= W && P.cw >= 8u) {
+		if (x0 + kChunk <= W && (S444 || P.cw >= 8u)) {
 			uint32_t c[kChunk];
-			chunk_rgb(yrow, ua, ub, va, vb, x0, (int)P.cw, near_a, c);
+			if constexpr (S444) chunk_yuv444(yrow, ua, va, x0, c);
+			else chunk_rgb(yrow, ua, ub, va, vb, x0, (int)P.cw, near_a, c);
 			if constexpr (PLANAR) {
 #pragma unroll
 				for (int ch = 0; ch < C; ch++) {
@@ -130,10 +137,10 @@ __global__ __launch_bounds__(kThreads) void tensor_kernel(const Vp8gTensorDesc* 
 			}
 			continue;
 		}
-		// generic chunk (a row's last, partial chunk; images narrower than 15 pixels): pixel by pixel
+		// generic chunk (a row's last, partial chunk; 4:2:0 images narrower than 15 pixels): pixel by pixel
 		const uint32_t xe = min(x0 + kChunk, W);
 		for (uint32_t x = x0; x < xe; x++) {
-			const uint32_t col = pixel_rgb(yrow, ua, ub, va, vb, x, P.cw, near_a);
+			const uint32_t col = S444 ? yuv_rgb(yrow[x], ua[x], va[x]) : pixel_rgb(yrow, ua, ub, va, vb, x, P.cw, near_a);
 			const size_t px = (size_t)y * W + x;
 #pragma unroll
 			for (int ch = 0; ch < C; ch++) {
@@ -142,6 +149,20 @@ __global__ __launch_bounds__(kThreads) void tensor_kernel(const Vp8gTensorDesc* 
 			}
 		}
 	}
+}
+
+template <uint32_t DT, bool PLANAR, bool BGR, int C>
+__global__ __launch_bounds__(kThreads) void tensor_kernel(const Vp8gTensorDesc* __restrict__ D, const Vp8gTensorAlpha* __restrict__ A,
+                                                          uint32_t total, TensorParams P, const uint8_t* __restrict__ src,
+                                                          uint8_t* __restrict__ dst) {
+	tensor_body<DT, PLANAR, BGR, C, false>(D, A, total, P, src, dst);
+}
+
+template <uint32_t DT, bool PLANAR, bool BGR, int C>
+__global__ __launch_bounds__(kThreads) void tensor_kernel_444(const Vp8gTensorDesc* __restrict__ D, const Vp8gTensorAlpha* __restrict__ A,
+                                                              uint32_t total, TensorParams P, const uint8_t* __restrict__ src,
+                                                              uint8_t* __restrict__ dst) {
+	tensor_body<DT, PLANAR, BGR, C, true>(D, A, total, P, src, dst);
 }
 
 // ---- ARGB sources (vp8g_tensor_batch_device_argb) ------------------------------
@@ -217,6 +238,7 @@ using KernelFn = void (*)(const Vp8gTensorDesc*, const Vp8gTensorAlpha*, uint32_
 	{ {VP8G_T_ROW(K, VP8G_T_U8, 3), VP8G_T_ROW(K, VP8G_T_F16, 3), VP8G_T_ROW(K, VP8G_T_BF16, 3), VP8G_T_ROW(K, VP8G_T_F32, 3)}, \
 	  {VP8G_T_ROW(K, VP8G_T_U8, 4), VP8G_T_ROW(K, VP8G_T_F16, 4), VP8G_T_ROW(K, VP8G_T_BF16, 4), VP8G_T_ROW(K, VP8G_T_F32, 4)} }
 const KernelFn kKernels[2][4][2][2] = VP8G_T_TABLE(tensor_kernel);
+const KernelFn kKernels444[2][4][2][2] = VP8G_T_TABLE(tensor_kernel_444);
 const KernelFnArgb kKernelsArgb[2][4][2][2] = VP8G_T_TABLE(tensor_kernel_argb);
 #undef VP8G_T_TABLE
 #undef VP8G_T_ROW
@@ -281,6 +303,7 @@ int launch_tensor(bool ptrs_ok, const Desc* h, uint32_t n, const Vp8gTensorOpt* 
 }
 
 bool strides_ok(const Vp8gTensorDesc& d, const Vp8gTensorOpt& t) { return d.stride_y >= t.width && d.stride_uv >= (t.width + 1u) / 2u; }
+bool strides_ok_444(const Vp8gTensorDesc& d, const Vp8gTensorOpt& t) { return d.stride_y >= t.width && d.stride_uv >= t.width; }
 
 }  // namespace
 
@@ -313,6 +336,24 @@ VP8G_API int vp8g_tensor_batch_device_a(const Vp8gTensorDesc* h, const Vp8gTenso
 	    d_descs && ha && d_alpha, h, n, t, tasks_per_image, d_src, d_dst, stream,
 	    [&](uint32_t i) { return strides_ok(h[i], *t) && (ha[i].src_a == VP8G_T_OPAQUE || ha[i].stride_a >= t->width); },
 	    kKernels[1], d_descs, d_alpha);
+}
+
+// 4:4:4 planes (vp8g_make_scale_desc_444's output): the descriptor is vp8g_make_tensor_desc's but for the chroma stride
+VP8G_API int vp8g_make_tensor_desc_444(const Vp8gTensorOpt* t, uint64_t src_y, uint64_t src_u, uint64_t src_v, uint32_t stride_y,
+                                       uint32_t stride_uv, uint64_t dst_offset, uint32_t task0, Vp8gTensorDesc* d) {
+	if (!opt_ok(t) || stride_uv < t->width) return vp8g::fail(EINVAL);
+	return vp8g_make_tensor_desc(t, src_y, src_u, src_v, stride_y, stride_uv, dst_offset, task0, d);
+}
+
+VP8G_API int vp8g_tensor_batch_device_444(const Vp8gTensorDesc* h, const Vp8gTensorDesc* d_descs, const Vp8gTensorAlpha* ha,
+                                          const Vp8gTensorAlpha* d_alpha, uint32_t n, const Vp8gTensorOpt* t, uint32_t channels,
+                                          const uint8_t* d_src, void* d_dst, void* stream) {
+	const bool with_a = channels == 4u;  // (3: both alpha arrays NULL; 4: both given)
+	return launch_tensor(
+	    d_descs && (channels == 3u || with_a) && (ha != nullptr) == with_a && (d_alpha != nullptr) == with_a, h, n, t, tasks_per_image, d_src,
+	    d_dst, stream,
+	    [&](uint32_t i) { return strides_ok_444(h[i], *t) && (!with_a || ha[i].src_a == VP8G_T_OPAQUE || ha[i].stride_a >= t->width); },
+	    kKernels444[with_a], d_descs, d_alpha);
 }
 
 VP8G_API int vp8g_make_tensor_argb_desc(const Vp8gTensorOpt* t, uint32_t channels, uint64_t src, uint64_t dst_offset, uint32_t task0,

@@ -15,6 +15,13 @@
  *                                           equals dwebp's.  Other modes take neither option (usage).
  *   decoder -ppm  <file.webp> <out.ppm>     recon + loop filter + RGB (m08 writer, on the GPU)
  *   decoder -png  <file.webp> <out.png>     recon + loop filter + RGB (m09 writer, on the GPU)
+ *   decoder -rgb [-crop x y w h] [-scale w h [-expand]] <file.webp> <out.ppm>
+ *                                           the PPM of `dwebp -ppm [-crop] [-scale]`: libwebp's RGB of the cropped /
+ *                                           rescaled picture.  With -scale: Y, U and V each rescaled on the GPU straight
+ *                                           to the target size, VP8YuvToRgb per pixel, no upsampler; the loop filter
+ *                                           follows libwebp's rule as for -yuvf -scale.  With -crop alone: the m08 writer
+ *                                           on the window.  Without options: -ppm's file.  (A mode of its own: -ppm and
+ *                                           -png keep refusing both options, as ever.)
  *   decoder -diff_mb <file.webp> <oracle.i420>   per-macroblock SAD of our -yuv vs a file
  *
  * Output (-yuv/-yuvf): raw I420, Y (w*h) then U then V (each ceil(w/2)*ceil(h/2)), no header;
@@ -41,6 +48,7 @@ static void usage(void) {
 	fputs("  decoder -yuv|-yuvf [-crop x y w h] [-scale w h [-expand]] <file.webp> <out.i420>\n", stderr);
 	fputs("  decoder -ppm <file.webp> <out.ppm>\n", stderr);
 	fputs("  decoder -png <file.webp> <out.png>\n", stderr);
+	fputs("  decoder -rgb [-crop x y w h] [-scale w h [-expand]] <file.webp> <out.ppm>\n", stderr);
 	fputs("  decoder -diff_mb <file.webp> <oracle.i420>\n", stderr);
 }
 
@@ -119,6 +127,59 @@ static int cmd_yuv(const char* in, const char* out_path, int filtered, const Vp8
 		return 1;
 	}
 	return 0;
+}
+
+/* -rgb with options.  A target size: libwebp's scaled RGB (yuv420_rescale_rgb: Y, U and V each rescaled on the GPU
+ * straight to the target, VP8YuvToRgb per pixel) behind a P6 header.  A crop alone: the window through the m08 writer. */
+static int cmd_ppm_scaled(const char* in, const char* out_path, const Vp8gScaleOpt* opt) {
+	Vp8KeyFrameHeader kf;
+	Vp8DecodedFrame d;
+	if (front(in, &kf, &d) != 0) return 1;
+	Vp8fScaleGeom g;
+	if (vp8f_scale_resolve(kf.width, kf.height, opt, &g) != 0) {
+		fputs("error: bad -crop / -scale for this picture (the crop must lie inside it; downscale only without -expand)\n", stderr);
+		vp8_decoded_frame_free(&d);
+		return 1;
+	}
+	const int filtered = vp8f_scale_filtered(kf.width, kf.height, opt, 1);
+	Yuv420Image img, win;
+	uint8_t* rgb = NULL;
+	uint32_t w = 0, h = 0;
+	int rc = filtered ? vp8_reconstruct_keyframe_yuv_filtered(&kf, &d, &img) : vp8_reconstruct_keyframe_yuv(&kf, &d, &img);
+	vp8_decoded_frame_free(&d);
+	if (rc != 0) {
+		fputs("error: VP8 reconstruction failed\n", stderr);
+		const char* he = vp8g_last_error();
+		if (he && *he) fprintf(stderr, "  (%s)\n", he);
+		return 1;
+	}
+	memset(&win, 0, sizeof(win));
+	rc = g.scaling ? yuv420_rescale_rgb(&img, opt, &rgb, &w, &h) : yuv420_rescale(&img, opt, &win);
+	yuv420_free(&img);
+	if (rc != 0) {
+		fputs("error: crop / rescale failed\n", stderr);
+		const char* he = vp8g_last_error();
+		if (he && *he) fprintf(stderr, "  (%s)\n", he);
+		return 1;
+	}
+	int wrc = -1;
+	const int fd = open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+	if (fd < 0) {
+		fputs("error: cannot open output file\n", stderr);
+	} else {
+		if (g.scaling) {
+			char head[64];
+			const int hn = snprintf(head, sizeof(head), "P6\n%u %u\n255\n", w, h);
+			wrc = write_all(fd, (const uint8_t*)head, (size_t)hn) | write_all(fd, rgb, (size_t)w * h * 3u);
+		} else {
+			wrc = yuv420_write_ppm_fd(fd, &win);
+		}
+		close(fd);
+		if (wrc != 0) fputs("error: PPM write failed\n", stderr);
+	}
+	free(rgb);
+	yuv420_free(&win);
+	return wrc == 0 ? 0 : 1;
 }
 
 /* reference src/main.c:706-773 (-ppm) and :775-844 (-png): filtered reconstruction, then the
@@ -235,8 +296,9 @@ int main(int argc, char** argv) {
 		}
 		return cmd_info(argv[2]);
 	}
-	if (!strcmp(cmd, "-yuv") || !strcmp(cmd, "-yuvf")) {
-		if (argc == 4) return cmd_yuv(argv[2], argv[3], cmd[4] == 'f', NULL);
+	const int is_rgb = !strcmp(cmd, "-rgb");
+	if (!strcmp(cmd, "-yuv") || !strcmp(cmd, "-yuvf") || is_rgb) {
+		if (argc == 4) return is_rgb ? cmd_rgb(argv[2], argv[3], 0) : cmd_yuv(argv[2], argv[3], cmd[4] == 'f', NULL);
 		/* [-crop x y w h] [-scale w h] before the two file names */
 		Vp8gScaleOpt opt;
 		memset(&opt, 0, sizeof(opt));
@@ -269,7 +331,7 @@ int main(int argc, char** argv) {
 			usage();
 			return 2;
 		}
-		return cmd_yuv(argv[a], argv[a + 1], cmd[4] == 'f', &opt);
+		return is_rgb ? cmd_ppm_scaled(argv[a], argv[a + 1], &opt) : cmd_yuv(argv[a], argv[a + 1], cmd[4] == 'f', &opt);
 	}
 	if (!strcmp(cmd, "-ppm") || !strcmp(cmd, "-png")) {
 		if (argc != 4) {

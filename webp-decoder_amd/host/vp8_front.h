@@ -117,6 +117,15 @@ int vp8f_scale_i420(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint32
                     uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, uint8_t* dy, uint8_t* du, uint8_t* dv,
                     uint32_t dstride_y, uint32_t dstride_uv);
 
+/* The three planes of libwebp's scaled RGB of a lossy picture: an option WITH a target size resolved
+ * as above; Y from the luma window, U and V from the chroma window (ceil(win / 2) at (left / 2, top / 2)), every plane to
+ * the same out_w x out_h with the plane arithmetic of vp8f_scale_i420 -- each axis of a plane shrinks or expands as its own
+ * sizes say (128 -> 100 shrinks luma and expands chroma 64 -> 100), whatever VP8G_SCALE_EXPAND says of the luma target.
+ * dy, du, dv: tight out_w x out_h planes.  The pixel is then VP8YuvToRgb(Y, U, V): no upsampler.  0, or -1 + errno
+ * (EINVAL as vp8f_scale_resolve, and for an option without a target size; ENOMEM). */
+int vp8f_scale_yuv444(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint32_t stride_y, uint32_t stride_uv,
+                      uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, uint8_t* dy, uint8_t* du, uint8_t* dv);
+
 /* vp8f_scale_resolve for an ARGB picture (a lossless file): the same rules, but the window's origin is
  * taken as given -- libwebp rounds it down to even only where there is chroma to stay aligned with. */
 int vp8f_scale_resolve_argb(uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, Vp8fScaleGeom* g);

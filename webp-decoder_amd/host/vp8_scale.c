@@ -236,6 +236,32 @@ int vp8f_scale_i420(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint32
 	return 0;
 }
 
+/* libwebp's scaled RGB of a lossy picture (WebPDecode with use_scaling into MODE_RGB / MODE_RGBA, dwebp -ppm -scale;
+ * DESIGN.md §14.2): Y, U and V each go straight to the target size -- chroma from its own window, ceil(window / 2) at
+ * (left / 2, top / 2), each axis shrinking or expanding as its own sizes say whatever VP8G_SCALE_EXPAND says of luma --
+ * and the pixel is VP8YuvToRgb of the three samples; no upsampler. */
+int vp8f_scale_yuv444(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint32_t stride_y, uint32_t stride_uv,
+                      uint32_t width, uint32_t height, const Vp8gScaleOpt* opt, uint8_t* dy, uint8_t* du, uint8_t* dv) {
+	Vp8fScaleGeom g;
+	if (!y || !u || !v || !dy || !du || !dv || vp8f_scale_resolve(width, height, opt, &g) != 0 || !g.scaling || stride_y < width ||
+	    stride_uv < (width + 1u) / 2u) {
+		errno = EINVAL;
+		return -1;
+	}
+	uint32_t* work = (uint32_t*)malloc((size_t)2 * g.out_w * sizeof(uint32_t));
+	if (!work) {
+		errno = ENOMEM;
+		return -1;
+	}
+	const uint32_t cw = (g.win_w + 1u) / 2u, ch = (g.win_h + 1u) / 2u;
+	const size_t co = (size_t)(g.top / 2u) * stride_uv + g.left / 2u;
+	scale_plane(y + (size_t)g.top * stride_y + g.left, stride_y, g.win_w, g.win_h, dy, g.out_w, g.out_w, g.out_h, work);
+	scale_plane(u + co, stride_uv, cw, ch, du, g.out_w, g.out_w, g.out_h, work);
+	scale_plane(v + co, stride_uv, cw, ch, dv, g.out_w, g.out_w, g.out_h, work);
+	free(work);
+	return 0;
+}
+
 /* ---- ARGB pictures (lossless files): libwebp's 4-channel rescaler ------------------------------
  *
  * libwebp rescales the rows of a VP8L picture as four interleaved byte channels, each with exactly the

@@ -417,6 +417,9 @@ def host_lib():
         lib.vp8f_scale_filtered.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(Vp8gScaleOpt), C.c_int]
         lib.vp8f_scale_i420.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                         C.POINTER(Vp8gScaleOpt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        if hasattr(lib, "vp8f_scale_yuv444"):  # (libraries built before libwebp's scaled RGB)
+            lib.vp8f_scale_yuv444.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                              C.POINTER(Vp8gScaleOpt), C.c_void_p, C.c_void_p, C.c_void_p]
         lib.webp_parse_simple_lossy.argtypes = [ByteSpan, C.c_void_p]
         lib.vp8_parse_keyframe_header.argtypes = [ByteSpan, C.POINTER(Vp8KeyFrameHeader)]
         lib.webp_locate_still.argtypes = [ByteSpan, C.c_uint, C.POINTER(WebPStill)]
@@ -589,6 +592,12 @@ def gpu_lib():
             lib.vp8g_decode_webp_anim_tensor_scaled.argtypes = [P(ByteSpan), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, P(Vp8gScaleOpt),
                                                                 C.c_uint32, C.c_uint64, P(Vp8gTensorOpt), C.c_uint32, C.c_void_p,
                                                                 P(C.c_uint32), P(C.c_int)]
+        if hasattr(lib, "vp8g_tensor_batch_device_444"):  # (libraries built before libwebp's scaled RGB)
+            lib.vp8g_make_scale_desc_444.argtypes = lib.vp8g_make_scale_desc.argtypes
+            lib.vp8g_make_tensor_desc_444.argtypes = lib.vp8g_make_tensor_desc.argtypes
+            lib.vp8g_tensor_batch_device_444.argtypes = [P(Vp8gTensorDesc), C.c_void_p, P(Vp8gTensorAlpha), C.c_void_p, C.c_uint32,
+                                                         P(Vp8gTensorOpt), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.vp8g_decode_webp_batch_tensor_rgb.argtypes = lib.vp8g_decode_webp_batch_tensor_any.argtypes
         lib._typed = True
     return lib
 
@@ -1107,7 +1116,12 @@ def host_tensor(i420: bytes, w: int, h: int, opt: Vp8gTensorOpt, alpha=None):
         planar = opt.layout == T_LAYOUTS["NCHW"]
         return torch.cat([rgb3, a.unsqueeze(0 if planar else 2)], dim=0 if planar else 2).contiguous()
     ppm = oracle_encode(i420, w, h, "ppm")
-    rgb = np.frombuffer(ppm, np.uint8, w * h * 3, len(ppm) - w * h * 3).reshape(h, w, 3)
+    return _rgb_elements(np.frombuffer(ppm, np.uint8, w * h * 3, len(ppm) - w * h * 3).reshape(h, w, 3), opt)
+
+
+def _rgb_elements(rgb, opt: Vp8gTensorOpt):
+    """host_tensor from the RGB bytes on ([h, w, 3] uint8): channel order, elements, layout."""
+    import torch
     if opt.flags & VP8G_T_BGR:
         rgb = rgb[:, :, ::-1]
     if opt.dtype == T_DTYPES["uint8"]:
@@ -1172,6 +1186,167 @@ def gpu_tensor(i420_list, w: int, h: int, opt: Vp8gTensorOpt, alpha=None):
         S.call(lib, "vp8g_tensor_batch_device", descs, d_descs, n, C.byref(opt), src, out, stream.cuda_stream)
     stream.synchronize()
     return out
+
+
+# ---- scaled RGB exact to libwebp's: 4:4:4 planes ----------------------------
+
+
+def yuv_to_rgb(y, u, v) -> np.ndarray:
+    """libwebp's VP8YuvToRgb on uint8 arrays of one shape: [..., 3] uint8 (14-bit fixed point, clip of v >> 6)."""
+    y, u, v = (np.asarray(a).astype(np.int32) for a in (y, u, v))
+    yy = (y * 19077) >> 8
+    r = yy + ((v * 26149) >> 8) - 14234
+    g = yy - ((u * 6419) >> 8) - ((v * 13320) >> 8) + 8708
+    b = yy + ((u * 33050) >> 8) - 17685
+    return (np.clip(np.stack([r, g, b], axis=-1), 0, 16383) >> 6).astype(np.uint8)
+
+
+def host_scale_yuv444(i420: bytes, w: int, h: int, opt: Vp8gScaleOpt) -> np.ndarray:
+    """vp8f_scale_yuv444 on I420 bytes: the three planes libwebp converts to a scaled RGB picture, uint8 [3, oh, ow]
+    (Y, U, V each rescaled straight to the target size).  ValueError for an option that does not fit or has no target size."""
+    a = np.frombuffer(i420, dtype=np.uint8)
+    assert a.size == i420_size(w, h)
+    if not (opt.scaled_w or opt.scaled_h):
+        raise ValueError("host_scale_yuv444: an option without a target size")
+    ow, oh = scaled_size(w, h, opt)
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    out = np.empty((3, oh, ow), np.uint8)
+    sb, ob = a.ctypes.data, out.ctypes.data
+    if host_lib().vp8f_scale_yuv444(sb, sb + w * h, sb + w * h + cw * ch, w, cw, w, h, C.byref(opt), ob, ob + ow * oh, ob + 2 * ow * oh) != 0:
+        raise RuntimeError(f"vp8f_scale_yuv444 failed: errno={C.get_errno()}")
+    return out
+
+
+def host_scale_rgb(i420: bytes, w: int, h: int, opt: Vp8gScaleOpt, alpha=None) -> np.ndarray:
+    """libwebp's scaled RGB of a decoded lossy picture on the host (WebPDecode with use_scaling into MODE_RGB, or, with
+    alpha = the picture's uint8 [h, w] plane, MODE_RGBA): uint8 [oh, ow, 3 | 4].  The I420 must be decoded as libwebp
+    decodes for that option (vp8f_scale_filtered with VP8G_SCALE_DWEBP_FILTER)."""
+    p = host_scale_yuv444(i420, w, h, opt)
+    rgb = yuv_to_rgb(p[0], p[1], p[2])
+    if alpha is None:
+        return rgb
+    return np.concatenate([rgb, host_scale_plane(alpha, opt)[:, :, None]], axis=2)
+
+
+def host_tensor_444(planes, opt: Vp8gTensorOpt, alpha=None):
+    """host_tensor for three uint8 [h, w] planes (Y, U, V of the picture's own size): pixel = VP8YuvToRgb of its own
+    samples, then the elements and layout of host_tensor.  alpha as there."""
+    import torch
+    y, u, v = (np.asarray(p, dtype=np.uint8) for p in planes)
+    assert y.shape == u.shape == v.shape == (opt.height, opt.width)
+    rgb3 = _rgb_elements(yuv_to_rgb(y, u, v), opt)
+    if alpha is None:
+        return rgb3
+    a = host_alpha_channel(np.full(y.shape, 255, np.uint8) if isinstance(alpha, str) else alpha, opt)
+    planar = opt.layout == T_LAYOUTS["NCHW"]
+    return torch.cat([rgb3, a.unsqueeze(0 if planar else 2)], dim=0 if planar else 2).contiguous()
+
+
+def stage_scale_batch(jobs, guard: int = 64, fill: int = 0xEE, src_shift: int = 1):
+    """The host half of gpu_scale_batch.  jobs: (kind, data, w, h, opt) with kind "444" (I420 bytes through
+    vp8g_make_scale_desc_444), "420" (I420 bytes through vp8g_make_scale_desc) or "plane" (a uint8 [h, w] plane through
+    vp8g_make_scale_desc_plane).  Every source starts src_shift bytes off a 16-byte boundary; every output has guard bytes
+    around it."""
+    lib = gpu_lib()
+    descs = (Vp8gScaleDesc * len(jobs))()
+    source, dst, task0, shapes = S.Source(), S.Guarded(guard, fill), 0, []
+    for i, (kind, data, w, h, opt) in enumerate(jobs):
+        ow, oh = scaled_size(w, h, opt)
+        cw, ch = (w + 1) // 2, (h + 1) // 2
+        if kind == "plane":
+            o = source.put(np.asarray(data, dtype=np.uint8).reshape(h, w), 16, src_shift)
+            rc = lib.vp8g_make_scale_desc_plane(w, h, o, w, C.byref(opt), dst.add(ow * oh), task0, C.byref(descs[i]))
+            shapes.append((oh, ow))
+        else:
+            a = np.frombuffer(data, np.uint8)
+            assert a.size == i420_size(w, h)
+            o = source.put(a, 16, src_shift)
+            if kind == "444":
+                rc = lib.vp8g_make_scale_desc_444(w, h, o, o + w * h, o + w * h + cw * ch, w, cw, C.byref(opt), dst.add(3 * ow * oh), task0,
+                                                  C.byref(descs[i]))
+                shapes.append((3, oh, ow))
+            else:
+                rc = lib.vp8g_make_scale_desc(w, h, o, o + w * h, o + w * h + cw * ch, w, cw, C.byref(opt), dst.add(i420_size(ow, oh)), task0,
+                                              C.byref(descs[i]))
+                shapes.append((i420_size(ow, oh),))
+        if rc != 0:
+            raise ValueError(f"scale descriptor {i} ({kind}) refused: errno={C.get_errno()}")
+        task0 += descs[i].ntasks
+    return SimpleNamespace(descs=descs, source=source, src=source.finish(), dst=dst, shapes=shapes)
+
+
+def gpu_scale_batch(jobs, guard: int = 64, fill: int = 0xEE, src_shift: int = 1):
+    """vp8g_scale_batch_device over mixed descriptors (stage_scale_batch) in one call: per job the three planes uint8
+    [3, oh, ow] ("444"), the scaled I420 bytes as a flat uint8 array ("420") or the plane uint8 [oh, ow] ("plane")."""
+    st = stage_scale_batch(jobs, guard, fill, src_shift)
+    host = _run("vp8g_scale_batch_device", st, "gpu_scale_batch: bytes outside the outputs").numpy()
+    return [host[o:o + n].reshape(shape).copy() for (o, n), shape in zip(st.dst.regions, st.shapes)]
+
+
+def gpu_scale_yuv444(i420_list, sizes, opts):
+    """vp8g_make_scale_desc_444 + vp8g_scale_batch_device over I420 pictures (sizes: (w, h) each; opts: one Vp8gScaleOpt
+    each) in one launch: the list of uint8 [3, oh, ow] planes, as host_scale_yuv444 gives them."""
+    return gpu_scale_batch([("444", b, w, h, o) for b, (w, h), o in zip(i420_list, sizes, opts)])
+
+
+def stage_tensor_444(planes_list, w: int, h: int, opt: Vp8gTensorOpt, alpha=None, guard: int = 64, fill: int = 0xEE, src_shift: int = 1,
+                     src_pad: int = 0):
+    """The host half of gpu_tensor_444: descriptors (and alpha entries), the planes -- every one src_shift bytes off a
+    16-byte boundary, rows padded by src_pad -- and the destination with guard bytes around every slot."""
+    lib = gpu_lib()
+    n, channels = len(planes_list), 3 if alpha is None else 4
+    if alpha is not None and len(alpha) != n:
+        raise ValueError("gpu_tensor_444: one alpha entry per picture")
+    slot = lib.vp8g_tensor_slot_size(C.byref(opt)) if alpha is None else lib.vp8g_tensor_slot_size_a(C.byref(opt))
+    if not slot or (w, h) != (opt.width, opt.height):
+        raise ValueError("gpu_tensor_444: invalid options or picture size")
+    descs, al = (Vp8gTensorDesc * n)(), (Vp8gTensorAlpha * n)() if alpha is not None else None
+    source, dst, task0 = S.Source(), S.Guarded(guard, fill), 0
+
+    def put(plane):
+        p = np.asarray(plane, dtype=np.uint8)
+        if p.shape != (h, w):
+            raise ValueError("gpu_tensor_444: a plane of another size")
+        return source.put(np.pad(p, ((0, 0), (0, src_pad)), constant_values=S.PAD), 16, src_shift)
+
+    for i, planes in enumerate(planes_list):
+        oy, ou, ov = (put(p) for p in planes)
+        if lib.vp8g_make_tensor_desc_444(C.byref(opt), oy, ou, ov, w + src_pad, w + src_pad, dst.add(slot), task0, C.byref(descs[i])) != 0:
+            raise ValueError("vp8g_make_tensor_desc_444 failed")
+        task0 += descs[i].ntasks
+        if alpha is not None:
+            al[i] = Vp8gTensorAlpha(T_OPAQUE, 0, 0) if alpha[i] is None else Vp8gTensorAlpha(put(alpha[i]), w + src_pad, 0)
+    return SimpleNamespace(descs=descs, alpha=al, channels=channels, source=source, src=source.finish(), dst=dst, opt=opt)
+
+
+def run_tensor_444(st, mutate=None, null=(), channels=None, ptr_shift=(0, 0), einval=None):
+    """The device half: upload, vp8g_tensor_batch_device_444, and the slots back as torch CPU tensors ([C, H, W] or
+    [H, W, C] each) once the guard bytes are seen to hold their fill.  For the refusals: mutate() breaks the host copies
+    after the device copies are made, null names arguments passed as NULL ("descs", "d_descs", "alpha", "d_alpha", "src",
+    "dst"), channels overrides the count, ptr_shift = bytes added to the (source, output) pointers; einval as S.call."""
+    import torch
+    opt = st.opt
+    d_src, d_dst, d_descs = S.upload(st.src), st.dst.on_device(), device_copy(st.descs)
+    d_al = device_copy(st.alpha) if st.alpha is not None else None
+    if mutate:
+        mutate()
+    args = {"descs": st.descs, "d_descs": d_descs, "alpha": st.alpha, "d_alpha": d_al, "src": (d_src, ptr_shift[0]), "dst": (d_dst, ptr_shift[1])}
+    a = {k: (None if k in null else v) for k, v in args.items()}
+    stream = S.stream()
+    S.call(gpu_lib(), "vp8g_tensor_batch_device_444", a["descs"], a["d_descs"], a["alpha"], a["d_alpha"], len(st.descs), C.byref(opt),
+           st.channels if channels is None else channels, a["src"], a["dst"], stream.cuda_stream, einval=einval,
+           untouched=(d_dst, st.dst.fill))
+    stream.synchronize()
+    host = st.dst.fetch(d_dst, "gpu_tensor_444: bytes outside the slots")
+    shape = _tensor_shape(1, opt, st.channels)[1:]
+    return [host[o:o + nb].clone().view(_torch_dtype(opt)).reshape(shape) for o, nb in st.dst.regions]
+
+
+def gpu_tensor_444(planes_list, w: int, h: int, opt: Vp8gTensorOpt, alpha=None, **stage):
+    """vp8g_tensor_batch_device_444 over pictures given as (Y, U, V) uint8 [h, w] planes of one size, in one launch: the
+    list of torch CPU tensors [3, H, W] / [H, W, 3] (4 channels with alpha: a list with one uint8 [h, w] plane or None
+    = opaque per picture).  The planes start off their alignment and the slots sit between guard bytes (stage_tensor_444)."""
+    return run_tensor_444(stage_tensor_444(planes_list, w, h, opt, alpha, **stage))
 
 
 # ---- lossless (VP8L) images (DESIGN.md §17) -------------------------------------------------
@@ -1522,13 +1697,9 @@ def wrap_anim_frame(data: bytes, f: dict) -> bytes:
     return b"RIFF" + (len(body) + 4).to_bytes(4, "little") + b"WEBP" + body
 
 
-def host_still_argb(data: bytes) -> np.ndarray:
-    """A still .webp (lossy, lossy with alpha, or lossless) on the host as uint32 [h, w] 0xAARRGGBB, the bytes
-    WebPDecodeRGBA gives: the lossless restatement, or the oracle's reconstruction (loop filter on) and RGB conversion
-    with the alpha plane of host_alpha_plane (255 without one)."""
-    c = parse_any(data)
-    if c["lossless"]:
-        return host_lossless_argb(data)
+def decode_lossy_still(data: bytes, c: dict | None = None) -> Frame:
+    """The VP8 frame of a lossy still (simple or extended container; c = its parse_any record) through the host front end."""
+    c = c or parse_any(data)
     kf, fr, st = Vp8KeyFrameHeader(), Vp8DecodedFrame(), C.c_int(0)
     p = data[c["vp8_chunk_offset"]:c["vp8_chunk_offset"] + c["vp8_chunk_size"]]
     simple = b"RIFF" + (len(p) + (len(p) & 1) + 12).to_bytes(4, "little") + b"WEBPVP8 " + len(p).to_bytes(4, "little") + p + (
@@ -1536,7 +1707,35 @@ def host_still_argb(data: bytes) -> np.ndarray:
     buf, _ = _c_bytes(simple)
     if host_lib().vp8f_decode_memory(buf, len(simple), C.byref(kf), C.byref(fr), C.byref(st)) != 0:
         raise OSError(C.get_errno() or 22, f"vp8f_decode_memory (stage {st.value})")
-    f = Frame(kf, fr)
+    return Frame(kf, fr)
+
+
+def host_still_scaled_rgb(data: bytes, opt: Vp8gScaleOpt, channels: int = 4) -> np.ndarray:
+    """A lossy still .webp on the host as libwebp decodes it into MODE_RGB / MODE_RGBA with the cropping / scaling of
+    `opt` (which has a target size): front end, the oracle's reconstruction with the loop filter as
+    vp8f_scale_filtered decides it, host_scale_rgb with the alpha plane of host_alpha_plane (opaque without one).
+    uint8 [oh, ow, channels]."""
+    c = parse_any(data)
+    f = decode_lossy_still(data, c)
+    w, h = f.width, f.height
+    i420 = oracle_reconstruct(f, bool(host_lib().vp8f_scale_filtered(w, h, C.byref(opt), 1)))
+    f.free()
+    a = host_alpha_plane(data) if channels == 4 and c["extended"] else None
+    rgb = host_scale_rgb(i420, w, h, opt, a)
+    if channels == 3 or a is not None:
+        return rgb
+    # (a picture without alpha is opaque: libwebp rescales no plane for it -- a rescaled plane of 255 is not 255 everywhere)
+    return np.concatenate([rgb, np.full(rgb.shape[:2] + (1,), 255, np.uint8)], axis=2)
+
+
+def host_still_argb(data: bytes) -> np.ndarray:
+    """A still .webp (lossy, lossy with alpha, or lossless) on the host as uint32 [h, w] 0xAARRGGBB, the bytes
+    WebPDecodeRGBA gives: the lossless restatement, or the oracle's reconstruction (loop filter on) and RGB conversion
+    with the alpha plane of host_alpha_plane (255 without one)."""
+    c = parse_any(data)
+    if c["lossless"]:
+        return host_lossless_argb(data)
+    f = decode_lossy_still(data, c)
     w, h = f.width, f.height
     ppm = oracle_encode(oracle_reconstruct(f, True), w, h, "ppm")
     f.free()
@@ -1722,7 +1921,7 @@ def gpu_decode_webp_batch_x(files: list[bytes], scale=None, filtered: bool = Tru
 
 def gpu_decode_webp_batch_tensor(files: list[bytes], opt: Vp8gTensorOpt, scale=None, filtered: bool = True, threads: int = 0,
                                  device_m05: bool = False, multi_partition: bool = False, extended: bool = False,
-                                 alpha: bool = False, lossless: bool = False, lossless_scale: bool = False):
+                                 alpha: bool = False, lossless: bool = False, lossless_scale: bool = False, libwebp_rgb: bool = False):
     """vp8g_decode_webp_batch_tensor: .webp images decoded, optionally cropped / downscaled (scale: None,
     one Vp8gScaleOpt for every frame, or a list of one per frame), converted and left on the device.
     Returns (torch.Tensor on the device, [N, 3, H, W] or [N, H, W, 3] of the requested dtype, list of
@@ -1733,7 +1932,10 @@ def gpu_decode_webp_batch_tensor(files: list[bytes], opt: Vp8gTensorOpt, scale=N
     lossless_scale (VP8G_X_LOSSLESS_SCALE; needs lossless): then a lossless file's option is applied as libwebp applies
     it to such a file -- the crop window's origin as given, not rounded to even, and RGBA bit-exact to libwebp's
     (host_scale_argb) -- and only an option that does not fit the file, or whose result is not the tensor's size, fails
-    (EINVAL).  torch only allocates the tensor: its data_ptr() is handed to the C call."""
+    (EINVAL).  libwebp_rgb: vp8g_decode_webp_batch_tensor_rgb with the flags the other keywords give (implies the extended
+    container): a lossy file whose option has a target size gets libwebp's own scaled RGB -- Y, U and V each rescaled to
+    the target, VP8YuvToRgb per pixel, no upsampler (host_scale_rgb; dwebp -ppm -scale with dwebp_filter) -- and every other
+    frame goes as without it.  torch only allocates the tensor: its data_ptr() is handed to the C call."""
     import time
     import torch
     extended = extended or alpha  # (alpha arrives through the _x call only)
@@ -1749,11 +1951,11 @@ def gpu_decode_webp_batch_tensor(files: list[bytes], opt: Vp8gTensorOpt, scale=N
     torch.cuda.synchronize(dev)
     st = (C.c_int * n)()
     t0 = time.perf_counter()
-    if lossless or lossless_scale:
-        rc = lib.vp8g_decode_webp_batch_tensor_any(spans, n, int(filtered), threads, bflags, c_opts, nopts, C.byref(opt),
-                                                   (VP8G_X_LOSSLESS if lossless else 0) | (VP8G_X_ALPHA if alpha else 0)
-                                                   | (VP8G_X_LOSSLESS_SCALE if lossless_scale else 0),
-                                                   C.c_void_p(out.data_ptr()), st)
+    if lossless or lossless_scale or libwebp_rgb:
+        entry = lib.vp8g_decode_webp_batch_tensor_rgb if libwebp_rgb else lib.vp8g_decode_webp_batch_tensor_any
+        rc = entry(spans, n, int(filtered), threads, bflags, c_opts, nopts, C.byref(opt),
+                   (VP8G_X_LOSSLESS if lossless else 0) | (VP8G_X_ALPHA if alpha else 0) | (VP8G_X_LOSSLESS_SCALE if lossless_scale else 0),
+                   C.c_void_p(out.data_ptr()), st)
     elif extended:  # (routed to the _x call only when asked)
         rc = lib.vp8g_decode_webp_batch_tensor_x(spans, n, int(filtered), threads, bflags, c_opts, nopts, C.byref(opt),
                                                  VP8G_X_ALPHA if alpha else 0, C.c_void_p(out.data_ptr()), st)
